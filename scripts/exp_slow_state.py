@@ -1,6 +1,6 @@
 """The slow state of the narrow-row launch (profiles/r5af_*, r6j): which launches of a process are slow — by workspace (the mirror's default one /
 a search context's own) and by stream (torch's default stream / a stream of its own) — with and without the history of a bench process
-(two contexts + two streams used on another index first) and with GPU_MAX_HW_QUEUES unset / 16.
+(two contexts + two streams used on another index first) and with GPU_MAX_HW_QUEUES unset / 2.
 usage: exp_slow_state.py            (runs itself in sub-processes, one per environment)
        exp_slow_state.py child <history 0|1>"""
 import os
@@ -11,7 +11,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 if len(sys.argv) < 2 or sys.argv[1] != "child":
-    for hwq in (None, "4"):
+    for hwq in (None, "2"):
         for hist in ("0", "1"):
             env = dict(os.environ)
             env.pop("GPU_MAX_HW_QUEUES", None)

@@ -62,3 +62,47 @@ def test_single_process_default_does_not_launch_anything():
     assert r.returncode == 0, r.stderr[-2000:]
     j = _line(r.stdout)
     assert j["n_gpus"] == 1 and j["backend"] is None
+
+
+def test_dump_outputs_writes_float_arrays_and_a_fixed_sample_beyond_the_budget(tmp_path):
+    """--dump-outputs: the arrays of the last timed step as float32 / float64 .npy, all rows while they fit, beyond the budget the
+    same seeded sample of query rows in every array (and its row numbers), identical from call to call."""
+    prog = """
+import sys
+import numpy as np
+out = sys.argv[1]
+sys.argv = sys.argv[:1]
+import bench
+rng = np.random.default_rng(5)
+nq, ef = 300, 16
+lab = rng.integers(0, 1 << 40, (nq, ef), dtype=np.int64)
+lab[:, -1] = -1
+d = rng.random((nq, ef), dtype=np.float32)
+c = rng.integers(0, ef + 1, nq).astype(np.uint32)
+arrays = {"labels": lab, "dists": d, "counts": c}
+np.save(out + "/src_labels.npy", lab)
+np.save(out + "/src_dists.npy", d)
+np.save(out + "/src_counts.npy", c)
+bench.dump_outputs(out + "/full", arrays)
+bench.DUMP_BUDGET_BYTES = 100 * (16 * 8 + 16 * 4 + 8)
+bench.dump_outputs(out + "/a", arrays)
+bench.dump_outputs(out + "/b", arrays)
+"""
+    r = subprocess.run([sys.executable, "-c", prog, str(tmp_path)], cwd=ROOT, capture_output=True, text=True, timeout=300,
+                       env=dict(os.environ, PYTHONPATH=ROOT))
+    assert r.returncode == 0, r.stderr[-2000:]
+    import numpy as np
+    src = {k: np.load(tmp_path / f"src_{k}.npy") for k in ("labels", "dists", "counts")}
+    full = {k: np.load(tmp_path / "full" / f"{k}.npy") for k in ("labels", "dists", "counts")}
+    assert not (tmp_path / "full" / "query_index.npy").exists()
+    assert full["labels"].dtype == np.float64 and full["dists"].dtype == np.float32 and full["counts"].dtype == np.float64
+    for k in src:
+        assert (full[k] == src[k]).all()
+    a = {k: np.load(tmp_path / "a" / f"{k}.npy") for k in ("labels", "dists", "counts", "query_index")}
+    b = {k: np.load(tmp_path / "b" / f"{k}.npy") for k in ("labels", "dists", "counts", "query_index")}
+    rows = a["query_index"].astype(np.int64)
+    assert 0 < len(rows) < 100 and (np.diff(rows) > 0).all()
+    assert sum(v.nbytes for v in a.values()) <= 100 * (16 * 8 + 16 * 4 + 8)
+    for k in ("labels", "dists", "counts"):
+        assert (a[k] == src[k][rows]).all() and (a[k] == b[k]).all()
+    assert (a["query_index"] == b["query_index"]).all()

@@ -5,9 +5,11 @@ client library's drop-in symbols and their failure behaviour; the device path be
 server is covered by tests/test_gpu_server.py."""
 import json
 import os
+import shutil
 import socket
 import struct
 import subprocess
+import tempfile
 import threading
 import time
 
@@ -61,14 +63,21 @@ def test_product_server_refuses_to_start_without_a_device():
         ServerProcess().start()
 
 
-def test_client_fails_loudly_without_a_server(tmp_path):
-    with pytest.raises(RemoteError) as e:
-        RemoteClient(str(tmp_path / "nobody-listens"))
-    assert e.value.code == -23
-    exe = SU.build_c_client("dropin_demo")
-    env = dict(os.environ, PG_EMBEDDING_GPU_SERVER=str(tmp_path / "nobody-listens"))
-    r = subprocess.run([exe, "50", "8", "3", "8", "8", "2"], capture_output=True, text=True, env=env)
-    assert r.returncode != 0 and "cannot reach hnsw_gpu_server" in r.stderr
+def test_client_fails_loudly_without_a_server():
+    # a short directory as ServerProcess makes one: pytest's tmp_path can be longer than a socket path may be (sun_path),
+    # and then the client stops at "socket path too long" before it ever tries to connect
+    tmp = tempfile.mkdtemp(prefix="hgs_")
+    try:
+        path = os.path.join(tmp, "nobody-listens")
+        with pytest.raises(RemoteError) as e:
+            RemoteClient(path)
+        assert e.value.code == -23
+        exe = SU.build_c_client("dropin_demo")
+        env = dict(os.environ, PG_EMBEDDING_GPU_SERVER=path)
+        r = subprocess.run([exe, "50", "8", "3", "8", "8", "2"], capture_output=True, text=True, env=env)
+        assert r.returncode != 0 and "cannot reach hnsw_gpu_server" in r.stderr
+    finally:
+        shutil.rmtree(tmp, ignore_errors=True)
 
 
 @pytest.mark.parametrize("func", [pg.DIST_L2, pg.DIST_COSINE, pg.DIST_MANHATTAN])
@@ -645,14 +654,15 @@ def test_linger_gathers_a_batch_before_launching(double_bin, lanes):
         c0.close()
 
 
-def test_a_restarted_server_is_picked_up_again(double_bin, tmp_path):
+def test_a_restarted_server_is_picked_up_again(double_bin):
     """The server goes away and comes back on the same socket (its mirrors are gone with it): the next
     request of a connected client reconnects by itself; a search on a mirror the new server does not
     have says so (NOKEY) and works again after the upload."""
     dim, m, n, efs = 16, 4, 300, 10
     port, X = port_index(n, dim, m, 16, efs, pg.DIST_L2, seed=95)
     meta = pg.make_meta(dim, m, 16, efs, pg.DIST_L2)
-    path = str(tmp_path / "sock")
+    tmp = tempfile.mkdtemp(prefix="hgs_")                 # short: pytest's tmp_path can be longer than sun_path
+    path = os.path.join(tmp, "sock")
     s1 = ServerProcess(socket_path=path, binary=double_bin).start()
     c = RemoteClient(path)
     c.upload(meta, 1, 1, port.raw(), n)
@@ -676,6 +686,7 @@ def test_a_restarted_server_is_picked_up_again(double_bin, tmp_path):
     finally:
         s2.stop()
         c.close()
+        shutil.rmtree(tmp, ignore_errors=True)
 
 
 def test_server_stops_cleanly_on_sigterm(double_bin):
