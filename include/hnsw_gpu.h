@@ -153,6 +153,28 @@ int hnsw_gpu_search_base_dev(hnsw_gpu_index *ix, const coord_t *d_queries, size_
 							 idx_t *d_idx, dist_t *d_dists, uint32_t *d_counts,
 							 uint32_t *d_stats, void *stream);
 
+/* Reduced rows: fp16 / bf16 search rows with exact fp32 re-ranking of the results.
+ * A mirror may keep, in an allocation of its own, a 16-bit copy of its rows (+50 % of the fp32 row bytes: 1.5 GB at 1M x 768).
+ * The graph is always built and changed from the fp32 rows; every writer of the rows (create / update_from_flat, append,
+ * append_dev, insert_one, insert_candidates, reserve) leaves the copy to be brought up to date by the next reduced search, on
+ * that search's stream.  A reduced search walks over the copy (beam form, one wave per query: ef <= 256, <= 512 on rows
+ * wider than 256 floats) in base mode, then re-scores its <= ef candidates against the fp32 rows: labels, distances and counts
+ * as hnsw_gpu_search_batch_dev returns them, every distance the exact canonical fp32 distance; the id set is approximate
+ * and may differ from the fp32 walk's.  d_stats counts the walk only (not the re-rank's <= ef evaluations).  Requests the
+ * reduced walk does not cover (other forms, HNSW_GPU_REF_ORDER=1, a format that is not enabled) fail with HNSW_GPU_ERR_ARG
+ * before anything is launched. */
+enum { HNSW_GPU_ROWS_F32 = 0, HNSW_GPU_ROWS_F16 = 1, HNSW_GPU_ROWS_BF16 = 2 };
+/* build (HNSW_GPU_ROWS_F16 / _BF16) or free (HNSW_GPU_ROWS_F32) the copy; synchronous */
+int hnsw_gpu_index_set_reduced_rows(hnsw_gpu_index *ix, int format);
+/* the copy's format (HNSW_GPU_ROWS_F32 = none) */
+int hnsw_gpu_index_reduced_rows(const hnsw_gpu_index *ix);
+/* device-pointer form (as hnsw_gpu_search_batch_dev); `format` must be the copy's format */
+int hnsw_gpu_search_batch_reduced_dev(hnsw_gpu_index *ix, int format, const coord_t *d_queries, size_t nq, size_t ef,
+									  label_t *d_labels, dist_t *d_dists, uint32_t *d_counts, uint32_t *d_stats, void *stream);
+/* host-pointer form (as hnsw_gpu_search_batch) */
+int hnsw_gpu_search_batch_reduced(hnsw_gpu_index *ix, int format, const coord_t *queries, size_t nq, size_t ef,
+								  label_t *labels, dist_t *dists, uint32_t *counts);
+
 /* Milliseconds the most recent search kernel of this index spent on the device,
  * from HIP events recorded on its stream around the launch (waits for it). */
 int hnsw_gpu_last_search_ms(hnsw_gpu_index *ix, float *ms);

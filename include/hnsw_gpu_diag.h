@@ -67,6 +67,13 @@ double hnsw_gpu_last_bruteforce_clock_mhz(void);
  * No query of the fused kernel can read rows faster from HBM than this dependency-free gather. */
 int hnsw_gpu_gather_roof(hnsw_gpu_index *ix, int loads_per_lane, int waves_per_cu, unsigned iters, float *gbps);
 
+/* The reduced copy of the rows (hnsw_gpu_index_set_reduced_rows) in natural element order, un-swizzled: out[e * dim + j] = the 16-bit
+ * value of element e, coordinate j (n * dim values).  Brings the copy up to date first; synchronous.  For tests. */
+int hnsw_gpu_index_export_reduced_rows(hnsw_gpu_index *ix, uint16_t *out);
+/* Milliseconds the re-rank kernel of the last reduced-row search spent on the device (its own HIP event pair; waits for it).
+ * hnsw_gpu_last_search_ms spans the walk AND the re-rank: the walk alone is the difference. */
+int hnsw_gpu_last_rerank_ms(hnsw_gpu_index *ix, float *ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -124,6 +124,12 @@ def gpu_lib():
     L.hnsw_gpu_search_batch.argtypes = [vp, vp, sz, sz, vp, vp, vp]
     L.hnsw_gpu_search_batch_dev.argtypes = [vp, vp, sz, sz, vp, vp, vp, vp, vp]
     L.hnsw_gpu_search_base_dev.argtypes = [vp, vp, sz, sz, vp, vp, vp, vp, vp]
+    L.hnsw_gpu_index_set_reduced_rows.argtypes = [vp, i32]
+    L.hnsw_gpu_index_reduced_rows.argtypes = [vp]
+    L.hnsw_gpu_search_batch_reduced_dev.argtypes = [vp, i32, vp, sz, sz, vp, vp, vp, vp, vp]
+    L.hnsw_gpu_search_batch_reduced.argtypes = [vp, i32, vp, sz, sz, vp, vp, vp]
+    L.hnsw_gpu_index_export_reduced_rows.argtypes = [vp, vp]
+    L.hnsw_gpu_last_rerank_ms.argtypes = [vp, _f32p]
     L.hnsw_gpu_last_search_ms.argtypes = [vp, _f32p]
     L.hnsw_gpu_search_ms.argtypes = [vp, C.c_uint, _f32p]
     L.hnsw_gpu_last_search_slots.argtypes = [vp, _u32p]

@@ -47,6 +47,7 @@
 #pragma once
 #include <type_traits>
 #include "device_dist.h"
+#include "device_rows16.h"
 
 namespace pgemb {
 
@@ -111,7 +112,9 @@ struct SearchArgs
 	                              // wave w polls copy w % STREAM_COPIES, so that the idle waves of a stream do not all read ONE line of ONE L2 channel
 	uint32_t stream_ring;         // slots of the query / result ring (a power of two): ticket t lives in slot t & (ring - 1)
 	uint32_t stream_light;        // 1 = a stream's results are written with system-scope stores and its completion flag follows vmcnt(0);
-	                              // 0 = plain stores + a full system-scope release per answered query (signal_done)
+	                              // 0 = plain stores + a full system-scope release per answered query (signal_done)	// reduced-row walk (beam kernel with a ShapeR16 shape, device_rows16.h): the 16-bit copy of the rows, uint4 units per row, 256-byte blocks per row
+	const uint4 *rows16;
+	uint32_t rstride4, nblk;
 };
 
 // Abort word + health words of a search workspace.
@@ -1742,6 +1745,17 @@ __device__ __forceinline__ ColdArgs cold_args(const SearchArgs &)
 }
 #endif
 
+// The beam kernel's row scoring: fp32 rows (score_rows_fit), or the 16-bit copy when SH is a reduced-row shape (device_rows16.h)
+template <int FUNC, typename SH, int RPG = SH::RPG, typename RowId>
+__device__ __forceinline__ void beam_score_rows(const SearchArgs &a, const float4 *q4, RowId rowid, uint32_t nrows, float *out, int lane)
+{
+	constexpr int FMT = rows_format_of<SH>::value;
+	if constexpr (FMT == ROWS_F32)
+		score_rows_fit<FUNC, SH::KB, RPG>(a.vec, a.stride, q4, a.nchunks, a.kiters, rowid, nrows, out, lane);
+	else
+		score_rows16_fit<FUNC, FMT, SH::KB, RPG>(a.rows16, a.rstride4, q4, a.nblk, rowid, nrows, out, lane);
+}
+
 template <int FUNC, typename SH, int UREG, bool TEAM = false, bool LEAN = false>
 __global__ __launch_bounds__(TEAM ? 512 : 256, (UREG >= 16 && SH::MIN_WAVES > 2) ? 2 : SH::MIN_WAVES) void hnsw_search_kernel_beam(const SearchArgs a)
 {
@@ -1905,7 +1919,7 @@ __global__ __launch_bounds__(TEAM ? 512 : 256, (UREG >= 16 && SH::MIN_WAVES > 2)
 			const uint32_t ep = c->entry;                                  // hnswalg.cpp:55-65
 			{
 				auto one = [ep](uint32_t) { return ep; };
-				score_rows<FUNC, SH::KB, 1>(a.vec, a.stride, q4, a.nchunks, a.kiters, one, 1u, newdist, lane);
+				beam_score_rows<FUNC, SH, 1>(a, q4, one, 1u, newdist, lane);
 			}
 			wave_sync();
 			const float d0 = finish_dist<FUNC>(newdist[0], newdist[OUT2], qnorm);
@@ -2142,15 +2156,15 @@ __global__ __launch_bounds__(TEAM ? 512 : 256, (UREG >= 16 && SH::MIN_WAVES > 2)
 							}
 						}
 						if (jm == 0)
-							score_rows_fit<FUNC, SH::KB, SH::RPG>(a.vec, a.stride, q4, a.nchunks, a.kiters, by_id, nscore, newdist, lane);
+							beam_score_rows<FUNC, SH>(a, q4, by_id, nscore, newdist, lane);
 						else
 						{
-							score_rows_fit<FUNC, SH::KB, SH::RPG>(a.vec, a.stride, q4, a.nchunks, a.kiters, by_id, PASS, newdist, lane);
+							beam_score_rows<FUNC, SH>(a, q4, by_id, PASS, newdist, lane);
 							const uint32_t covered = PASS + PASS * (uint32_t) __builtin_popcount(jm);   // what I and the slice helpers take; the rest (few helpers) is mine too
 							if (covered < nscore)
 							{
 								auto rest = [ids, covered](uint32_t r) { return ids[covered + r]; };
-								score_rows_fit<FUNC, SH::KB, SH::RPG>(a.vec, a.stride, q4, a.nchunks, a.kiters, rest, nscore - covered, newdist + covered, lane);
+								beam_score_rows<FUNC, SH>(a, q4, rest, nscore - covered, newdist + covered, lane);
 							}
 							uint32_t lo = PASS, ngot = 0;
 							for (uint32_t mm = jm; mm; mm &= mm - 1, lo += PASS)
@@ -2179,7 +2193,7 @@ __global__ __launch_bounds__(TEAM ? 512 : 256, (UREG >= 16 && SH::MIN_WAVES > 2)
 								{
 									{ uint32_t *hw = cold_args(a)->health; if (hw && lane == 0) atomicAdd(hw + HEALTH_SLICE_TIMEOUTS, 1u); }
 									auto part = [ids, lo](uint32_t r) { return ids[lo + r]; };
-									score_rows_fit<FUNC, SH::KB, SH::RPG>(a.vec, a.stride, q4, a.nchunks, a.kiters, part, cnt, newdist + lo, lane);
+									beam_score_rows<FUNC, SH>(a, q4, part, cnt, newdist + lo, lane);
 								}
 							}
 							if (ngot) { uint32_t *hw = cold_args(a)->health; if (hw && lane == 0) atomicAdd(hw + HEALTH_SLICES_DELIVERED, ngot); }

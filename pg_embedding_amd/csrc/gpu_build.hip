@@ -474,9 +474,20 @@ static int insert_impl(hnsw_gpu_index *ix, const coord_t *point, label_t label, 
 	return HNSW_GPU_OK;
 }
 
+// (both insert entry points write row `idx` of the fp32 rows: the reduced copy converts it again before the next reduced search)
+static int insert_marked(hnsw_gpu_index *ix, const coord_t *point, label_t label, idx_t idx, const idx_t *cand_idx, const dist_t *cand_dist,
+						 uint32_t ncand, idx_t *mine, idx_t *others)
+{
+	if (!ix) return insert_impl(ix, point, label, idx, cand_idx, cand_dist, ncand, mine, others);
+	std::unique_lock<std::recursive_mutex> lock_(ix->mu);
+	const int rc = insert_impl(ix, point, label, idx, cand_idx, cand_dist, ncand, mine, others);
+	rows16_mark(ix, idx, (size_t) idx + 1);
+	return rc;
+}
+
 extern "C" int hnsw_gpu_index_insert_one(hnsw_gpu_index *ix, const coord_t *point, label_t label, idx_t idx, idx_t *mine, idx_t *others)
 {
-	return insert_impl(ix, point, label, idx, nullptr, nullptr, 0, mine, others);
+	return insert_marked(ix, point, label, idx, nullptr, nullptr, 0, mine, others);
 }
 
 // The same with the candidate list given: what searchBaseLayer(point, ef = efConstruction) returned on THIS mirror a moment ago
@@ -486,6 +497,6 @@ extern "C" int hnsw_gpu_index_insert_candidates(hnsw_gpu_index *ix, const coord_
 												const dist_t *cand_dist, uint32_t ncand, idx_t *mine, idx_t *others)
 {
 	if (!cand_idx || !cand_dist) return fail(HNSW_GPU_ERR_ARG, "NULL candidate list");
-	return insert_impl(ix, point, label, idx, cand_idx, cand_dist, ncand, mine, others);
+	return insert_marked(ix, point, label, idx, cand_idx, cand_dist, ncand, mine, others);
 }
 

@@ -183,3 +183,16 @@ extern "C" int hnsw_gpu_index_placement(hnsw_gpu_index *ix, uint64_t *out16)
 	memcpy(out16, v, sizeof(v));
 	return HNSW_GPU_OK;
 }
+
+// the re-rank kernel of the last reduced-row search alone (hnsw_gpu_search_batch_reduced_dev): its own event pair (waits for it)
+extern "C" int hnsw_gpu_last_rerank_ms(hnsw_gpu_index *ix, float *ms)
+{
+	std::unique_lock<std::recursive_mutex> lock_;
+	if (ix) lock_ = std::unique_lock<std::recursive_mutex>(ix->mu);
+	if (!ix || !ms) return fail(HNSW_GPU_ERR_ARG, "NULL argument");
+	if (!ix->rr_valid) return fail(HNSW_GPU_ERR_ARG, "no reduced-row search yet");
+	HIPCHK(hipSetDevice(ix->device));
+	HIPCHK(hipEventSynchronize(ix->rr_e1));
+	HIPCHK(hipEventElapsedTime(ms, ix->rr_e0, ix->rr_e1));
+	return HNSW_GPU_OK;
+}

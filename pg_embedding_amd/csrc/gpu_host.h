@@ -151,7 +151,26 @@ struct hnsw_gpu_index
 	hipEvent_t bf_e0 = nullptr, bf_e1 = nullptr;
 	// hnsw_gpu_search_batch, copy path: before the upload / after the last download (hnsw_gpu_last_batch_ms)
 	hipEvent_t hb0 = nullptr, hb1 = nullptr; bool hb_valid = false;
+	// reduced rows (device_rows16.h, hnsw_gpu_index_set_reduced_rows): a 16-bit copy of `vec` in an allocation of its own (the arena's
+	// placement stays as it is), rows16_cap rows of rows16_bytes; rows [dirty_lo, dirty_hi) have been written since their last conversion
+	// and are converted by the next reduced search, on its stream, before its walk
+	int      rows_fmt = 0;            // HNSW_GPU_ROWS_F32 = no copy
+	void    *rows16 = nullptr; size_t rows16_cap = 0; uint32_t rows16_bytes = 0;
+	size_t   dirty_lo = 0, dirty_hi = 0;
+	// per-launch scratch of the reduced search: the walk's element numbers (grow-only)
+	uint32_t *rr_cand = nullptr; size_t rr_bytes = 0;
+	hipEvent_t rr_e0 = nullptr, rr_e1 = nullptr; bool rr_valid = false;    // around the last re-rank kernel (hnsw_gpu_last_rerank_ms)
 };
+
+// rows [lo, hi) of `vec` were (or are about to be) written: the reduced copy, if any, converts them again before the next reduced search
+static inline void rows16_mark(hnsw_gpu_index *ix, size_t lo, size_t hi)
+{
+	if (!ix->rows_fmt || lo >= hi) return;
+	if (ix->dirty_lo >= ix->dirty_hi) { ix->dirty_lo = lo; ix->dirty_hi = hi; return; }
+	ix->dirty_lo = std::min(ix->dirty_lo, lo);
+	ix->dirty_hi = std::max(ix->dirty_hi, hi);
+}
+int rows16_sync(hnsw_gpu_index *ix, hipStream_t stream);
 
 int ensure_scratch(hnsw_gpu_index *ix, size_t bytes);
 int import_range(hnsw_gpu_index *ix, const void *elements, size_t first, size_t count, size_t n_total);
@@ -159,7 +178,8 @@ int import_range(hnsw_gpu_index *ix, const void *elements, size_t first, size_t 
 // ---- search (gpu_search.hip) ----------------------------------------------------------------------
 static const size_t LDS_PER_CU = 160 * 1024;
 int launch_search(hnsw_gpu_index *ix, SearchWs *w, const float *d_queries, size_t q_stride, size_t nq, size_t ef, int mode,
-				  uint64_t *d_labels, uint32_t *d_idx, float *d_dists, uint32_t *d_counts, uint32_t *d_stats, hipStream_t stream);
+				  uint64_t *d_labels, uint32_t *d_idx, float *d_dists, uint32_t *d_counts, uint32_t *d_stats, hipStream_t stream,
+				  int rows = 0);          // rows: HNSW_GPU_ROWS_F16 / _BF16 = walk over the reduced copy (mode 1 only; hnsw_gpu_search_batch_reduced_dev)
 int poll_limit_s();
 int poll_done_flag(const volatile uint32_t *flag, const char *what, SearchWs *w);
 int ws_search_ms(int device, SearchWs *w, unsigned back, float *ms);

@@ -23,6 +23,28 @@ static search_kernel_t pick_search_kernel(int func, uint32_t kiters, int rreg, b
 	}
 }
 
+static search_kernel_t pick_rows16_kernel(int func, uint32_t kiters, int rreg, int fmt)
+{
+	switch (shape_index(kiters))
+	{
+		case 0:  return pick_rows16_kernel_shape2x4(func, rreg, fmt);
+		case 1:  return pick_rows16_kernel_shape4x2(func, rreg, fmt);
+		case 2:  return pick_rows16_kernel_shape8x2(func, rreg, fmt);
+		default: return pick_rows16_kernel_shape12x2(func, rreg, fmt);
+	}
+}
+
+static rerank_kernel_t pick_rerank_kernel(int func, uint32_t kiters)
+{
+	switch (shape_index(kiters))
+	{
+		case 0:  return pick_rerank_kernel_shape2x4(func);
+		case 1:  return pick_rerank_kernel_shape4x2(func);
+		case 2:  return pick_rerank_kernel_shape8x2(func);
+		default: return pick_rerank_kernel_shape12x2(func);
+	}
+}
+
 static const size_t VIS_BUDGET_BYTES = (size_t) 24 << 30;     // cap on bitmap workspace
 static const size_t SET_BUDGET_BYTES = (size_t) 8 << 30;      // cap on the HBM result/candidate areas (generic form)
 // (no cap on the effective beam: beyond WIDE_EF_MIN the wide-beam form keeps both sets with a second level of chunk extremes,
@@ -31,7 +53,7 @@ static const size_t WIDE_EF_MIN = 2048;
 
 int launch_search(hnsw_gpu_index *ix, SearchWs *w, const float *d_queries, size_t q_stride, size_t nq, size_t ef, int mode,
 						 uint64_t *d_labels, uint32_t *d_idx, float *d_dists, uint32_t *d_counts,
-						 uint32_t *d_stats, hipStream_t stream)
+						 uint32_t *d_stats, hipStream_t stream, int rows)
 {
 	std::unique_lock<std::recursive_mutex> lock_;
 	if (ix) lock_ = std::unique_lock<std::recursive_mutex>(ix->mu);
@@ -98,15 +120,36 @@ int launch_search(hnsw_gpu_index *ix, SearchWs *w, const float *d_queries, size_
 #else
 	else rreg = 0;                                           // HNSW_GPU_BEAM=0, or a mirror of >= 2^31 elements: the generic form
 #endif
+	// Reduced-row walk (device_rows16.h; hnsw_gpu_search_batch_reduced_dev): the one-wave beam form only — no team, no narrow-row or
+	// LEAN kernels, no wide-beam / generic forms, no reference-order arithmetic, no streams or traces.  Refused here, before anything is
+	// launched or allocated.
+	if (rows)
+	{
+		if (mode != 1 || !ix->rows16 || ix->rows_fmt != rows) return fail(HNSW_GPU_ERR_INTERNAL, "reduced-row walk without its copy");
+		if (reforder) return fail(HNSW_GPU_ERR_ARG, "reduced rows: HNSW_GPU_REF_ORDER=1 has no reduced-row kernels");
+		if (rreg >= 0)
+			return fail(HNSW_GPU_ERR_ARG, "reduced rows: ef %zu needs a form the reduced-row walk does not have (the beam form: ef <= 256, "
+						"<= 512 on rows wider than 256 floats; not with HNSW_GPU_BEAM=0 or HNSW_GPU_FORCE_LDS_HEAPS=1)", ef);
+		if (w->stream_host_next || w->pops_next || w->evals_next || w->times_next || w->done_next)
+			return fail(HNSW_GPU_ERR_ARG, "reduced rows: no streams, traces or completion flags");
+		if (!pick_rows16_kernel(func_code, a.kiters, rreg, rows)) return fail(HNSW_GPU_ERR_ARG, "reduced rows: no kernel for %d set registers at this width", -rreg);
+	}
 	const size_t ucap = rreg < 0 ? (size_t) 64 * (size_t) -rreg : 0;      // beam form: slots of the accepted set
 	// Team form wanted for this launch?  (decided for good further down, once the LDS carve is known)
 	const int treq = (int) knob(K_TEAM, -1);
 	const size_t auto_nq = (size_t) knob(K_TEAM_MAX_NQ, (long long) ix->num_cu);
 	const bool stream_launch = w->stream_host_next != nullptr;
-	const bool team_wanted = rreg < 0 && !reforder && (stream_launch || (treq != 0 && (treq > 0 || ix->stride > 320 || nq <= auto_nq)));
+	const bool team_wanted = rreg < 0 && !reforder && !rows && (stream_launch || (treq != 0 && (treq > 0 || ix->stride > 320 || nq <= auto_nq)));
 	// narrow rows, hot form: beam kernel with <= 4 set registers, one sum per row (L2 / Manhattan), not a team
 	const bool narrow5 = shape_index(a.kiters) == 0 && (rreg == -2 || rreg == -4) && (int) ix->meta.dist_func != F_COSINE &&
-						 !team_wanted && !reforder && knob(K_NARROW5, 1) != 0;
+						 !team_wanted && !reforder && !rows && knob(K_NARROW5, 1) != 0;
+	if (rows)
+	{
+		// the query image covers round_up(blocks, KB) * 2 chunk-steps of the reduced shape (the same as the fp32 shape's for every width)
+		const uint32_t nblk = rows16_blocks(a.kiters), kb = rows16_shape_kb(shape_index(a.kiters));
+		a.qpad_floats = std::max<uint32_t>(a.qpad_floats, (nblk + kb - 1) / kb * kb * 128);
+		a.rows16 = (const uint4 *) ix->rows16; a.nblk = nblk; a.rstride4 = ix->rows16_bytes / 16;
+	}
 	size_t off = (size_t) a.qpad_floats * 4;
 	// reference-order arithmetic: the per-wave stage of its transposed accumulation sits right behind the query image (device_dist.h, score_rows_ref)
 	if (reforder) off += (size_t) 8 * (func_code == F_COSINE_REF ? 2 : 1) * REF_STAGE_ROW * 4;
@@ -256,7 +299,7 @@ int launch_search(hnsw_gpu_index *ix, SearchWs *w, const float *d_queries, size_
 	a.off_ctl = (uint32_t) ((size_t) wpb * a.wave_bytes);
 	const size_t lds = (size_t) wpb * a.wave_bytes + (team ? wpb * sizeof(TeamCtl) : 0);
 	const bool lean = narrow5 && !team && !w->pops_next && !w->evals_next && !w->times_next && knob(K_LEAN, 1) != 0;
-	search_kernel_t kern = pick_search_kernel(func_code, a.kiters, rreg, team, narrow5, lean);
+	search_kernel_t kern = rows ? pick_rows16_kernel(func_code, a.kiters, rreg, rows) : pick_search_kernel(func_code, a.kiters, rreg, team, narrow5, lean);
 	if (!kern) return fail(HNSW_GPU_ERR_INTERNAL, "no kernel for this configuration");
 	{
 		static const char *const shapes[4] = { "Shape2x4", "Shape4x2", "Shape8x2", "Shape12x2" };
@@ -265,7 +308,9 @@ int launch_search(hnsw_gpu_index *ix, SearchWs *w, const float *d_queries, size_
 		if (shape_index(a.kiters) == 3 && knob(K_SHAPE_12X1, 0)) shp = "Shape12x1";
 #endif
 		if (narrow5 && !team) shp = "Shape2x2";
-		if (rreg < 0) snprintf(w->kname, sizeof(w->kname), "pgemb::hnsw_search_kernel_beam<%d, pgemb::%s, %d, %s, %s>", func_code, shp, -rreg, team ? "true" : "false", lean ? "true" : "false");
+		static const char *const rshapes[4] = { "1, 4, 4", "2, 4, 4", "4, 2, 4", "6, 2, 2" };
+		if (rows) snprintf(w->kname, sizeof(w->kname), "pgemb::hnsw_search_kernel_beam<%d, pgemb::ShapeR16<%d, %s>, %d, false, false>", func_code, rows, rshapes[shape_index(a.kiters)], -rreg);
+		else if (rreg < 0) snprintf(w->kname, sizeof(w->kname), "pgemb::hnsw_search_kernel_beam<%d, pgemb::%s, %d, %s, %s>", func_code, shp, -rreg, team ? "true" : "false", lean ? "true" : "false");
 		else if (rreg == 3) snprintf(w->kname, sizeof(w->kname), "pgemb::hnsw_search_kernel_wide<%d, pgemb::%s>", (int) ix->meta.dist_func, shp);
 		else if (rreg >= 2) snprintf(w->kname, sizeof(w->kname), "pgemb::hnsw_search_kernel_reg<%d, pgemb::%s, %d>", (int) ix->meta.dist_func, shp, rreg);
 		else snprintf(w->kname, sizeof(w->kname), "pgemb::hnsw_search_kernel_lds<%d, pgemb::%s, %s>", (int) ix->meta.dist_func, shp, rreg == 1 ? "true" : "false");
@@ -409,6 +454,128 @@ extern "C" int hnsw_gpu_search_base_dev(hnsw_gpu_index *ix, const coord_t *d_que
 										void *stream)
 {
 	return launch_search(ix, ix ? &ix->ws : nullptr, d_queries, ix ? ix->meta.dim : 0, nq, ef, 1, nullptr, d_idx, d_dists, d_counts, d_stats, (hipStream_t) stream);
+}
+
+// Reduced-row search (device_rows16.h, device_rerank.h): the walk over the 16-bit copy in base mode into the mirror's scratch, then the
+// exact re-rank against the fp32 rows into the caller's buffers.  Every refusal comes before anything is launched (the outputs are
+// untouched).  d_stats: the walk's evaluations and hops (the re-rank's <= ef row evaluations are not counted); the event pair of
+// hnsw_gpu_last_search_ms spans both kernels.
+// the walk form a reduced search of this ef would take, as launch_search decides it (which refuses the same cases again): 0 = the
+// one-wave beam form has it, else the error code with its message
+static int reduced_form_check(hnsw_gpu_index *ix, int format, size_t ef)
+{
+	knobs_init();
+	const size_t efc = std::min(ef, std::max<size_t>(ix->n, 1));
+	const uint32_t kiters = (ix->stride / 4 + 15) / 16;
+	if (knob(K_REF_ORDER, 0) > 0) return fail(HNSW_GPU_ERR_ARG, "reduced rows: HNSW_GPU_REF_ORDER=1 has no reduced-row kernels");
+	const bool use_beam = knob(K_BEAM, 1) != 0 && ix->cap < 0x80000000ull && knob(K_FORCE_LDS_HEAPS, 0) <= 0;
+	const bool beam16 = efc > 256 && efc <= 512 && (knob_is_set(K_BEAM16) ? knob(K_BEAM16, 0) > 0 : shape_index(kiters) >= 2);
+	if (!use_beam || !(efc <= 256 || beam16))
+		return fail(HNSW_GPU_ERR_ARG, "reduced rows: ef %zu needs a form the reduced-row walk does not have (the beam form: ef <= 256, "
+					"<= 512 on rows wider than 256 floats; not with HNSW_GPU_BEAM=0 or HNSW_GPU_FORCE_LDS_HEAPS=1)", ef);
+	const int rreg = efc <= 64 ? -2 : (efc <= 128 ? -4 : (efc <= 256 ? -8 : -16));
+	if (!pick_rows16_kernel((int) ix->meta.dist_func, kiters, rreg, format))
+		return fail(HNSW_GPU_ERR_ARG, "reduced rows: no kernel for %d set registers at this width", -rreg);
+	return HNSW_GPU_OK;
+}
+
+extern "C" int hnsw_gpu_search_batch_reduced_dev(hnsw_gpu_index *ix, int format, const coord_t *d_queries, size_t nq, size_t ef,
+												 label_t *d_labels, dist_t *d_dists, uint32_t *d_counts, uint32_t *d_stats, void *stream)
+{
+	std::unique_lock<std::recursive_mutex> lock_;
+	if (ix) lock_ = std::unique_lock<std::recursive_mutex>(ix->mu);
+	if (!ix) return fail(HNSW_GPU_ERR_ARG, "index is NULL");
+	if (format != ROWS_F16 && format != ROWS_BF16) return fail(HNSW_GPU_ERR_ARG, "reduced rows: format %d is not a 16-bit format", format);
+	if (ix->rows_fmt != format)
+		return fail(HNSW_GPU_ERR_ARG, "reduced rows: format %d is not enabled on this index (it holds %d; hnsw_gpu_index_set_reduced_rows)", format, ix->rows_fmt);
+	if (nq == 0) return HNSW_GPU_OK;
+	if (!d_queries || !d_labels || !d_counts) return fail(HNSW_GPU_ERR_ARG, "NULL buffer");
+	if (ef == 0 || ef >= 0xFFFFFFFFull) return fail(HNSW_GPU_ERR_ARG, "ef %zu out of range", ef);
+	if (nq >= 0xFFFFFFFFull) return fail(HNSW_GPU_ERR_ARG, "too many queries");
+	const int func = (int) ix->meta.dist_func;
+	const uint32_t nchunks = ix->stride / 4, kiters = (nchunks + 15) / 16;
+	const rerank_kernel_t rk = pick_rerank_kernel(func, kiters);
+	if (!rk) return fail(HNSW_GPU_ERR_ARG, "reduced rows: unknown distance function %d", func);
+	// re-rank LDS per wave: [query image | 2 x 64 sums | ef distance keys | ef labels]
+	RerankArgs r;
+	memset(&r, 0, sizeof(r));
+	r.qpad_floats = (uint32_t) round_up(kiters, shape_kb(shape_index(kiters))) * 64;
+	r.off_lab = (uint32_t) round_up(((size_t) r.qpad_floats + 2 * OUT2) * 4 + ef * 4, 16);
+	r.wave_bytes = (uint32_t) round_up((size_t) r.off_lab + ef * 8, 16);
+	uint32_t wpb = 4;
+	while (wpb > 1 && (size_t) wpb * r.wave_bytes > 64 * 1024) wpb >>= 1;
+	if ((size_t) wpb * r.wave_bytes > 64 * 1024) return fail(HNSW_GPU_ERR_ARG, "reduced rows: ef %zu needs too much LDS for the re-rank", ef);
+	if (int rc0 = reduced_form_check(ix, format, ef)) return rc0;
+	HIPCHK(hipSetDevice(ix->device));
+	hipStream_t s = (hipStream_t) stream;
+	// the walk's candidates: nq * ef element numbers (grow-only scratch of the mirror; a new allocation waits for the old one's users)
+	const size_t cb = nq * ef * 4;
+	if (cb > ix->rr_bytes)
+	{
+		if (ix->rr_cand) { HIPCHK(hipDeviceSynchronize()); (void) hipFree(ix->rr_cand); }
+		ix->rr_cand = nullptr; ix->rr_bytes = 0;
+		HIPCHK(hipMalloc(&ix->rr_cand, cb));
+		ix->rr_bytes = cb;
+	}
+	int rc = rows16_sync(ix, s);
+	if (rc) return rc;
+	rc = launch_search(ix, &ix->ws, d_queries, ix->meta.dim, nq, ef, 1, nullptr, ix->rr_cand, nullptr, d_counts, d_stats, s, format);
+	if (rc) return rc;
+	r.vec = ix->vec; r.labels = ix->labels;
+	r.stride = ix->stride; r.nchunks = nchunks; r.kiters = kiters; r.dim = (uint32_t) ix->meta.dim;
+	r.queries = d_queries; r.q_stride = (uint32_t) ix->meta.dim; r.nq = (uint32_t) nq; r.out_stride = (uint32_t) ef;
+	r.cand = ix->rr_cand; r.out_labels = d_labels; r.out_dists = d_dists; r.counts = d_counts;
+	const size_t lds = (size_t) wpb * r.wave_bytes;
+	if (lds > 48 * 1024) HIPCHK(hipFuncSetAttribute((const void *) rk, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
+	if (!ix->rr_e0) { HIPCHK(hipEventCreate(&ix->rr_e0)); HIPCHK(hipEventCreate(&ix->rr_e1)); }
+	ix->rr_valid = false;
+	HIPCHK(hipEventRecord(ix->rr_e0, s));
+	hipLaunchKernelGGL(rk, dim3((uint32_t) ((nq + wpb - 1) / wpb)), dim3(wpb * 64), lds, s, r);
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipEventRecord(ix->rr_e1, s));
+	ix->rr_valid = true;
+	{
+		SearchWs *w = &ix->ws;                                  // the walk's event pair now ends behind the re-rank
+		const int evi = (int) ((w->launches - 1) % SearchWs::EV_RING);
+		HIPCHK(hipEventRecord(w->ev1[evi], s));
+	}
+	return HNSW_GPU_OK;
+}
+
+extern "C" int hnsw_gpu_search_batch_reduced(hnsw_gpu_index *ix, int format, const coord_t *queries, size_t nq, size_t ef,
+											 label_t *labels, dist_t *dists, uint32_t *counts)
+{
+	std::unique_lock<std::recursive_mutex> lock_;
+	if (ix) lock_ = std::unique_lock<std::recursive_mutex>(ix->mu);
+	if (!ix) return fail(HNSW_GPU_ERR_ARG, "index is NULL");
+	if (format != ROWS_F16 && format != ROWS_BF16) return fail(HNSW_GPU_ERR_ARG, "reduced rows: format %d is not a 16-bit format", format);
+	if (ix->rows_fmt != format)
+		return fail(HNSW_GPU_ERR_ARG, "reduced rows: format %d is not enabled on this index (it holds %d; hnsw_gpu_index_set_reduced_rows)", format, ix->rows_fmt);
+	if (nq == 0) return HNSW_GPU_OK;
+	if (!queries || !labels || !counts) return fail(HNSW_GPU_ERR_ARG, "NULL buffer");
+	if (ef == 0 || ef >= 0xFFFFFFFFull) return fail(HNSW_GPU_ERR_ARG, "ef %zu out of range", ef);
+	if (int rc0 = reduced_form_check(ix, format, ef)) return rc0;
+	HIPCHK(hipSetDevice(ix->device));
+	const size_t dim = ix->meta.dim;
+	const size_t qb = round_up(nq * dim * 4, 256), lb = round_up(nq * ef * 8, 256), db = round_up(nq * ef * 4, 256), cb = round_up(nq * 4, 256);
+	int rc = ensure_scratch(ix, qb + lb + db + cb);
+	if (rc) return rc;
+	char *p = (char *) ix->scratch;
+	float *dq = (float *) p; uint64_t *dl = (uint64_t *) (p + qb); float *dd = (float *) (p + qb + lb);
+	uint32_t *dc = (uint32_t *) (p + qb + lb + db);
+	HIPCHK(hipMemcpy(dq, queries, nq * dim * 4, hipMemcpyHostToDevice));
+	rc = hnsw_gpu_search_batch_reduced_dev(ix, format, dq, nq, ef, dl, dd, dc, nullptr, nullptr);
+	if (rc) return rc;
+	// (the outputs are filled only when every query has its result)
+	std::vector<uint32_t> c(nq);
+	HIPCHK(hipMemcpy(c.data(), dc, nq * 4, hipMemcpyDeviceToHost));
+	for (size_t i = 0; i < nq; i++)
+		if (c[i] == ABORTED_COUNT)
+			return fail(HNSW_GPU_ERR_INTERNAL, "the search launch was asked to end early (abort word): query %zu has no result", i);
+	HIPCHK(hipMemcpy(labels, dl, nq * ef * 8, hipMemcpyDeviceToHost));
+	if (dists) HIPCHK(hipMemcpy(dists, dd, nq * ef * 4, hipMemcpyDeviceToHost));
+	memcpy(counts, c.data(), nq * 4);
+	return HNSW_GPU_OK;
 }
 
 // Poll a completion flag the kernel stores into pinned host memory.  0 = set; otherwise an error: the kernel ended

@@ -345,6 +345,10 @@ extern "C" void hnsw_gpu_index_destroy(hnsw_gpu_index *ix)
 	if (ix->bf_e1) (void) hipEventDestroy(ix->bf_e1);
 	if (ix->hb0) (void) hipEventDestroy(ix->hb0);
 	if (ix->hb1) (void) hipEventDestroy(ix->hb1);
+	if (ix->rows16) (void) hipFree(ix->rows16);
+	if (ix->rr_cand) (void) hipFree(ix->rr_cand);
+	if (ix->rr_e0) (void) hipEventDestroy(ix->rr_e0);
+	if (ix->rr_e1) (void) hipEventDestroy(ix->rr_e1);
 	delete ix;
 }
 
@@ -452,6 +456,7 @@ int import_range(hnsw_gpu_index *ix, const void *elements, size_t first, size_t 
 	const size_t per = std::max<size_t>(1, STAGE_BYTES / esz);
 	uint32_t *bad = ix->misc;
 	if (count == 0) return HNSW_GPU_OK;
+	rows16_mark(ix, first, first + count);
 	HIPCHK(hipMemset(bad, 0, 4));
 	const size_t nbuf = count > per ? 2 : 1;
 	const size_t buf_bytes = round_up(std::min(per, count) * esz, 256);
@@ -550,6 +555,7 @@ extern "C" int hnsw_gpu_index_append_dev(hnsw_gpu_index *ix, const coord_t *d_ve
 	if (!d_vectors) return fail(HNSW_GPU_ERR_ARG, "vectors is NULL");
 	if (ix->n + n > ix->cap) return fail(HNSW_GPU_ERR_ARG, "append exceeds capacity (%zu + %zu > %zu)", ix->n, n, ix->cap);
 	HIPCHK(hipSetDevice(ix->device));
+	rows16_mark(ix, ix->n, ix->n + n);
 	const uint32_t blocks = (uint32_t) ((n + 3) / 4);
 	hipLaunchKernelGGL(append_rows_kernel, dim3(blocks), dim3(256), 0, (hipStream_t) stream, d_vectors, d_labels,
 					   (uint32_t) ix->n, (uint32_t) n, (uint32_t) ix->meta.dim, ix->stride, ix->lstride, ix->vec,
@@ -698,6 +704,93 @@ extern "C" int hnsw_gpu_index_update_from_flat(hnsw_gpu_index *ix, const void *e
 	if (rc) return rc;
 	ix->n = n_total;
 	ix->xnorm_n = 0;            // cached row norms are stale
+	return HNSW_GPU_OK;
+}
+
+// ------------------------------------------------------------------------------------
+// reduced rows: a 16-bit copy of the rows for hnsw_gpu_search_batch_reduced_dev (device_rows16.h)
+// ------------------------------------------------------------------------------------
+// Bring the copy up to date on `stream`: (re)allocate it when the mirror's capacity grew (reserve), then convert the rows written since
+// the last conversion.  The conversion reads `vec` on the stream of the search that needs it, so it is ordered against the writers
+// exactly as that search's own reads of `vec` would be.
+int rows16_sync(hnsw_gpu_index *ix, hipStream_t stream)
+{
+	if (!ix->rows_fmt) return HNSW_GPU_OK;
+	if (ix->rows16_cap < ix->cap)
+	{
+		if (ix->rows16) { HIPCHK(hipDeviceSynchronize()); (void) hipFree(ix->rows16); }
+		ix->rows16 = nullptr; ix->rows16_cap = 0;
+		const hipError_t e = hipMalloc(&ix->rows16, ix->cap * (size_t) ix->rows16_bytes);
+		if (e != hipSuccess)
+		{
+			ix->rows16 = nullptr; ix->rows_fmt = 0; ix->dirty_lo = ix->dirty_hi = 0;
+			(void) hipGetLastError();
+			return fail(HNSW_GPU_ERR_NOMEM, "reduced rows: cannot allocate %zu bytes: %s (the copy is dropped)", ix->cap * (size_t) ix->rows16_bytes, hipGetErrorString(e));
+		}
+		ix->rows16_cap = ix->cap;
+		ix->dirty_lo = 0; ix->dirty_hi = ix->n;
+	}
+	const size_t lo = ix->dirty_lo, hi = std::min(ix->dirty_hi, ix->n);
+	ix->dirty_lo = ix->dirty_hi = 0;
+	if (lo >= hi) return HNSW_GPU_OK;
+	const uint32_t nchunks = ix->stride / 4, nblk = rows16_blocks((nchunks + 15) / 16);
+	const size_t threads = (hi - lo) * nblk * 16;
+	const dim3 grid((uint32_t) ((threads + 255) / 256));
+	if (ix->rows_fmt == ROWS_BF16)
+		hipLaunchKernelGGL(rows16_convert_kernel<ROWS_BF16>, grid, dim3(256), 0, stream, ix->vec, ix->stride, nchunks, nblk, lo, hi - lo, (uint4 *) ix->rows16);
+	else
+		hipLaunchKernelGGL(rows16_convert_kernel<ROWS_F16>, grid, dim3(256), 0, stream, ix->vec, ix->stride, nchunks, nblk, lo, hi - lo, (uint4 *) ix->rows16);
+	HIPCHK(hipGetLastError());
+	return HNSW_GPU_OK;
+}
+
+extern "C" int hnsw_gpu_index_set_reduced_rows(hnsw_gpu_index *ix, int format)
+{
+	std::unique_lock<std::recursive_mutex> lock_;
+	if (ix) lock_ = std::unique_lock<std::recursive_mutex>(ix->mu);
+	if (!ix) return fail(HNSW_GPU_ERR_ARG, "index is NULL");
+	if (format != ROWS_F32 && format != ROWS_F16 && format != ROWS_BF16) return fail(HNSW_GPU_ERR_ARG, "unknown reduced-row format %d", format);
+	HIPCHK(hipSetDevice(ix->device));
+	if (format != ix->rows_fmt && ix->rows16)
+	{
+		HIPCHK(hipDeviceSynchronize());                      // (a reduced search in flight may still read the old copy)
+		(void) hipFree(ix->rows16);
+		ix->rows16 = nullptr; ix->rows16_cap = 0;
+	}
+	ix->rows_fmt = format;
+	ix->dirty_lo = ix->dirty_hi = 0;
+	if (format == ROWS_F32) return HNSW_GPU_OK;
+	const uint32_t nchunks = ix->stride / 4;
+	ix->rows16_bytes = rows16_blocks((nchunks + 15) / 16) * 256u;
+	if (ix->rows16) ix->dirty_hi = ix->n, ix->dirty_lo = 0;                // same format again: convert everything anew
+	int rc = rows16_sync(ix, nullptr);
+	if (rc) return rc;
+	HIPCHK(hipStreamSynchronize(nullptr));
+	return HNSW_GPU_OK;
+}
+
+extern "C" int hnsw_gpu_index_reduced_rows(const hnsw_gpu_index *ix) { return ix ? ix->rows_fmt : ROWS_F32; }
+
+extern "C" int hnsw_gpu_index_export_reduced_rows(hnsw_gpu_index *ix, uint16_t *out)
+{
+	std::unique_lock<std::recursive_mutex> lock_;
+	if (ix) lock_ = std::unique_lock<std::recursive_mutex>(ix->mu);
+	if (!ix || !out) return fail(HNSW_GPU_ERR_ARG, "NULL argument");
+	if (!ix->rows_fmt) return fail(HNSW_GPU_ERR_ARG, "this index has no reduced rows (hnsw_gpu_index_set_reduced_rows)");
+	HIPCHK(hipSetDevice(ix->device));
+	int rc = rows16_sync(ix, nullptr);
+	if (rc) return rc;
+	const size_t vals = ix->n * ix->meta.dim;
+	if (vals == 0) return HNSW_GPU_OK;
+	uint16_t *d = nullptr;
+	HIPCHK(hipMalloc(&d, vals * 2));
+	const uint32_t nblk = ix->rows16_bytes / 256;
+	hipLaunchKernelGGL(rows16_export_kernel<0>, dim3((uint32_t) ((vals + 255) / 256)), dim3(256), 0, 0, (const uint16_t *) ix->rows16,
+					   (uint32_t) ix->meta.dim, nblk, ix->n, d);
+	hipError_t e = hipGetLastError();
+	if (e == hipSuccess) e = hipMemcpy(out, d, vals * 2, hipMemcpyDeviceToHost);
+	(void) hipFree(d);
+	if (e != hipSuccess) return fail(HNSW_GPU_ERR_HIP, "reduced rows: download failed: %s", hipGetErrorString(e));
 	return HNSW_GPU_OK;
 }
 

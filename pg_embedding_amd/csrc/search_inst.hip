@@ -7,12 +7,20 @@ namespace pgemb {
 
 #if SEARCH_INST_SHAPE == 1
 search_kernel_t pick_kernel_shape2x4(int func, int rreg, bool team) { return pick_search_kernel_s<Shape2x4>(func, rreg, team); }
+search_kernel_t pick_rows16_kernel_shape2x4(int func, int rreg, int fmt) { return pick_rows16_kernel_s<ShapeR1x4, false>(func, rreg, fmt); }
+rerank_kernel_t pick_rerank_kernel_shape2x4(int func) { return pick_rerank_kernel_s<Shape2x4>(func); }
 #elif SEARCH_INST_SHAPE == 2
 search_kernel_t pick_kernel_shape4x2(int func, int rreg, bool team) { return pick_search_kernel_s<Shape4x2>(func, rreg, team); }
+search_kernel_t pick_rows16_kernel_shape4x2(int func, int rreg, int fmt) { return pick_rows16_kernel_s<ShapeR2x4, false>(func, rreg, fmt); }
+rerank_kernel_t pick_rerank_kernel_shape4x2(int func) { return pick_rerank_kernel_s<Shape4x2>(func); }
 #elif SEARCH_INST_SHAPE == 3
 search_kernel_t pick_kernel_shape8x2(int func, int rreg, bool team) { return pick_search_kernel_s<Shape8x2>(func, rreg, team); }
+search_kernel_t pick_rows16_kernel_shape8x2(int func, int rreg, int fmt) { return pick_rows16_kernel_s<ShapeR4x2, true>(func, rreg, fmt); }
+rerank_kernel_t pick_rerank_kernel_shape8x2(int func) { return pick_rerank_kernel_s<Shape8x2>(func); }
 #elif SEARCH_INST_SHAPE == 4
 search_kernel_t pick_kernel_shape12x2(int func, int rreg, bool team) { return pick_search_kernel_s<Shape12x2>(func, rreg, team); }
+search_kernel_t pick_rows16_kernel_shape12x2(int func, int rreg, int fmt) { return pick_rows16_kernel_s<ShapeR6x2, true>(func, rreg, fmt); }
+rerank_kernel_t pick_rerank_kernel_shape12x2(int func) { return pick_rerank_kernel_s<Shape12x2>(func); }
 #elif SEARCH_INST_SHAPE == 5
 // LEAN = a launch that asked for no pop sequence, no evaluation trace and no clock stamps: those optional outputs (and the abort
 // poll inside the walk; the one between queries stays) cost the issue-bound narrow-row kernel 30 spilled SGPRs in and around its

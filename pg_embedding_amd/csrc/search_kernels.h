@@ -5,10 +5,12 @@
 #include "device_dist.h"
 #include "device_search.h"
 #include "device_search_wide.h"
+#include "device_rerank.h"
 
 namespace pgemb {
 
 typedef void (*search_kernel_t)(const SearchArgs);
+typedef void (*rerank_kernel_t)(const RerankArgs);
 
 // rreg: 0 = generic form, sets in LDS; 1 = generic form, sets in HBM (any ef); 2 / 4 = two-set register form for ef <= 128 / 256
 //       (experiment builds only),
@@ -90,11 +92,61 @@ inline search_kernel_t pick_search_kernel_s(int func, int rreg, bool team)
 }
 
 
+// Reduced-row walk (device_rows16.h): beam form, one wave per query, L2 / cosine / Manhattan in canonical arithmetic, 2 / 4 / 8 / 16 set
+// registers (16 only where the fp32 walk would use them: rows wider than 256 floats); RSH = the reduced-row load shape of the unit.
+template <template <int> class RSH, bool U16>
+inline search_kernel_t pick_rows16_kernel_s(int func, int rreg, int fmt)
+{
+	if (fmt != ROWS_F16 && fmt != ROWS_BF16) return nullptr;
+	const bool bf = fmt == ROWS_BF16;
+#define PGEMB_R16(U) \
+	switch (func) \
+	{ \
+		case F_L2:     return bf ? hnsw_search_kernel_beam<F_L2, RSH<ROWS_BF16>, U, false> : hnsw_search_kernel_beam<F_L2, RSH<ROWS_F16>, U, false>; \
+		case F_COSINE: return bf ? hnsw_search_kernel_beam<F_COSINE, RSH<ROWS_BF16>, U, false> : hnsw_search_kernel_beam<F_COSINE, RSH<ROWS_F16>, U, false>; \
+		case F_MANHATTAN: return bf ? hnsw_search_kernel_beam<F_MANHATTAN, RSH<ROWS_BF16>, U, false> : hnsw_search_kernel_beam<F_MANHATTAN, RSH<ROWS_F16>, U, false>; \
+		default:       return nullptr; \
+	}
+	switch (rreg)
+	{
+		case -2: PGEMB_R16(2)
+		case -4: PGEMB_R16(4)
+		case -8: PGEMB_R16(8)
+		case -16:
+			if constexpr (U16) { PGEMB_R16(16) }
+			return nullptr;
+		default: return nullptr;
+	}
+#undef PGEMB_R16
+}
+
+// exact re-rank of a reduced-row walk against the fp32 rows (device_rerank.h), with the unit's fp32 load shape
+template <typename SH>
+inline rerank_kernel_t pick_rerank_kernel_s(int func)
+{
+	switch (func)
+	{
+		case F_L2:        return rerank_kernel<F_L2, SH>;
+		case F_COSINE:    return rerank_kernel<F_COSINE, SH>;
+		case F_MANHATTAN: return rerank_kernel<F_MANHATTAN, SH>;
+		default:          return nullptr;
+	}
+}
+
 // one function per load shape, each defined in its own translation unit (search_inst.hip)
 search_kernel_t pick_kernel_shape2x4(int func, int rreg, bool team);
 search_kernel_t pick_kernel_shape4x2(int func, int rreg, bool team);
 search_kernel_t pick_kernel_shape8x2(int func, int rreg, bool team);
 search_kernel_t pick_kernel_shape12x2(int func, int rreg, bool team);
+// reduced-row walks and their re-rank, by the same shape index (shape_index(kiters) 0..3 -> the units of Shape2x4 .. Shape12x2)
+search_kernel_t pick_rows16_kernel_shape2x4(int func, int rreg, int fmt);
+search_kernel_t pick_rows16_kernel_shape4x2(int func, int rreg, int fmt);
+search_kernel_t pick_rows16_kernel_shape8x2(int func, int rreg, int fmt);
+search_kernel_t pick_rows16_kernel_shape12x2(int func, int rreg, int fmt);
+rerank_kernel_t pick_rerank_kernel_shape2x4(int func);
+rerank_kernel_t pick_rerank_kernel_shape4x2(int func);
+rerank_kernel_t pick_rerank_kernel_shape8x2(int func);
+rerank_kernel_t pick_rerank_kernel_shape12x2(int func);
 // the hot narrow-row form (rows of <= 128 floats, beam form with 2 / 4 set registers, L2 / Manhattan, one wave per query)
 search_kernel_t pick_kernel_shape2x2(int func, int rreg, bool lean);
 #ifdef HNSW_EXPERIMENT

@@ -19,6 +19,15 @@ OPCLASS = {"ann_l2_ops": DIST_L2, "ann_cos_ops": DIST_COSINE, "ann_manhattan_ops
 DEFAULT_M, DEFAULT_EF_CONSTRUCTION, DEFAULT_EF_SEARCH = 100, 16, 64   # embedding.c:111-113
 LABEL_DELETED = np.uint64(1) << np.uint64(48)          # embedding.c:44,948-953
 NO_LABEL = np.uint64(0xFFFFFFFFFFFFFFFF)
+# reduced rows (include/hnsw_gpu.h HNSW_GPU_ROWS_*): the 16-bit copy a search may walk over before its exact fp32 re-rank
+ROWS_F32, ROWS_F16, ROWS_BF16 = 0, 1, 2
+_ROWS = {None: ROWS_F32, "f32": ROWS_F32, "f16": ROWS_F16, "bf16": ROWS_BF16}
+
+
+def _rows_code(rows) -> int:
+    if rows not in _ROWS:
+        raise ValueError(f"rows must be None, 'f16' or 'bf16', not {rows!r}")
+    return _ROWS[rows]
 
 
 def make_meta(dims: int, m: int = DEFAULT_M, efconstruction: int = DEFAULT_EF_CONSTRUCTION,
@@ -178,18 +187,39 @@ class GpuIndex:
               "hnsw_gpu_index_set_deleted_batch")
 
     # -------------------------------------------------------------------- search
-    def search(self, queries: np.ndarray, ef: Optional[int] = None):
+    def search(self, queries: np.ndarray, ef: Optional[int] = None, rows: Optional[str] = None):
         """Batch of hnsw_search() calls with host buffers.
-        Returns (labels[nq, ef] u64, dists[nq, ef] f32, counts[nq] u32)."""
+        Returns (labels[nq, ef] u64, dists[nq, ef] f32, counts[nq] u32).
+        rows="f16" | "bf16": walk over the reduced copy of the rows (set_reduced_rows), then re-rank exactly in fp32."""
         ef = int(ef or self.meta.efSearch)
+        code = _rows_code(rows)
         queries = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, self.meta.dim)
         nq = queries.shape[0]
         labels = np.empty((nq, ef), np.uint64)
         dists = np.empty((nq, ef), np.float32)
         counts = np.empty(nq, np.uint32)
+        if code:
+            check(self.L.hnsw_gpu_search_batch_reduced(self._h, code, queries.ctypes.data, nq, ef, labels.ctypes.data,
+                                                       dists.ctypes.data, counts.ctypes.data), "hnsw_gpu_search_batch_reduced")
+            return labels, dists, counts
         check(self.L.hnsw_gpu_search_batch(self._h, queries.ctypes.data, nq, ef, labels.ctypes.data,
                                            dists.ctypes.data, counts.ctypes.data), "hnsw_gpu_search_batch")
         return labels, dists, counts
+
+    def set_reduced_rows(self, rows: Optional[str]) -> None:
+        """Build ("f16" / "bf16") or free (None) the 16-bit copy of the rows that search(rows=...) walks over (+50 % of the
+        fp32 row bytes, an allocation of its own).  Writers of the rows keep it current."""
+        check(self.L.hnsw_gpu_index_set_reduced_rows(self._h, _rows_code(rows)), "hnsw_gpu_index_set_reduced_rows")
+
+    def reduced_rows(self) -> Optional[str]:
+        return {ROWS_F32: None, ROWS_F16: "f16", ROWS_BF16: "bf16"}[self.L.hnsw_gpu_index_reduced_rows(self._h)]
+
+    def export_reduced_rows(self) -> np.ndarray:
+        """The reduced copy in natural order: [count, dim] float16 (f16) or uint16 bit patterns (bf16)."""
+        n, dim = self.count, self.meta.dim
+        out = np.empty((n, dim), np.uint16)
+        check(self.L.hnsw_gpu_index_export_reduced_rows(self._h, out.ctypes.data), "hnsw_gpu_index_export_reduced_rows")
+        return out.view(np.float16) if self.reduced_rows() == "f16" else out
 
     def search_trace(self, query: np.ndarray, ef: Optional[int] = None, base: bool = False, pops_cap: int = 1 << 16):
         """One query with its walk (hnsw_gpu_search_trace): (labels-or-element-numbers[count] u64, dists[count] f32,
@@ -230,12 +260,17 @@ class GpuIndex:
         assert have == min(npops.value, pops_cap)
         return labels[:cnt.value], dists[:cnt.value], pops[:have].copy(), int(nev.value), polls
 
-    def search_torch(self, queries, ef: Optional[int] = None, out=None, stats: bool = False, base: bool = False):
+    def search_torch(self, queries, ef: Optional[int] = None, out=None, stats: bool = False, base: bool = False,
+                     rows: Optional[str] = None):
         """Same with everything resident in HBM (torch tensors only carry the pointers).
         `out` may be a dict from a previous call to reuse its buffers.  With base=True runs
-        searchBaseLayer only and returns element numbers under 'idx'."""
+        searchBaseLayer only and returns element numbers under 'idx'.  rows="f16" | "bf16": the reduced-row
+        walk + exact fp32 re-rank (not with base=True: the base walk has no re-rank)."""
         torch = _torch()
         ef = int(ef or self.meta.efSearch)
+        code = _rows_code(rows)
+        if code and base:
+            raise ValueError("rows= cannot be combined with base=True (the base walk has no re-rank)")
         assert queries.is_cuda and queries.dtype == torch.float32 and queries.is_contiguous()
         nq = queries.shape[0]
         dev = queries.device
@@ -253,6 +288,10 @@ class GpuIndex:
             check(self.L.hnsw_gpu_search_base_dev(self._h, queries.data_ptr(), nq, ef, out["idx"].data_ptr(),
                                                   out["dists"].data_ptr(), out["counts"].data_ptr(),
                                                   _dptr(out.get("stats")), s), "hnsw_gpu_search_base_dev")
+        elif code:
+            check(self.L.hnsw_gpu_search_batch_reduced_dev(self._h, code, queries.data_ptr(), nq, ef, out["labels"].data_ptr(),
+                                                           out["dists"].data_ptr(), out["counts"].data_ptr(),
+                                                           _dptr(out.get("stats")), s), "hnsw_gpu_search_batch_reduced_dev")
         else:
             check(self.L.hnsw_gpu_search_batch_dev(self._h, queries.data_ptr(), nq, ef, out["labels"].data_ptr(),
                                                    out["dists"].data_ptr(), out["counts"].data_ptr(),
@@ -264,6 +303,12 @@ class GpuIndex:
         the launch stream around the kernel; the last 64 launches are kept)."""
         ms = C.c_float(0)
         check(self.L.hnsw_gpu_search_ms(self._h, back, C.byref(ms)), "hnsw_gpu_search_ms")
+        return float(ms.value)
+
+    def last_rerank_ms(self) -> float:
+        """the re-rank kernel of the last reduced-row search alone (last_search_ms spans walk + re-rank)"""
+        ms = C.c_float(0)
+        check(self.L.hnsw_gpu_last_rerank_ms(self._h, C.byref(ms)), "hnsw_gpu_last_rerank_ms")
         return float(ms.value)
 
     def last_batch_ms(self):
