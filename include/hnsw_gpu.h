@@ -343,10 +343,13 @@ int hnsw_gpu_bruteforce_dev(hnsw_gpu_index *ix, const coord_t *d_queries, size_t
 							idx_t *d_idx, dist_t *d_dists, void *stream);
 
 /* Same result (exact, same distances), but the Q x N scoring runs as a dense f32 contraction on
- * the matrix cores (v_mfma_f32_32x32x2_f32) used as a filter against a per-query bound; the few
+ * the matrix cores (v_mfma_f32_32x32x2_f32) used as a filter against a per-query bound whose
+ * round-off margin holds for any summation order (D 2^-24 scale, relative to |q|^2 + |x|^2); the
  * survivors are re-scored with the canonical distance code (device_bf_mfma.h).  This is the
- * "batched queries as an MFMA GEMM" form of BASELINE config 5; L2 and cosine only (Manhattan
- * falls back to the scan above).  Synchronises `stream`. */
+ * "batched queries as an MFMA GEMM" form of BASELINE config 5; L2 and cosine only.  The scan above
+ * answers instead for Manhattan, tables under 4096 rows, (dim, k) pairs whose re-score step does not
+ * fit in LDS, and calls where the filter keeps more rows than a query's candidate list holds (16384).
+ * NaN cosine distances (zero rows) are outside the contract.  Synchronises `stream`. */
 int hnsw_gpu_bruteforce_mfma_dev(hnsw_gpu_index *ix, const coord_t *d_queries, size_t nq, size_t k,
 								 idx_t *d_idx, dist_t *d_dists, void *stream);
 /* Device milliseconds of the GEMM/filter kernel of the last call above (MFMA roofline figure:

@@ -61,6 +61,10 @@ int hnsw_gpu_index_placement(hnsw_gpu_index *ix, uint64_t *out16);
  * shader-clock ticks / constant-clock ticks. */
 double hnsw_gpu_last_bruteforce_clock_mhz(void);
 
+/* Rows that passed the MFMA filter of the last hnsw_gpu_bruteforce_mfma_dev call on `ix`, per query: *mean and *max over its
+ * queries (counts past the candidate list's capacity included).  Both 0 when that call did not run the filter. */
+int hnsw_gpu_last_bruteforce_survivors(hnsw_gpu_index *ix, double *mean, uint32_t *max);
+
 /* Practical roof of the search kernel's memory access pattern on THIS mirror's row table: independent
  * waves gathering random whole rows with 16-byte loads, `loads_per_lane` (4/8/12/16/24) in flight per lane,
  * `waves_per_cu` resident waves per CU, `iters` gathers per wave; best of three timed repetitions in GB/s.

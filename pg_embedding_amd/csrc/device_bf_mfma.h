@@ -17,6 +17,25 @@
 // L2 uses |q|^2 + |x|^2 - 2 q.x, cosine 1 - q.x / sqrt(|q|^2 |x|^2) (distfunc.c:133-145);
 // Manhattan is not a contraction and is not offered here.
 //
+// The margin (make_bounds_kernel) must cover the round-off of steps 1 and 2 for EVERY summation order, since neither the canonical code's
+// order nor the MFMA's is the other's.  With u = 2^-24 and D = dim, a sum of D terms in f32 in any order (fma or not) is within
+// g = D u (1 + O(D u)) of the exact sum, relative to the sum of the terms' magnitudes:
+//   L2.  |q|^2, |x|^2 each err by <= g |q|^2, g |x|^2; q.x by <= g sum|q_i x_i| <= g (|q|^2 + |x|^2) / 2.  So the filter's value
+//        |q|^2 + |x|^2 - 2 q.x is within 2 g (|q|^2 + |x|^2) of |q - x|^2, plus a few roundings of the combination: the error scales with
+//        the NORMS, not with the distance (a query equal to a constant row of 1536 floats: |q - x|^2 = 0, error ~1e-4 |q|^2).  The canonical
+//        distance t of a row (a rounded sqrt of D rounded squares) has |q - x|^2 <= t^2 (1 + (D + 10) u).  Hence: pass if
+//            |q|^2 + |x|^2 - 2 q.x <= tau^2 (1 + e1) + eD (|q|^2 + |x|^2) + abs,   e1 = (D + 32) u,  eD = 2 (D + 32) u,
+//        abs = (D + 32) 2^-146 for subnormal terms, whose round-off is absolute (at most 2^-150 per operation).  eD |x|^2 rides in the
+//        per-lane |x|^2 the filter loads anyway (xs2 = (1 - eD) |x|^2), eD |q|^2 in the query's bound; all of it is halved (|q|^2 / 2 +
+//        |x|^2 / 2 - q.x), so two finite norms cannot overflow their sum.
+//   cosine.  |q.x| errs by <= g |q| |x| (Cauchy-Schwarz), sqrt(|q|^2) sqrt(|x|^2) by <= (g + 2u) |q| |x|, so either side's cosine is within
+//        2 g + O(u) of the exact one, and the comparison dot >= (1 - tau - e) sqrt(|q|^2) sqrt(|x|^2) keeps every row within tau for
+//        e = (5 D + 32) u.
+// Non-finite values keep rows, never drop them: the comparisons are written so that NaN passes, a non-finite |x|^2 makes the lane's
+// value NaN, and a non-finite |q|^2 or tau (or a cosine tau >= 1: the canonical product |q|^2 |x|^2 may overflow to a distance of 1)
+// keeps every row for that query.  Data for which the margin passes most rows (thousands of ties at tau, a bound that is inf) overflow
+// a query's candidate list, and the call ends in the canonical scan.
+//
 // Tiling (round 5): block = 4 waves, 128 queries x 128 rows per block (8 waves and 256 x 256 for launches with tiles enough: BfTile below), K in
 // steps of BF_TK floats.  Tiles go from global memory
 // straight into LDS (global_load_lds_dwordx4) in whole 128-byte lines, bank-swizzled on the source side; operands are read with
@@ -82,6 +101,7 @@ struct BfArgs
 	const float *xnorm;        // |x|^2
 	uint32_t nq, n, stride, qstride, ksteps;
 	int func;
+	float xscale;              // L2: (1 - eD) / 2, the filter's |x|^2 factor (make_bounds_kernel: the margin's |x|^2 share, halved)
 	uint32_t *cand;            // [nq][cap]
 	uint32_t *cand_cnt;        // [nq]
 	uint32_t cap;
@@ -149,7 +169,7 @@ __global__ __launch_bounds__(128 * WM, WM == 2 ? 2 : 1) void bf_mfma_filter_kern
 	for (int j = 0; j < NJ; j++)
 	{
 		const float xn = a.xnorm[min(r0 + wn * (32 * NJ) + j * 32 + col, a.n - 1)];
-		xs2[j] = (a.func == F_COSINE) ? __builtin_sqrtf(xn) : xn;
+		xs2[j] = !(xn <= __FLT_MAX__) ? __builtin_nanf("") : (a.func == F_COSINE) ? __builtin_sqrtf(xn) : a.xscale * xn;   // (NaN: always passes)
 	}
 
 	// Tiles go global -> LDS directly (global_load_lds_dwordx4: no staging registers, no ds_write).  The LDS image is what the hardware
@@ -258,11 +278,11 @@ __global__ __launch_bounds__(128 * WM, WM == 2 ? 2 : 1) void bf_mfma_filter_kern
 				{
 					const uint32_t q = q0 + ql + e1;
 					const float dot = acc[i][j][e4 * 4 + e1];
-					bool pass;
+					bool pass;                                            // (written so that a NaN passes)
 					if (a.func == F_COSINE)
-						pass = dot >= qb[e1] * xs2[j];                   // 1 - dot/sqrt(nq nx) <= tau (+margin)
+						pass = !(dot < qb[e1] * xs2[j]);                 // 1 - dot/sqrt(nq nx) <= tau (+margin)
 					else
-						pass = qn[e1] + xs2[j] - 2.f * dot <= qb[e1];    // |q-x|^2 <= tau^2 (+margin)
+						pass = !(qn[e1] + xs2[j] - dot > qb[e1]);        // |q-x|^2 / 2 <= tau^2 / 2 (+margin)
 					if (BF_ABLATE) pass = pass && dot == 12345.678f;      // (timing-only builds compute garbage: keep it out of the lists)
 					if (pass && rok && q < a.nq)
 					{
@@ -313,23 +333,27 @@ __global__ void pad_queries_kernel(const float *__restrict__ q, uint32_t nq, uin
 	out[i] = c < dim ? q[(size_t) r * dim + c] : 0.f;
 }
 
-// tau_q (canonical k-th distance over the sample) -> the filter's comparison value with margin
-__global__ void make_bounds_kernel(const float *__restrict__ tau, const float *__restrict__ qnorm, uint32_t nq, int func,
+// tau_q (canonical k-th distance over the sample) -> the filter's comparison value with margin (derivation: header).  L2 also halves
+// |q|^2 in place: the filter compares |q|^2 / 2 + (1 - eD) |x|^2 / 2 - q.x with the halved bound.
+__global__ void make_bounds_kernel(const float *__restrict__ tau, float *__restrict__ qnorm, uint32_t nq, int func, uint32_t dim,
 								   float *__restrict__ qbound)
 {
 	const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
 	if (q >= nq) return;
-	const float t = tau[q];
+	const float t = tau[q], nqv = qnorm[q];
+	const float d = (float) dim + 32.f, u = 0x1p-24f;
 	if (func == F_COSINE)
 	{
-		// pass if dot >= (1 - tau - eps) * sqrt(nq) * sqrt(nx); eps covers both summation orders
-		qbound[q] = (1.f - t - 2e-5f - 1e-5f * __builtin_fabsf(t)) * __builtin_sqrtf(qnorm[q]);
-		if (!(t == t)) qbound[q] = -__builtin_inff();               // NaN bound: keep everything
+		// pass if dot >= (1 - tau - e) * sqrt(nq) * sqrt(nx)
+		const bool keep_all = !(t < 1.f) || !(t > -__builtin_inff()) || !(nqv <= __FLT_MAX__);     // NaN, +-inf, >= 1; |q|^2 inf or NaN
+		qbound[q] = keep_all ? -__builtin_inff() : (1.f - t - (5.f * (float) dim + 32.f) * u) * __builtin_sqrtf(nqv);
 	}
 	else
 	{
-		// pass if |q|^2 + |x|^2 - 2 dot <= tau^2 (1 + eps) + eps' (|q|^2 + ...): generous
-		qbound[q] = t * t * (1.f + 1e-4f) + 1e-5f * (qnorm[q] + t * t) + 1e-12f;
+		// pass if (|q|^2 + (1 - eD) |x|^2) / 2 - dot <= (tau^2 (1 + e1) + eD |q|^2) / 2 + abs
+		const bool keep_all = !(t <= __FLT_MAX__) || !(nqv <= __FLT_MAX__);
+		qbound[q] = keep_all ? __builtin_inff() : 0.5f * (t * t * (1.f + d * u) + 2.f * d * u * nqv) + d * 0x1p-146f;
+		qnorm[q] = 0.5f * nqv;
 	}
 }
 

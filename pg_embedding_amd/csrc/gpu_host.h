@@ -148,6 +148,7 @@ struct hnsw_gpu_index
 	// exhaustive MFMA scorer: |row|^2 cache + scratch
 	float *xnorm = nullptr; size_t xnorm_n = 0, xnorm_cap = 0;
 	void *bf = nullptr; size_t bf_bytes = 0;
+	size_t bf_cnt_off = 0, bf_cnt_nq = 0;         // where the last call left its per-query candidate counts in `bf` (hnsw_gpu_last_bruteforce_survivors)
 	hipEvent_t bf_e0 = nullptr, bf_e1 = nullptr;
 	// hnsw_gpu_search_batch, copy path: before the upload / after the last download (hnsw_gpu_last_batch_ms)
 	hipEvent_t hb0 = nullptr, hb1 = nullptr; bool hb_valid = false;

@@ -303,6 +303,7 @@ extern "C" int hnsw_gpu_bruteforce_mfma_dev(hnsw_gpu_index *ix, const coord_t *d
 	if (nq == 0) return HNSW_GPU_OK;
 	if (k == 0 || k > 1024) return fail(HNSW_GPU_ERR_ARG, "k %zu out of range [1, 1024]", k);
 	if (nq > 65535) return fail(HNSW_GPU_ERR_ARG, "at most 65535 queries per call");
+	ix->bf_cnt_nq = 0;
 	const int func = (int) ix->meta.dist_func;
 	if (func == F_MANHATTAN || ix->n < 4096)          // not a contraction / too small to matter
 		return hnsw_gpu_bruteforce_dev(ix, d_queries, nq, k, d_idx, d_dists, stream_);
@@ -316,6 +317,11 @@ extern "C" int hnsw_gpu_bruteforce_mfma_dev(hnsw_gpu_index *ix, const coord_t *d
 	hipStream_t s = (hipStream_t) stream_;
 	const uint32_t n = (uint32_t) ix->n, stride = ix->stride, dim = (uint32_t) ix->meta.dim;
 	const uint32_t nchunks = stride / 4, kiters = (nchunks + 15) / 16;
+	// the re-score step holds a query image and a k-list per wave in LDS; where that does not fit, the scan's answer (before any launch)
+	const uint32_t qpadf = (uint32_t) round_up(kiters, 4) * 64;
+	const size_t wave_bytes = round_up((size_t) qpadf * 4 + (k + 1) * 8 + 128 * 4, 16);
+	const size_t lds = wave_bytes * 4;
+	if (lds > 64 * 1024) return hnsw_gpu_bruteforce_dev(ix, d_queries, nq, k, d_idx, d_dists, stream_);
 
 	// |row|^2 cache
 	if (ix->xnorm_cap < ix->n)
@@ -367,15 +373,17 @@ extern "C" int hnsw_gpu_bruteforce_mfma_dev(hnsw_gpu_index *ix, const coord_t *d
 		// reuse make_bounds on a compacted tau array: write tau into `bound` first
 		hipLaunchKernelGGL(fill_u32_kernel, dim3(1), dim3(1), 0, s, overflow, (size_t) 1, 0u);
 		HIPCHK(hipMemcpy2DAsync(bound, 4, sdist + (k - 1), k * 4, 4, nq, hipMemcpyDeviceToDevice, s));
-		hipLaunchKernelGGL(make_bounds_kernel, dim3((uint32_t) ((nq + 255) / 256)), dim3(256), 0, s, bound, qn, (uint32_t) nq, func, bound);
+		hipLaunchKernelGGL(make_bounds_kernel, dim3((uint32_t) ((nq + 255) / 256)), dim3(256), 0, s, bound, qn, (uint32_t) nq, func, dim, bound);
 	}
 	HIPCHK(hipMemsetAsync(cnt, 0, nq * 4, s));
+	ix->bf_cnt_off = o_cnt; ix->bf_cnt_nq = nq;
 
 	// 2. the dense contraction + filter
 	BfArgs a;
 	memset(&a, 0, sizeof(a));
 	a.queries = qpad; a.qnorm = qn; a.qbound = bound; a.vec = ix->vec; a.xnorm = ix->xnorm;
 	a.nq = (uint32_t) nq; a.n = n; a.stride = stride; a.qstride = qstride; a.ksteps = qstride / BF_TK; a.func = func;
+	a.xscale = 0.5f * (1.f - 2.f * ((float) dim + 32.f) * 0x1p-24f);          // (1 - eD) / 2: make_bounds_kernel
 	a.cand = cand; a.cand_cnt = cnt; a.cap = cap; a.clocks = (unsigned long long *) (B + o_clk);
 	HIPCHK(hipMemsetAsync(a.clocks, 0, 16, s));                  // (written only by a block from the middle of the launch that does not exit early: a small table must not leave stale ticks behind)
 	if (!ix->bf_e0) { HIPCHK(hipEventCreate(&ix->bf_e0)); HIPCHK(hipEventCreate(&ix->bf_e1)); }
@@ -398,10 +406,6 @@ extern "C" int hnsw_gpu_bruteforce_mfma_dev(hnsw_gpu_index *ix, const coord_t *d
 	HIPCHK(hipEventRecord(e1, s));
 
 	// 3. canonical re-score of the survivors
-	const uint32_t qpadf = (uint32_t) round_up(kiters, 4) * 64;
-	const size_t wave_bytes = round_up((size_t) qpadf * 4 + (k + 1) * 8 + 128 * 4, 16);
-	const size_t lds = wave_bytes * 4;
-	if (lds > 64 * 1024) return fail(HNSW_GPU_ERR_ARG, "k/dim too large for the rescoring step");
 #define RS_LAUNCH(F)                                                                                                      \
 	hipLaunchKernelGGL(bf_rescore_kernel<F>, dim3((uint32_t) ((nq + 3) / 4)), dim3(256), lds, s, ix->vec, dim, stride,      \
 					   nchunks, kiters, qpadf, d_queries, (uint32_t) nq, cand, cnt, cap, (uint32_t) k, d_idx, d_dists, overflow)
@@ -419,6 +423,21 @@ extern "C" int hnsw_gpu_bruteforce_mfma_dev(hnsw_gpu_index *ix, const coord_t *d
 }
 
 extern "C" int hnsw_gpu_last_bruteforce_tile(void) { return g_last_bf_tile; }
+
+extern "C" int hnsw_gpu_last_bruteforce_survivors(hnsw_gpu_index *ix, double *mean, uint32_t *max)
+{
+	if (!ix || !mean || !max) return fail(HNSW_GPU_ERR_ARG, "NULL argument");
+	std::lock_guard<std::recursive_mutex> lock_(ix->mu);
+	*mean = 0.0; *max = 0;
+	if (!ix->bf || !ix->bf_cnt_nq) return HNSW_GPU_OK;
+	std::vector<uint32_t> c(ix->bf_cnt_nq);
+	HIPCHK(hipSetDevice(ix->device));
+	HIPCHK(hipMemcpy(c.data(), (char *) ix->bf + ix->bf_cnt_off, c.size() * 4, hipMemcpyDeviceToHost));
+	double sum = 0.0;
+	for (uint32_t v : c) { sum += v; *max = std::max(*max, v); }
+	*mean = sum / (double) c.size();
+	return HNSW_GPU_OK;
+}
 
 /* device time of the MFMA filter kernel of the most recent hnsw_gpu_bruteforce_mfma_dev call */
 extern "C" float hnsw_gpu_last_bruteforce_gemm_ms(void) { return g_last_bf_gemm_ms; }
