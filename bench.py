@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — queries/sec of the HNSW search hot path on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 A "step" is one pass of the hot path over one batch of `--nq` (default 40 000) synthetic queries
 (already resident in HBM): the fused searchBaseLayer/searchKnn kernel over an HBM-resident index.
@@ -17,11 +17,15 @@ the index and its own query batch (queries are the independent units; no data-pa
 scaling.  --mode sharded (BASELINE config C4): the rows are partitioned over the ranks, every rank
 searches every query on its shard, ONE packed all-gather + the device merge kernel -> strong scaling.
 
-Prints ONE JSON line on rank 0 (see the contract in the task description) with two extra
+A plain run does only what the headline needs: it builds the index and the queries, warms up, times the --steps steps, writes
+--dump-outputs and prints ONE JSON line on rank 0 (metric, value, unit, ms_per_step, higher_is_better, dtype, the workload).
+--full runs every other leg as well and prints the long record: the headline line then carries two extra
 objects: "roofline" (dominant kernel vs the HBM roof from HIP events on the kernel's own stream: algorithmic bytes over
 the nominal peak, the REPLAY of the launch's own row trace as the roof the kernel cannot beat, the share of its reads no
 cache can hold, and the same on a cache-hostile table: roofline.hbm_only) and "cpu_baseline" (the reference's CPU path on the same graph bytes, bounded sample,
-host cores of this box, with every id mismatch against the reference classified).
+host cores of this box, with every id mismatch against the reference classified).  The recall gate of the metric, the smaller and
+one-query launches, the other configurations and the multi-GPU extras are --full legs too.  The timed steps and their inputs are
+the same in both forms.
 """
 from __future__ import annotations
 
@@ -52,6 +56,12 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the headline (recall gate, smaller launches, one-query latency, roofs and traces, "
+                         "host-pointer form, CPU baseline, cache-hostile table, serial-vs-batched build, other configs, multi-GPU "
+                         "extras) and print the long record; without it the run sets up, warms up, times --steps, writes "
+                         "--dump-outputs and prints the headline line, nothing else.  The --no-* / --nq-small / --hostile-* / "
+                         "--serial-rows / --cpu-seconds / --recall-queries / --alloc-probe options shape those legs")
     ap.add_argument("--rows", dest="n", type=int, default=0, help="index rows (default 1M; 10M in --mode sharded)")
     ap.add_argument("--dim", type=int, default=768)
     ap.add_argument("--hnsw-m", dest="m", type=int, default=16, help="m reloption (maxM = 2m)")
@@ -466,67 +476,69 @@ def main():
         Q = gmm_torch(args.nq, args.dim, k=args.clusters, sigma=0.3, seed=42, stream=1 + rank, device=dev)
         built_by = "device build"
 
-    # ---- recall@10 against exhaustive search with the same metric ---------------------
-    nrec = min(args.recall_queries, args.nq)
-    truth, _ = ix.bruteforce_torch(Q[:nrec].contiguous(), 10, mfma=True)
-    out = ix.search_torch(Q, args.ef, stats=True)
-    torch.cuda.synchronize()
-    labels0 = out["labels"].clone()
-    recall = recall_at_k(labels0[:nrec].cpu().numpy(), truth.cpu().numpy(), 10)
-    stats = out["stats"].cpu().numpy().astype(np.int64)
-    counts = out["counts"].cpu().numpy().astype(np.int64)
-    E, H = stats[:, 0], stats[:, 1]
-    bytes_q = alg_bytes(stats, counts, args.dim, args.m)
-    bytes_launch = float(bytes_q.sum())
-
-    # ---- the same hot path at a smaller launch (the fixed ramp-up/drain cost of a launch is
-    # amortised over fewer queries); done BEFORE the timed region so that the last launches of
-    # the process — the ones profiles/ summarises — are the headline workload
-    small = None
-    if args.nq_small and args.nq_small < args.nq:
-        Qs = Q[:args.nq_small].contiguous()
-        bs = ix.search_torch(Qs, args.ef)
-        ms_small = []
-        for _ in range(3):
-            ix.search_torch(Qs, args.ef, out=bs)
-            ms_small.append(ix.last_search_ms())
-        small = {"queries_per_launch": args.nq_small, "kernel_ms": float(np.median(ms_small)),
-                 "queries_per_s": args.nq_small / float(np.median(ms_small)) * 1e3,
-                 "achieved_GBps": float(bytes_q[:args.nq_small].sum()) / float(np.median(ms_small)) / 1e6}
-
-    # ---- two search contexts on two streams: consecutive small launches overlap (the next one
-    # fills the CUs the previous one frees while it drains).  Extra figure, not `value`.
-    pipelined = None
-    if small is not None:
-        pipelined = two_streams(ix, Q[:args.nq_small].contiguous(), args.ef, labels0[:args.nq_small], dev)
-
-    # ---- single query per launch: the reference's own call shape (embedding.c:317), device time only.  Measured twice: right here,
-    # behind seconds of sustained full-chip load (the device's clocks are down: the state `value` is measured in), and after one
-    # second of idle (the state a backend that calls once in a while finds the device in) — the same 40 queries, medians of both.
-    single = None
-    if rank == 0:
-        q1 = Q[:1].contiguous()
-        b1 = ix.search_torch(q1, args.ef)
-
-        def one_by_one():
-            ms1 = []
-            for i in range(48):
-                ix.search_torch(Q[i:i + 1].contiguous(), args.ef, out=b1)
-                ms1.append(ix.last_search_ms())
-            return ms1
-        hot = one_by_one()
+    # ---- --full: the legs that run in front of the timed region (a plain run goes straight to it)
+    if args.full:
+        # ---- recall@10 against exhaustive search with the same metric ---------------------
+        nrec = min(args.recall_queries, args.nq)
+        truth, _ = ix.bruteforce_torch(Q[:nrec].contiguous(), 10, mfma=True)
+        out = ix.search_torch(Q, args.ef, stats=True)
         torch.cuda.synchronize()
-        time.sleep(1.0)
-        idle = one_by_one()
-        single = {"kernel_ms_median": float(np.median(hot[8:])), "kernel_ms_mean": float(np.mean(hot[8:])),
-                  "kernel_ms_median_after_idle": float(np.median(idle[8:])), "kernel": ix.last_search_kernel()}
+        labels0 = out["labels"].clone()
+        recall = recall_at_k(labels0[:nrec].cpu().numpy(), truth.cpu().numpy(), 10)
+        stats = out["stats"].cpu().numpy().astype(np.int64)
+        counts = out["counts"].cpu().numpy().astype(np.int64)
+        E, H = stats[:, 0], stats[:, 1]
+        bytes_q = alg_bytes(stats, counts, args.dim, args.m)
+        bytes_launch = float(bytes_q.sum())
 
-    # ---- roofs measured on this device: dependency-free gather of this table's rows, plain copy
-    g_rand, g_cfg = random_gather(ix)
-    copy_gbps = copy_roof(dev)
-    # ---- this launch's own trace: replay roof + reuse distances (BEFORE the timed region: the traced launch stores 6 KB
-    # more per query and must not be one of the launches the timing and profiles/ summarise)
-    tr_raw = trace_roof(ix, Q, args.ef) if rank == 0 else None
+        # ---- the same hot path at a smaller launch (the fixed ramp-up/drain cost of a launch is
+        # amortised over fewer queries); done BEFORE the timed region so that the last launches of
+        # the process — the ones profiles/ summarises — are the headline workload
+        small = None
+        if args.nq_small and args.nq_small < args.nq:
+            Qs = Q[:args.nq_small].contiguous()
+            bs = ix.search_torch(Qs, args.ef)
+            ms_small = []
+            for _ in range(3):
+                ix.search_torch(Qs, args.ef, out=bs)
+                ms_small.append(ix.last_search_ms())
+            small = {"queries_per_launch": args.nq_small, "kernel_ms": float(np.median(ms_small)),
+                     "queries_per_s": args.nq_small / float(np.median(ms_small)) * 1e3,
+                     "achieved_GBps": float(bytes_q[:args.nq_small].sum()) / float(np.median(ms_small)) / 1e6}
+
+        # ---- two search contexts on two streams: consecutive small launches overlap (the next one
+        # fills the CUs the previous one frees while it drains).  Extra figure, not `value`.
+        pipelined = None
+        if small is not None:
+            pipelined = two_streams(ix, Q[:args.nq_small].contiguous(), args.ef, labels0[:args.nq_small], dev)
+
+        # ---- single query per launch: the reference's own call shape (embedding.c:317), device time only.  Measured twice: right here,
+        # behind seconds of sustained full-chip load (the device's clocks are down: the state `value` is measured in), and after one
+        # second of idle (the state a backend that calls once in a while finds the device in) — the same 40 queries, medians of both.
+        single = None
+        if rank == 0:
+            q1 = Q[:1].contiguous()
+            b1 = ix.search_torch(q1, args.ef)
+
+            def one_by_one():
+                ms1 = []
+                for i in range(48):
+                    ix.search_torch(Q[i:i + 1].contiguous(), args.ef, out=b1)
+                    ms1.append(ix.last_search_ms())
+                return ms1
+            hot = one_by_one()
+            torch.cuda.synchronize()
+            time.sleep(1.0)
+            idle = one_by_one()
+            single = {"kernel_ms_median": float(np.median(hot[8:])), "kernel_ms_mean": float(np.mean(hot[8:])),
+                      "kernel_ms_median_after_idle": float(np.median(idle[8:])), "kernel": ix.last_search_kernel()}
+
+        # ---- roofs measured on this device: dependency-free gather of this table's rows, plain copy
+        g_rand, g_cfg = random_gather(ix)
+        copy_gbps = copy_roof(dev)
+        # ---- this launch's own trace: replay roof + reuse distances (BEFORE the timed region: the traced launch stores 6 KB
+        # more per query and must not be one of the launches the timing and profiles/ summarise)
+        tr_raw = trace_roof(ix, Q, args.ef) if rank == 0 else None
 
     # ---- timed region -----------------------------------------------------------------
     bufs = ix.search_torch(Q, args.ef)           # allocate outputs once
@@ -538,11 +550,22 @@ def main():
         ix.search_torch(Q, args.ef, out=bufs)
     barrier()
     elapsed = time.perf_counter() - t0
-    same = bool((bufs["labels"] == labels0).all().item())
-    kernel_name = ix.last_search_kernel()
     if args.dump_outputs and rank == 0:
         # what a caller of the timed path receives from its last step (outside the timed region; rank 0's own queries)
         dump_outputs(args.dump_outputs, {k: bufs[k].cpu().numpy() for k in ("labels", "dists", "counts")})
+    if not args.full:
+        tmax = torch.tensor([elapsed], dtype=torch.float64, device=dev)
+        if use_dist:
+            dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
+        if rank == 0:
+            sys.stdout.write(json.dumps(headline(args, float(tmax.item()), world, ref_path, built_by)) + "\n")
+            sys.stdout.flush()
+        ix.close()
+        if use_dist:
+            dist.destroy_process_group()
+        return
+    same = bool((bufs["labels"] == labels0).all().item())
+    kernel_name = ix.last_search_kernel()
     # per-launch kernel time of exactly the K timed launches, from the HIP events the library
     # recorded on the launch stream around each kernel
     kernel_ms = [ix.last_search_ms(back) for back in range(min(args.steps, 64))]
@@ -563,33 +586,11 @@ def main():
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dist.all_reduce(rec_t, op=dist.ReduceOp.MIN)
     elapsed = float(tmax.item())
-    total_queries = args.nq * args.steps * world
-    qps = total_queries / elapsed
 
     achieved = bytes_launch / (kms * 1e-3) / 1e9
     traffic, traffic_src = pmc_traffic(args, kernel_name, "reference" if ref_path else "device (batched)")
-    result = {
-        "metric": "queries/sec at recall@10>=0.95, 1Mx768 L2 efsearch=128",
-        "value": qps,
-        "unit": "queries/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": elapsed / args.steps * 1e3,
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "f32",
-        "data": "synthetic",
-        "config": {
-            "workload": f"HNSW search: {args.n}x{args.dim} fp32 GMM({args.clusters}, sigma 0.3), "
-                        f"{args.metric}, m={args.m}, efconstruction={args.efc} ({built_by}), "
-                        f"efsearch={args.ef}, {args.nq} queries/step/GPU resident in HBM",
-            "graph_built_by": "reference" if ref_path else "device (batched)",
-            "rows": args.n, "dims": args.dim, "m": args.m, "efsearch": args.ef,
-            "queries_per_step_per_gpu": args.nq,
-            "parallelism": "replica per GPU, queries sharded" if world > 1 else "single GPU",
-        },
+    result = headline(args, elapsed, world, ref_path, built_by)
+    result.update({
         "ranks": {"world_size_reported_by_backend": world, "backend": backend or "none (single process)",
                   "self_launched": os.environ.get("PGEMB_BENCH_SELF_LAUNCHED") == "1",
                   "queries_per_s_per_rank": [args.nq * args.steps / t for t in per_rank],
@@ -628,7 +629,7 @@ def main():
         "smaller_launch": small,
         "smaller_launch_two_streams": pipelined,
         "single_query_launch": single,
-    }
+    })
 
     # ---- the host-pointer form of the same batch (hnsw_gpu_search_batch): what a caller without device buffers pays on top
     # (Everything from here on is an extra leg next to a headline that is already complete: a leg that fails says so under its own key
@@ -668,6 +669,34 @@ def main():
         emit(result)
     if use_dist:
         dist.destroy_process_group()
+
+
+def headline(args, elapsed, world, ref_path, built_by):
+    """the keys of the headline line, from the wall time of the slowest rank's --steps timed steps"""
+    total_queries = args.nq * args.steps * world
+    return {
+        "metric": "queries/sec at recall@10>=0.95, 1Mx768 L2 efsearch=128",
+        "value": total_queries / elapsed,
+        "unit": "queries/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": elapsed / args.steps * 1e3,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f32",
+        "data": "synthetic",
+        "config": {
+            "workload": f"HNSW search: {args.n}x{args.dim} fp32 GMM({args.clusters}, sigma 0.3), "
+                        f"{args.metric}, m={args.m}, efconstruction={args.efc} ({built_by}), "
+                        f"efsearch={args.ef}, {args.nq} queries/step/GPU resident in HBM",
+            "graph_built_by": "reference" if ref_path else "device (batched)",
+            "rows": args.n, "dims": args.dim, "m": args.m, "efsearch": args.ef,
+            "queries_per_step_per_gpu": args.nq,
+            "parallelism": "replica per GPU, queries sharded" if world > 1 else "single GPU",
+        },
+    }
 
 
 HEADLINE_KEYS = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
