@@ -358,6 +358,19 @@ float hnsw_gpu_last_bruteforce_gemm_ms(void);
 /* queries (= rows) per block tile of that launch: 128 or 256 (256 x 256 tiles are picked for launches with thousands of tiles) */
 int hnsw_gpu_last_bruteforce_tile(void);
 
+/* Same result as hnsw_gpu_bruteforce_dev (exact, same distances); the Q x N part runs as an fp16 / bf16 MFMA filter over the
+ * mirror's reduced copy (`format` must be the copy's format: HNSW_GPU_ERR_ARG otherwise, before any launch).  The query is converted
+ * to the copy's format and layout; the filter's margin adds a bound on the 16-bit dot product's error, built from the measured
+ * residuals |q - q~| and |x - x~| (device_bf_mfma16.h); the survivors are re-scored with the canonical fp32 code.  Brings the copy
+ * up to date first, on `stream`, as a reduced search does.  Argument rules are those of hnsw_gpu_bruteforce_mfma_dev (k in
+ * [1, 1024], nq <= 65535, non-NULL pointers), and so are the cases the scan answers (Manhattan, tables under 4096 rows, a device
+ * without gfx950's LDS, a (dim, k) pair whose re-score step does not fit in LDS).  A query whose candidate list overflows (the 16-bit
+ * bound is looser than the f32 one) makes the call fall back to hnsw_gpu_bruteforce_mfma_dev, which falls back to the scan in turn;
+ * hnsw_gpu_last_bruteforce_form (hnsw_gpu_diag.h) names the form that answered.  The kernel time, tile and survivors of the last
+ * filter launch are reported by the diagnostics of the f32 form.  Synchronises `stream`. */
+int hnsw_gpu_bruteforce_reduced_dev(hnsw_gpu_index *ix, int format, const coord_t *d_queries, size_t nq, size_t k,
+									idx_t *d_idx, dist_t *d_dists, void *stream);
+
 /* ----------------------------------------------------------------- multi-shard */
 
 /* Merge `nlists` per-shard result lists per query (each ef entries: ascending by

@@ -61,9 +61,14 @@ int hnsw_gpu_index_placement(hnsw_gpu_index *ix, uint64_t *out16);
  * shader-clock ticks / constant-clock ticks. */
 double hnsw_gpu_last_bruteforce_clock_mhz(void);
 
-/* Rows that passed the MFMA filter of the last hnsw_gpu_bruteforce_mfma_dev call on `ix`, per query: *mean and *max over its
+/* Rows that passed the MFMA filter of the last hnsw_gpu_bruteforce_mfma_dev or _reduced_dev call on `ix`, per query: *mean and *max over its
  * queries (counts past the candidate list's capacity included).  Both 0 when that call did not run the filter. */
 int hnsw_gpu_last_bruteforce_survivors(hnsw_gpu_index *ix, double *mean, uint32_t *max);
+
+/* The form that answered the last exhaustive call on `ix` (hnsw_gpu_bruteforce_dev, _mfma_dev, _reduced_dev): the canonical scan, the
+ * f32 MFMA filter or the fp16 / bf16 MFMA filter over the reduced copy.  -1 before the first such call (and for a NULL index). */
+enum { HNSW_GPU_BF_FORM_SCAN = 0, HNSW_GPU_BF_FORM_F32 = 1, HNSW_GPU_BF_FORM_F16 = 2, HNSW_GPU_BF_FORM_BF16 = 3 };
+int hnsw_gpu_last_bruteforce_form(hnsw_gpu_index *ix);
 
 /* Practical roof of the search kernel's memory access pattern on THIS mirror's row table: independent
  * waves gathering random whole rows with 16-byte loads, `loads_per_lane` (4/8/12/16/24) in flight per lane,

@@ -165,6 +165,8 @@ def gpu_lib():
     L.hnsw_gpu_last_bruteforce_clock_mhz.restype = C.c_double
     L.hnsw_gpu_last_bruteforce_tile.restype = C.c_int
     L.hnsw_gpu_last_bruteforce_survivors.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_uint32)]
+    L.hnsw_gpu_bruteforce_reduced_dev.argtypes = [vp, i32, vp, sz, sz, vp, vp, vp]
+    L.hnsw_gpu_last_bruteforce_form.argtypes = [vp]
     L.hnsw_gpu_device_wait.argtypes = [C.c_int, vp]
     L.hnsw_gpu_shared_alloc.argtypes = [C.c_int, C.c_size_t, C.POINTER(vp), C.c_char_p]
     L.hnsw_gpu_shared_open.argtypes = [C.c_int, C.c_char_p, C.POINTER(vp)]

@@ -161,12 +161,20 @@ struct hnsw_gpu_index
 	// per-launch scratch of the reduced search: the walk's element numbers (grow-only)
 	uint32_t *rr_cand = nullptr; size_t rr_bytes = 0;
 	hipEvent_t rr_e0 = nullptr, rr_e1 = nullptr; bool rr_valid = false;    // around the last re-rank kernel (hnsw_gpu_last_rerank_ms)
+	// exhaustive k-NN over the reduced copy (device_bf_mfma16.h): per row { |x|^2, |x|', ex' } of the copy's format r16x_fmt, valid for
+	// rows [0, r16x_n) except [r16x_lo, r16x_hi), which were written since (rows16_mark); reallocation and set_reduced_rows clear r16x_n
+	float4  *r16x = nullptr; size_t r16x_cap = 0, r16x_n = 0, r16x_lo = 0, r16x_hi = 0; int r16x_fmt = 0;
+	int      bf_form = -1;            // the form that answered the last exhaustive call (HNSW_GPU_BF_FORM_*, hnsw_gpu_last_bruteforce_form)
 };
 
 // rows [lo, hi) of `vec` were (or are about to be) written: the reduced copy, if any, converts them again before the next reduced search
+// (the same range widens a second one: the per-row terms of the exhaustive filter over the copy, which a reduced search's conversion
+// does not refresh)
 static inline void rows16_mark(hnsw_gpu_index *ix, size_t lo, size_t hi)
 {
 	if (!ix->rows_fmt || lo >= hi) return;
+	if (ix->r16x_lo >= ix->r16x_hi) { ix->r16x_lo = lo; ix->r16x_hi = hi; }
+	else { ix->r16x_lo = std::min(ix->r16x_lo, lo); ix->r16x_hi = std::max(ix->r16x_hi, hi); }
 	if (ix->dirty_lo >= ix->dirty_hi) { ix->dirty_lo = lo; ix->dirty_hi = hi; return; }
 	ix->dirty_lo = std::min(ix->dirty_lo, lo);
 	ix->dirty_hi = std::max(ix->dirty_hi, hi);

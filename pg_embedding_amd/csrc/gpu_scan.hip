@@ -2,6 +2,7 @@
 // One translation unit of libhnsw_gpu.so (csrc/gpu_host.h lists them); gfx950 only, plain HIP runtime, no framework types in any signature.
 #include "gpu_host.h"
 #include "device_bf_mfma.h"
+#include "device_bf_mfma16.h"
 
 // ------------------------------------------------------------------------------------
 // batched distances (hnsw_dist_func over many rows)
@@ -271,7 +272,10 @@ extern "C" int hnsw_gpu_bruteforce_dev(hnsw_gpu_index *ix, const coord_t *d_quer
 									   dist_t *d_dists, void *stream)
 {
 	if (!ix) return fail(HNSW_GPU_ERR_ARG, "NULL argument");
-	return bruteforce_prefix(ix, ix->n, d_queries, nq, k, d_idx, d_dists, stream);
+	std::lock_guard<std::recursive_mutex> lock_(ix->mu);
+	const int rc = bruteforce_prefix(ix, ix->n, d_queries, nq, k, d_idx, d_dists, stream);
+	if (!rc && nq) ix->bf_form = HNSW_GPU_BF_FORM_SCAN;
+	return rc;
 }
 
 // ------------------------------------------------------------------------------------
@@ -419,7 +423,176 @@ extern "C" int hnsw_gpu_bruteforce_mfma_dev(hnsw_gpu_index *ix, const coord_t *d
 	(void) hipEventElapsedTime(&g_last_bf_gemm_ms, e0, e1);
 	if (ovf)      // a candidate list overflowed (bound far too loose for some query): canonical scan instead
 		return hnsw_gpu_bruteforce_dev(ix, d_queries, nq, k, d_idx, d_dists, stream_);
+	ix->bf_form = HNSW_GPU_BF_FORM_F32;
 	return HNSW_GPU_OK;
+}
+
+// ------------------------------------------------------------------------------------
+// exhaustive k-NN with the filter on the 16-bit matrix cores, over the reduced copy (device_bf_mfma16.h)
+// ------------------------------------------------------------------------------------
+// The per-row terms of the bound, brought up to date on `s` after rows16_sync: rows never computed for this format, and rows written since
+// (rows16_mark widens r16x_lo / r16x_hi as it widens the copy's dirty range; a reduced search clears only the latter)
+static int r16x_sync(hnsw_gpu_index *ix, hipStream_t s)
+{
+	if (ix->r16x_cap < ix->cap)
+	{
+		if (ix->r16x) (void) hipFree(ix->r16x);
+		ix->r16x = nullptr; ix->r16x_cap = 0; ix->r16x_n = 0;
+		HIPCHK(hipMalloc(&ix->r16x, ix->cap * sizeof(float4)));
+		ix->r16x_cap = ix->cap;
+	}
+	if (ix->r16x_fmt != ix->rows_fmt) { ix->r16x_n = 0; ix->r16x_fmt = ix->rows_fmt; }
+	size_t lo = ix->n, hi = 0;
+	if (ix->r16x_n < ix->n) { lo = ix->r16x_n; hi = ix->n; }
+	if (ix->r16x_lo < ix->r16x_hi) { lo = std::min(lo, ix->r16x_lo); hi = std::max(hi, std::min(ix->r16x_hi, ix->n)); }
+	ix->r16x_lo = ix->r16x_hi = 0;
+	ix->r16x_n = ix->n;
+	if (lo >= hi) return HNSW_GPU_OK;
+	const dim3 grid((uint32_t) ((hi - lo + 3) / 4));
+	if (ix->rows_fmt == ROWS_BF16)
+		hipLaunchKernelGGL(r16_row_terms_kernel<ROWS_BF16>, grid, dim3(256), 0, s, ix->vec, ix->stride, (uint32_t) ix->meta.dim, lo, hi - lo, ix->r16x);
+	else
+		hipLaunchKernelGGL(r16_row_terms_kernel<ROWS_F16>, grid, dim3(256), 0, s, ix->vec, ix->stride, (uint32_t) ix->meta.dim, lo, hi - lo, ix->r16x);
+	HIPCHK(hipGetLastError());
+	return HNSW_GPU_OK;
+}
+
+template <int FMT, int WM, int NJ>
+static int bf16_filter_launch(R16Args &a, uint32_t nq, uint32_t n, hipStream_t s)
+{
+	using T = R16Tile<WM, NJ>;
+	a.nqt = (nq + T::TQ - 1) / T::TQ;
+	a.nrt = (n + T::TR - 1) / T::TR;
+	const uint32_t rgroups = (a.nrt + 7) / 8;
+	HIPCHK(hipFuncSetAttribute((const void *) bf16_filter_kernel<FMT, WM, NJ>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) T::LDS_BYTES));
+	hipLaunchKernelGGL((bf16_filter_kernel<FMT, WM, NJ>), dim3(rgroups * a.nqt * 8), dim3(T::THREADS), T::LDS_BYTES, s, a);
+	return HNSW_GPU_OK;
+}
+
+extern "C" int hnsw_gpu_bruteforce_reduced_dev(hnsw_gpu_index *ix, int format, const coord_t *d_queries, size_t nq, size_t k,
+											   idx_t *d_idx, dist_t *d_dists, void *stream_)
+{
+	std::unique_lock<std::recursive_mutex> lock_;
+	if (ix) lock_ = std::unique_lock<std::recursive_mutex>(ix->mu);
+	if (!ix || !d_queries || !d_idx) return fail(HNSW_GPU_ERR_ARG, "NULL argument");
+	if ((format != ROWS_F16 && format != ROWS_BF16) || ix->rows_fmt != format || !ix->rows16)
+		return fail(HNSW_GPU_ERR_ARG, "reduced rows: format %d is not the copy this index holds (%d; hnsw_gpu_index_set_reduced_rows)", format, ix->rows_fmt);
+	if (nq == 0) return HNSW_GPU_OK;
+	if (k == 0 || k > 1024) return fail(HNSW_GPU_ERR_ARG, "k %zu out of range [1, 1024]", k);
+	if (nq > 65535) return fail(HNSW_GPU_ERR_ARG, "at most 65535 queries per call");
+	ix->bf_cnt_nq = 0;
+	const int func = (int) ix->meta.dist_func;
+	using Small = R16Tile<BF_WM, BF_NJ>;
+	using Big = R16Tile<4, 4>;
+	// the cases the f32 form answers with the scan get the scan here too (before any launch)
+	if (func == F_MANHATTAN || ix->n < 4096) return hnsw_gpu_bruteforce_dev(ix, d_queries, nq, k, d_idx, d_dists, stream_);
+	HIPCHK(hipSetDevice(ix->device));
+	if (!ix->gfx950 || ix->max_lds < Small::LDS_BYTES) return hnsw_gpu_bruteforce_dev(ix, d_queries, nq, k, d_idx, d_dists, stream_);
+	hipStream_t s = (hipStream_t) stream_;
+	const uint32_t n = (uint32_t) ix->n, stride = ix->stride, dim = (uint32_t) ix->meta.dim;
+	const uint32_t nchunks = stride / 4, kiters = (nchunks + 15) / 16;
+	const uint32_t qpadf = (uint32_t) round_up(kiters, 4) * 64;
+	const size_t wave_bytes = round_up((size_t) qpadf * 4 + (k + 1) * 8 + 128 * 4, 16);
+	const size_t lds = wave_bytes * 4;
+	if (lds > 64 * 1024) return hnsw_gpu_bruteforce_dev(ix, d_queries, nq, k, d_idx, d_dists, stream_);
+
+	// the copy and the bound's per-row terms, current on this stream
+	int rc = rows16_sync(ix, s);
+	if (!rc) rc = r16x_sync(ix, s);
+	if (rc) return rc;
+	const uint32_t nunits = ix->rows16_bytes / 16;
+
+	const uint32_t cap = 16384;
+	const size_t sample = std::min<size_t>(ix->n, std::max<size_t>(8192, (size_t) k * ix->n / 2048));
+	const size_t o_q = 0;
+	const size_t o_qn = o_q + round_up(nq * (size_t) ix->rows16_bytes, 256);
+	const size_t o_qt = o_qn + round_up(nq * 4, 256);
+	const size_t o_sidx = o_qt + round_up(nq * 8, 256);
+	const size_t o_sdist = o_sidx + round_up(nq * k * 4, 256);
+	const size_t o_bound = o_sdist + round_up(nq * k * 4, 256);
+	const size_t o_cnt = o_bound + round_up(nq * 4, 256);
+	const size_t o_cand = o_cnt + round_up(nq * 4 + 64, 256);
+	const size_t o_clk = o_cand + round_up(nq * (size_t) cap * 4, 256);
+	const size_t total = o_clk + 256;
+	if (total > ix->bf_bytes)
+	{
+		if (ix->bf) (void) hipFree(ix->bf);
+		ix->bf = nullptr; ix->bf_bytes = 0;
+		HIPCHK(hipMalloc(&ix->bf, total));
+		ix->bf_bytes = total;
+	}
+	char *B = (char *) ix->bf;
+	uint4 *q16 = (uint4 *) (B + o_q);
+	float *qn = (float *) (B + o_qn), *sdist = (float *) (B + o_sdist), *bound = (float *) (B + o_bound);
+	float2 *qterms = (float2 *) (B + o_qt);
+	uint32_t *sidx = (uint32_t *) (B + o_sidx), *cnt = (uint32_t *) (B + o_cnt), *cand = (uint32_t *) (B + o_cand);
+	uint32_t *overflow = cnt + nq;
+
+	// 1. the same bound per query as the f32 form: a canonical scan of the sample rows, then make_bounds_kernel's margin
+	rc = bruteforce_prefix(ix, sample, d_queries, nq, k, sidx, sdist, s);
+	if (rc) return rc;
+	const dim3 qgrid((uint32_t) ((nq + 3) / 4));
+	if (format == ROWS_BF16)
+		hipLaunchKernelGGL(r16_query_kernel<ROWS_BF16>, qgrid, dim3(256), 0, s, d_queries, (uint32_t) nq, dim, nunits, q16, qn, qterms);
+	else
+		hipLaunchKernelGGL(r16_query_kernel<ROWS_F16>, qgrid, dim3(256), 0, s, d_queries, (uint32_t) nq, dim, nunits, q16, qn, qterms);
+	hipLaunchKernelGGL(fill_u32_kernel, dim3(1), dim3(1), 0, s, overflow, (size_t) 1, 0u);
+	HIPCHK(hipMemcpy2DAsync(bound, 4, sdist + (k - 1), k * 4, 4, nq, hipMemcpyDeviceToDevice, s));
+	hipLaunchKernelGGL(make_bounds_kernel, dim3((uint32_t) ((nq + 255) / 256)), dim3(256), 0, s, bound, qn, (uint32_t) nq, func, dim, bound);
+	HIPCHK(hipMemsetAsync(cnt, 0, nq * 4, s));
+	ix->bf_cnt_off = o_cnt; ix->bf_cnt_nq = nq;
+
+	// 2. the 16-bit contraction + filter
+	R16Args a;
+	memset(&a, 0, sizeof(a));
+	a.queries = q16; a.qnorm = qn; a.qbound = bound; a.qterms = qterms; a.rows = (const uint4 *) ix->rows16; a.xterms = ix->r16x;
+	a.nq = (uint32_t) nq; a.n = n; a.nunits = nunits; a.ksteps = nunits / R16_CH; a.func = func;
+	a.xscale = 0.5f * (1.f - 2.f * ((float) dim + 32.f) * 0x1p-24f);          // (1 - eD) / 2: make_bounds_kernel
+	a.eabs = r16_abs_term(dim);
+	a.cand = cand; a.cand_cnt = cnt; a.cap = cap; a.clocks = (unsigned long long *) (B + o_clk);
+	HIPCHK(hipMemsetAsync(a.clocks, 0, 16, s));
+	if (!ix->bf_e0) { HIPCHK(hipEventCreate(&ix->bf_e0)); HIPCHK(hipEventCreate(&ix->bf_e1)); }
+	hipEvent_t e0 = ix->bf_e0, e1 = ix->bf_e1;
+	HIPCHK(hipEventRecord(e0, s));
+	{
+		// the f32 form's rule for the 256 x 256 tile (and its test knob), where the device has the LDS for it
+		const uint64_t nqt_s = (nq + Small::TQ - 1) / Small::TQ;
+		const uint64_t big_blocks = ((nq + Big::TQ - 1) / Big::TQ) * ((n + Big::TR - 1) / Big::TR);
+		const long long min_blocks = knob(K_BF_BIG_MIN_BLOCKS, 2048);
+		const bool big = ix->max_lds >= Big::LDS_BYTES && min_blocks != 0 &&
+						 (min_blocks < 0 || (nqt_s % 2 == 0 && big_blocks >= (uint64_t) min_blocks));
+		if (format == ROWS_BF16)
+			rc = big ? bf16_filter_launch<ROWS_BF16, 4, 4>(a, (uint32_t) nq, n, s) : bf16_filter_launch<ROWS_BF16, BF_WM, BF_NJ>(a, (uint32_t) nq, n, s);
+		else
+			rc = big ? bf16_filter_launch<ROWS_F16, 4, 4>(a, (uint32_t) nq, n, s) : bf16_filter_launch<ROWS_F16, BF_WM, BF_NJ>(a, (uint32_t) nq, n, s);
+		if (rc) return rc;
+		g_last_bf_tile = big ? Big::TQ : Small::TQ;
+	}
+	HIPCHK(hipEventRecord(e1, s));
+
+	// 3. canonical re-score of the survivors against the fp32 rows
+#define RS_LAUNCH(F)                                                                                                      \
+	hipLaunchKernelGGL(bf_rescore_kernel<F>, dim3((uint32_t) ((nq + 3) / 4)), dim3(256), lds, s, ix->vec, dim, stride,      \
+					   nchunks, kiters, qpadf, d_queries, (uint32_t) nq, cand, cnt, cap, (uint32_t) k, d_idx, d_dists, overflow)
+	if (func == F_L2) RS_LAUNCH(F_L2); else RS_LAUNCH(F_COSINE);
+#undef RS_LAUNCH
+	HIPCHK(hipGetLastError());
+	uint32_t ovf = 0;
+	HIPCHK(hipMemcpyAsync(&ovf, overflow, 4, hipMemcpyDeviceToHost, s));
+	HIPCHK(hipMemcpyAsync(g_last_bf_clocks, a.clocks, 16, hipMemcpyDeviceToHost, s));
+	HIPCHK(hipStreamSynchronize(s));
+	(void) hipEventElapsedTime(&g_last_bf_gemm_ms, e0, e1);
+	if (ovf)      // the 16-bit bound is looser: a list that overflowed here may not in f32 (which falls back to the scan in turn)
+		return hnsw_gpu_bruteforce_mfma_dev(ix, d_queries, nq, k, d_idx, d_dists, stream_);
+	ix->bf_form = format == ROWS_BF16 ? HNSW_GPU_BF_FORM_BF16 : HNSW_GPU_BF_FORM_F16;
+	return HNSW_GPU_OK;
+}
+
+extern "C" int hnsw_gpu_last_bruteforce_form(hnsw_gpu_index *ix)
+{
+	if (!ix) return -1;
+	std::lock_guard<std::recursive_mutex> lock_(ix->mu);
+	return ix->bf_form;
 }
 
 extern "C" int hnsw_gpu_last_bruteforce_tile(void) { return g_last_bf_tile; }

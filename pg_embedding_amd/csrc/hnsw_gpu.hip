@@ -346,6 +346,7 @@ extern "C" void hnsw_gpu_index_destroy(hnsw_gpu_index *ix)
 	if (ix->hb0) (void) hipEventDestroy(ix->hb0);
 	if (ix->hb1) (void) hipEventDestroy(ix->hb1);
 	if (ix->rows16) (void) hipFree(ix->rows16);
+	if (ix->r16x) (void) hipFree(ix->r16x);
 	if (ix->rr_cand) (void) hipFree(ix->rr_cand);
 	if (ix->rr_e0) (void) hipEventDestroy(ix->rr_e0);
 	if (ix->rr_e1) (void) hipEventDestroy(ix->rr_e1);
@@ -729,6 +730,7 @@ int rows16_sync(hnsw_gpu_index *ix, hipStream_t stream)
 		}
 		ix->rows16_cap = ix->cap;
 		ix->dirty_lo = 0; ix->dirty_hi = ix->n;
+		ix->r16x_n = 0;                                 // (the exhaustive filter's per-row terms follow the copy)
 	}
 	const size_t lo = ix->dirty_lo, hi = std::min(ix->dirty_hi, ix->n);
 	ix->dirty_lo = ix->dirty_hi = 0;
@@ -759,6 +761,7 @@ extern "C" int hnsw_gpu_index_set_reduced_rows(hnsw_gpu_index *ix, int format)
 	}
 	ix->rows_fmt = format;
 	ix->dirty_lo = ix->dirty_hi = 0;
+	ix->r16x_n = 0; ix->r16x_lo = ix->r16x_hi = 0;                         // (rows written while there was no copy were not marked)
 	if (format == ROWS_F32) return HNSW_GPU_OK;
 	const uint32_t nchunks = ix->stride / 4;
 	ix->rows16_bytes = rows16_blocks((nchunks + 15) / 16) * 256u;

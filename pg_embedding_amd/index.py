@@ -404,9 +404,13 @@ class GpuIndex:
         check(self.L.hnsw_gpu_last_search_slots(self._h, C.byref(v)), "hnsw_gpu_last_search_slots")
         return int(v.value)
 
-    def bruteforce_torch(self, queries, k: int, mfma: bool = False):
+    def bruteforce_torch(self, queries, k: int, mfma: bool = False, rows: Optional[str] = None):
         """Exact k nearest elements (idx, dists) by exhaustive scoring — recall ground truth.
-        mfma=True runs the Q x N part as an f32 GEMM on the matrix cores (same result)."""
+        mfma=True runs the Q x N part as an f32 GEMM on the matrix cores (same result).  rows="f16" | "bf16" (with mfma=True)
+        runs it as an fp16 / bf16 GEMM over the reduced copy of the rows (set_reduced_rows), again with the same result."""
+        if rows is not None and not mfma:
+            raise ValueError("rows= selects the MFMA filter's operand: it needs mfma=True")
+        code = _rows_code(rows)
         torch = _torch()
         assert queries.is_cuda and queries.dtype == torch.float32 and queries.is_contiguous()
         nq = queries.shape[0]
@@ -416,10 +420,26 @@ class GpuIndex:
         step = 4096 if mfma else 32768
         for q0 in range(0, nq, step):
             q1 = min(nq, q0 + step)
+            if code != ROWS_F32:
+                check(self.L.hnsw_gpu_bruteforce_reduced_dev(self._h, code, queries[q0:q1].data_ptr(), q1 - q0, k,
+                                                             idx[q0:q1].data_ptr(), dst[q0:q1].data_ptr(), s),
+                      "hnsw_gpu_bruteforce_reduced_dev")
+                continue
             fn = self.L.hnsw_gpu_bruteforce_mfma_dev if mfma else self.L.hnsw_gpu_bruteforce_dev
             check(fn(self._h, queries[q0:q1].data_ptr(), q1 - q0, k,
                      idx[q0:q1].data_ptr(), dst[q0:q1].data_ptr(), s), "hnsw_gpu_bruteforce")
         return idx, dst
+
+    def last_bruteforce_survivors(self):
+        """(mean, max) rows per query that passed the MFMA filter of the last exhaustive call (hnsw_gpu_last_bruteforce_survivors)."""
+        mean, mx = C.c_double(0.0), C.c_uint32(0)
+        check(self.L.hnsw_gpu_last_bruteforce_survivors(self._h, C.byref(mean), C.byref(mx)), "hnsw_gpu_last_bruteforce_survivors")
+        return float(mean.value), int(mx.value)
+
+    def last_bruteforce_form(self) -> Optional[str]:
+        """The form that answered the last exhaustive call on this mirror: "scan", "f32", "f16" or "bf16" (the MFMA filters), or
+        None before the first one (hnsw_gpu_last_bruteforce_form)."""
+        return {0: "scan", 1: "f32", 2: "f16", 3: "bf16"}.get(int(self.L.hnsw_gpu_last_bruteforce_form(self._h)))
 
 
 class SearchContext:
