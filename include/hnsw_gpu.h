@@ -142,10 +142,20 @@ int hnsw_gpu_search_batch(hnsw_gpu_index *ix, const coord_t *queries, size_t nq,
 /* Device-pointer form: everything resident in HBM, enqueued on `stream`
  * (hipStream_t or NULL), no synchronisation.
  *   d_stats : NULL or nq*2 u32 = {distance evaluations E_q, hops H_q} per query
- *             (the counts of hnswalg.cpp:59,96 and :76 — SURVEY.md §8d). */
+ *             (the counts of hnswalg.cpp:59,96 and :76 — SURVEY.md §8d).
+ * Locality order: a batch of 8 192 queries or more (this call, hnsw_gpu_search_batch_reduced_dev and the traced launch; not the
+ * host-pointer forms) runs its
+ * queries in the order of a device-side key that groups queries near each other in the table, so that the walks resident at one
+ * time share cached rows.  Every query's results, counts and stats are the same in any order, at the same position of the outputs;
+ * only the time at which a query runs changes.  HNSW_GPU_LOCALITY=0 in the environment keeps the caller's order. */
 int hnsw_gpu_search_batch_dev(hnsw_gpu_index *ix, const coord_t *d_queries, size_t nq, size_t ef,
 							  label_t *d_labels, dist_t *d_dists, uint32_t *d_counts,
 							  uint32_t *d_stats, void *stream);
+/* The same launch, always in the caller's order, whatever the batch size: for callers whose batches are one shard of a larger
+ * search (hnsw_gpu_server's shard searches, ShardedIndex), whose latency the order's key would only add to. */
+int hnsw_gpu_search_batch_caller_order_dev(hnsw_gpu_index *ix, const coord_t *d_queries, size_t nq, size_t ef,
+										   label_t *d_labels, dist_t *d_dists, uint32_t *d_counts,
+										   uint32_t *d_stats, void *stream);
 
 /* searchBaseLayer() alone (hnswalg.cpp:42-114): element numbers + distances
  * ascending by (distance, idx), no label lookup / vacuum filter.  Device pointers. */
@@ -203,7 +213,8 @@ int hnsw_gpu_index_health(hnsw_gpu_index *ix, uint32_t *out8);
  * then on it takes the remaining queries of the launch without walking.  No wait in the kernels is unbounded, so this is for
  * the unknown: a launch that never ends costs its caller's patience, not the device.  What an aborted launch leaves behind is
  * DEFINED per query: a query it finished has its results and its count, every other query has count HNSW_GPU_COUNT_ABORTED
- * (and no completion flag); the host-pointer calls return an error for such a launch, a caller of the asynchronous
+ * (and no completion flag).  The unanswered queries need not be a suffix of the batch: a batch in locality order (hnsw_gpu_search_batch_dev)
+ * runs its queries in another order, so look at every count; the host-pointer calls return an error for such a launch, a caller of the asynchronous
  * device-pointer forms looks at the counts (or at hnsw_gpu_index_health [5] before and after).  The workspace is re-zeroed
  * by the next launch.  Callable from ANY thread, also while another thread is blocked inside a search call on the same mirror.
  * hnsw_gpu_index_abort: the mirror's default workspace only.  hnsw_gpu_abort_all: every workspace of every mirror, context

@@ -35,7 +35,9 @@ int hnsw_gpu_team_counters(hnsw_gpu_index *ix, uint32_t *out16);
  * *bytes = row bytes one repetition reads; word_sum (NULL, or for tests): the sum mod 2^64 of the 32-bit patterns of every word
  * one repetition read for the trace — equal to the same sum over the traced rows of the table.  The search kernel should not beat
  * the best replay of its own trace: search time / replay time is the cost of the walk's dependent chain, bytes / replay time
- * what the memory system gives this access pattern (bench.py: roofline.replay). */
+ * what the memory system gives this access pattern (bench.py: roofline.replay).  A trace is replayed in the order its launch ran in
+ * (the locality order of a large batch) when d_evals is the buffer the last traced launch of the mirror's workspace wrote; any other
+ * buffer in its own row order. */
 int hnsw_gpu_search_traced_dev(hnsw_gpu_index *ix, const coord_t *d_queries, size_t nq, size_t ef,
                                label_t *d_labels, dist_t *d_dists, uint32_t *d_counts, uint32_t *d_stats,
                                idx_t *d_evals, size_t evals_cap, uint64_t *d_times, void *stream);
@@ -82,6 +84,12 @@ int hnsw_gpu_index_export_reduced_rows(hnsw_gpu_index *ix, uint16_t *out);
 /* Milliseconds the re-rank kernel of the last reduced-row search spent on the device (its own HIP event pair; waits for it).
  * hnsw_gpu_last_search_ms spans the walk AND the re-rank: the walk alone is the difference. */
 int hnsw_gpu_last_rerank_ms(hnsw_gpu_index *ix, float *ms);
+
+/* The locality order of the last search launch of the mirror's default workspace (hnsw_gpu_search_batch_dev): *nq = the queries
+ * it ran in that order (0 = it ran in the caller's order: a small batch, a base / one-query / host-pointer / caller-order call,
+ * HNSW_GPU_LOCALITY=0), perm[t] = the query ticket t walked and keys[i] = the sort key of query i (t, i < min(*nq, cap); perm and
+ * keys may be NULL; perm is the stable argsort of keys).  Waits for the device.  For tests. */
+int hnsw_gpu_last_search_order(hnsw_gpu_index *ix, uint32_t *perm, uint32_t *keys, size_t cap, size_t *nq);
 
 #ifdef __cplusplus
 }

@@ -123,6 +123,7 @@ def gpu_lib():
     L.hnsw_gpu_index_destroy.argtypes = [vp]
     L.hnsw_gpu_search_batch.argtypes = [vp, vp, sz, sz, vp, vp, vp]
     L.hnsw_gpu_search_batch_dev.argtypes = [vp, vp, sz, sz, vp, vp, vp, vp, vp]
+    L.hnsw_gpu_search_batch_caller_order_dev.argtypes = [vp, vp, sz, sz, vp, vp, vp, vp, vp]
     L.hnsw_gpu_search_base_dev.argtypes = [vp, vp, sz, sz, vp, vp, vp, vp, vp]
     L.hnsw_gpu_index_set_reduced_rows.argtypes = [vp, i32]
     L.hnsw_gpu_index_reduced_rows.argtypes = [vp]
@@ -133,6 +134,7 @@ def gpu_lib():
     L.hnsw_gpu_last_search_ms.argtypes = [vp, _f32p]
     L.hnsw_gpu_search_ms.argtypes = [vp, C.c_uint, _f32p]
     L.hnsw_gpu_last_search_slots.argtypes = [vp, _u32p]
+    L.hnsw_gpu_last_search_order.argtypes = [vp, vp, vp, sz, C.POINTER(C.c_size_t)]
     L.hnsw_gpu_index_health.argtypes = [vp, _u32p]
     L.hnsw_gpu_index_insert_one.argtypes = [vp, vp, C.c_uint64, C.c_uint32, vp, vp]
     L.hnsw_gpu_index_insert_candidates.argtypes = [vp, vp, C.c_uint64, C.c_uint32, vp, vp, C.c_uint32, vp, vp]

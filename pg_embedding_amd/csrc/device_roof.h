@@ -60,11 +60,12 @@ __global__ __launch_bounds__(256) void gather_roof_kernel(const float4 *__restri
 // the search kernel's own: the replay must be limited by the memory system, not by integer divisions.
 // CHECK (tests only): also sums the bit patterns of every word the trace asks for (mod 2^64, order-free) into *check, so a test
 // can tell that the replay read exactly the traced rows, whole.
+// perm: null, or the locality order the traced launch ran in (device_order.h): ticket t replays query perm[t], as the search did.
 constexpr uint32_t REPLAY_STAGE = 512;
 template <int KB, int RPG, bool CHECK>
 __global__ __launch_bounds__(256) void replay_roof_kernel(const float4 *__restrict__ base, uint32_t row_f4, const uint32_t *__restrict__ evals,
 														   uint32_t evals_cap, const uint32_t *__restrict__ nevals, uint32_t nq, uint32_t parts,
-														   uint32_t *ticket, float *out, unsigned long long *check)
+														   uint32_t *ticket, float *out, unsigned long long *check, const uint32_t *__restrict__ perm)
 {
 	// row ids staged in LDS, REPLAY_STAGE at a time (the search kernel has its ids in LDS too: a pass must not wait for an id
 	// load before it can issue its row loads); dynamic LDS: 4 waves x REPLAY_STAGE x 4 bytes
@@ -84,7 +85,8 @@ __global__ __launch_bounds__(256) void replay_roof_kernel(const float4 *__restri
 		if (lane == 0) tk = atomicAdd(ticket, 1u);
 		tk = __builtin_amdgcn_readfirstlane(tk);
 		if (tk >= nq * parts) break;
-		const uint32_t qi = tk / parts, part = tk - qi * parts;
+		const uint32_t tq = tk / parts, part = tk - tq * parts;
+		const uint32_t qi = perm ? perm[tq] : tq;            // (the traced launch's locality order, if it had one)
 		uint32_t ne = nevals[2 * (size_t) qi];               // (the search kernel's stats array: {evals, hops} per query)
 		ne = ne < evals_cap ? ne : evals_cap;
 		const uint32_t lo = (uint32_t) ((uint64_t) ne * part / parts), hi = (uint32_t) ((uint64_t) ne * (part + 1) / parts);

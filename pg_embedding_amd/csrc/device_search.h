@@ -115,6 +115,8 @@ struct SearchArgs
 	                              // 0 = plain stores + a full system-scope release per answered query (signal_done)	// reduced-row walk (beam kernel with a ShapeR16 shape, device_rows16.h): the 16-bit copy of the rows, uint4 units per row, 256-byte blocks per row
 	const uint4 *rows16;
 	uint32_t rstride4, nblk;
+	// locality order (beam kernel, plain launches only; device_order.h): null, or nq query numbers — ticket t walks query perm[t]
+	const uint32_t *perm;
 };
 
 // Abort word + health words of a search workspace.
@@ -1862,7 +1864,15 @@ __global__ __launch_bounds__(TEAM ? 512 : 256, (UREG >= 16 && SH::MIN_WAVES > 2)
 		else if (qi >= c->nq) break;
 		// (an abort request is sticky for this wave: it takes the remaining tickets without walking and marks every query it does not
 		// answer with count 0xFFFFFFFF, so that the caller of an interrupted launch can tell which rows of its outputs are results)
+		// (the gate counts tickets, so that how often a launch looks does not depend on its order)
 		if (!aborted && (qi & c->abort_mask) == 0u && abort_word_set(c->abort_word)) aborted = true;
+		// Locality order (device_order.h): ticket qi walks query perm[qi].  One load per query; from here on qi is the query number —
+		// its input, every output and its clock stamps (and the walking wave's LDS image of it, all a helper ever reads)
+		if (!stream)
+		{
+			const uint32_t *perm = c->perm;
+			if (perm) qi = __builtin_amdgcn_readfirstlane(perm[qi]);
+		}
 		if (__builtin_amdgcn_readfirstlane((int) aborted))
 		{
 			if (lane == 0) c->out_counts[qi] = ABORTED_COUNT;

@@ -14,7 +14,9 @@ extern "C" int hnsw_gpu_search_traced_dev(hnsw_gpu_index *ix, const coord_t *d_q
 	if (!d_evals || evals_cap == 0 || evals_cap > 0xFFFFFFFFull || !d_stats) return fail(HNSW_GPU_ERR_ARG, "trace buffers missing");
 	std::lock_guard<std::recursive_mutex> g(ix->mu);
 	ix->ws.evals_next = d_evals; ix->ws.evals_cap_next = (uint32_t) evals_cap; ix->ws.times_next = d_times;
-	const int rc = launch_search(ix, &ix->ws, d_queries, ix->meta.dim, nq, ef, 0, d_labels, nullptr, d_dists, d_counts, d_stats, (hipStream_t) stream);
+	// (in the same order as the untraced launch of the same batch: the replay of this trace re-reads the rows in the order they were walked)
+	const int rc = launch_search(ix, &ix->ws, d_queries, ix->meta.dim, nq, ef, 0, d_labels, nullptr, d_dists, d_counts, d_stats, (hipStream_t) stream,
+								 0, true);
 	ix->ws.evals_next = nullptr; ix->ws.evals_cap_next = 0; ix->ws.times_next = nullptr;
 	return rc;
 }
@@ -107,6 +109,10 @@ extern "C" int hnsw_gpu_replay_roof_parts(hnsw_gpu_index *ix, const idx_t *d_eva
 	float best = 1e30f;
 	int rc = HNSW_GPU_OK;
 	const int shape = kb * 100 + rpg;
+	// the trace is replayed in the order its launch ran in: when d_evals IS the trace the last launch of the mirror's workspace wrote and
+	// that launch ran in locality order (hnsw_gpu_search_traced_dev orders a large batch as hnsw_gpu_search_batch_dev does), its perm;
+	// any other buffer (an older trace, a copy, a permuted trace) is replayed in its own row order
+	const uint32_t *perm = (ix->ws.ord_nq == nq && ix->ws.ord_evals && ix->ws.ord_evals == d_evals) ? ix->ws.ord + ix->ws.ord_perm_off : nullptr;
 	for (int rep = 0; rep < 4 && rc == HNSW_GPU_OK; rep++)
 	{
 		(void) hipMemsetAsync(ticket, 0, 16, nullptr);           // ticket + the (test-only) word sum behind it
@@ -115,8 +121,8 @@ extern "C" int hnsw_gpu_replay_roof_parts(hnsw_gpu_index *ix, const idx_t *d_eva
 		switch (shape)
 		{
 #define ROOF(K, R) case K * 100 + R: \
-				if (word_sum) hipLaunchKernelGGL((replay_roof_kernel<K, R, true>), dim3(blocks), dim3(256), 4 * REPLAY_STAGE * 4, nullptr, base, row_f4, d_evals, (uint32_t) evals_cap, d_stats, (uint32_t) nq, (uint32_t) parts, ticket, out, d_check); \
-				else hipLaunchKernelGGL((replay_roof_kernel<K, R, false>), dim3(blocks), dim3(256), 4 * REPLAY_STAGE * 4, nullptr, base, row_f4, d_evals, (uint32_t) evals_cap, d_stats, (uint32_t) nq, (uint32_t) parts, ticket, out, d_check); \
+				if (word_sum) hipLaunchKernelGGL((replay_roof_kernel<K, R, true>), dim3(blocks), dim3(256), 4 * REPLAY_STAGE * 4, nullptr, base, row_f4, d_evals, (uint32_t) evals_cap, d_stats, (uint32_t) nq, (uint32_t) parts, ticket, out, d_check, perm); \
+				else hipLaunchKernelGGL((replay_roof_kernel<K, R, false>), dim3(blocks), dim3(256), 4 * REPLAY_STAGE * 4, nullptr, base, row_f4, d_evals, (uint32_t) evals_cap, d_stats, (uint32_t) nq, (uint32_t) parts, ticket, out, d_check, perm); \
 				break
 			ROOF(2, 2); ROOF(2, 4); ROOF(2, 8); ROOF(4, 2); ROOF(4, 4); ROOF(8, 2); ROOF(12, 1); ROOF(12, 2); ROOF(6, 4);
 #undef ROOF
@@ -194,5 +200,18 @@ extern "C" int hnsw_gpu_last_rerank_ms(hnsw_gpu_index *ix, float *ms)
 	HIPCHK(hipSetDevice(ix->device));
 	HIPCHK(hipEventSynchronize(ix->rr_e1));
 	HIPCHK(hipEventElapsedTime(ms, ix->rr_e0, ix->rr_e1));
+	return HNSW_GPU_OK;
+}
+
+extern "C" int hnsw_gpu_last_search_order(hnsw_gpu_index *ix, uint32_t *perm, uint32_t *keys, size_t cap, size_t *nq)
+{
+	if (!ix || !nq) return fail(HNSW_GPU_ERR_ARG, "NULL argument");
+	std::lock_guard<std::recursive_mutex> g(ix->mu);
+	HIPCHK(hipSetDevice(ix->device));
+	HIPCHK(hipDeviceSynchronize());
+	*nq = ix->ws.ord_nq;
+	const size_t take = std::min<size_t>(ix->ws.ord_nq, cap);
+	if (perm && take) HIPCHK(hipMemcpy(perm, ix->ws.ord + ix->ws.ord_perm_off, take * 4, hipMemcpyDeviceToHost));
+	if (keys && take) HIPCHK(hipMemcpy(keys, ix->ws.ord, take * 4, hipMemcpyDeviceToHost));        // (the keys sit in front of the perm)
 	return HNSW_GPU_OK;
 }

@@ -53,9 +53,9 @@ enum Knob : int
 {
 	// operational (environment, read once)
 	K_BEAM, K_FORCE_LDS_HEAPS, K_TEAM, K_TEAM_MAX_NQ, K_WIDE_EF_MIN, K_REF_ORDER, K_NO_POLL, K_POLL_LIMIT_S, K_INSERT_FUSED,
-	K_BLOCKS_PER_CU, K_STREAM_LIGHT,
+	K_BLOCKS_PER_CU, K_STREAM_LIGHT, K_LOCALITY,
 	// test knobs (hnsw_gpu_config_set only)
-	K_BEAM16, K_NARROW5, K_LEAN, K_HASH_ENTRIES, K_LDS_SET_MIN_WAVES, K_TEAM_SPEC, K_TEAM_WPB, K_NARROW_WPB, K_ABORT_POLL_LOG2, K_MAX_BLOCKS, K_SHARDED_NO_PEER, K_BF_BIG_MIN_BLOCKS,
+	K_BEAM16, K_NARROW5, K_LEAN, K_HASH_ENTRIES, K_LDS_SET_MIN_WAVES, K_TEAM_SPEC, K_TEAM_WPB, K_NARROW_WPB, K_ABORT_POLL_LOG2, K_MAX_BLOCKS, K_SHARDED_NO_PEER, K_BF_BIG_MIN_BLOCKS, K_LOCALITY_MIN_NQ,
 #ifdef HNSW_EXPERIMENT
 	K_WIDE_WAVES, K_SHAPE_12X1, K_TEAM_MAINS, K_TEAM_COUNTERS,
 #endif
@@ -102,6 +102,11 @@ struct SearchWs
 	int abort_sent = 0;                                  // (atomic) an abort was requested: the next launch re-zeroes the workspace
 	uint32_t abort_requests = 0;                         // (atomic) abort requests this workspace has received in its life (hnsw_gpu_index_health [5])
 	int64_t busy_since_ms = 0;                           // (atomic) steady-clock ms of the last launch, 0 = known idle (watchdog)
+	// locality order of large batches (device_order.h): keys | perm | chunk histograms, grow-only; ord_nq = queries the LAST launch of
+	// this workspace ran in that order (0 = the caller's order), its perm at ord + ord_perm_off
+	uint32_t *ord = nullptr; size_t ord_words = 0;
+	uint32_t ord_nq = 0; size_t ord_perm_off = 0;
+	const uint32_t *ord_evals = nullptr;                 // the evaluation trace that launch wrote (traced launches), else null
 };
 
 extern std::mutex &g_ws_mu;                              // guards the registry of workspaces (abort + watchdog, hnsw_gpu.hip)
@@ -165,6 +170,9 @@ struct hnsw_gpu_index
 	// rows [0, r16x_n) except [r16x_lo, r16x_hi), which were written since (rows16_mark); reallocation and set_reduced_rows clear r16x_n
 	float4  *r16x = nullptr; size_t r16x_cap = 0, r16x_n = 0, r16x_lo = 0, r16x_hi = 0; int r16x_fmt = 0;
 	int      bf_form = -1;            // the form that answered the last exhaustive call (HNSW_GPU_BF_FORM_*, hnsw_gpu_last_bruteforce_form)
+	// pivots of the locality order (device_order.h): [kd][P] prefixes | P ranks, built from the rows on a search's stream.  Every writer of
+	// `vec` clears piv_valid (rows16_mark, reserve); a stale set would only cost speed — the order is a permutation whatever the keys
+	float   *piv = nullptr; uint32_t piv_P = 0, piv_kd = 0; size_t piv_n = 0; bool piv_valid = false;
 };
 
 // rows [lo, hi) of `vec` were (or are about to be) written: the reduced copy, if any, converts them again before the next reduced search
@@ -172,6 +180,7 @@ struct hnsw_gpu_index
 // does not refresh)
 static inline void rows16_mark(hnsw_gpu_index *ix, size_t lo, size_t hi)
 {
+	ix->piv_valid = false;                          // (the locality order's pivots are rows too)
 	if (!ix->rows_fmt || lo >= hi) return;
 	if (ix->r16x_lo >= ix->r16x_hi) { ix->r16x_lo = lo; ix->r16x_hi = hi; }
 	else { ix->r16x_lo = std::min(ix->r16x_lo, lo); ix->r16x_hi = std::max(ix->r16x_hi, hi); }
@@ -188,7 +197,8 @@ int import_range(hnsw_gpu_index *ix, const void *elements, size_t first, size_t 
 static const size_t LDS_PER_CU = 160 * 1024;
 int launch_search(hnsw_gpu_index *ix, SearchWs *w, const float *d_queries, size_t q_stride, size_t nq, size_t ef, int mode,
 				  uint64_t *d_labels, uint32_t *d_idx, float *d_dists, uint32_t *d_counts, uint32_t *d_stats, hipStream_t stream,
-				  int rows = 0);          // rows: HNSW_GPU_ROWS_F16 / _BF16 = walk over the reduced copy (mode 1 only; hnsw_gpu_search_batch_reduced_dev)
+				  int rows = 0,           // rows: HNSW_GPU_ROWS_F16 / _BF16 = walk over the reduced copy (mode 1 only; hnsw_gpu_search_batch_reduced_dev)
+				  bool order = false);    // order: a batch entry point that runs large batches in locality order (device_order.h)
 int poll_limit_s();
 int poll_done_flag(const volatile uint32_t *flag, const char *what, SearchWs *w);
 int ws_search_ms(int device, SearchWs *w, unsigned back, float *ms);

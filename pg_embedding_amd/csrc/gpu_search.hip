@@ -1,6 +1,7 @@
 // gpu_search.hip — launch planning of the search kernels (csrc/device_search.h), the search entry points, one traced walk, search contexts
 // One translation unit of libhnsw_gpu.so (csrc/gpu_host.h lists them); gfx950 only, plain HIP runtime, no framework types in any signature.
 #include "gpu_host.h"
+#include "device_order.h"
 
 // ------------------------------------------------------------------------------------
 // search
@@ -51,9 +52,57 @@ static const size_t SET_BUDGET_BYTES = (size_t) 8 << 30;      // cap on the HBM 
 // device_search_wide.h; what bounds a beam is the per-slot scratch, 24 bytes per result slot, under SET_BUDGET_BYTES)
 static const size_t WIDE_EF_MIN = 2048;
 
+// Locality order of a large batch (device_order.h): batches of at least ORDER_MIN_NQ queries through a batch entry point
+// (hnsw_gpu_search_batch_dev, _batch_reduced_dev, the traced launch) run in the order of a device-side key, one permutation per launch.
+// Below it (one-query and small calls), and for streams, contexts, the host-pointer form, the build's own walks and the sharded paths,
+// the tickets are the caller's order as before.  HNSW_GPU_LOCALITY=0 forces the caller's order everywhere.
+// (threshold: profiles/locality_order_ceiling.json — on / off at 1M x 768: -12 % at 2 048 queries, -3.5 % at 4 096, +1.7 % at 8 192,
+// +2.7 % at 40 000; a batch about the size of the ~2 000 resident walks gains nothing from its order and pays the key)
+static const size_t ORDER_MIN_NQ = 8192;
+
+// keys + stable counting sort of `nq` queries on `stream`, into w->ord (pivots rebuilt first when a writer has touched the rows):
+// returns the permutation (device), or null on an error already reported
+static const uint32_t *build_order(hnsw_gpu_index *ix, SearchWs *w, const float *d_queries, size_t q_stride, size_t nq, hipStream_t stream)
+{
+	const uint32_t P = (uint32_t) std::min<size_t>(ORDER_PIVOTS, ix->n);
+	const uint32_t kd = std::min<uint32_t>(ORDER_DIMS, (uint32_t) ix->meta.dim);
+	if (!ix->piv)
+	{
+		if (hipMalloc(&ix->piv, ((size_t) ORDER_PIVOTS * ORDER_DIMS + ORDER_PIVOTS) * 4) != hipSuccess)
+		{ ix->piv = nullptr; fail(HNSW_GPU_ERR_NOMEM, "locality order: no room for the pivots"); return nullptr; }
+		ix->piv_valid = false;
+	}
+	uint32_t *rank = reinterpret_cast<uint32_t *>(ix->piv + (size_t) ORDER_PIVOTS * ORDER_DIMS);
+	if (!ix->piv_valid || ix->piv_n != ix->n || ix->piv_P != P || ix->piv_kd != kd)
+	{
+		hipLaunchKernelGGL(order_pivots_kernel, dim3((P * kd + 255) / 256), dim3(256), 0, stream, ix->vec, ix->stride, (uint32_t) ix->n, P, kd, ix->piv);
+		hipLaunchKernelGGL(order_rank_kernel, dim3(1), dim3(1024), ORDER_RANK_LDS, stream, ix->piv, P, kd, rank);
+		ix->piv_valid = true; ix->piv_n = ix->n; ix->piv_P = P; ix->piv_kd = kd;
+	}
+	const uint32_t nch = (uint32_t) ((nq + ORDER_CHUNK - 1) / ORDER_CHUNK);
+	const size_t hist_words = (size_t) P * nch;
+	const size_t words = 2 * nq + hist_words;
+	if (words > w->ord_words)
+	{
+		if (w->ord) (void) hipFree(w->ord);           // (hipFree waits for the launches still using it)
+		w->ord = nullptr; w->ord_words = 0;
+		if (hipMalloc(&w->ord, words * 4) != hipSuccess) { w->ord = nullptr; fail(HNSW_GPU_ERR_NOMEM, "locality order: no room for %zu keys", nq); return nullptr; }
+		w->ord_words = words;
+	}
+	uint32_t *key = w->ord, *perm = w->ord + nq, *hist = w->ord + 2 * nq;
+	hipLaunchKernelGGL(order_key_kernel, dim3((uint32_t) ((nq + ORDER_QT - 1) / ORDER_QT)), dim3(256), ORDER_KEY_LDS, stream, d_queries, (uint32_t) q_stride,
+					   (uint32_t) nq, ix->piv, rank, P, kd, key);
+	hipLaunchKernelGGL(order_hist_kernel, dim3(nch), dim3(256), ORDER_TABLE_LDS, stream, key, (uint32_t) nq, P, nch, hist);
+	hipLaunchKernelGGL(order_scan_kernel, dim3(1), dim3(1024), ORDER_TABLE_LDS, stream, hist, (uint32_t) hist_words);
+	hipLaunchKernelGGL(order_scatter_kernel, dim3(nch), dim3(64), ORDER_TABLE_LDS, stream, key, (uint32_t) nq, P, nch, hist, perm);
+	if (hipGetLastError() != hipSuccess) { fail(HNSW_GPU_ERR_HIP, "locality order: launch failed"); return nullptr; }
+	w->ord_perm_off = nq;
+	return perm;
+}
+
 int launch_search(hnsw_gpu_index *ix, SearchWs *w, const float *d_queries, size_t q_stride, size_t nq, size_t ef, int mode,
 						 uint64_t *d_labels, uint32_t *d_idx, float *d_dists, uint32_t *d_counts,
-						 uint32_t *d_stats, hipStream_t stream, int rows)
+						 uint32_t *d_stats, hipStream_t stream, int rows, bool order)
 {
 	std::unique_lock<std::recursive_mutex> lock_;
 	if (ix) lock_ = std::unique_lock<std::recursive_mutex>(ix->mu);
@@ -432,6 +481,16 @@ int launch_search(hnsw_gpu_index *ix, SearchWs *w, const float *d_queries, size_
 
 	const int evi = (int) (w->launches % SearchWs::EV_RING);
 	HIPCHK(hipEventRecord(w->ev0[evi], stream));
+	// locality order: the beam kernel's plain launches of a large batch (the key and the sort run inside the launch's event pair)
+	w->ord_nq = 0; w->ord_evals = nullptr;
+	if (order && rreg < 0 && !stream_launch && a.n > 0 && knob(K_LOCALITY, 1) != 0 &&
+		nq >= (size_t) std::max<long long>(1, knob(K_LOCALITY_MIN_NQ, (long long) ORDER_MIN_NQ)))
+	{
+		// (the order is only an optimisation: where it cannot be built — no memory for its buffers — the launch runs in the caller's order)
+		a.perm = build_order(ix, w, d_queries, q_stride, nq, stream);
+		if (a.perm) { w->ord_nq = (uint32_t) nq; w->ord_evals = a.out_evals; }
+		else (void) hipGetLastError();
+	}
 	// (a stream is resident by design: the library's watchdog does not time it — its host stops it, hnsw_gpu_stream_close)
 	__atomic_store_n(&w->busy_since_ms, stream_launch ? (int64_t) 0 : now_ms(), __ATOMIC_SEQ_CST);
 	hipLaunchKernelGGL(kern, dim3((uint32_t) blocks), dim3(wpb * 64), lds, stream, a);
@@ -445,6 +504,14 @@ int launch_search(hnsw_gpu_index *ix, SearchWs *w, const float *d_queries, size_
 extern "C" int hnsw_gpu_search_batch_dev(hnsw_gpu_index *ix, const coord_t *d_queries, size_t nq, size_t ef,
 										 label_t *d_labels, dist_t *d_dists, uint32_t *d_counts, uint32_t *d_stats,
 										 void *stream)
+{
+	return launch_search(ix, ix ? &ix->ws : nullptr, d_queries, ix ? ix->meta.dim : 0, nq, ef, 0, d_labels, nullptr, d_dists, d_counts, d_stats, (hipStream_t) stream,
+						 0, true);
+}
+
+extern "C" int hnsw_gpu_search_batch_caller_order_dev(hnsw_gpu_index *ix, const coord_t *d_queries, size_t nq, size_t ef,
+													  label_t *d_labels, dist_t *d_dists, uint32_t *d_counts, uint32_t *d_stats,
+													  void *stream)
 {
 	return launch_search(ix, ix ? &ix->ws : nullptr, d_queries, ix ? ix->meta.dim : 0, nq, ef, 0, d_labels, nullptr, d_dists, d_counts, d_stats, (hipStream_t) stream);
 }
@@ -479,8 +546,8 @@ static int reduced_form_check(hnsw_gpu_index *ix, int format, size_t ef)
 	return HNSW_GPU_OK;
 }
 
-extern "C" int hnsw_gpu_search_batch_reduced_dev(hnsw_gpu_index *ix, int format, const coord_t *d_queries, size_t nq, size_t ef,
-												 label_t *d_labels, dist_t *d_dists, uint32_t *d_counts, uint32_t *d_stats, void *stream)
+static int search_batch_reduced(hnsw_gpu_index *ix, int format, const coord_t *d_queries, size_t nq, size_t ef,
+								label_t *d_labels, dist_t *d_dists, uint32_t *d_counts, uint32_t *d_stats, void *stream, bool order)
 {
 	std::unique_lock<std::recursive_mutex> lock_;
 	if (ix) lock_ = std::unique_lock<std::recursive_mutex>(ix->mu);
@@ -519,7 +586,7 @@ extern "C" int hnsw_gpu_search_batch_reduced_dev(hnsw_gpu_index *ix, int format,
 	}
 	int rc = rows16_sync(ix, s);
 	if (rc) return rc;
-	rc = launch_search(ix, &ix->ws, d_queries, ix->meta.dim, nq, ef, 1, nullptr, ix->rr_cand, nullptr, d_counts, d_stats, s, format);
+	rc = launch_search(ix, &ix->ws, d_queries, ix->meta.dim, nq, ef, 1, nullptr, ix->rr_cand, nullptr, d_counts, d_stats, s, format, order);
 	if (rc) return rc;
 	r.vec = ix->vec; r.labels = ix->labels;
 	r.stride = ix->stride; r.nchunks = nchunks; r.kiters = kiters; r.dim = (uint32_t) ix->meta.dim;
@@ -540,6 +607,12 @@ extern "C" int hnsw_gpu_search_batch_reduced_dev(hnsw_gpu_index *ix, int format,
 		HIPCHK(hipEventRecord(w->ev1[evi], s));
 	}
 	return HNSW_GPU_OK;
+}
+
+extern "C" int hnsw_gpu_search_batch_reduced_dev(hnsw_gpu_index *ix, int format, const coord_t *d_queries, size_t nq, size_t ef,
+												 label_t *d_labels, dist_t *d_dists, uint32_t *d_counts, uint32_t *d_stats, void *stream)
+{
+	return search_batch_reduced(ix, format, d_queries, nq, ef, d_labels, d_dists, d_counts, d_stats, stream, true);
 }
 
 extern "C" int hnsw_gpu_search_batch_reduced(hnsw_gpu_index *ix, int format, const coord_t *queries, size_t nq, size_t ef,
@@ -564,7 +637,7 @@ extern "C" int hnsw_gpu_search_batch_reduced(hnsw_gpu_index *ix, int format, con
 	float *dq = (float *) p; uint64_t *dl = (uint64_t *) (p + qb); float *dd = (float *) (p + qb + lb);
 	uint32_t *dc = (uint32_t *) (p + qb + lb + db);
 	HIPCHK(hipMemcpy(dq, queries, nq * dim * 4, hipMemcpyHostToDevice));
-	rc = hnsw_gpu_search_batch_reduced_dev(ix, format, dq, nq, ef, dl, dd, dc, nullptr, nullptr);
+	rc = search_batch_reduced(ix, format, dq, nq, ef, dl, dd, dc, nullptr, nullptr, false);     // (host-pointer form: the caller's order)
 	if (rc) return rc;
 	// (the outputs are filled only when every query has its result)
 	std::vector<uint32_t> c(nq);

@@ -42,10 +42,10 @@ struct KnobDef { const char *name; bool env; };
 static const KnobDef g_knob_def[K_COUNT] = {
 	{ "HNSW_GPU_BEAM", true }, { "HNSW_GPU_FORCE_LDS_HEAPS", true }, { "HNSW_GPU_TEAM", true }, { "HNSW_GPU_TEAM_MAX_NQ", true },
 	{ "HNSW_GPU_WIDE_EF_MIN", true }, { "HNSW_GPU_REF_ORDER", true }, { "HNSW_GPU_NO_POLL", true }, { "HNSW_GPU_POLL_LIMIT_S", true },
-	{ "HNSW_GPU_INSERT_FUSED", true }, { "HNSW_GPU_BLOCKS_PER_CU", true }, { "HNSW_GPU_STREAM_LIGHT", true },
+	{ "HNSW_GPU_INSERT_FUSED", true }, { "HNSW_GPU_BLOCKS_PER_CU", true }, { "HNSW_GPU_STREAM_LIGHT", true }, { "HNSW_GPU_LOCALITY", true },
 	{ "HNSW_GPU_BEAM16", false }, { "HNSW_GPU_NARROW5", false }, { "HNSW_GPU_LEAN", false }, { "HNSW_GPU_HASH_ENTRIES", false }, { "HNSW_GPU_LDS_SET_MIN_WAVES", false },
 	{ "HNSW_GPU_TEAM_SPEC", false }, { "HNSW_GPU_TEAM_WPB", false }, { "HNSW_GPU_NARROW_WPB", false }, { "HNSW_GPU_ABORT_POLL_LOG2", false }, { "HNSW_GPU_MAX_BLOCKS", false }, { "HNSW_GPU_SHARDED_NO_PEER", false },
-	{ "HNSW_GPU_BF_BIG_MIN_BLOCKS", false },
+	{ "HNSW_GPU_BF_BIG_MIN_BLOCKS", false }, { "HNSW_GPU_LOCALITY_MIN_NQ", false },
 #ifdef HNSW_EXPERIMENT
 	{ "HNSW_GPU_WIDE_WAVES", false }, { "HNSW_GPU_SHAPE_12X1", false }, { "HNSW_GPU_TEAM_MAINS", false }, { "HNSW_GPU_TEAM_COUNTERS", false },
 #endif
@@ -232,6 +232,7 @@ void ws_free(SearchWs *w)
 	if (w->vlog) (void) hipFree(w->vlog);
 	if (w->team_dbg) (void) hipFree(w->team_dbg);
 	if (w->ticket) (void) hipFree(w->ticket);
+	if (w->ord) (void) hipFree(w->ord);
 	for (int i = 0; i < SearchWs::EV_RING; i++)
 	{
 		if (w->ev0[i]) (void) hipEventDestroy(w->ev0[i]);
@@ -347,6 +348,7 @@ extern "C" void hnsw_gpu_index_destroy(hnsw_gpu_index *ix)
 	if (ix->hb1) (void) hipEventDestroy(ix->hb1);
 	if (ix->rows16) (void) hipFree(ix->rows16);
 	if (ix->r16x) (void) hipFree(ix->r16x);
+	if (ix->piv) (void) hipFree(ix->piv);
 	if (ix->rr_cand) (void) hipFree(ix->rr_cand);
 	if (ix->rr_e0) (void) hipEventDestroy(ix->rr_e0);
 	if (ix->rr_e1) (void) hipEventDestroy(ix->rr_e1);
@@ -681,6 +683,7 @@ extern "C" int hnsw_gpu_index_reserve(hnsw_gpu_index *ix, size_t capacity)
 	if (ix->ws.vlog) (void) hipFree(ix->ws.vlog);
 	ix->ws.vis = nullptr; ix->ws.vlog = nullptr; ix->ws.vis_slots = 0; ix->ws.vis_words = 0;
 	ix->generation++;         // contexts notice and rebuild their bitmaps
+	ix->piv_valid = false;    // (the rows did not change; the locality order's pivots are rebuilt all the same)
 	return HNSW_GPU_OK;
 }
 

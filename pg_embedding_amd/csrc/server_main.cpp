@@ -50,6 +50,10 @@
 
 #include "hgs_io.h"
 #include "hnsw_gpu.h"
+// (weak: the server's CPU test double of the library has no locality order and so no caller-order entry point; the shard search then
+// takes hnsw_gpu_search_batch_dev, which in that double is the caller's order too)
+extern "C" int hnsw_gpu_search_batch_caller_order_dev(hnsw_gpu_index *, const coord_t *, size_t, size_t, label_t *, dist_t *, uint32_t *,
+													  uint32_t *, void *) __attribute__((weak));
 
 namespace {
 
@@ -1585,8 +1589,10 @@ void do_control(CReq &r)
 		int rc;
 		float ms = 0.f;
 		e->begin_read();
-		rc = hnsw_gpu_search_batch_dev(e->ix, (const coord_t *) pin.p, nq, ef, (label_t *) ((char *) r.c->shard_buf + off_l),
-									   (dist_t *) ((char *) r.c->shard_buf + off_d), (uint32_t *) ((char *) pin.p + qb), nullptr, nullptr);
+		// (a shard of the front's search: the caller's order — the locality order's key would read the queries from pinned host memory
+		// in front of the walk and only add to this batch's latency)
+		rc = (hnsw_gpu_search_batch_caller_order_dev ? hnsw_gpu_search_batch_caller_order_dev : hnsw_gpu_search_batch_dev)(e->ix, (const coord_t *) pin.p, nq, ef, (label_t *) ((char *) r.c->shard_buf + off_l),
+													(dist_t *) ((char *) r.c->shard_buf + off_d), (uint32_t *) ((char *) pin.p + qb), nullptr, nullptr);
 		if (rc == HNSW_GPU_OK) rc = hnsw_gpu_last_search_ms(e->ix, &ms);      // (waits for the launch: the lists are in the front's memory)
 		e->end_read();
 		e->last_used.store(now_ns());

@@ -261,16 +261,19 @@ class GpuIndex:
         return labels[:cnt.value], dists[:cnt.value], pops[:have].copy(), int(nev.value), polls
 
     def search_torch(self, queries, ef: Optional[int] = None, out=None, stats: bool = False, base: bool = False,
-                     rows: Optional[str] = None):
+                     rows: Optional[str] = None, order: bool = True):
         """Same with everything resident in HBM (torch tensors only carry the pointers).
         `out` may be a dict from a previous call to reuse its buffers.  With base=True runs
         searchBaseLayer only and returns element numbers under 'idx'.  rows="f16" | "bf16": the reduced-row
-        walk + exact fp32 re-rank (not with base=True: the base walk has no re-rank)."""
+        walk + exact fp32 re-rank (not with base=True: the base walk has no re-rank).  order=False: the caller's order whatever the batch
+        size (hnsw_gpu_search_batch_caller_order_dev; fp32 rows only) — large batches otherwise run in locality order."""
         torch = _torch()
         ef = int(ef or self.meta.efSearch)
         code = _rows_code(rows)
         if code and base:
             raise ValueError("rows= cannot be combined with base=True (the base walk has no re-rank)")
+        if code and not order:
+            raise ValueError("order=False is for fp32 rows (hnsw_gpu_search_batch_caller_order_dev)")
         assert queries.is_cuda and queries.dtype == torch.float32 and queries.is_contiguous()
         nq = queries.shape[0]
         dev = queries.device
@@ -292,6 +295,10 @@ class GpuIndex:
             check(self.L.hnsw_gpu_search_batch_reduced_dev(self._h, code, queries.data_ptr(), nq, ef, out["labels"].data_ptr(),
                                                            out["dists"].data_ptr(), out["counts"].data_ptr(),
                                                            _dptr(out.get("stats")), s), "hnsw_gpu_search_batch_reduced_dev")
+        elif not order:
+            check(self.L.hnsw_gpu_search_batch_caller_order_dev(self._h, queries.data_ptr(), nq, ef, out["labels"].data_ptr(),
+                                                                out["dists"].data_ptr(), out["counts"].data_ptr(),
+                                                                _dptr(out.get("stats")), s), "hnsw_gpu_search_batch_caller_order_dev")
         else:
             check(self.L.hnsw_gpu_search_batch_dev(self._h, queries.data_ptr(), nq, ef, out["labels"].data_ptr(),
                                                    out["dists"].data_ptr(), out["counts"].data_ptr(),
@@ -398,6 +405,19 @@ class GpuIndex:
         out = {k: (int(v[2 * i]), int(v[2 * i + 1])) for i, k in enumerate(names)}
         out["aligned_2MiB"] = all(out[k][0] % (2 << 20) == 0 for k in ("rows", "links", "labels"))
         return out
+
+    def last_search_order(self, keys: bool = False):
+        """The locality order of the last search launch of the default workspace (hnsw_gpu_last_search_order): None when it ran in
+        the caller's order, else an int64 array perm (ticket t walked query perm[t]); keys=True: (perm, the queries' sort keys)."""
+        import numpy as np
+        n = C.c_size_t(0)
+        check(self.L.hnsw_gpu_last_search_order(self._h, None, None, 0, C.byref(n)), "hnsw_gpu_last_search_order")
+        if n.value == 0:
+            return None
+        perm = np.empty(n.value, np.uint32)
+        key = np.empty(n.value, np.uint32)
+        check(self.L.hnsw_gpu_last_search_order(self._h, perm.ctypes.data, key.ctypes.data, n.value, C.byref(n)), "hnsw_gpu_last_search_order")
+        return (perm.astype(np.int64), key.astype(np.int64)) if keys else perm.astype(np.int64)
 
     def last_search_slots(self) -> int:
         v = C.c_uint32(0)

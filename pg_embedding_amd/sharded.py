@@ -82,7 +82,7 @@ class ShardedIndex:
                 raise ValueError("need a GpuIndex or a local_search callable")
 
             def local_search(q, ef, out=None):
-                res = index.search_torch(q, ef, out=out)
+                res = index.search_torch(q, ef, out=out, order=False)       # (a shard of a larger search: the caller's order)
                 return res["labels"], res["dists"]
             local_search.writes_in_place = True          # (takes `out`: labels / dists / counts tensors to write into)
         self.merge_packed = None
