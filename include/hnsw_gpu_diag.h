@@ -47,6 +47,10 @@ int hnsw_gpu_replay_roof(hnsw_gpu_index *ix, const idx_t *d_evals, size_t evals_
  * queries than resident waves in which `parts` waves share the rows of one walk (parts = 1: the call above). */
 int hnsw_gpu_replay_roof_parts(hnsw_gpu_index *ix, const idx_t *d_evals, size_t evals_cap, const uint32_t *d_stats, size_t nq,
                                unsigned slots, int kb, int rpg, unsigned parts, float *ms, double *bytes, uint64_t *word_sum);
+/* ... with the trace in its own row order and its tickets dealt per XCD in chunks of `chunk` queries (a power of two, 2..65536), as
+ * the search deals an ordered batch, or with chunk = 0 by one global ticket. */
+int hnsw_gpu_replay_roof_dealt(hnsw_gpu_index *ix, const idx_t *d_evals, size_t evals_cap, const uint32_t *d_stats, size_t nq,
+                               unsigned slots, int kb, int rpg, unsigned chunk, float *ms, double *bytes, uint64_t *word_sum);
 
 /* Shader clock (MHz) the most recent search launch of the mirror's default workspace ran at: shader-clock ticks over ticks of
  * the constant 100 MHz clock, both read by the launch's first wave when it starts and when it leaves (waits for the launch).
@@ -56,7 +60,7 @@ int hnsw_gpu_last_search_clock_mhz(hnsw_gpu_index *ix, double *mhz);
 
 /* Where the mirror and its default search workspace sit in the device's address space: out[2*i] = device address, out[2*i+1] =
  * bytes, for i = 0 arena (one allocation holding rows | links | labels, each on a 2 MiB boundary), 1 rows, 2 links, 3 labels,
- * 4 visited bitmaps, 5 bitmap logs, 6 prune scratch of the beam form, 7 ticket word.  `out` holds 16 values. */
+ * 4 visited bitmaps, 5 bitmap logs, 6 prune scratch of the beam form, 7 ticket words.  `out` holds 16 values. */
 int hnsw_gpu_index_placement(hnsw_gpu_index *ix, uint64_t *out16);
 
 /* Shader clock (MHz) a block of the MFMA filter kernel of the last hnsw_gpu_bruteforce_mfma_dev call saw over its K loop:
@@ -85,6 +89,9 @@ int hnsw_gpu_index_export_reduced_rows(hnsw_gpu_index *ix, uint16_t *out);
  * hnsw_gpu_last_search_ms spans the walk AND the re-rank: the walk alone is the difference. */
 int hnsw_gpu_last_rerank_ms(hnsw_gpu_index *ix, float *ms);
 
+/* The chunk C in which the most recent launch of the mirror's default workspace dealt its ordered batch per XCD, or 0 when
+ * it took its queries from one global ticket (a launch in the caller's order, or HNSW_GPU_XCD_TICKETS=0). */
+int hnsw_gpu_last_search_chunk(hnsw_gpu_index *ix, uint32_t *chunk);
 /* The locality order of the last search launch of the mirror's default workspace (hnsw_gpu_search_batch_dev): *nq = the queries
  * it ran in that order (0 = it ran in the caller's order: a small batch, a base / one-query / host-pointer / caller-order call,
  * HNSW_GPU_LOCALITY=0), perm[t] = the query ticket t walked and keys[i] = the sort key of query i (t, i < min(*nq, cap); perm and

@@ -135,6 +135,7 @@ def gpu_lib():
     L.hnsw_gpu_search_ms.argtypes = [vp, C.c_uint, _f32p]
     L.hnsw_gpu_last_search_slots.argtypes = [vp, _u32p]
     L.hnsw_gpu_last_search_order.argtypes = [vp, vp, vp, sz, C.POINTER(C.c_size_t)]
+    L.hnsw_gpu_last_search_chunk.argtypes = [vp, C.POINTER(C.c_uint32)]
     L.hnsw_gpu_index_health.argtypes = [vp, _u32p]
     L.hnsw_gpu_index_insert_one.argtypes = [vp, vp, C.c_uint64, C.c_uint32, vp, vp]
     L.hnsw_gpu_index_insert_candidates.argtypes = [vp, vp, C.c_uint64, C.c_uint32, vp, vp, C.c_uint32, vp, vp]
@@ -145,6 +146,7 @@ def gpu_lib():
     L.hnsw_gpu_search_traced_dev.argtypes = [vp, vp, sz, sz, vp, vp, vp, vp, vp, sz, vp, vp]
     L.hnsw_gpu_replay_roof.argtypes = [vp, vp, sz, vp, sz, C.c_uint, i32, i32, _f32p, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
     L.hnsw_gpu_replay_roof_parts.argtypes = [vp, vp, sz, vp, sz, C.c_uint, i32, i32, C.c_uint, _f32p, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
+    L.hnsw_gpu_replay_roof_dealt.argtypes = [vp, vp, sz, vp, sz, C.c_uint, i32, i32, C.c_uint, _f32p, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
     L.hnsw_gpu_index_abort.argtypes = [vp]
     L.hnsw_gpu_abort_all.restype = i32
     L.hnsw_gpu_ctx_create.argtypes = [vp, C.POINTER(vp)]

@@ -7,6 +7,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "device_tickets.h"
 
 namespace pgemb {
 
@@ -61,11 +62,14 @@ __global__ __launch_bounds__(256) void gather_roof_kernel(const float4 *__restri
 // CHECK (tests only): also sums the bit patterns of every word the trace asks for (mod 2^64, order-free) into *check, so a test
 // can tell that the replay read exactly the traced rows, whole.
 // perm: null, or the locality order the traced launch ran in (device_order.h): ticket t replays query perm[t], as the search did.
+// log2c: 0 = one global ticket; else the tickets are dealt per XCD in chunks of 1 << log2c (device_tickets.h; `ticket` then holds
+// XCD_TICKETS counters), as the search deals an ordered launch.
 constexpr uint32_t REPLAY_STAGE = 512;
 template <int KB, int RPG, bool CHECK>
 __global__ __launch_bounds__(256) void replay_roof_kernel(const float4 *__restrict__ base, uint32_t row_f4, const uint32_t *__restrict__ evals,
 														   uint32_t evals_cap, const uint32_t *__restrict__ nevals, uint32_t nq, uint32_t parts,
-														   uint32_t *ticket, float *out, unsigned long long *check, const uint32_t *__restrict__ perm)
+														   uint32_t *ticket, float *out, unsigned long long *check, const uint32_t *__restrict__ perm,
+														   uint32_t log2c)
 {
 	// row ids staged in LDS, REPLAY_STAGE at a time (the search kernel has its ids in LDS too: a pass must not wait for an id
 	// load before it can issue its row loads); dynamic LDS: 4 waves x REPLAY_STAGE x 4 bytes
@@ -82,8 +86,12 @@ __global__ __launch_bounds__(256) void replay_roof_kernel(const float4 *__restri
 		// (parts > 1: a query's trace is cut into `parts` equal pieces that different waves gather — the roof of a launch in which
 		// `parts` waves share one walk's rows, i.e. of fewer queries than resident waves)
 		uint32_t tk = 0;
-		if (lane == 0) tk = atomicAdd(ticket, 1u);
-		tk = __builtin_amdgcn_readfirstlane(tk);
+		if (log2c) tk = xcd_ticket_claim(ticket, nq * parts, log2c, lane);
+		else
+		{
+			if (lane == 0) tk = atomicAdd(ticket, 1u);
+			tk = __builtin_amdgcn_readfirstlane(tk);
+		}
 		if (tk >= nq * parts) break;
 		const uint32_t tq = tk / parts, part = tk - tq * parts;
 		const uint32_t qi = perm ? perm[tq] : tq;            // (the traced launch's locality order, if it had one)

@@ -48,6 +48,7 @@
 #include <type_traits>
 #include "device_dist.h"
 #include "device_rows16.h"
+#include "device_tickets.h"
 
 namespace pgemb {
 
@@ -103,6 +104,7 @@ struct SearchArgs
 	uint32_t tm_spec;           // helpers of rank < tm_spec speculate (packages); the others score slices of the walking wave's rows
 	const uint32_t *abort_word; // null, or the workspace's abort word in pinned host memory (banner at abort_requested)
 	uint32_t abort_mask;        // a wave looks at the abort word at the top of query number qi when (qi & abort_mask) == 0: every 16th by default
+	                            // (ordered launches: qi = the position in the ordered batch)
 	uint32_t *health;           // HEALTH_WORDS device words: time-out and abort counters of the workspace
 	uint32_t *team_dbg;         // null, or 16 counters for the whole launch (hnsw_gpu_team_counters): hops with helpers,
 	                            // link-list hits, ids looked up, distance hits, hops that still scored rows, all hops
@@ -117,6 +119,8 @@ struct SearchArgs
 	uint32_t rstride4, nblk;
 	// locality order (beam kernel, plain launches only; device_order.h): null, or nq query numbers — ticket t walks query perm[t]
 	const uint32_t *perm;
+	uint32_t xcd_log2c;           // with perm: 0 = one global ticket, else log2 of the chunk C of per-XCD dealing (device_tickets.h; the ticket
+	                              // buffer then holds XCD_TICKETS counters)
 };
 
 // Abort word + health words of a search workspace.
@@ -1834,9 +1838,14 @@ __global__ __launch_bounds__(TEAM ? 512 : 256, (UREG >= 16 && SH::MIN_WAVES > 2)
 	{
 		ColdArgs c = cold_args(a);                                    // this query's cold arguments: loaded here, dead before the walk
 		if (TEAM && wib >= c->team_mains) break;                      // this wave only ever helps
+		const uint32_t log2c = stream ? 0u : c->xcd_log2c;
 		uint32_t qi = 0;
-		if (lane == 0) qi = atomicAdd(c->ticket, 1u);
-		qi = __builtin_amdgcn_readfirstlane(qi);
+		if (log2c) qi = xcd_ticket_claim(c->ticket, c->nq, log2c, (uint32_t) lane);   // (a position of the ordered batch, or nq)
+		else
+		{
+			if (lane == 0) qi = atomicAdd(c->ticket, 1u);
+			qi = __builtin_amdgcn_readfirstlane(qi);
+		}
 		if (stream)
 		{
 			bool leave = false;
@@ -1864,7 +1873,8 @@ __global__ __launch_bounds__(TEAM ? 512 : 256, (UREG >= 16 && SH::MIN_WAVES > 2)
 		else if (qi >= c->nq) break;
 		// (an abort request is sticky for this wave: it takes the remaining tickets without walking and marks every query it does not
 		// answer with count 0xFFFFFFFF, so that the caller of an interrupted launch can tell which rows of its outputs are results)
-		// (the gate counts tickets, so that how often a launch looks does not depend on its order)
+		// (the gate counts tickets, so that how often a launch looks does not depend on its order; a launch dealt per XCD counts the
+		// positions of the ordered batch, one per query as well: nq / 16 looks either way)
 		if (!aborted && (qi & c->abort_mask) == 0u && abort_word_set(c->abort_word)) aborted = true;
 		// Locality order (device_order.h): ticket qi walks query perm[qi].  One load per query; from here on qi is the query number —
 		// its input, every output and its clock stamps (and the walking wave's LDS image of it, all a helper ever reads)

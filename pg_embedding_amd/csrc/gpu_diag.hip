@@ -87,10 +87,30 @@ extern "C" int hnsw_gpu_replay_roof(hnsw_gpu_index *ix, const idx_t *d_evals, si
 	return hnsw_gpu_replay_roof_parts(ix, d_evals, evals_cap, d_stats, nq, slots, kb, rpg, 1, ms, bytes, word_sum);
 }
 
+// log2c < 0: the tickets are dealt as the traced launch dealt them when d_evals is its trace, else by one global ticket; 0: one global
+// ticket; > 0: per XCD in chunks of 1 << log2c (device_tickets.h)
+static int replay_roof(hnsw_gpu_index *ix, const idx_t *d_evals, size_t evals_cap, const uint32_t *d_stats, size_t nq, unsigned slots, int kb,
+					   int rpg, unsigned parts, int log2c, float *ms, double *bytes, uint64_t *word_sum);
+
 // The same with every query's trace cut into `parts` equal pieces gathered by different waves: the roof of a launch that gives one
 // walk's rows to `parts` waves (fewer queries than resident waves).
 extern "C" int hnsw_gpu_replay_roof_parts(hnsw_gpu_index *ix, const idx_t *d_evals, size_t evals_cap, const uint32_t *d_stats, size_t nq,
 										  unsigned slots, int kb, int rpg, unsigned parts, float *ms, double *bytes, uint64_t *word_sum)
+{
+	return replay_roof(ix, d_evals, evals_cap, d_stats, nq, slots, kb, rpg, parts, -1, ms, bytes, word_sum);
+}
+
+// The trace in its own row order, its tickets dealt per XCD in chunks of `chunk` (a power of two) or, with chunk 0, by one global
+// ticket: what per-XCD dealing gives an ordered batch (scripts/exp_xcd_tickets.py)
+extern "C" int hnsw_gpu_replay_roof_dealt(hnsw_gpu_index *ix, const idx_t *d_evals, size_t evals_cap, const uint32_t *d_stats, size_t nq,
+										  unsigned slots, int kb, int rpg, unsigned chunk, float *ms, double *bytes, uint64_t *word_sum)
+{
+	if (chunk == 1 || chunk > 65536 || (chunk & (chunk - 1))) return fail(HNSW_GPU_ERR_ARG, "chunk must be 0 or a power of two 2..65536");
+	return replay_roof(ix, d_evals, evals_cap, d_stats, nq, slots, kb, rpg, 1, chunk ? __builtin_ctz(chunk) : 0, ms, bytes, word_sum);
+}
+
+static int replay_roof(hnsw_gpu_index *ix, const idx_t *d_evals, size_t evals_cap, const uint32_t *d_stats, size_t nq, unsigned slots, int kb,
+					   int rpg, unsigned parts, int log2c, float *ms, double *bytes, uint64_t *word_sum)
 {
 	std::unique_lock<std::recursive_mutex> lock_;
 	if (ix) lock_ = std::unique_lock<std::recursive_mutex>(ix->mu);
@@ -113,16 +133,28 @@ extern "C" int hnsw_gpu_replay_roof_parts(hnsw_gpu_index *ix, const idx_t *d_eva
 	// that launch ran in locality order (hnsw_gpu_search_traced_dev orders a large batch as hnsw_gpu_search_batch_dev does), its perm;
 	// any other buffer (an older trace, a copy, a permuted trace) is replayed in its own row order
 	const uint32_t *perm = (ix->ws.ord_nq == nq && ix->ws.ord_evals && ix->ws.ord_evals == d_evals) ? ix->ws.ord + ix->ws.ord_perm_off : nullptr;
+	// ... and its tickets are dealt as that launch dealt them (the same counters and chunk: per-XCD dealing places a region's walks
+	// on one L2, and a replay dealt otherwise would not be the roof of that launch)
+	// (parts > 1 — several waves per query — is no launch the search deals; positions are 32-bit below XCD_TICKETS_MAX_NQ tickets)
+	const uint32_t lc = log2c >= 0 ? (uint32_t) log2c : (perm && parts == 1 ? ix->ws.ord_log2c : 0u);
+	uint32_t *counters = nullptr;
+	if (lc && nq * (size_t) parts >= XCD_TICKETS_MAX_NQ) rc = fail(HNSW_GPU_ERR_ARG, "dealt replay: at most %u tickets", XCD_TICKETS_MAX_NQ - 1);
+	else if (lc)
+	{
+		if (hipMalloc(&counters, XCD_TICKET_BYTES) != hipSuccess) rc = fail(HNSW_GPU_ERR_NOMEM, "replay roof: no room for the ticket counters");
+		else ticket = counters;
+	}
 	for (int rep = 0; rep < 4 && rc == HNSW_GPU_OK; rep++)
 	{
-		(void) hipMemsetAsync(ticket, 0, 16, nullptr);           // ticket + the (test-only) word sum behind it
+		(void) hipMemsetAsync(ix->misc + 12, 0, 16, nullptr);    // ticket + the (test-only) word sum behind it
+		if (counters) (void) hipMemsetAsync(counters, 0, XCD_TICKET_BYTES, nullptr);
 		(void) hipEventRecord(e0, nullptr);
 		const float4 *base = (const float4 *) ix->vec;
 		switch (shape)
 		{
 #define ROOF(K, R) case K * 100 + R: \
-				if (word_sum) hipLaunchKernelGGL((replay_roof_kernel<K, R, true>), dim3(blocks), dim3(256), 4 * REPLAY_STAGE * 4, nullptr, base, row_f4, d_evals, (uint32_t) evals_cap, d_stats, (uint32_t) nq, (uint32_t) parts, ticket, out, d_check, perm); \
-				else hipLaunchKernelGGL((replay_roof_kernel<K, R, false>), dim3(blocks), dim3(256), 4 * REPLAY_STAGE * 4, nullptr, base, row_f4, d_evals, (uint32_t) evals_cap, d_stats, (uint32_t) nq, (uint32_t) parts, ticket, out, d_check, perm); \
+				if (word_sum) hipLaunchKernelGGL((replay_roof_kernel<K, R, true>), dim3(blocks), dim3(256), 4 * REPLAY_STAGE * 4, nullptr, base, row_f4, d_evals, (uint32_t) evals_cap, d_stats, (uint32_t) nq, (uint32_t) parts, ticket, out, d_check, perm, lc); \
+				else hipLaunchKernelGGL((replay_roof_kernel<K, R, false>), dim3(blocks), dim3(256), 4 * REPLAY_STAGE * 4, nullptr, base, row_f4, d_evals, (uint32_t) evals_cap, d_stats, (uint32_t) nq, (uint32_t) parts, ticket, out, d_check, perm, lc); \
 				break
 			ROOF(2, 2); ROOF(2, 4); ROOF(2, 8); ROOF(4, 2); ROOF(4, 4); ROOF(8, 2); ROOF(12, 1); ROOF(12, 2); ROOF(6, 4);
 #undef ROOF
@@ -137,6 +169,7 @@ extern "C" int hnsw_gpu_replay_roof_parts(hnsw_gpu_index *ix, const idx_t *d_eva
 	}
 	(void) hipEventDestroy(e0);
 	(void) hipEventDestroy(e1);
+	if (counters) (void) hipFree(counters);
 	if (rc) return rc;
 	*ms = best;
 	if (word_sum) HIPCHK(hipMemcpy(word_sum, d_check, 8, hipMemcpyDeviceToHost));   // of the last repetition
@@ -185,7 +218,7 @@ extern "C" int hnsw_gpu_index_placement(hnsw_gpu_index *ix, uint64_t *out16)
 		(uint64_t) (uintptr_t) w.vis, w.vis_slots * w.vis_words * 4,
 		(uint64_t) (uintptr_t) w.vlog, w.vis_slots * (size_t) w.logcap * 4,
 		(uint64_t) (uintptr_t) w.beam, w.beam_keys * 8,
-		(uint64_t) (uintptr_t) w.ticket, 64 };
+		(uint64_t) (uintptr_t) w.ticket, XCD_TICKET_BYTES };
 	memcpy(out16, v, sizeof(v));
 	return HNSW_GPU_OK;
 }
@@ -200,6 +233,14 @@ extern "C" int hnsw_gpu_last_rerank_ms(hnsw_gpu_index *ix, float *ms)
 	HIPCHK(hipSetDevice(ix->device));
 	HIPCHK(hipEventSynchronize(ix->rr_e1));
 	HIPCHK(hipEventElapsedTime(ms, ix->rr_e0, ix->rr_e1));
+	return HNSW_GPU_OK;
+}
+
+extern "C" int hnsw_gpu_last_search_chunk(hnsw_gpu_index *ix, uint32_t *chunk)
+{
+	if (!ix || !chunk) return fail(HNSW_GPU_ERR_ARG, "NULL argument");
+	std::lock_guard<std::recursive_mutex> g(ix->mu);
+	*chunk = ix->ws.ord_log2c ? 1u << ix->ws.ord_log2c : 0u;
 	return HNSW_GPU_OK;
 }
 

@@ -53,7 +53,7 @@ enum Knob : int
 {
 	// operational (environment, read once)
 	K_BEAM, K_FORCE_LDS_HEAPS, K_TEAM, K_TEAM_MAX_NQ, K_WIDE_EF_MIN, K_REF_ORDER, K_NO_POLL, K_POLL_LIMIT_S, K_INSERT_FUSED,
-	K_BLOCKS_PER_CU, K_STREAM_LIGHT, K_LOCALITY,
+	K_BLOCKS_PER_CU, K_STREAM_LIGHT, K_LOCALITY, K_XCD_TICKETS,
 	// test knobs (hnsw_gpu_config_set only)
 	K_BEAM16, K_NARROW5, K_LEAN, K_HASH_ENTRIES, K_LDS_SET_MIN_WAVES, K_TEAM_SPEC, K_TEAM_WPB, K_NARROW_WPB, K_ABORT_POLL_LOG2, K_MAX_BLOCKS, K_SHARDED_NO_PEER, K_BF_BIG_MIN_BLOCKS, K_LOCALITY_MIN_NQ,
 #ifdef HNSW_EXPERIMENT
@@ -106,6 +106,7 @@ struct SearchWs
 	// this workspace ran in that order (0 = the caller's order), its perm at ord + ord_perm_off
 	uint32_t *ord = nullptr; size_t ord_words = 0;
 	uint32_t ord_nq = 0; size_t ord_perm_off = 0;
+	uint32_t ord_log2c = 0;                              // and how its tickets were dealt (SearchArgs::xcd_log2c)
 	const uint32_t *ord_evals = nullptr;                 // the evaluation trace that launch wrote (traced launches), else null
 };
 
@@ -113,6 +114,7 @@ extern std::mutex &g_ws_mu;                              // guards the registry 
 int64_t now_ms();
 int abort_ws_locked(SearchWs *w);                        // g_ws_mu held
 int ws_init(SearchWs *w);
+uint32_t xcd_chunk_log2(size_t nq);                     // per-XCD dealing of an ordered launch (gpu_search.hip)
 void ws_free(SearchWs *w);
 
 // ---- the device mirror ------------------------------------------------------------------------

@@ -60,6 +60,19 @@ static const size_t WIDE_EF_MIN = 2048;
 // +2.7 % at 40 000; a batch about the size of the ~2 000 resident walks gains nothing from its order and pays the key)
 static const size_t ORDER_MIN_NQ = 8192;
 
+// Per-XCD dealing of an ordered launch's tickets (device_tickets.h): log2 of the chunk C, or 0 for one global ticket.
+// C is the largest power of two <= nq / 128, within 32 .. 512: every counter deals at least ~16 chunks, so that the end of the launch,
+// where waves steal from foreign counters, is no longer than with one ticket (profiles/xcd_tickets_ceiling.md, 1M x 768: best C 256-512
+// at 40 000 queries, 64-128 at 8 192).  HNSW_GPU_XCD_TICKETS=0 forces the global ticket; a value of 2 or more forces that chunk (rounded down
+// to a power of two; measurement and tests).
+uint32_t xcd_chunk_log2(size_t nq)
+{
+	const long long k = knob(K_XCD_TICKETS, 1);
+	if (k <= 0 || nq >= XCD_TICKETS_MAX_NQ) return 0;
+	const unsigned long long c = k >= 2 ? (unsigned long long) k : std::min<unsigned long long>(512, std::max<unsigned long long>(32, nq / 128));
+	return std::min<uint32_t>(16, 63 - (uint32_t) __builtin_clzll(c));
+}
+
 // keys + stable counting sort of `nq` queries on `stream`, into w->ord (pivots rebuilt first when a writer has touched the rows):
 // returns the permutation (device), or null on an error already reported
 static const uint32_t *build_order(hnsw_gpu_index *ix, SearchWs *w, const float *d_queries, size_t q_stride, size_t nq, hipStream_t stream)
@@ -477,18 +490,22 @@ int launch_search(hnsw_gpu_index *ix, SearchWs *w, const float *d_queries, size_
 	w->pops_next = nullptr; w->pops_cap_next = 0;
 	a.out_evals = w->evals_next; a.evals_cap = w->evals_cap_next; a.out_times = w->times_next;
 	w->evals_next = nullptr; w->evals_cap_next = 0; w->times_next = nullptr;
-	HIPCHK(hipMemsetAsync(w->ticket, 0, 8, stream));
+	HIPCHK(hipMemsetAsync(w->ticket, 0, XCD_TICKET_BYTES, stream));        // (the global ticket and the per-XCD counters)
 
 	const int evi = (int) (w->launches % SearchWs::EV_RING);
 	HIPCHK(hipEventRecord(w->ev0[evi], stream));
 	// locality order: the beam kernel's plain launches of a large batch (the key and the sort run inside the launch's event pair)
-	w->ord_nq = 0; w->ord_evals = nullptr;
+	w->ord_nq = 0; w->ord_evals = nullptr; w->ord_log2c = 0;
 	if (order && rreg < 0 && !stream_launch && a.n > 0 && knob(K_LOCALITY, 1) != 0 &&
 		nq >= (size_t) std::max<long long>(1, knob(K_LOCALITY_MIN_NQ, (long long) ORDER_MIN_NQ)))
 	{
 		// (the order is only an optimisation: where it cannot be built — no memory for its buffers — the launch runs in the caller's order)
 		a.perm = build_order(ix, w, d_queries, q_stride, nq, stream);
-		if (a.perm) { w->ord_nq = (uint32_t) nq; w->ord_evals = a.out_evals; }
+		if (a.perm)
+		{
+			a.xcd_log2c = xcd_chunk_log2(nq);
+			w->ord_nq = (uint32_t) nq; w->ord_evals = a.out_evals; w->ord_log2c = a.xcd_log2c;
+		}
 		else (void) hipGetLastError();
 	}
 	// (a stream is resident by design: the library's watchdog does not time it — its host stops it, hnsw_gpu_stream_close)

@@ -42,7 +42,7 @@ struct KnobDef { const char *name; bool env; };
 static const KnobDef g_knob_def[K_COUNT] = {
 	{ "HNSW_GPU_BEAM", true }, { "HNSW_GPU_FORCE_LDS_HEAPS", true }, { "HNSW_GPU_TEAM", true }, { "HNSW_GPU_TEAM_MAX_NQ", true },
 	{ "HNSW_GPU_WIDE_EF_MIN", true }, { "HNSW_GPU_REF_ORDER", true }, { "HNSW_GPU_NO_POLL", true }, { "HNSW_GPU_POLL_LIMIT_S", true },
-	{ "HNSW_GPU_INSERT_FUSED", true }, { "HNSW_GPU_BLOCKS_PER_CU", true }, { "HNSW_GPU_STREAM_LIGHT", true }, { "HNSW_GPU_LOCALITY", true },
+	{ "HNSW_GPU_INSERT_FUSED", true }, { "HNSW_GPU_BLOCKS_PER_CU", true }, { "HNSW_GPU_STREAM_LIGHT", true }, { "HNSW_GPU_LOCALITY", true }, { "HNSW_GPU_XCD_TICKETS", true },
 	{ "HNSW_GPU_BEAM16", false }, { "HNSW_GPU_NARROW5", false }, { "HNSW_GPU_LEAN", false }, { "HNSW_GPU_HASH_ENTRIES", false }, { "HNSW_GPU_LDS_SET_MIN_WAVES", false },
 	{ "HNSW_GPU_TEAM_SPEC", false }, { "HNSW_GPU_TEAM_WPB", false }, { "HNSW_GPU_NARROW_WPB", false }, { "HNSW_GPU_ABORT_POLL_LOG2", false }, { "HNSW_GPU_MAX_BLOCKS", false }, { "HNSW_GPU_SHARDED_NO_PEER", false },
 	{ "HNSW_GPU_BF_BIG_MIN_BLOCKS", false }, { "HNSW_GPU_LOCALITY_MIN_NQ", false },
@@ -205,8 +205,8 @@ static void ws_unregister(SearchWs *w)
 
 int ws_init(SearchWs *w)
 {
-	HIPCHK(hipMalloc(&w->ticket, 64));
-	HIPCHK(hipMemset(w->ticket, 0, 64));
+	HIPCHK(hipMalloc(&w->ticket, XCD_TICKET_BYTES));           // (the global ticket is the first word; ordered launches use all XCD_TICKETS counters)
+	HIPCHK(hipMemset(w->ticket, 0, XCD_TICKET_BYTES));
 	HIPCHK(hipMalloc(&w->health, HEALTH_WORDS * 4));
 	HIPCHK(hipMemset(w->health, 0, HEALTH_WORDS * 4));
 	HIPCHK(hipHostMalloc((void **) &w->abort_host, 64, hipHostMallocDefault));

@@ -379,6 +379,15 @@ class GpuIndex:
                                                 parts, C.byref(ms), C.byref(by), C.byref(ws) if word_sum else None), "hnsw_gpu_replay_roof")
         return (float(ms.value), float(by.value), int(ws.value)) if word_sum else (float(ms.value), float(by.value))
 
+    def replay_roof_dealt(self, traced: dict, slots: int, chunk: int, kb: int = 12, rpg: int = 2, word_sum: bool = False):
+        """(ms, bytes) of hnsw_gpu_replay_roof_dealt: the trace in its own row order, its tickets dealt per XCD in chunks of `chunk`
+        queries (0 = one global ticket); with word_sum=True also the sum of the bit patterns of every word it read."""
+        ms, by, ws = C.c_float(0), C.c_double(0), C.c_uint64(0)
+        ev = traced["evals"]
+        check(self.L.hnsw_gpu_replay_roof_dealt(self._h, ev.data_ptr(), ev.shape[1], traced["stats"].data_ptr(), ev.shape[0], slots, kb, rpg,
+                                                chunk, C.byref(ms), C.byref(by), C.byref(ws) if word_sum else None), "hnsw_gpu_replay_roof_dealt")
+        return (float(ms.value), float(by.value), int(ws.value)) if word_sum else (float(ms.value), float(by.value))
+
     def health(self) -> dict:
         """Health words of the default search workspace (include/hnsw_gpu.h, hnsw_gpu_index_health): all zero in a healthy life."""
         v = (C.c_uint32 * 8)()
@@ -418,6 +427,13 @@ class GpuIndex:
         key = np.empty(n.value, np.uint32)
         check(self.L.hnsw_gpu_last_search_order(self._h, perm.ctypes.data, key.ctypes.data, n.value, C.byref(n)), "hnsw_gpu_last_search_order")
         return (perm.astype(np.int64), key.astype(np.int64)) if keys else perm.astype(np.int64)
+
+    def last_search_chunk(self) -> int:
+        """The chunk in which the last search launch of the default workspace dealt its ordered batch per XCD
+        (hnsw_gpu_last_search_chunk); 0 = one global ticket."""
+        v = C.c_uint32(0)
+        check(self.L.hnsw_gpu_last_search_chunk(self._h, C.byref(v)), "hnsw_gpu_last_search_chunk")
+        return int(v.value)
 
     def last_search_slots(self) -> int:
         v = C.c_uint32(0)
