@@ -185,6 +185,30 @@ int hnsw_gpu_search_batch_reduced_dev(hnsw_gpu_index *ix, int format, const coor
 int hnsw_gpu_search_batch_reduced(hnsw_gpu_index *ix, int format, const coord_t *queries, size_t nq, size_t ef,
 								  label_t *labels, dist_t *dists, uint32_t *counts);
 
+/* The index scan around the search, hnsw_gettuple (embedding.c:284-370), for nq queries at once, with an optional allow filter
+ * (csrc/device_indexscan.h).  Per query: hand out the results of a search at ef0; when they are used up and the search came back
+ * full, double ef, search again, drop the labels handed out before that round (embedding.c:355-363) and go on, until a search comes
+ * back short, brings nothing new, or 2 * ef would pass max_ef (0 = no cap).  Returned per query: the first `limit` labels of that
+ * sequence that pass the query's filter, in hand-out order, each with the distance it had in the round that appended it.
+ * Hand-out order is the reference's: ascending by (distance, label) within the labels ONE round appended, NOT globally sorted across
+ * rounds.  A label the filter drops is still handed out (it counts for the de-duplication); it just does not count toward limit.
+ *   d_allow      NULL = every label passes; else nfilters bitmaps over label VALUES, ceil(allow_bits / 32) words apart: bit l of a
+ *                bitmap (word l / 32, bit l % 32) says whether label l passes, labels >= allow_bits do not
+ *   d_allow_of   NULL = every query uses bitmap 0; else nq bitmap numbers (< nfilters: the caller's contract)
+ *   d_labels     nq*limit, unused tail = ~0      d_dists  nq*limit or NULL, tail = +inf      d_counts  nq results per query
+ *   d_scan_stats NULL or nq*4: { last ef searched, rounds (= searches), tuples handed out (= what the executor pulled),
+ *                1 if the scan itself ended / 0 if it stopped at limit }
+ * Rounds after the first search only the queries still scanning.  fp32 rows, the mirror's default workspace; one host wait per round
+ * (at most log2(max_ef / ef0) + 1 rounds): the call synchronises `stream`.  limit == 0, ef0 == 0, max_ef below ef0, a bitmap of no
+ * bits: HNSW_GPU_ERR_ARG before anything is launched; a round whose workspace cannot be allocated: HNSW_GPU_ERR_NOMEM. */
+int hnsw_gpu_scan_batch_dev(hnsw_gpu_index *ix, const coord_t *d_queries, size_t nq, size_t ef0, size_t max_ef, size_t limit,
+							const uint32_t *d_allow, size_t allow_bits, size_t nfilters, const uint32_t *d_allow_of,
+							label_t *d_labels, dist_t *d_dists, uint32_t *d_counts, uint32_t *d_scan_stats, void *stream);
+/* Host-pointer form: copies in, runs on the default stream, copies out. */
+int hnsw_gpu_scan_batch(hnsw_gpu_index *ix, const coord_t *queries, size_t nq, size_t ef0, size_t max_ef, size_t limit,
+						const uint32_t *allow, size_t allow_bits, size_t nfilters, const uint32_t *allow_of,
+						label_t *labels, dist_t *dists, uint32_t *counts, uint32_t *scan_stats);
+
 /* Milliseconds the most recent search kernel of this index spent on the device,
  * from HIP events recorded on its stream around the launch (waits for it). */
 int hnsw_gpu_last_search_ms(hnsw_gpu_index *ix, float *ms);

@@ -98,6 +98,11 @@ int hnsw_gpu_last_search_chunk(hnsw_gpu_index *ix, uint32_t *chunk);
  * keys may be NULL; perm is the stable argsort of keys).  Waits for the device.  For tests. */
 int hnsw_gpu_last_search_order(hnsw_gpu_index *ix, uint32_t *perm, uint32_t *keys, size_t cap, size_t *nq);
 
+/* Where the time of the mirror's last hnsw_gpu_scan_batch[_dev] call went, per round: *rounds = rounds it ran; for r < min(*rounds, cap):
+ * active[r] = queries that took part, ef[r] = the width searched, search_ms[r] = the search launch, handout_ms[r] = what followed until the
+ * round's active count was written (table reset, hand-out and compaction kernels), from HIP events on the call's stream.  Any array may be NULL. */
+int hnsw_gpu_last_scan_rounds(hnsw_gpu_index *ix, uint32_t *rounds, uint32_t *active, uint32_t *ef, float *search_ms, float *handout_ms, size_t cap);
+
 #ifdef __cplusplus
 }
 #endif

@@ -110,6 +110,22 @@ struct SearchWs
 	const uint32_t *ord_evals = nullptr;                 // the evaluation trace that launch wrote (traced launches), else null
 };
 
+// ---- the batched index scan (device_indexscan.h, hnsw_gpu_scan_batch_dev) ------------------------
+// Buffers of one mirror's scan calls.  Each is reused from call to call and from round to round while it is large enough; what a late,
+// wide round made larger than SCAN_KEEP_BYTES is freed when its call ends.
+struct ScanBuf { void *p = nullptr; size_t bytes = 0; };
+struct ScanWs
+{
+	static const int MAX_ROUNDS = 40;                    // (ef doubles per round and stays below 2^32)
+	ScanBuf rows, tab[2], q, state, act[2];
+	uint32_t *host = nullptr;                            // pinned: [0] active count of the next round, [1] error flag
+	hipEvent_t ev[3 * MAX_ROUNDS] = {};                  // per round: before the search | after it | after hand-out + compaction
+	// the last call, per round (hnsw_gpu_last_scan_rounds)
+	uint32_t nrounds = 0, r_active[MAX_ROUNDS] = {}, r_ef[MAX_ROUNDS] = {};
+	float r_search_ms[MAX_ROUNDS] = {}, r_handout_ms[MAX_ROUNDS] = {};
+};
+void scan_ws_free(ScanWs *s);
+
 extern std::mutex &g_ws_mu;                              // guards the registry of workspaces (abort + watchdog, hnsw_gpu.hip)
 int64_t now_ms();
 int abort_ws_locked(SearchWs *w);                        // g_ws_mu held
@@ -175,6 +191,7 @@ struct hnsw_gpu_index
 	// pivots of the locality order (device_order.h): [kd][P] prefixes | P ranks, built from the rows on a search's stream.  Every writer of
 	// `vec` clears piv_valid (rows16_mark, reserve); a stale set would only cost speed — the order is a permutation whatever the keys
 	float   *piv = nullptr; uint32_t piv_P = 0, piv_kd = 0; size_t piv_n = 0; bool piv_valid = false;
+	ScanWs   scan;                    // the batched index scan's buffers and per-round figures (device_indexscan.h)
 };
 
 // rows [lo, hi) of `vec` were (or are about to be) written: the reduced copy, if any, converts them again before the next reduced search

@@ -1,7 +1,8 @@
-// gpu_search.hip — launch planning of the search kernels (csrc/device_search.h), the search entry points, one traced walk, search contexts
+// gpu_search.hip — launch planning of the search kernels (csrc/device_search.h), the search entry points, one traced walk, search contexts, the batched index scan
 // One translation unit of libhnsw_gpu.so (csrc/gpu_host.h lists them); gfx950 only, plain HIP runtime, no framework types in any signature.
 #include "gpu_host.h"
 #include "device_order.h"
+#include "device_indexscan.h"
 
 // ------------------------------------------------------------------------------------
 // search
@@ -1093,3 +1094,200 @@ extern "C" int hnsw_gpu_search_batch_ctx_flags(hnsw_gpu_ctx *c, const coord_t *d
 	return rc;
 }
 
+
+// ------------------------------------------------------------------------------------
+// the batched index scan (device_indexscan.h)
+// ------------------------------------------------------------------------------------
+// hnsw_gettuple's loop (embedding.c:284-370) for nq queries at once: round 0 searches every query at ef0 through launch_search (the
+// plain batch path, locality order of large batches included), the hand-out kernel takes each row into the query's scan state, the
+// compaction kernel lists the queries that go on, the host reads their number (the one wait of a round) and the next round searches
+// only those, gathered, at twice the width.  The walk kernels are the search's own; nothing here changes what a search returns.
+static const size_t SCAN_KEEP_BYTES = (size_t) 64 << 20;      // a buffer larger than this does not outlive its call
+
+void scan_ws_free(ScanWs *s)
+{
+	ScanBuf *all[] = {&s->rows, &s->tab[0], &s->tab[1], &s->q, &s->state, &s->act[0], &s->act[1]};
+	for (ScanBuf *b : all) { if (b->p) (void) hipFree(b->p); b->p = nullptr; b->bytes = 0; }
+	if (s->host) (void) hipHostFree(s->host);
+	s->host = nullptr;
+	for (hipEvent_t &e : s->ev) { if (e) (void) hipEventDestroy(e); e = nullptr; }
+}
+
+static int scan_buf(ScanBuf *b, size_t bytes, const char *what)
+{
+	if (bytes <= b->bytes) return HNSW_GPU_OK;
+	if (b->p) (void) hipFree(b->p);                           // (waits for the launches still using it)
+	b->p = nullptr; b->bytes = 0;
+	if (hipMalloc(&b->p, bytes) != hipSuccess)
+	{
+		b->p = nullptr;
+		(void) hipGetLastError();
+		return fail(HNSW_GPU_ERR_NOMEM, "index scan: no room for %s (%zu bytes)", what, bytes);
+	}
+	b->bytes = bytes;
+	return HNSW_GPU_OK;
+}
+
+static void scan_trim(ScanWs *s)
+{
+	ScanBuf *all[] = {&s->rows, &s->tab[0], &s->tab[1], &s->q, &s->state, &s->act[0], &s->act[1]};
+	for (ScanBuf *b : all)
+		if (b->bytes > SCAN_KEEP_BYTES) { (void) hipFree(b->p); b->p = nullptr; b->bytes = 0; }
+}
+
+// the caller's contract, checked before anything is launched or copied (the outputs stay untouched)
+static int scan_check(hnsw_gpu_index *ix, const void *queries, size_t nq, size_t ef0, size_t max_ef, size_t limit, const void *allow,
+					  size_t allow_bits, size_t nfilters, const void *allow_of, const void *labels, const void *counts)
+{
+	if (!ix) return fail(HNSW_GPU_ERR_ARG, "index is NULL");
+	if (nq == 0) return HNSW_GPU_OK;
+	if (!queries || !labels || !counts) return fail(HNSW_GPU_ERR_ARG, "NULL buffer");
+	if (nq >= 0xFFFFFFFFull) return fail(HNSW_GPU_ERR_ARG, "too many queries");
+	if (limit == 0 || limit >= 0xFFFFFFFFull) return fail(HNSW_GPU_ERR_ARG, "index scan: limit %zu out of range", limit);
+	if (ef0 == 0 || ef0 >= 0x7FFFFFFFull) return fail(HNSW_GPU_ERR_ARG, "index scan: ef %zu out of range", ef0);
+	if (max_ef && max_ef < ef0) return fail(HNSW_GPU_ERR_ARG, "index scan: max_ef %zu is below the start width %zu", max_ef, ef0);
+	if (allow && (allow_bits == 0 || nfilters == 0)) return fail(HNSW_GPU_ERR_ARG, "index scan: an allow filter of no bits");
+	if (allow && ((allow_bits + 31) / 32 >= 0xFFFFFFFFull || nfilters >= 0xFFFFFFFFull)) return fail(HNSW_GPU_ERR_ARG, "index scan: allow filter too large");
+	if (!allow && allow_of) return fail(HNSW_GPU_ERR_ARG, "index scan: filter numbers without an allow filter");
+	return HNSW_GPU_OK;
+}
+
+extern "C" int hnsw_gpu_scan_batch_dev(hnsw_gpu_index *ix, const coord_t *d_queries, size_t nq, size_t ef0, size_t max_ef, size_t limit,
+									   const uint32_t *d_allow, size_t allow_bits, size_t nfilters, const uint32_t *d_allow_of,
+									   label_t *d_labels, dist_t *d_dists, uint32_t *d_counts, uint32_t *d_scan_stats, void *stream)
+{
+	std::unique_lock<std::recursive_mutex> lock_;
+	if (ix) lock_ = std::unique_lock<std::recursive_mutex>(ix->mu);
+	if (int rc0 = scan_check(ix, d_queries, nq, ef0, max_ef, limit, d_allow, allow_bits, nfilters, d_allow_of, d_labels, d_counts)) return rc0;
+	if (nq == 0) return HNSW_GPU_OK;
+	HIPCHK(hipSetDevice(ix->device));
+	hipStream_t s = (hipStream_t) stream;
+	ScanWs *sw = &ix->scan;
+	const size_t dim = ix->meta.dim, n = std::max<size_t>(ix->n, 1);
+	if (!sw->host) HIPCHK(hipHostMalloc((void **) &sw->host, 64, hipHostMallocDefault));
+	// state of the call: hlen | slot_of | finished | the device's copy of the active count | the stats when the caller wants none
+	int rc = scan_buf(&sw->state, (3 * nq + 64 + (d_scan_stats ? 0 : 4 * nq)) * 4, "the scan state");
+	if (rc) return rc;
+	uint32_t *hlen = (uint32_t *) sw->state.p, *slot_of = hlen + nq, *finished = slot_of + nq, *d_count = finished + nq;
+	uint32_t *stats = d_scan_stats ? d_scan_stats : d_count + 64;
+	sw->host[0] = 0; sw->host[1] = 0;
+	sw->nrounds = 0;
+	{
+		const size_t cells = std::max(nq * limit, nq);
+		hipLaunchKernelGGL(scan_init_kernel, dim3((uint32_t) std::min<size_t>((cells + 255) / 256, 8192)), dim3(256), 0, s, (uint32_t) nq, (uint32_t) limit,
+						   d_labels, d_dists, d_counts, stats, hlen, slot_of, finished);
+		HIPCHK(hipGetLastError());
+	}
+	size_t ef = ef0, nact = nq, hbound = 0, old_cap = 0;
+	const uint32_t *act = nullptr;
+	const float *qs = d_queries;
+	const uint64_t *old_tab = nullptr;
+	uint32_t round = 0;
+	for (;; round++)
+	{
+		if (round >= (uint32_t) ScanWs::MAX_ROUNDS) { rc = fail(HNSW_GPU_ERR_INTERNAL, "index scan: more than %d rounds", ScanWs::MAX_ROUNDS); break; }
+		// H after this round holds at most what the searches so far can have returned; the table keeps a load of at most 1/2
+		hbound += std::min(ef, n);
+		size_t cap = 64;
+		while (cap < 2 * hbound) cap <<= 1;
+		if (cap > 0x80000000ull) { rc = fail(HNSW_GPU_ERR_NOMEM, "index scan: a membership table of %zu slots", cap); break; }
+		const size_t lb = round_up(nact * ef * 8, 256), db = round_up(nact * ef * 4, 256), cb = round_up(nact * 4, 256);
+		ScanBuf *tb = &sw->tab[round & 1], *ab = &sw->act[round & 1];
+		if ((rc = scan_buf(&sw->rows, lb + db + cb, "a round's result rows"))) break;
+		if ((rc = scan_buf(tb, nact * cap * 8, "a round's membership tables"))) break;
+		if ((rc = scan_buf(ab, nact * 4, "the list of active queries"))) break;
+		uint64_t *rl = (uint64_t *) sw->rows.p;
+		float *rd = (float *) ((char *) sw->rows.p + lb);
+		uint32_t *rcnt = (uint32_t *) ((char *) sw->rows.p + lb + db);
+		hipEvent_t *ev = sw->ev + 3 * round;
+		for (int i = 0; i < 3; i++)
+			if (!ev[i] && hipEventCreate(&ev[i]) != hipSuccess) { ev[i] = nullptr; rc = fail(HNSW_GPU_ERR_HIP, "index scan: hipEventCreate failed"); break; }
+		if (rc) break;
+		if (hipEventRecord(ev[0], s) != hipSuccess) { rc = fail(HNSW_GPU_ERR_HIP, "index scan: hipEventRecord failed"); break; }
+		if ((rc = launch_search(ix, &ix->ws, qs, dim, nact, ef, 0, rl, nullptr, rd, rcnt, nullptr, s, 0, true))) break;
+		if (hipEventRecord(ev[1], s) != hipSuccess || hipMemsetAsync(tb->p, 0xFF, nact * cap * 8, s) != hipSuccess)
+		{ rc = fail(HNSW_GPU_ERR_HIP, "index scan: enqueue failed"); break; }
+		ScanRound a;
+		memset(&a, 0, sizeof(a));
+		a.act = act; a.nact = (uint32_t) nact; a.ef = (uint32_t) ef; a.round = round;
+		a.max_ef = (uint32_t) std::min<size_t>(max_ef, 0xFFFFFFFFull); a.limit = (uint32_t) limit;
+		a.row_labels = rl; a.row_dists = rd; a.row_counts = rcnt;
+		a.old_tab = old_tab; a.old_cap = (uint32_t) old_cap; a.new_tab = (uint64_t *) tb->p; a.new_cap = (uint32_t) cap;
+		a.allow = d_allow; a.allow_bits = allow_bits; a.allow_words = (uint32_t) ((allow_bits + 31) / 32); a.allow_of = d_allow_of;
+		a.out_labels = d_labels; a.out_dists = d_dists; a.out_counts = d_counts;
+		a.stats = stats; a.hlen = hlen; a.slot_of = slot_of; a.finished = finished; a.err_host = sw->host + 1;
+		hipLaunchKernelGGL(scan_handout_kernel, dim3((uint32_t) ((nact + SCAN_WPB - 1) / SCAN_WPB)), dim3(SCAN_WPB * 64), 0, s, a);
+		hipLaunchKernelGGL(scan_compact_kernel, dim3(1), dim3(SCAN_COMPACT_THREADS), SCAN_COMPACT_LDS, s, act, (uint32_t) nact, (const uint32_t *) finished,
+						   (uint32_t *) ab->p, d_count, sw->host);
+		if (hipGetLastError() != hipSuccess || hipEventRecord(ev[2], s) != hipSuccess) { rc = fail(HNSW_GPU_ERR_HIP, "index scan: launch failed"); break; }
+		if (hipStreamSynchronize(s) != hipSuccess) { rc = fail(HNSW_GPU_ERR_HIP, "index scan: the round did not complete"); break; }
+		sw->r_active[round] = (uint32_t) nact; sw->r_ef[round] = (uint32_t) ef; sw->nrounds = round + 1;
+		if (sw->host[1]) { rc = fail(HNSW_GPU_ERR_INTERNAL, "the search launch was asked to end early (abort word): the scan has no result"); break; }
+		const size_t next = sw->host[0];
+		if (next == 0) break;
+		if (next > nact) { rc = fail(HNSW_GPU_ERR_INTERNAL, "index scan: %zu active queries out of %zu", next, nact); break; }
+		if (ef * 2 >= 0xFFFFFFFFull) { rc = fail(HNSW_GPU_ERR_ARG, "index scan: the doubled ef %zu is out of range", ef * 2); break; }
+		if ((rc = scan_buf(&sw->q, next * dim * 4, "the active queries"))) break;
+		hipLaunchKernelGGL(scan_gather_kernel, dim3((uint32_t) ((next + SCAN_WPB - 1) / SCAN_WPB)), dim3(SCAN_WPB * 64), 0, s, d_queries, (uint32_t) dim,
+						   (const uint32_t *) ab->p, (uint32_t) next, (float *) sw->q.p);
+		act = (const uint32_t *) ab->p; qs = (const float *) sw->q.p;
+		old_tab = (const uint64_t *) tb->p; old_cap = cap;
+		nact = next; ef *= 2;
+	}
+	if (rc) (void) hipStreamSynchronize(s);
+	for (uint32_t r = 0; r < sw->nrounds; r++)
+	{
+		sw->r_search_ms[r] = 0.f; sw->r_handout_ms[r] = 0.f;
+		(void) hipEventElapsedTime(&sw->r_search_ms[r], sw->ev[3 * r], sw->ev[3 * r + 1]);
+		(void) hipEventElapsedTime(&sw->r_handout_ms[r], sw->ev[3 * r + 1], sw->ev[3 * r + 2]);
+	}
+	scan_trim(sw);
+	return rc;
+}
+
+extern "C" int hnsw_gpu_scan_batch(hnsw_gpu_index *ix, const coord_t *queries, size_t nq, size_t ef0, size_t max_ef, size_t limit,
+								   const uint32_t *allow, size_t allow_bits, size_t nfilters, const uint32_t *allow_of,
+								   label_t *labels, dist_t *dists, uint32_t *counts, uint32_t *scan_stats)
+{
+	std::unique_lock<std::recursive_mutex> lock_;
+	if (ix) lock_ = std::unique_lock<std::recursive_mutex>(ix->mu);
+	if (int rc0 = scan_check(ix, queries, nq, ef0, max_ef, limit, allow, allow_bits, nfilters, allow_of, labels, counts)) return rc0;
+	if (nq == 0) return HNSW_GPU_OK;
+	HIPCHK(hipSetDevice(ix->device));
+	const size_t dim = ix->meta.dim, words = allow ? (allow_bits + 31) / 32 : 0;
+	const size_t qb = round_up(nq * dim * 4, 256), fb = round_up(nfilters * words * 4, 256), ob = round_up(allow_of ? nq * 4 : 0, 256),
+				 lb = round_up(nq * limit * 8, 256), db = round_up(nq * limit * 4, 256), cb = round_up(nq * 4, 256), sb = round_up(nq * 16, 256);
+	int rc = ensure_scratch(ix, qb + fb + ob + lb + db + cb + sb);
+	if (rc) return rc;
+	char *p = (char *) ix->scratch;
+	float *dq = (float *) p; uint32_t *df = (uint32_t *) (p + qb), *dof = (uint32_t *) (p + qb + fb);
+	uint64_t *dl = (uint64_t *) (p + qb + fb + ob); float *dd = (float *) (p + qb + fb + ob + lb);
+	uint32_t *dc = (uint32_t *) (p + qb + fb + ob + lb + db), *ds = (uint32_t *) (p + qb + fb + ob + lb + db + cb);
+	HIPCHK(hipMemcpy(dq, queries, nq * dim * 4, hipMemcpyHostToDevice));
+	if (allow) HIPCHK(hipMemcpy(df, allow, nfilters * words * 4, hipMemcpyHostToDevice));
+	if (allow_of) HIPCHK(hipMemcpy(dof, allow_of, nq * 4, hipMemcpyHostToDevice));
+	rc = hnsw_gpu_scan_batch_dev(ix, dq, nq, ef0, max_ef, limit, allow ? df : nullptr, allow_bits, nfilters, allow_of ? dof : nullptr, dl, dd, dc, ds, nullptr);
+	if (rc) return rc;
+	HIPCHK(hipMemcpy(labels, dl, nq * limit * 8, hipMemcpyDeviceToHost));
+	if (dists) HIPCHK(hipMemcpy(dists, dd, nq * limit * 4, hipMemcpyDeviceToHost));
+	HIPCHK(hipMemcpy(counts, dc, nq * 4, hipMemcpyDeviceToHost));
+	if (scan_stats) HIPCHK(hipMemcpy(scan_stats, ds, nq * 16, hipMemcpyDeviceToHost));
+	return HNSW_GPU_OK;
+}
+
+extern "C" int hnsw_gpu_last_scan_rounds(hnsw_gpu_index *ix, uint32_t *rounds, uint32_t *active, uint32_t *ef, float *search_ms, float *handout_ms, size_t cap)
+{
+	std::unique_lock<std::recursive_mutex> lock_;
+	if (ix) lock_ = std::unique_lock<std::recursive_mutex>(ix->mu);
+	if (!ix || !rounds) return fail(HNSW_GPU_ERR_ARG, "NULL argument");
+	const ScanWs *sw = &ix->scan;
+	*rounds = sw->nrounds;
+	for (size_t r = 0; r < sw->nrounds && r < cap; r++)
+	{
+		if (active) active[r] = sw->r_active[r];
+		if (ef) ef[r] = sw->r_ef[r];
+		if (search_ms) search_ms[r] = sw->r_search_ms[r];
+		if (handout_ms) handout_ms[r] = sw->r_handout_ms[r];
+	}
+	return HNSW_GPU_OK;
+}

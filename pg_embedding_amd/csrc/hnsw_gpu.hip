@@ -352,6 +352,7 @@ extern "C" void hnsw_gpu_index_destroy(hnsw_gpu_index *ix)
 	if (ix->rr_cand) (void) hipFree(ix->rr_cand);
 	if (ix->rr_e0) (void) hipEventDestroy(ix->rr_e0);
 	if (ix->rr_e1) (void) hipEventDestroy(ix->rr_e1);
+	scan_ws_free(&ix->scan);
 	delete ix;
 }
 

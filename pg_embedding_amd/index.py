@@ -62,6 +62,51 @@ def _dptr(t) -> int:
     return 0 if t is None else t.data_ptr()
 
 
+def _pack_allow_numpy(allow):
+    """allow filter -> (packed uint32 words [nfilters, words] or None, allow_bits, nfilters); bit l of a filter = word l // 32, bit l % 32"""
+    if allow is None:
+        return None, 0, 0
+    a = np.asarray(allow)
+    if a.ndim == 1:
+        a = a[None, :]
+    if a.ndim != 2 or a.shape[1] == 0:
+        raise ValueError("allow must be [allow_bits] or [nfilters, allow_bits]")
+    if a.dtype == np.bool_:
+        bits = a.shape[1]
+        words = np.packbits(a, axis=1, bitorder="little")
+        pad = (-words.shape[1]) % 4
+        if pad:
+            words = np.concatenate([words, np.zeros((a.shape[0], pad), np.uint8)], axis=1)
+        return np.ascontiguousarray(words).view(np.uint32), bits, a.shape[0]
+    if a.dtype in (np.uint32, np.int32):
+        return np.ascontiguousarray(a).view(np.uint32), 32 * a.shape[1], a.shape[0]
+    raise ValueError("allow must be a bool array or packed 32-bit words")
+
+
+def _pack_allow_torch(allow, dev):
+    """the same for torch tensors on `dev`: (int32 words tensor or None, allow_bits, nfilters)"""
+    if allow is None:
+        return None, 0, 0
+    torch = _torch()
+    a = allow.to(dev)
+    if a.dim() == 1:
+        a = a[None, :]
+    if a.dim() != 2 or a.shape[1] == 0:
+        raise ValueError("allow must be [allow_bits] or [nfilters, allow_bits]")
+    if a.dtype == torch.bool:
+        nf, bits = a.shape
+        pad = (-bits) % 32
+        if pad:
+            a = torch.cat([a, torch.zeros((nf, pad), dtype=torch.bool, device=dev)], dim=1)
+        # bit j of a word has weight 2^j; bit 31 is the int32 sign bit, so sum in int64 and wrap
+        w = (a.view(nf, -1, 32).to(torch.int64) << torch.arange(32, device=dev, dtype=torch.int64)).sum(dim=2)
+        w = torch.where(w >= (1 << 31), w - (1 << 32), w).to(torch.int32)
+        return w.contiguous(), bits, nf
+    if a.dtype == torch.int32:
+        return a.contiguous(), 32 * a.shape[1], a.shape[0]
+    raise ValueError("allow must be a bool tensor or a packed int32 tensor")
+
+
 class GpuIndex:
     """An HBM-resident mirror of one HNSW index on one MI355X."""
 
@@ -304,6 +349,65 @@ class GpuIndex:
                                                    out["dists"].data_ptr(), out["counts"].data_ptr(),
                                                    _dptr(out.get("stats")), s), "hnsw_gpu_search_batch_dev")
         return out
+
+    # ---------------------------------------------------------------- index scan
+    def scan(self, queries: np.ndarray, limit: int, ef: Optional[int] = None, max_ef: Optional[int] = None, allow=None, allow_of=None,
+             stats: bool = False):
+        """The index scan around the search (hnsw_gettuple's efSearch doubling, scan.py::IndexScan) for a batch, host buffers
+        (hnsw_gpu_scan_batch): per query the first `limit` labels of the scan that pass its allow filter, in hand-out order.
+        allow: None (every label passes), a bool array [allow_bits] or [nfilters, allow_bits] over label values, or packed uint32 /
+        int32 words ([words] or [nfilters, words]: then all 32 * words bits count); allow_of: [nq] filter numbers (None: filter 0).
+        Returns (labels[nq, limit] u64, dists[nq, limit] f32, counts[nq] u32), plus stats[nq, 4] u32 = (last ef, rounds, tuples handed
+        out, 1 if the scan itself ended) with stats=True."""
+        ef = int(ef or self.meta.efSearch)
+        queries = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, self.meta.dim)
+        nq = queries.shape[0]
+        words, bits, nf = _pack_allow_numpy(allow)
+        of = None if allow_of is None else np.ascontiguousarray(allow_of, dtype=np.uint32).reshape(nq)
+        labels = np.empty((nq, limit), np.uint64)
+        dists = np.empty((nq, limit), np.float32)
+        counts = np.empty(nq, np.uint32)
+        st = np.empty((nq, 4), np.uint32) if stats else None
+        check(self.L.hnsw_gpu_scan_batch(self._h, queries.ctypes.data, nq, ef, int(max_ef or 0), int(limit),
+                                         None if words is None else words.ctypes.data, bits, nf, None if of is None else of.ctypes.data,
+                                         labels.ctypes.data, dists.ctypes.data, counts.ctypes.data, None if st is None else st.ctypes.data),
+              "hnsw_gpu_scan_batch")
+        return (labels, dists, counts, st) if stats else (labels, dists, counts)
+
+    def scan_torch(self, queries, limit: int, ef: Optional[int] = None, max_ef: Optional[int] = None, allow=None, allow_of=None,
+                   stats: bool = False):
+        """scan() with everything resident in HBM (hnsw_gpu_scan_batch_dev on torch's current stream, which the call synchronises).
+        allow: None, a bool tensor [allow_bits] / [nfilters, allow_bits], or an already packed int32 tensor [words] / [nfilters, words];
+        allow_of: an integer tensor [nq].  Returns a dict: labels [nq, limit] int64 (tail -1), dists [nq, limit] (tail +inf), counts [nq]
+        int32, stats [nq, 4] int32 or None."""
+        torch = _torch()
+        ef = int(ef or self.meta.efSearch)
+        assert queries.is_cuda and queries.dtype == torch.float32 and queries.is_contiguous()
+        nq = queries.shape[0]
+        dev = queries.device
+        words, bits, nf = _pack_allow_torch(allow, dev)
+        of = None if allow_of is None else allow_of.to(device=dev, dtype=torch.int32).contiguous()
+        if of is not None and of.numel() != nq:
+            raise ValueError("allow_of names one filter per query")
+        out = {"labels": torch.empty((nq, limit), dtype=torch.int64, device=dev),
+               "dists": torch.empty((nq, limit), dtype=torch.float32, device=dev),
+               "counts": torch.empty(nq, dtype=torch.int32, device=dev),
+               "stats": torch.empty((nq, 4), dtype=torch.int32, device=dev) if stats else None}
+        s = torch.cuda.current_stream(dev).cuda_stream
+        check(self.L.hnsw_gpu_scan_batch_dev(self._h, queries.data_ptr(), nq, ef, int(max_ef or 0), int(limit), _dptr(words), bits, nf, _dptr(of),
+                                             out["labels"].data_ptr(), out["dists"].data_ptr(), out["counts"].data_ptr(),
+                                             _dptr(out["stats"]), s), "hnsw_gpu_scan_batch_dev")
+        return out
+
+    def last_scan_rounds(self):
+        """Per round of the last scan call: dicts of active queries, ef, search ms, hand-out + compaction ms (hnsw_gpu_last_scan_rounds)."""
+        cap = 40
+        n = C.c_uint32(0)
+        act, ef = np.zeros(cap, np.uint32), np.zeros(cap, np.uint32)
+        sm, hm = np.zeros(cap, np.float32), np.zeros(cap, np.float32)
+        check(self.L.hnsw_gpu_last_scan_rounds(self._h, C.byref(n), act.ctypes.data, ef.ctypes.data, sm.ctypes.data, hm.ctypes.data, cap),
+              "hnsw_gpu_last_scan_rounds")
+        return [{"active": int(act[r]), "ef": int(ef[r]), "search_ms": float(sm[r]), "handout_ms": float(hm[r])} for r in range(min(n.value, cap))]
 
     def last_search_ms(self, back: int = 0) -> float:
         """Device time of the search kernel launched `back` launches ago (HIP events recorded on
