@@ -411,7 +411,26 @@ int hnsw_gpu_bruteforce_reduced_dev(hnsw_gpu_index *ix, int format, const coord_
 /* Merge `nlists` per-shard result lists per query (each ef entries: ascending by
  * (dist, label), tail padded with dist=+inf / label=~0) into the ef best overall.
  * Stands in for nothing in the single-process reference; it is the one exchange
- * step of a row-sharded index.  Layout: d_in_*[list][query][ef]. */
+ * step of a row-sharded index.  Layout: d_in_*[list][query][ef].
+ *
+ * The contract (tests/test_gpu_merge_topk.py pins it):
+ *  - every input list is sorted ascending by (dist, label), real entries first;
+ *    fewer than ef real entries, none at all and nlists == 1 are fine.  Distances
+ *    order by the total order of their bit patterns: negative values (cosine)
+ *    before -0.0 before +0.0 before positive ones, +inf last; +inf under a real
+ *    label is a real entry;
+ *  - padding is label ~0 with dist +inf, at the tail of a list only; an entry whose
+ *    label is ~0 is never emitted.  The output has the same form: d_out_counts[q]
+ *    real entries, then label ~0 / dist +inf up to ef;
+ *  - the lists need not be disjoint (replicated shards, results merged again):
+ *    entries with equal (dist, label) are all kept, ordered by list number and,
+ *    within a list, by position, which decides which copy survives at position
+ *    ef - 1;
+ *  - what the merge does with NaN distances or unsorted lists is unspecified.
+ * d_out_dists may be NULL (labels and counts only); every other pointer is required.
+ * nq == 0 returns HNSW_GPU_OK and touches nothing.  A NULL buffer, nlists == 0,
+ * ef == 0, nlists * ef >= 2^32 - 1 or nq >= 2^31 - 1 returns HNSW_GPU_ERR_ARG and
+ * touches nothing.  Asynchronous on `stream` (NULL = the null stream of `device`). */
 int hnsw_gpu_merge_topk_dev(int device, const label_t *d_in_labels, const dist_t *d_in_dists,
 							size_t nlists, size_t nq, size_t ef,
 							label_t *d_out_labels, dist_t *d_out_dists, uint32_t *d_out_counts,
@@ -419,7 +438,9 @@ int hnsw_gpu_merge_topk_dev(int device, const label_t *d_in_labels, const dist_t
 
 /* Same with the per-list arrays anywhere in memory: list l's labels start at d_in_labels +
  * l*label_list_stride (in label_t), its distances at d_in_dists + l*dist_list_stride (in dist_t).  Lets ONE
- * gathered buffer of per-rank blocks [labels | dists] be merged in place (one all-gather per search). */
+ * gathered buffer of per-rank blocks [labels | dists] be merged in place (one all-gather per search).
+ * The two strides are independent of each other; a stride below nq * ef returns
+ * HNSW_GPU_ERR_ARG.  Nothing between the lists is read. */
 int hnsw_gpu_merge_topk_strided_dev(int device, const label_t *d_in_labels, size_t label_list_stride,
 									const dist_t *d_in_dists, size_t dist_list_stride, size_t nlists,
 									size_t nq, size_t ef, label_t *d_out_labels, dist_t *d_out_dists,

@@ -43,7 +43,7 @@ __global__ __launch_bounds__(64) void topk_merge_kernel(const uint64_t *__restri
 						const uint32_t mid = (lo + hi) >> 1;
 						const uint64_t ol = in_labels[m * lstep + ob + mid];
 						const uint32_t od = ord_f32(in_dists[m * dstep + ob + mid]);
-						// equal keys (cannot happen for disjoint shards) go to the lower list number
+						// equal keys (replicated shards, results merged again; never for disjoint shards) go to the lower list number
 						const bool below = (ol != ~0ull) && (dl_less(od, ol, d, lab) || (od == d && ol == lab && m < l));
 						if (below) lo = mid + 1; else hi = mid;
 					}

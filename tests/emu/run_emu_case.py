@@ -375,6 +375,37 @@ def sharded():
     return out
 
 
+def sharded_edges():
+    """hnsw_gpu_sharded_search[_dev] over shards that hand the merge short, empty and padded lists (tests/sharded_edges.py: shards
+    of 1, 3, 5 and 40 rows next to one of 900, a fully vacuumed shard, an empty one), L2 and cosine, beams of 20, 100 and 200 (the
+    wide-beam form, and beams larger than a shard): labels, distance bits, counts and the padded tail == oracle per shard + CPU
+    merge.  Shard r on emulated device r % devices."""
+    import merge_util as MU
+    import sharded_edges as E
+    from pg_embedding_amd._lib import gpu_lib
+    ndev = gpu_lib().hnsw_gpu_device_count()
+    setenv({})
+    out = {"devices": ndev, "cases": []}
+    nq = 6
+    for func in (pg.DIST_L2, pg.DIST_COSINE):
+        Q = gmm(nq, E.DIM, k=12, seed=78, stream=1)
+        for name, sizes, vacuumed in E.LAYOUTS:
+            shards, ports = E.build_shards(sizes, vacuumed, func, lambda r: r % ndev)
+            sh = pg.LocalShardedIndex(shards)
+            for ef in (20, 100, 200):
+                want = E.oracle_merge(ports, Q, ef)
+                got = sh.search(Q, ef)
+                lab = np.full((nq, ef), 0x1111111111111111, np.uint64); dst = np.full((nq, ef), -7.0, np.float32); cnt = np.full(nq, 0x22222222, np.uint32)
+                rc = sh.L.hnsw_gpu_sharded_search_dev(sh._h, Q.ctypes.data, nq, ef, lab.ctypes.data, dst.ctypes.data, cnt.ctypes.data, None)
+                assert rc == 0, sh.L.hnsw_gpu_last_error()
+                out["cases"].append({"layout": name, "func": int(func), "ef": ef, "queries": 2 * nq, "short_outputs": int((want[2] < ef).sum()),
+                                     "wrong": int(MU.mismatches(got, want).sum() + MU.mismatches((lab, dst, cnt), want).sum())})
+            sh.close()
+            for ix in shards:
+                ix.close()
+    return out
+
+
 def others():
     """the other kernels behind the C-ABI: serial device insert (graph bytes == the oracle's), batched insert (searchable),
     the walk's pop sequence, vacuum flags, export, the canonical exhaustive scan"""
@@ -548,4 +579,4 @@ def stream():
 
 
 if __name__ == "__main__":
-    print(json.dumps({"accept": accept, "forms": forms, "second_walk": second_walk, "others": others, "abort": abort, "traced": traced, "sharded": sharded, "moving_helpers": moving_helpers, "wide": wide, "reforder": reforder, "insert": insert, "stream": stream}[sys.argv[1]]()))
+    print(json.dumps({"accept": accept, "forms": forms, "second_walk": second_walk, "others": others, "abort": abort, "traced": traced, "sharded": sharded, "sharded_edges": sharded_edges, "moving_helpers": moving_helpers, "wide": wide, "reforder": reforder, "insert": insert, "stream": stream}[sys.argv[1]]()))

@@ -3,8 +3,10 @@ shard + CPU merge (the parity definition of SURVEY.md §8e)."""
 import numpy as np
 import pytest
 
+import merge_util
 import oracle
 import pg_embedding_amd as pg
+import sharded_edges
 from pg_embedding_amd.datasets import gmm
 from pg_embedding_amd.sharded import ShardedIndex, shard_range
 
@@ -239,3 +241,65 @@ def test_shards_in_two_processes_meet_in_one_shared_buffer():
         assert (md[q, :order.size].view(np.uint32) == d[order].view(np.uint32)).all()
     ix.close()
     check(L.hnsw_gpu_shared_free(0, base), "hnsw_gpu_shared_free")
+
+
+@pytest.mark.parametrize("func", [pg.DIST_L2, pg.DIST_COSINE, pg.DIST_MANHATTAN], ids=["l2", "cosine", "manhattan"])
+@pytest.mark.parametrize("layout", sharded_edges.LAYOUTS, ids=[x[0] for x in sharded_edges.LAYOUTS])
+def test_short_empty_and_vacuumed_shards(layout, func, gpu_count):
+    """Shards that hand the merge kernel short, empty and padded lists (tests/sharded_edges.py): shards of 1, 3, 5 and 40 rows next
+    to one of 900, a fully vacuumed shard between two live ones, a single shard of one row, an empty shard first.  Beams of 20,
+    100, 200 and 1000 (larger than the shards; the wide-beam form above 64), host-pointer and device-pointer form: labels,
+    distance bits, counts and the padded tail of every query == oracle per shard + CPU merge."""
+    import torch
+    name, sizes, vacuumed = layout
+    nq = 64
+    Q = gmm(nq, sharded_edges.DIM, k=12, seed=78, stream=1)
+    shards, ports = sharded_edges.build_shards(sizes, vacuumed, func, lambda r: r % max(gpu_count, 1))
+    sh = pg.LocalShardedIndex(shards)
+    dq = torch.from_numpy(Q).cuda(shards[0].device)
+    short = 0
+    for ef in (20, 100, 200, 1000):
+        want = sharded_edges.oracle_merge(ports, Q, ef)
+        short += int((want[2] < ef).sum())
+        got = sh.search(Q, ef)
+        wrong = merge_util.mismatches(got, want)
+        assert not wrong.any(), (name, ef, "host pointers", np.flatnonzero(wrong)[:8])
+        tl, td, tc = sh.search_torch(dq, ef)
+        torch.cuda.synchronize()
+        wrong = merge_util.mismatches((tl.cpu().numpy(), td.cpu().numpy(), tc.cpu().numpy()), want)
+        assert not wrong.any(), (name, ef, "device pointers", np.flatnonzero(wrong)[:8])
+    assert short > 0                                        # every layout is shorter than the widest beam
+    sh.close()
+    for s in shards:
+        s.close()
+
+
+def test_buffers_grow_between_calls_on_different_user_streams(gpu_count):
+    """One LocalShardedIndex called four times in a row with (nq, ef) = (8, 20), (300, 200), (8, 20), (300, 64), alternating between
+    two user streams and with no host synchronisation between the calls: the gather buffer grows under the second call, and the
+    calls pass through the wait for the previous call's merge on the OTHER stream (the `merged` event of
+    hnsw_gpu_sharded_search_dev).  Every result == oracle per shard + CPU merge.  A regression exercise of that path, not a proof
+    that the wait is needed: without it this test could only fail by losing a race against a short merge kernel."""
+    import torch
+    shards, ports = sharded_edges.build_shards((700, 900, 800), (), pg.DIST_L2, lambda r: r % max(gpu_count, 1))
+    sh = pg.LocalShardedIndex(shards)
+    dev = shards[0].device
+    calls = [(8, 20), (300, 200), (8, 20), (300, 64)]
+    Qs = [gmm(nq, sharded_edges.DIM, k=12, seed=79 + i, stream=1) for i, (nq, ef) in enumerate(calls)]
+    dqs = [torch.from_numpy(Q).cuda(dev) for Q in Qs]
+    streams = [torch.cuda.Stream(dev), torch.cuda.Stream(dev)]
+    torch.cuda.synchronize()
+    got = []
+    for i, (nq, ef) in enumerate(calls):
+        with torch.cuda.stream(streams[i % 2]):
+            got.append(sh.search_torch(dqs[i], ef))
+    for s in streams:
+        s.synchronize()
+    torch.cuda.synchronize()
+    for i, (nq, ef) in enumerate(calls):
+        tl, td, tc = got[i]
+        wrong = merge_util.mismatches((tl.cpu().numpy(), td.cpu().numpy(), tc.cpu().numpy()), sharded_edges.oracle_merge(ports, Qs[i], ef))
+        assert not wrong.any(), (i, nq, ef, np.flatnonzero(wrong)[:8])
+    sh.close()
+    for s in shards:
+        s.close()

@@ -182,6 +182,18 @@ def test_native_sharded_search_with_shards_on_several_emulated_devices(emu_lib, 
     assert all(c["wrong"] == 0 for c in res["cases"]), res
 
 
+def test_native_sharded_search_over_short_empty_and_vacuumed_shards(emu_lib):
+    """Shards that hand the merge kernel short, empty and padded lists (tests/sharded_edges.py): shards of 1, 3, 5 and 40 rows next
+    to one of 900, a fully vacuumed shard between two live ones, a single shard of one row, an empty shard first; L2 and cosine,
+    beams of 20, 100 and 200 (larger than most of these shards; the wide-beam form above 64), host-pointer and device-pointer form,
+    the shards dealt over three emulated devices: labels, distance bits, counts and the padded tail == oracle per shard + CPU merge."""
+    res = run_case("sharded_edges", emu_lib, {"SIMT_EMU_DEVICES": "3"}, timeout=900)
+    assert res["devices"] == 3 and len(res["cases"]) == 2 * 5 * 3
+    assert all(c["wrong"] == 0 for c in res["cases"]), [c for c in res["cases"] if c["wrong"]]
+    assert sum(c["short_outputs"] for c in res["cases"]) > 0
+    print(f"edge shards on the emulator: {sum(c['queries'] for c in res['cases'])} (case, query) comparisons in {len(res['cases'])} cases")
+
+
 def test_the_emulator_notices_a_store_into_another_devices_memory():
     """teeth of the test above: the same source with the peer enabling removed (but the direct-store path kept) must die on the
     first cross-device store"""
