@@ -209,6 +209,30 @@ int hnsw_gpu_scan_batch(hnsw_gpu_index *ix, const coord_t *queries, size_t nq, s
 						const uint32_t *allow, size_t allow_bits, size_t nfilters, const uint32_t *allow_of,
 						label_t *labels, dist_t *dists, uint32_t *counts, uint32_t *scan_stats);
 
+/* Exact filtered k-NN: a canonical scan over the allowed rows only (csrc/device_filtered_knn.h) — the exact counterpart of the filtered
+ * index scan above for SELECTIVE filters, where the graph scan needs a beam about k / selectivity wide, several rounds, and is still
+ * approximate.  The filter convention is hnsw_gpu_scan_batch_dev's (nfilters bitmaps over label VALUES, ceil(allow_bits / 32) words apart,
+ * labels >= allow_bits do not pass, d_allow_of NULL = bitmap 0 for every query), except that d_allow is REQUIRED (without a filter:
+ * hnsw_gpu_bruteforce_dev).  Per query q with bitmap b: A(b) = the elements that are not vacuumed (bit 48 of the label word) and whose
+ * label passes b (two elements holding one label are both in A(b)).  The result is the min(k, |A(b)|) elements of A(b) with the smallest
+ * (canonical fp32 distance, element number) — hnsw_gpu_bruteforce_dev's selection — written in ascending order of (distance, label), equal
+ * pairs by element number: hnsw_search's order.  Every distance is the one the search and hnsw_dist_func compute, bit for bit (a NaN
+ * cosine distance, i.e. a zero row, is outside the contract).
+ *   d_labels  nq*k, unused tail = ~0     d_dists  nq*k or NULL, tail = +inf     d_idx  nq*k element numbers or NULL, tail = 0xFFFFFFFF
+ *   d_counts  nq results per query (= min(k, |A(b)|))
+ * The work per query is |A(b)| rows, not n: the filter is first turned into one ascending list of element numbers per bitmap (4 bytes
+ * per allowed row and bitmap, kept in the mirror between calls up to 64 MiB), and queries that share a bitmap share its list.  k outside
+ * [1, 1024], nq > 65535, allow_bits == 0, nfilters == 0, a NULL required pointer, k and dim too large for one block's LDS:
+ * HNSW_GPU_ERR_ARG before anything is launched (outputs untouched); nq == 0: OK, nothing touched; a list that cannot be allocated:
+ * HNSW_GPU_ERR_NOMEM.  fp32 rows; the call synchronises `stream` (once for the lists' total size, once at its end). */
+int hnsw_gpu_filtered_knn_dev(hnsw_gpu_index *ix, const coord_t *d_queries, size_t nq, size_t k,
+							  const uint32_t *d_allow, size_t allow_bits, size_t nfilters, const uint32_t *d_allow_of,
+							  label_t *d_labels, dist_t *d_dists, idx_t *d_idx, uint32_t *d_counts, void *stream);
+/* Host-pointer form: copies in, runs on the default stream, copies out. */
+int hnsw_gpu_filtered_knn(hnsw_gpu_index *ix, const coord_t *queries, size_t nq, size_t k,
+						  const uint32_t *allow, size_t allow_bits, size_t nfilters, const uint32_t *allow_of,
+						  label_t *labels, dist_t *dists, idx_t *idx, uint32_t *counts);
+
 /* Milliseconds the most recent search kernel of this index spent on the device,
  * from HIP events recorded on its stream around the launch (waits for it). */
 int hnsw_gpu_last_search_ms(hnsw_gpu_index *ix, float *ms);

@@ -103,6 +103,12 @@ int hnsw_gpu_last_search_order(hnsw_gpu_index *ix, uint32_t *perm, uint32_t *key
  * round's active count was written (table reset, hand-out and compaction kernels), from HIP events on the call's stream.  Any array may be NULL. */
 int hnsw_gpu_last_scan_rounds(hnsw_gpu_index *ix, uint32_t *rounds, uint32_t *active, uint32_t *ef, float *search_ms, float *handout_ms, size_t cap);
 
+/* The mirror's last hnsw_gpu_filtered_knn[_dev] call: out[0] = entries of all allowed lists together (sum over the bitmaps b of |A(b)|),
+ * out[1] = rows the scan kernel scored (every wave adds its slice's length: equal to the sum over the queries q of |A(b(q))|, and NOT
+ * nq * n — the call reads the allowed rows only), out[2] = the list build and out[3] = scan + merge + emit, both in MICROSECONDS from
+ * HIP events on the call's stream (the list build includes the call's wait for the lists' total size).  Zeros before the first call. */
+int hnsw_gpu_last_filtered_knn(hnsw_gpu_index *ix, uint64_t out[4]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -134,6 +134,9 @@ def gpu_lib():
     L.hnsw_gpu_scan_batch_dev.argtypes = [vp, vp, sz, sz, sz, sz, vp, sz, sz, vp, vp, vp, vp, vp, vp]
     L.hnsw_gpu_scan_batch.argtypes = [vp, vp, sz, sz, sz, sz, vp, sz, sz, vp, vp, vp, vp, vp]
     L.hnsw_gpu_last_scan_rounds.argtypes = [vp, _u32p, vp, vp, vp, vp, sz]
+    L.hnsw_gpu_filtered_knn_dev.argtypes = [vp, vp, sz, sz, vp, sz, sz, vp, vp, vp, vp, vp, vp]
+    L.hnsw_gpu_filtered_knn.argtypes = [vp, vp, sz, sz, vp, sz, sz, vp, vp, vp, vp, vp]
+    L.hnsw_gpu_last_filtered_knn.argtypes = [vp, _u64p]
     L.hnsw_gpu_last_search_ms.argtypes = [vp, _f32p]
     L.hnsw_gpu_search_ms.argtypes = [vp, C.c_uint, _f32p]
     L.hnsw_gpu_last_search_slots.argtypes = [vp, _u32p]

@@ -1,0 +1,302 @@
+// device_filtered_knn.h — exact filtered k-NN: a canonical scan over the allowed rows only (hnsw_gpu_filtered_knn_dev, gpu_scan.hip;
+// DESIGN §4.11).
+//
+// A(b) = the elements that are not vacuumed (bit 48 of the label word) and whose label passes bitmap b (the allow filter of
+// device_indexscan.h: bit l of a bitmap says whether label l passes, labels >= allow_bits do not).  Four steps, all deterministic:
+//
+//   1. fk_count_kernel   one wave per (bitmap, segment of FK_SEG rows): how many of its rows are in A(b) (ballot + popcount)
+//      fk_offsets_kernel one block: exclusive scan of those counts, bitmap-major -> where every (bitmap, segment) starts in the lists;
+//                        the total and the longest list go to a pinned host pair (the call's one wait before the scan)
+//      fk_fill_kernel    the count kernel's pass again, writing element numbers: list b = A(b) ascending, lists back to back, 4 bytes
+//                        per entry (CSR: offsets off[b * nseg] .. off[(b + 1) * nseg])
+//   2. fk_scan_kernel    bruteforce_kernel (gpu_scan.hip) with the row functor reading the list: a wave takes a contiguous slice of its
+//                        query's list, 64 entries per step (loaded coalesced, once, into the wave's LDS), scores them with the canonical
+//                        score_rows<FUNC, 4, 2> + finish_dist and keeps a sorted top-k of (ord(dist) << 32 | ELEMENT) keys.  A query
+//                        uses as many waves as its own list is long (FK_WAVE_ROWS rows each at least, at most the launch's splits * 4).
+//   3. fk_emit_kernel    one wave per query: merges the query's partial lists (ranks by binary search: keys are unique), gathers the
+//                        labels of the <= k winners, ranks them by (dist, label, element) — hnsw_search's order — and writes labels,
+//                        distances, element numbers, the count and the padded tails.
+//
+// Selection by (dist, element), emission by (dist, label): the reference's two steps (topResults, then the sort of searchKnn's output).
+#pragma once
+#include "device_dist.h"
+#include "device_search.h"
+
+namespace pgemb {
+
+constexpr uint32_t FK_SEG = 1024;            // rows per (bitmap, segment) cell of the list build: one wave, 16 steps of 64 labels
+constexpr uint32_t FK_WAVE_ROWS = 64;        // a scanning wave gets at least this many list entries (or the query uses fewer waves)
+constexpr uint32_t FK_SCAN_THREADS = 256;    // the offsets kernel's one block
+// 1 = each XCD takes a contiguous eighth of the block order (the blocks of one list slice share one L2) and long lists get at least 8 splits.
+// Measured slower than the launch order on MI355X (profiles/filtered_knn_bench.json: tenant bitmaps 1.7-2.5x, the rest within 3 %), so it is
+// off; the variant build -DFK_XCD_REMAP=1 keeps the comparison repeatable.
+#ifndef FK_XCD_REMAP
+#define FK_XCD_REMAP 0
+#endif
+
+struct FkLists
+{
+	const uint64_t *labels; uint32_t n, nseg;
+	const uint32_t *allow; uint64_t allow_bits; uint32_t allow_words, nfilters;
+};
+
+// is element i (label word `lab`) in A(bits)?  the vacuum test and the bitmap test in one pass
+__device__ __forceinline__ bool fk_member(uint64_t lab, const uint32_t *bits, uint64_t allow_bits)
+{
+	const bool cand = !((lab >> 48) & 1ull) && lab < allow_bits;
+	const uint32_t w = bits[cand ? (size_t) (lab >> 5) : 0];          // (unconditional load, clamped: allow_bits >= 1)
+	return cand && ((w >> (lab & 31u)) & 1u);
+}
+
+// grid = nfilters * ceil(nseg / 4) blocks of 256, bitmap-major: wave wib of block (b, x) counts segment x * 4 + wib of bitmap b
+__device__ __forceinline__ bool fk_cell(const FkLists &a, uint32_t &b, uint32_t &seg)
+{
+	const uint32_t nsb = (a.nseg + 3u) / 4u;
+	b = blockIdx.x / nsb;
+	seg = (blockIdx.x - b * nsb) * 4u + (threadIdx.x >> 6);
+	return seg < a.nseg;
+}
+
+__global__ __launch_bounds__(256) void fk_count_kernel(const FkLists a, uint32_t *__restrict__ counts /* [nfilters][nseg] */)
+{
+	const uint32_t lane = threadIdx.x & 63u;
+	uint32_t b, seg;
+	if (!fk_cell(a, b, seg)) return;
+	const uint32_t *bits = a.allow + (size_t) b * a.allow_words;
+	const uint32_t r0 = seg * FK_SEG, r1 = min(a.n, r0 + FK_SEG);
+	uint32_t c = 0;
+	for (uint32_t base = r0; base < r1; base += 64)
+	{
+		const uint32_t i = base + lane;
+		const uint64_t lab = a.labels[i < r1 ? i : r1 - 1];
+		c += (uint32_t) __builtin_popcountll(__ballot(i < r1 && fk_member(lab, bits, a.allow_bits)));
+	}
+	if (lane == 0) counts[(size_t) b * a.nseg + seg] = c;
+}
+
+// ONE block of FK_SCAN_THREADS threads, each with a contiguous run of the cells: off[j] = sum of counts[0 .. j) for j <= ncells (64-bit:
+// the lists together may pass 2^32 entries); host[0] = the total, host[1] = the longest list (pinned host words).
+// Dynamic LDS: FK_SCAN_THREADS 64-bit words.
+__global__ __launch_bounds__(FK_SCAN_THREADS) void fk_offsets_kernel(const uint32_t *__restrict__ counts, uint32_t nseg, uint32_t nfilters,
+																	   uint64_t *__restrict__ off, uint64_t *__restrict__ host)
+{
+	extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+	uint64_t *part = reinterpret_cast<uint64_t *>(smem);
+	const uint32_t tid = threadIdx.x;
+	const size_t ncells = (size_t) nseg * nfilters;
+	const size_t per = (ncells + FK_SCAN_THREADS - 1) / FK_SCAN_THREADS;
+	const size_t j0 = (size_t) tid * per < ncells ? (size_t) tid * per : ncells, j1 = j0 + per < ncells ? j0 + per : ncells;
+	uint64_t sum = 0;
+	for (size_t j = j0; j < j1; j++) sum += counts[j];
+	part[tid] = sum;
+	__syncthreads();
+	uint64_t run = 0, total = 0;
+	for (uint32_t t = 0; t < FK_SCAN_THREADS; t++)
+	{
+		const uint64_t v = part[t];
+		run += t < tid ? v : 0ull;
+		total += v;
+	}
+	for (size_t j = j0; j < j1; j++) { off[j] = run; run += counts[j]; }
+	if (tid == 0) off[ncells] = total;
+	__syncthreads();                                                  // (the block's stores to off[] are visible to the block)
+	uint64_t longest = 0;
+	for (uint32_t b = tid; b < nfilters; b += FK_SCAN_THREADS)
+	{
+		const uint64_t len = off[(size_t) (b + 1) * nseg] - off[(size_t) b * nseg];
+		longest = len > longest ? len : longest;
+	}
+	part[tid] = longest;
+	__syncthreads();
+	if (tid == 0)
+	{
+		for (uint32_t t = 1; t < FK_SCAN_THREADS; t++) longest = part[t] > longest ? part[t] : longest;
+		host[0] = total; host[1] = longest;
+	}
+}
+
+// the count kernel's grid and pass; element numbers in ascending order (ballot + prefix popcount: no atomic, no scheduling in the order)
+__global__ __launch_bounds__(256) void fk_fill_kernel(const FkLists a, const uint64_t *__restrict__ off, uint32_t *__restrict__ list)
+{
+	const uint32_t lane = threadIdx.x & 63u;
+	uint32_t b, seg;
+	if (!fk_cell(a, b, seg)) return;
+	const uint64_t below = (1ull << lane) - 1ull;
+	const uint32_t *bits = a.allow + (size_t) b * a.allow_words;
+	const uint32_t r0 = seg * FK_SEG, r1 = min(a.n, r0 + FK_SEG);
+	uint32_t *dst = list + off[(size_t) b * a.nseg + seg];
+	uint32_t c = 0;
+	for (uint32_t base = r0; base < r1; base += 64)
+	{
+		const uint32_t i = base + lane;
+		const uint64_t lab = a.labels[i < r1 ? i : r1 - 1];
+		const bool in = i < r1 && fk_member(lab, bits, a.allow_bits);
+		const uint64_t m = __ballot(in);
+		if (in) dst[c + (uint32_t) __builtin_popcountll(m & below)] = i;
+		c += (uint32_t) __builtin_popcountll(m);
+	}
+}
+
+struct FkScan
+{
+	const float *vec; uint32_t dim, stride, nchunks, kiters, qpad_floats;
+	const float *queries; uint32_t nq, k, splits;
+	const uint32_t *list; const uint64_t *off; uint32_t nseg; const uint32_t *allow_of;
+	uint64_t *part;                  // [nq][splits * 4][k] ascending keys, ~0 = none
+	unsigned long long *scored;      // rows scored by the call (one atomic per wave)
+};
+
+// the waves query qi scans with, out of the launch's splits * 4, from the length of its own list
+__device__ __forceinline__ uint32_t fk_waves(uint32_t len, uint32_t splits)
+{
+	return min(splits * 4u, (len + FK_WAVE_ROWS - 1) / FK_WAVE_ROWS);
+}
+
+__device__ __forceinline__ void fk_list_of(const FkScan &a, uint32_t qi, const uint32_t *&list, uint32_t &len)
+{
+	const uint32_t b = a.allow_of ? a.allow_of[qi] : 0u;
+	const uint64_t o = a.off[(size_t) b * a.nseg];
+	list = a.list + o;
+	len = (uint32_t) (a.off[(size_t) (b + 1) * a.nseg] - o);          // (a list is a subset of the < 2^32 elements)
+}
+
+// grid = splits * nq blocks (rounded up to 8), 4 waves each.  Block order: query number fastest within a split, so the blocks resident at
+// one time cover few list slices and many queries.  (With FK_XCD_REMAP each XCD — blocks are dealt to the 8 XCDs round robin — gets a
+// contiguous eighth of that order, so that the blocks of one slice share one L2: measured, not faster, off.)
+// Per wave in LDS behind the query image: k + 1 keys | 2 x 64 sums | 64 element numbers.
+template <int FUNC>
+__global__ __launch_bounds__(256) void fk_scan_kernel(const FkScan a)
+{
+	extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+	const uint32_t nblk = a.splits * a.nq;
+#if FK_XCD_REMAP
+	const uint32_t per = gridDim.x >> 3;
+	const uint32_t L = (blockIdx.x & 7u) * per + (blockIdx.x >> 3);
+#else
+	const uint32_t L = blockIdx.x;
+#endif
+	if (L >= nblk) return;
+	const uint32_t sp = L / a.nq, qi = L - sp * a.nq;
+	const uint32_t *list; uint32_t len;
+	fk_list_of(a, qi, list, len);
+	const uint32_t nw = fk_waves(len, a.splits);
+	if (sp * 4u >= nw) return;                                        // (block-uniform) a short list leaves the later splits idle
+	float *qf = reinterpret_cast<float *>(smem);
+	const float4 *q4 = reinterpret_cast<const float4 *>(smem);
+	for (uint32_t e = threadIdx.x; e < a.qpad_floats; e += blockDim.x) qf[e] = (e < a.dim) ? a.queries[(size_t) qi * a.dim + e] : 0.f;
+	__syncthreads();
+	const int lane = threadIdx.x & 63;
+	const uint32_t wib = threadIdx.x >> 6, w = sp * 4u + wib, k = a.k;
+	if (w >= nw) return;                                              // (wave-uniform; no block barrier below)
+	unsigned char *wbase = smem + (size_t) a.qpad_floats * 4;
+	uint64_t *top = reinterpret_cast<uint64_t *>(wbase) + (size_t) wib * (k + 1);
+	float *sums = reinterpret_cast<float *>(wbase + (size_t) 4 * (k + 1) * 8) + wib * 128;
+	uint32_t *ids = reinterpret_cast<uint32_t *>(wbase + (size_t) 4 * (k + 1) * 8 + 4 * 128 * 4) + wib * 64;
+	const uint32_t lo = (uint32_t) ((uint64_t) len * w / nw), hi = (uint32_t) ((uint64_t) len * (w + 1) / nw);
+	float qnorm = 0.f;
+	if (FUNC == F_COSINE) qnorm = query_norm(q4, a.nchunks, a.kiters, lane);
+	uint32_t tsize = 0;
+	uint64_t worst = ~0ull;
+	for (uint32_t base = lo; base < hi; base += 64)
+	{
+		const uint32_t cnt = min(64u, hi - base);
+		const uint32_t id = list[base + min((uint32_t) lane, cnt - 1u)];      // one coalesced load per step; the tail re-reads its last entry
+		ids[lane] = id;
+		wave_sync();
+		auto listed = [ids](uint32_t r) { return ids[r]; };
+		score_rows<FUNC, 4, 2>(a.vec, a.stride, q4, a.nchunks, a.kiters, listed, cnt, sums, lane);
+		wave_sync();
+		const float dl = finish_dist<FUNC>(sums[lane], sums[OUT2 + lane], qnorm);
+		const uint64_t kl = ((uint64_t) ord_f32(dl) << 32) | id;
+		// only rows that can enter the current top-k are visited one by one
+		uint64_t todo = __ballot((uint32_t) lane < cnt && (tsize < k || kl < worst));
+		while (todo)
+		{
+			const uint32_t r = (uint32_t) __builtin_ctzll(todo);
+			todo &= todo - 1;
+			const uint64_t key = readlane_u64(kl, r);
+			if (tsize < k || key < worst)
+			{
+				tsize = sorted_insert(top, tsize, key, k, lane);
+				worst = top[tsize - 1];
+			}
+		}
+		wave_sync();
+	}
+	uint64_t *dst = a.part + ((size_t) qi * a.splits * 4u + w) * k;
+	for (uint32_t i = lane; i < k; i += 64) dst[i] = (i < tsize) ? top[i] : ~0ull;
+	if (lane == 0) atomicAdd(a.scored, (unsigned long long) (hi - lo));
+}
+
+struct FkEmit
+{
+	FkScan s;
+	const uint64_t *labels; uint32_t n;
+	uint64_t *out_labels; float *out_dists; uint32_t *out_idx; uint32_t *out_counts;
+};
+
+// One wave per query (block = 64 threads).  LDS: k winner keys | k labels.
+__global__ __launch_bounds__(64) void fk_emit_kernel(const FkEmit a)
+{
+	extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+	const uint32_t qi = blockIdx.x, lane = threadIdx.x, k = a.s.k;
+	uint64_t *win = reinterpret_cast<uint64_t *>(smem), *lab = win + k;
+	const uint32_t *list; uint32_t len;
+	fk_list_of(a.s, qi, list, len);
+	const uint32_t nlists = fk_waves(len, a.s.splits);
+	const uint32_t cnt = min(k, len);                                 // every listed row was scored: the merge finds min(k, |A|) keys
+	const uint64_t *src = a.s.part + (size_t) qi * a.s.splits * 4u * k;
+	// 1. the key merge (key_merge_kernel's ranks) over the lists this query's waves wrote
+	const uint32_t total = nlists * k;
+	for (uint32_t x = lane; x < total; x += 64)
+	{
+		const uint32_t l = x / k;
+		const uint64_t key = src[x];
+		if (key == ~0ull) continue;
+		uint32_t rank = x - l * k;
+		for (uint32_t m = 0; m < nlists && rank < k; m++)
+		{
+			if (m == l) continue;
+			const uint64_t *o = src + (size_t) m * k;
+			uint32_t lo = 0, hi = k;                                  // number of keys in list m below `key` (keys are unique: one element, one key)
+			while (lo < hi) { uint32_t mid = (lo + hi) >> 1; if (o[mid] < key) lo = mid + 1; else hi = mid; }
+			rank += lo;
+		}
+		if (rank < k) win[rank] = key;
+	}
+	wave_sync();
+	// 2. the winners' labels
+	for (uint32_t i = lane; i < cnt; i += 64) lab[i] = a.labels[min((uint32_t) win[i], a.n - 1u)];
+	wave_sync();
+	// 3. hnsw_search's order: ascending (distance, label); equal pairs by element number (win is ascending by (distance, element))
+	const size_t obase = (size_t) qi * k;
+	for (uint32_t b = 0; b < cnt; b += 64)
+	{
+		const uint32_t i = b + lane;
+		const bool in = i < cnt;
+		const uint64_t ki = in ? win[i] : 0, li = in ? lab[i] : 0;
+		const uint32_t di = (uint32_t) (ki >> 32);
+		uint32_t rank = 0;
+		for (uint32_t j = 0; j < cnt; j++)
+		{
+			const uint64_t kj = win[j], lj = lab[j];
+			const uint32_t dj = (uint32_t) (kj >> 32);
+			rank += (dj < di || (dj == di && (lj < li || (lj == li && kj < ki)))) ? 1u : 0u;
+		}
+		if (in)
+		{
+			a.out_labels[obase + rank] = li;
+			if (a.out_dists) a.out_dists[obase + rank] = unord_f32(di);
+			if (a.out_idx) a.out_idx[obase + rank] = (uint32_t) ki;
+		}
+	}
+	for (uint32_t i = cnt + lane; i < k; i += 64)
+	{
+		a.out_labels[obase + i] = ~0ull;
+		if (a.out_dists) a.out_dists[obase + i] = __builtin_inff();
+		if (a.out_idx) a.out_idx[obase + i] = LINK_NONE;
+	}
+	if (lane == 0) a.out_counts[qi] = cnt;
+}
+
+}  // namespace pgemb

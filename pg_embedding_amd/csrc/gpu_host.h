@@ -5,7 +5,7 @@
 //   hnsw_gpu.hip      errors, configuration, workspaces + watchdog, the mirror (create / import / export / append / reserve)
 //   gpu_search.hip    launch planning (launch_search), the search entry points, traces of one walk, search contexts
 //   gpu_stream.hip    streams: one resident launch fed by the host
-//   gpu_scan.hip      batched distances, exhaustive k-NN (canonical scan, MFMA filter)
+//   gpu_scan.hip      batched distances, exhaustive k-NN (canonical scan, MFMA filter), exact filtered k-NN over allowed lists
 //   gpu_build.hip     insert path: batched link step, single inserts
 //   gpu_sharded.hip   top-k merge, shards in one process, the exchange buffer shared between processes
 //   gpu_diag.hip      measurement only (include/hnsw_gpu_diag.h): traced launches, replay / gather roofs, clocks, placement
@@ -126,6 +126,18 @@ struct ScanWs
 };
 void scan_ws_free(ScanWs *s);
 
+// ---- exact filtered k-NN (device_filtered_knn.h, hnsw_gpu_filtered_knn_dev) -------------------------
+// Buffers of one mirror's calls, reused from call to call while they are large enough; one grown beyond 64 MiB is freed when its call ends.
+struct FkWs
+{
+	ScanBuf cells, list, part;                           // per-(bitmap, segment) counts | offsets | rows-scored word; the lists; the partial top-k lists
+	uint64_t *host = nullptr;                            // pinned: [0] entries of all lists, [1] the longest list, [2] rows scored
+	hipEvent_t ev[3] = {};                               // before the list build | after it | after the emit kernel
+	uint64_t listed = 0, scored = 0;                     // the last call (hnsw_gpu_last_filtered_knn)
+	float build_ms = 0.f, scan_ms = 0.f;
+};
+void fk_ws_free(FkWs *s);
+
 extern std::mutex &g_ws_mu;                              // guards the registry of workspaces (abort + watchdog, hnsw_gpu.hip)
 int64_t now_ms();
 int abort_ws_locked(SearchWs *w);                        // g_ws_mu held
@@ -192,6 +204,7 @@ struct hnsw_gpu_index
 	// `vec` clears piv_valid (rows16_mark, reserve); a stale set would only cost speed — the order is a permutation whatever the keys
 	float   *piv = nullptr; uint32_t piv_P = 0, piv_kd = 0; size_t piv_n = 0; bool piv_valid = false;
 	ScanWs   scan;                    // the batched index scan's buffers and per-round figures (device_indexscan.h)
+	FkWs     fk;                      // exact filtered k-NN: the allowed lists and the scan's partial results (device_filtered_knn.h)
 };
 
 // rows [lo, hi) of `vec` were (or are about to be) written: the reduced copy, if any, converts them again before the next reduced search

@@ -1,8 +1,10 @@
-// gpu_scan.hip — batched distances (hnsw_dist_func over many rows) and exhaustive k-NN: canonical scan, MFMA filter (csrc/device_bf_mfma.h)
+// gpu_scan.hip — batched distances (hnsw_dist_func over many rows), exhaustive k-NN: canonical scan, MFMA filter (csrc/device_bf_mfma.h), and exact
+// filtered k-NN: the canonical scan over lists of allowed rows (csrc/device_filtered_knn.h)
 // One translation unit of libhnsw_gpu.so (csrc/gpu_host.h lists them); gfx950 only, plain HIP runtime, no framework types in any signature.
 #include "gpu_host.h"
 #include "device_bf_mfma.h"
 #include "device_bf_mfma16.h"
+#include "device_filtered_knn.h"
 
 // ------------------------------------------------------------------------------------
 // batched distances (hnsw_dist_func over many rows)
@@ -585,6 +587,186 @@ extern "C" int hnsw_gpu_bruteforce_reduced_dev(hnsw_gpu_index *ix, int format, c
 	if (ovf)      // the 16-bit bound is looser: a list that overflowed here may not in f32 (which falls back to the scan in turn)
 		return hnsw_gpu_bruteforce_mfma_dev(ix, d_queries, nq, k, d_idx, d_dists, stream_);
 	ix->bf_form = format == ROWS_BF16 ? HNSW_GPU_BF_FORM_BF16 : HNSW_GPU_BF_FORM_F16;
+	return HNSW_GPU_OK;
+}
+
+// ------------------------------------------------------------------------------------
+// exact filtered k-NN: the canonical scan over the allowed rows only (device_filtered_knn.h)
+// ------------------------------------------------------------------------------------
+static const size_t FK_KEEP_BYTES = (size_t) 64 << 20;        // a buffer larger than this does not outlive its call (as the index scan's)
+static const size_t FK_PART_BYTES = (size_t) 1 << 30;         // the partial lists of a call: more splits are not worth more memory than this
+
+void fk_ws_free(FkWs *s)
+{
+	ScanBuf *all[] = {&s->cells, &s->list, &s->part};
+	for (ScanBuf *b : all) { if (b->p) (void) hipFree(b->p); b->p = nullptr; b->bytes = 0; }
+	if (s->host) (void) hipHostFree(s->host);
+	s->host = nullptr;
+	for (hipEvent_t &e : s->ev) { if (e) (void) hipEventDestroy(e); e = nullptr; }
+}
+
+static int fk_buf(ScanBuf *b, size_t bytes, const char *what)
+{
+	if (bytes <= b->bytes) return HNSW_GPU_OK;
+	if (b->p) (void) hipFree(b->p);
+	b->p = nullptr; b->bytes = 0;
+	if (hipMalloc(&b->p, bytes) != hipSuccess)
+	{
+		b->p = nullptr;
+		(void) hipGetLastError();
+		return fail(HNSW_GPU_ERR_NOMEM, "filtered k-NN: no room for %s (%zu bytes)", what, bytes);
+	}
+	b->bytes = bytes;
+	return HNSW_GPU_OK;
+}
+
+static void fk_trim(FkWs *s)
+{
+	ScanBuf *all[] = {&s->cells, &s->list, &s->part};
+	for (ScanBuf *b : all)
+		if (b->bytes > FK_KEEP_BYTES) { (void) hipFree(b->p); b->p = nullptr; b->bytes = 0; }
+}
+
+// the caller's contract, checked before anything is launched or copied (the outputs stay untouched)
+static int fk_check(hnsw_gpu_index *ix, const void *queries, size_t nq, size_t k, const void *allow, size_t allow_bits, size_t nfilters,
+					const void *labels, const void *counts)
+{
+	if (!ix) return fail(HNSW_GPU_ERR_ARG, "index is NULL");
+	if (nq == 0) return HNSW_GPU_OK;
+	if (!queries || !allow || !labels || !counts) return fail(HNSW_GPU_ERR_ARG, "filtered k-NN: NULL buffer (the filter is required: hnsw_gpu_bruteforce_dev takes none)");
+	if (k == 0 || k > 1024) return fail(HNSW_GPU_ERR_ARG, "k %zu out of range [1, 1024]", k);
+	if (nq > 65535) return fail(HNSW_GPU_ERR_ARG, "at most 65535 queries per call");
+	if (allow_bits == 0 || nfilters == 0) return fail(HNSW_GPU_ERR_ARG, "filtered k-NN: an allow filter of no bits");
+	if ((allow_bits + 31) / 32 >= 0xFFFFFFFFull || nfilters >= 0xFFFFFFFFull) return fail(HNSW_GPU_ERR_ARG, "filtered k-NN: allow filter too large");
+	const uint32_t kiters = (ix->stride / 4 + 15) / 16;
+	const size_t lds = round_up(kiters, 4) * 64 * 4 + (size_t) 4 * (k + 1) * 8 + 4 * 128 * 4 + 4 * 64 * 4;
+	if (lds > 64 * 1024) return fail(HNSW_GPU_ERR_ARG, "k/dim too large for filtered k-NN");
+	return HNSW_GPU_OK;
+}
+
+extern "C" int hnsw_gpu_filtered_knn_dev(hnsw_gpu_index *ix, const coord_t *d_queries, size_t nq, size_t k, const uint32_t *d_allow,
+										 size_t allow_bits, size_t nfilters, const uint32_t *d_allow_of, label_t *d_labels, dist_t *d_dists,
+										 idx_t *d_idx, uint32_t *d_counts, void *stream)
+{
+	std::unique_lock<std::recursive_mutex> lock_;
+	if (ix) lock_ = std::unique_lock<std::recursive_mutex>(ix->mu);
+	if (int rc0 = fk_check(ix, d_queries, nq, k, d_allow, allow_bits, nfilters, d_labels, d_counts)) return rc0;
+	if (nq == 0) return HNSW_GPU_OK;
+	HIPCHK(hipSetDevice(ix->device));
+	hipStream_t s = (hipStream_t) stream;
+	FkWs *fw = &ix->fk;
+	struct Trim { FkWs *w; ~Trim() { fk_trim(w); } } trim_{fw};   // on EVERY way out, errors included: no buffer above 64 MiB outlives its call
+	if (!fw->host) HIPCHK(hipHostMalloc((void **) &fw->host, 64, hipHostMallocDefault));
+	for (hipEvent_t &e : fw->ev)
+		if (!e) HIPCHK(hipEventCreate(&e));
+	fw->listed = fw->scored = 0; fw->build_ms = fw->scan_ms = 0.f;
+
+	// 1. the allowed lists: count per (bitmap, segment), offsets, fill
+	const size_t n = ix->n;
+	const uint32_t nseg = (uint32_t) std::max<size_t>(1, (n + FK_SEG - 1) / FK_SEG);
+	const size_t ncells = (size_t) nseg * nfilters, nsb = (nseg + 3) / 4;
+	if (nsb * nfilters >= 0x7FFFFFFFull) return fail(HNSW_GPU_ERR_ARG, "filtered k-NN: %zu filters over %zu rows are too many for one call", nfilters, n);
+	const size_t o_off = round_up(ncells * 4, 256), o_scored = o_off + round_up((ncells + 1) * 8, 256);
+	int rc = fk_buf(&fw->cells, o_scored + 256, "the list offsets");
+	if (rc) return rc;
+	uint32_t *cells = (uint32_t *) fw->cells.p;
+	uint64_t *off = (uint64_t *) ((char *) fw->cells.p + o_off);
+	unsigned long long *scored = (unsigned long long *) ((char *) fw->cells.p + o_scored);
+	FkLists fl;
+	memset(&fl, 0, sizeof(fl));
+	fl.labels = ix->labels; fl.n = (uint32_t) n; fl.nseg = nseg;
+	fl.allow = d_allow; fl.allow_bits = allow_bits; fl.allow_words = (uint32_t) ((allow_bits + 31) / 32); fl.nfilters = (uint32_t) nfilters;
+	fw->host[0] = fw->host[1] = fw->host[2] = 0;
+	HIPCHK(hipEventRecord(fw->ev[0], s));
+	hipLaunchKernelGGL(fk_count_kernel, dim3((uint32_t) (nsb * nfilters)), dim3(256), 0, s, fl, cells);
+	hipLaunchKernelGGL(fk_offsets_kernel, dim3(1), dim3(FK_SCAN_THREADS), FK_SCAN_THREADS * 8, s, (const uint32_t *) cells, nseg, (uint32_t) nfilters, off, fw->host);
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipStreamSynchronize(s));                              // the one wait before the scan: the lists are sized exactly
+	const size_t total = fw->host[0], longest = fw->host[1];
+	if (longest > n || total > n * nfilters) return fail(HNSW_GPU_ERR_INTERNAL, "filtered k-NN: %zu listed rows, longest list %zu, of %zu rows", total, longest, n);
+	if ((rc = fk_buf(&fw->list, total * 4, "the lists of allowed rows"))) return rc;
+	if (total) hipLaunchKernelGGL(fk_fill_kernel, dim3((uint32_t) (nsb * nfilters)), dim3(256), 0, s, fl, (const uint64_t *) off, (uint32_t *) fw->list.p);
+	HIPCHK(hipMemsetAsync(scored, 0, 8, s));
+	HIPCHK(hipEventRecord(fw->ev[1], s));
+
+	// 2. the listed scan.  Splits as the exhaustive scan chooses them, from the longest list (a query with a shorter one uses fewer
+	// waves: fk_waves).  (FK_XCD_REMAP variant builds: a list long enough for it gets at least one slice per XCD to keep apart.)
+	uint32_t splits = (uint32_t) std::max<size_t>(1, std::min<size_t>(64, (size_t) (4 * ix->num_cu) / nq));
+	if (FK_XCD_REMAP && longest >= 8192) splits = std::max(splits, 8u);
+	splits = (uint32_t) std::min<size_t>(splits, std::max<size_t>(1, longest / (4 * FK_WAVE_ROWS)));
+	while (splits > 1 && nq * splits * 4 * k * 8 > FK_PART_BYTES) splits /= 2;
+	if (longest && (rc = fk_buf(&fw->part, nq * splits * 4 * k * 8, "the partial result lists"))) return rc;   // (no list, no scan: the emit kernel reads no partial list)
+	const uint32_t nchunks = ix->stride / 4, kiters = (nchunks + 15) / 16;
+	FkEmit fe;
+	memset(&fe, 0, sizeof(fe));
+	FkScan &fs = fe.s;
+	fs.vec = ix->vec; fs.dim = (uint32_t) ix->meta.dim; fs.stride = ix->stride; fs.nchunks = nchunks; fs.kiters = kiters;
+	fs.qpad_floats = (uint32_t) round_up(kiters, 4) * 64;
+	fs.queries = d_queries; fs.nq = (uint32_t) nq; fs.k = (uint32_t) k; fs.splits = splits;
+	fs.list = (const uint32_t *) fw->list.p; fs.off = off; fs.nseg = nseg; fs.allow_of = d_allow_of;
+	fs.part = (uint64_t *) fw->part.p; fs.scored = scored;
+	fe.labels = ix->labels; fe.n = (uint32_t) n;
+	fe.out_labels = d_labels; fe.out_dists = d_dists; fe.out_idx = d_idx; fe.out_counts = d_counts;
+	const size_t lds = (size_t) fs.qpad_floats * 4 + (size_t) 4 * (k + 1) * 8 + 4 * 128 * 4 + 4 * 64 * 4;
+	const dim3 grid((uint32_t) round_up((size_t) splits * nq, 8));
+	if (longest)
+		switch ((int) ix->meta.dist_func)
+		{
+			case F_L2: hipLaunchKernelGGL(fk_scan_kernel<F_L2>, grid, dim3(256), lds, s, fs); break;
+			case F_COSINE: hipLaunchKernelGGL(fk_scan_kernel<F_COSINE>, grid, dim3(256), lds, s, fs); break;
+			default: hipLaunchKernelGGL(fk_scan_kernel<F_MANHATTAN>, grid, dim3(256), lds, s, fs); break;
+		}
+	// 3. merge + emit
+	hipLaunchKernelGGL(fk_emit_kernel, dim3((uint32_t) nq), dim3(64), k * 16, s, fe);
+	hipError_t e = hipGetLastError();
+	if (e == hipSuccess) e = hipEventRecord(fw->ev[2], s);
+	if (e == hipSuccess) e = hipMemcpyAsync(&fw->host[2], scored, 8, hipMemcpyDeviceToHost, s);
+	const hipError_t e2 = hipStreamSynchronize(s);
+	if (e == hipSuccess) e = e2;
+	if (e != hipSuccess) return fail(HNSW_GPU_ERR_HIP, "filtered k-NN: %s", hipGetErrorString(e));
+	fw->listed = total; fw->scored = fw->host[2];
+	(void) hipEventElapsedTime(&fw->build_ms, fw->ev[0], fw->ev[1]);
+	(void) hipEventElapsedTime(&fw->scan_ms, fw->ev[1], fw->ev[2]);
+	return HNSW_GPU_OK;
+}
+
+extern "C" int hnsw_gpu_filtered_knn(hnsw_gpu_index *ix, const coord_t *queries, size_t nq, size_t k, const uint32_t *allow, size_t allow_bits,
+									 size_t nfilters, const uint32_t *allow_of, label_t *labels, dist_t *dists, idx_t *idx, uint32_t *counts)
+{
+	std::unique_lock<std::recursive_mutex> lock_;
+	if (ix) lock_ = std::unique_lock<std::recursive_mutex>(ix->mu);
+	if (int rc0 = fk_check(ix, queries, nq, k, allow, allow_bits, nfilters, labels, counts)) return rc0;
+	if (nq == 0) return HNSW_GPU_OK;
+	HIPCHK(hipSetDevice(ix->device));
+	const size_t dim = ix->meta.dim, words = (allow_bits + 31) / 32;
+	const size_t qb = round_up(nq * dim * 4, 256), fb = round_up(nfilters * words * 4, 256), ob = round_up(allow_of ? nq * 4 : 0, 256),
+				 lb = round_up(nq * k * 8, 256), db = round_up(nq * k * 4, 256), ib = round_up(nq * k * 4, 256), cb = round_up(nq * 4, 256);
+	int rc = ensure_scratch(ix, qb + fb + ob + lb + db + ib + cb);
+	if (rc) return rc;
+	char *p = (char *) ix->scratch;
+	float *dq = (float *) p; uint32_t *df = (uint32_t *) (p + qb), *dof = (uint32_t *) (p + qb + fb);
+	uint64_t *dl = (uint64_t *) (p + qb + fb + ob); float *dd = (float *) (p + qb + fb + ob + lb);
+	uint32_t *di = (uint32_t *) (p + qb + fb + ob + lb + db), *dc = (uint32_t *) (p + qb + fb + ob + lb + db + ib);
+	HIPCHK(hipMemcpy(dq, queries, nq * dim * 4, hipMemcpyHostToDevice));
+	HIPCHK(hipMemcpy(df, allow, nfilters * words * 4, hipMemcpyHostToDevice));
+	if (allow_of) HIPCHK(hipMemcpy(dof, allow_of, nq * 4, hipMemcpyHostToDevice));
+	rc = hnsw_gpu_filtered_knn_dev(ix, dq, nq, k, df, allow_bits, nfilters, allow_of ? dof : nullptr, dl, dd, di, dc, nullptr);
+	if (rc) return rc;
+	HIPCHK(hipMemcpy(labels, dl, nq * k * 8, hipMemcpyDeviceToHost));
+	if (dists) HIPCHK(hipMemcpy(dists, dd, nq * k * 4, hipMemcpyDeviceToHost));
+	if (idx) HIPCHK(hipMemcpy(idx, di, nq * k * 4, hipMemcpyDeviceToHost));
+	HIPCHK(hipMemcpy(counts, dc, nq * 4, hipMemcpyDeviceToHost));
+	return HNSW_GPU_OK;
+}
+
+extern "C" int hnsw_gpu_last_filtered_knn(hnsw_gpu_index *ix, uint64_t out[4])
+{
+	if (!ix || !out) return fail(HNSW_GPU_ERR_ARG, "NULL argument");
+	std::lock_guard<std::recursive_mutex> lock_(ix->mu);
+	out[0] = ix->fk.listed;
+	out[1] = ix->fk.scored;
+	out[2] = (uint64_t) std::llround((double) ix->fk.build_ms * 1000.0);
+	out[3] = (uint64_t) std::llround((double) ix->fk.scan_ms * 1000.0);
 	return HNSW_GPU_OK;
 }
 

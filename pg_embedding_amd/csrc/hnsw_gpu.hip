@@ -353,6 +353,7 @@ extern "C" void hnsw_gpu_index_destroy(hnsw_gpu_index *ix)
 	if (ix->rr_e0) (void) hipEventDestroy(ix->rr_e0);
 	if (ix->rr_e1) (void) hipEventDestroy(ix->rr_e1);
 	scan_ws_free(&ix->scan);
+	fk_ws_free(&ix->fk);
 	delete ix;
 }
 

@@ -409,6 +409,58 @@ class GpuIndex:
               "hnsw_gpu_last_scan_rounds")
         return [{"active": int(act[r]), "ef": int(ef[r]), "search_ms": float(sm[r]), "handout_ms": float(hm[r])} for r in range(min(n.value, cap))]
 
+    # ---------------------------------------------------------------- exact filtered k-NN
+    def filtered_knn(self, queries: np.ndarray, k: int, allow, allow_of=None, return_idx: bool = False):
+        """Exact k nearest ALLOWED elements per query, host buffers (hnsw_gpu_filtered_knn): a canonical scan over the rows whose label
+        passes the query's filter and that are not vacuumed — |allowed| rows of work per query, not the table.  allow (required) and
+        allow_of as in scan().  Returns a dict: labels [nq, k] u64 in ascending (distance, label) order (tail ~0), dists [nq, k] f32
+        (tail +inf), counts [nq] u32 = min(k, allowed rows), and with return_idx=True idx [nq, k] u32 element numbers (tail 0xFFFFFFFF)."""
+        if allow is None:
+            raise ValueError("filtered_knn needs an allow filter (bruteforce_torch takes none)")
+        queries = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, self.meta.dim)
+        nq, k = queries.shape[0], int(k)
+        words, bits, nf = _pack_allow_numpy(allow)
+        of = None if allow_of is None else np.ascontiguousarray(allow_of, dtype=np.uint32).reshape(nq)
+        out = {"labels": np.empty((nq, k), np.uint64), "dists": np.empty((nq, k), np.float32), "counts": np.empty(nq, np.uint32)}
+        if return_idx:
+            out["idx"] = np.empty((nq, k), np.uint32)
+        check(self.L.hnsw_gpu_filtered_knn(self._h, queries.ctypes.data, nq, k, words.ctypes.data, bits, nf, None if of is None else of.ctypes.data,
+                                           out["labels"].ctypes.data, out["dists"].ctypes.data, out["idx"].ctypes.data if return_idx else None,
+                                           out["counts"].ctypes.data), "hnsw_gpu_filtered_knn")
+        return out
+
+    def filtered_knn_torch(self, queries, k: int, allow, allow_of=None, return_idx: bool = False):
+        """filtered_knn() with everything resident in HBM (hnsw_gpu_filtered_knn_dev on torch's current stream, which the call
+        synchronises).  allow: a bool tensor [allow_bits] / [nfilters, allow_bits] or an already packed int32 tensor; allow_of: an integer
+        tensor [nq].  Returns a dict: labels [nq, k] int64 (tail -1), dists [nq, k] (tail +inf), counts [nq] int32, idx [nq, k] int32
+        (tail -1) with return_idx=True."""
+        if allow is None:
+            raise ValueError("filtered_knn_torch needs an allow filter (bruteforce_torch takes none)")
+        torch = _torch()
+        assert queries.is_cuda and queries.dtype == torch.float32 and queries.is_contiguous()
+        nq, k, dev = queries.shape[0], int(k), queries.device
+        words, bits, nf = _pack_allow_torch(allow, dev)
+        of = None if allow_of is None else allow_of.to(device=dev, dtype=torch.int32).contiguous()
+        if of is not None and of.numel() != nq:
+            raise ValueError("allow_of names one filter per query")
+        out = {"labels": torch.empty((nq, k), dtype=torch.int64, device=dev),
+               "dists": torch.empty((nq, k), dtype=torch.float32, device=dev),
+               "counts": torch.empty(nq, dtype=torch.int32, device=dev)}
+        if return_idx:
+            out["idx"] = torch.empty((nq, k), dtype=torch.int32, device=dev)
+        s = torch.cuda.current_stream(dev).cuda_stream
+        check(self.L.hnsw_gpu_filtered_knn_dev(self._h, queries.data_ptr(), nq, k, words.data_ptr(), bits, nf, _dptr(of), out["labels"].data_ptr(),
+                                               out["dists"].data_ptr(), _dptr(out.get("idx")), out["counts"].data_ptr(), s),
+              "hnsw_gpu_filtered_knn_dev")
+        return out
+
+    def last_filtered_knn(self) -> dict:
+        """The last filtered_knn call on this mirror (hnsw_gpu_last_filtered_knn): entries of all allowed lists, rows the scan scored
+        (= the sum of the queries' own list lengths), list-build ms and scan + merge + emit ms."""
+        v = (C.c_uint64 * 4)()
+        check(self.L.hnsw_gpu_last_filtered_knn(self._h, v), "hnsw_gpu_last_filtered_knn")
+        return {"listed": int(v[0]), "rows_scored": int(v[1]), "build_ms": v[2] / 1000.0, "scan_ms": v[3] / 1000.0}
+
     def last_search_ms(self, back: int = 0) -> float:
         """Device time of the search kernel launched `back` launches ago (HIP events recorded on
         the launch stream around the kernel; the last 64 launches are kept)."""
