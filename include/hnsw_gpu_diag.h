@@ -97,6 +97,10 @@ int hnsw_gpu_last_search_chunk(hnsw_gpu_index *ix, uint32_t *chunk);
  * HNSW_GPU_LOCALITY=0), perm[t] = the query ticket t walked and keys[i] = the sort key of query i (t, i < min(*nq, cap); perm and
  * keys may be NULL; perm is the stable argsort of keys).  Waits for the device.  For tests. */
 int hnsw_gpu_last_search_order(hnsw_gpu_index *ix, uint32_t *perm, uint32_t *keys, size_t cap, size_t *nq);
+/* The locality order of a batch without its search: the kernels an ordered launch of these nq queries (device memory, rows of dim
+ * floats) runs, whatever nq is; perm[nq] and keys[nq] (host memory, keys may be NULL) as above.  Waits for the device; afterwards
+ * hnsw_gpu_last_search_order reports no order.  For tests and measurement. */
+int hnsw_gpu_locality_order_dev(hnsw_gpu_index *ix, const float *d_queries, size_t nq, uint32_t *perm, uint32_t *keys);
 
 /* Where the time of the mirror's last hnsw_gpu_scan_batch[_dev] call went, per round: *rounds = rounds it ran; for r < min(*rounds, cap):
  * active[r] = queries that took part, ef[r] = the width searched, search_ms[r] = the search launch, handout_ms[r] = what followed until the

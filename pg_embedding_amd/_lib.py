@@ -141,6 +141,7 @@ def gpu_lib():
     L.hnsw_gpu_search_ms.argtypes = [vp, C.c_uint, _f32p]
     L.hnsw_gpu_last_search_slots.argtypes = [vp, _u32p]
     L.hnsw_gpu_last_search_order.argtypes = [vp, vp, vp, sz, C.POINTER(C.c_size_t)]
+    L.hnsw_gpu_locality_order_dev.argtypes = [vp, vp, sz, vp, vp]
     L.hnsw_gpu_last_search_chunk.argtypes = [vp, C.POINTER(C.c_uint32)]
     L.hnsw_gpu_index_health.argtypes = [vp, _u32p]
     L.hnsw_gpu_index_insert_one.argtypes = [vp, vp, C.c_uint64, C.c_uint32, vp, vp]

@@ -14,9 +14,10 @@
 //             every 32nd pivot is a super-pivot, a pivot's rank is its place in the order (nearest super-pivot, distance to it,
 //             pivot number).
 //   key       of a query: the rank of its nearest pivot by squared L2 over the KD-float prefix, whatever the index's metric.
-//   sort      a stable counting sort on the device: per-chunk histograms, one exclusive scan over them in (key, chunk) order, a
-//             scatter in which every chunk of ORDER_CHUNK queries places its queries in query order.  Stable, so perm is a function of
-//             the keys alone (the same keys give the same order in every run) and equals a stable argsort of them.
+//   sort      a stable counting sort on the device: per-chunk histograms, an exclusive scan over them in (key, chunk) order — one wave
+//             per key scans its row of chunk counts, the scatter adds the scan of the P row totals — and a scatter in which every
+//             chunk of ORDER_CHUNK queries places its queries in query order.  Stable, so perm is a function of the keys alone (the
+//             same keys give the same order in every run) and equals a stable argsort of them.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -27,7 +28,9 @@ constexpr uint32_t ORDER_PIVOTS = 1024;       // P (at most)
 constexpr uint32_t ORDER_DIMS = 64;           // KD (at most): floats of the prefix the key is computed over
 constexpr uint32_t ORDER_SUPER_EVERY = 32;    // every 32nd pivot is a super-pivot
 constexpr uint32_t ORDER_CHUNK = 256;         // queries per chunk of the counting sort
-constexpr uint32_t ORDER_QT = 32;             // queries per block of the key kernel
+constexpr uint32_t ORDER_QT = 16;             // queries per block of the key kernel
+constexpr uint32_t ORDER_PT = 4;              // pivots per thread of the key kernel (256 threads: ORDER_PIVOTS / 256)
+static_assert(ORDER_PT * 256 == ORDER_PIVOTS, "a thread of the key kernel holds its ORDER_PT pivots' sums at once");
 // dynamic LDS of the kernels below (declared per kernel as the other kernels of the library do)
 constexpr size_t ORDER_RANK_LDS = ORDER_PIVOTS * 8;
 constexpr size_t ORDER_KEY_LDS = ORDER_DIMS * ORDER_QT * 4 + 4 * ORDER_QT * 8;
@@ -84,56 +87,71 @@ __global__ __launch_bounds__(1024) void order_rank_kernel(const float *piv, uint
 }
 
 // keys: key[q] = rank[nearest pivot of query q over the prefix] (ties: the lower pivot).  Block of 256 threads = ORDER_QT queries;
-// thread t scores pivots t, t + 256, ... against all of them, the query prefixes sit in LDS (read as broadcasts).
+// thread t scores pivots t, t + 256, ... against all of them, the query prefixes sit in LDS (read as broadcasts).  A thread holds
+// the sums of all its ORDER_PT pivots at once, so that one LDS read of four queries feeds ORDER_PT pivots (with one pivot per read the
+// kernel waits for LDS as long as it computes), and two queries share one packed instruction: each (query, pivot) sum is still the
+// one fmaf chain over d = 0 .. kd - 1, so the keys are what the one-pivot form gave.
+// zero: null, or `nzero` words that block 0 zeroes (the ticket counters of the search launch this order is for: the key kernel is
+// the first kernel of an ordered launch, which saves that launch a memset of its own).
+typedef float order_f32x2 __attribute__((ext_vector_type(2)));
 __global__ __launch_bounds__(256) void order_key_kernel(const float *queries, uint32_t q_stride, uint32_t nq, const float *piv,
-														const uint32_t *rank, uint32_t P, uint32_t kd, uint32_t *key)
+														const uint32_t *rank, uint32_t P, uint32_t kd, uint32_t *key, uint32_t *zero,
+														uint32_t nzero)
 {
 	extern __shared__ __attribute__((aligned(16))) unsigned char smem[];     // (dynamic LDS: ORDER_KEY_LDS bytes)
 	float *qs = reinterpret_cast<float *>(smem);                               // [d][q]
 	uint64_t *red = reinterpret_cast<uint64_t *>(smem + ORDER_DIMS * ORDER_QT * 4);
 	const uint32_t tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
 	const uint32_t q0 = blockIdx.x * ORDER_QT;
+	if (blockIdx.x == 0 && zero)
+		for (uint32_t i = tid; i < nzero; i += 256) zero[i] = 0u;
 	for (uint32_t i = tid; i < ORDER_DIMS * ORDER_QT; i += 256)
 	{
 		const uint32_t d = i / ORDER_QT, q = i % ORDER_QT;
 		qs[i] = (d < kd && q0 + q < nq) ? queries[(size_t) (q0 + q) * q_stride + d] : 0.f;
 	}
 	__syncthreads();
-	uint64_t best[ORDER_QT];
+	// (a pivot slot at or beyond P reads pivot P - 1 and is left out of the minimum below)
+	uint32_t pp[ORDER_PT];
 #pragma unroll
-	for (uint32_t q = 0; q < ORDER_QT; q++) best[q] = ~0ull;
-	for (uint32_t p = tid; p < P; p += 256)
+	for (uint32_t j = 0; j < ORDER_PT; j++) pp[j] = tid + 256u * j < P ? tid + 256u * j : P - 1;
+	order_f32x2 acc[ORDER_PT][ORDER_QT / 2];
+#pragma unroll
+	for (uint32_t j = 0; j < ORDER_PT; j++)
+#pragma unroll
+		for (uint32_t q = 0; q < ORDER_QT / 2; q++) acc[j][q] = (order_f32x2) (0.f);
+	for (uint32_t d = 0; d < kd; d++)
 	{
-		float acc[ORDER_QT];
+		order_f32x2 pv[ORDER_PT];
 #pragma unroll
-		for (uint32_t q = 0; q < ORDER_QT; q++) acc[q] = 0.f;
-		for (uint32_t d = 0; d < kd; d++)
+		for (uint32_t j = 0; j < ORDER_PT; j++) { const float t = piv[d * P + pp[j]]; pv[j] = (order_f32x2) { t, t }; }
+		const float4 *row = reinterpret_cast<const float4 *>(qs + d * ORDER_QT);
+#pragma unroll
+		for (uint32_t i = 0; i < ORDER_QT / 4; i++)
 		{
-			const float pv = piv[d * P + p];
-			const float4 *row = reinterpret_cast<const float4 *>(qs + d * ORDER_QT);
+			const float4 v = row[i];
+			const order_f32x2 lo = { v.x, v.y }, hi = { v.z, v.w };
 #pragma unroll
-			for (uint32_t j = 0; j < ORDER_QT / 4; j++)
+			for (uint32_t j = 0; j < ORDER_PT; j++)
 			{
-				const float4 v = row[j];
-				float t;
-				t = v.x - pv; acc[4 * j + 0] = fmaf(t, t, acc[4 * j + 0]);
-				t = v.y - pv; acc[4 * j + 1] = fmaf(t, t, acc[4 * j + 1]);
-				t = v.z - pv; acc[4 * j + 2] = fmaf(t, t, acc[4 * j + 2]);
-				t = v.w - pv; acc[4 * j + 3] = fmaf(t, t, acc[4 * j + 3]);
+				const order_f32x2 t0 = lo - pv[j], t1 = hi - pv[j];
+				acc[j][2 * i + 0] = __builtin_elementwise_fma(t0, t0, acc[j][2 * i + 0]);
+				acc[j][2 * i + 1] = __builtin_elementwise_fma(t1, t1, acc[j][2 * i + 1]);
 			}
-		}
-#pragma unroll
-		for (uint32_t q = 0; q < ORDER_QT; q++)
-		{
-			// (a sum of squares: its bit pattern orders like the value; a NaN sorts last)
-			const uint64_t k = ((uint64_t) __float_as_uint(acc[q]) << 32) | p;
-			best[q] = k < best[q] ? k : best[q];
 		}
 	}
 #pragma unroll
 	for (uint32_t q = 0; q < ORDER_QT; q++)
 	{
-		uint64_t v = best[q];
+		uint64_t v = ~0ull;
+#pragma unroll
+		for (uint32_t j = 0; j < ORDER_PT; j++)
+		{
+			// (a sum of squares: its bit pattern orders like the value; a NaN sorts last)
+			const float s = (q & 1u) ? acc[j][q / 2].y : acc[j][q / 2].x;
+			const uint64_t k = tid + 256u * j < P ? ((uint64_t) __float_as_uint(s) << 32) | (tid + 256u * j) : ~0ull;
+			v = k < v ? k : v;
+		}
 		for (int o = 32; o > 0; o >>= 1)
 		{
 			const uint32_t lo = (uint32_t) __shfl_xor((int) (uint32_t) v, o);
@@ -168,43 +186,61 @@ __global__ __launch_bounds__(256) void order_hist_kernel(const uint32_t *key, ui
 	for (uint32_t k = threadIdx.x; k < P; k += 256) hist[(size_t) k * nch + b] = h[k];
 }
 
-// exclusive scan of hist[0 .. m) in place: one block of 1024 threads, each owns a contiguous segment
-__global__ __launch_bounds__(1024) void order_scan_kernel(uint32_t *hist, uint32_t m)
+// inclusive scan over the 64 lanes of a wave (Hillis-Steele on lane permutes)
+__device__ __forceinline__ uint32_t order_wave_scan(uint32_t v, uint32_t lane)
 {
-	extern __shared__ __attribute__((aligned(16))) unsigned char smem[];     // (dynamic LDS: ORDER_TABLE_LDS bytes)
-	uint32_t *part = reinterpret_cast<uint32_t *>(smem);
-	const uint32_t t = threadIdx.x;
-	const uint32_t seg = (m + 1023) / 1024;
-	const uint32_t lo = t * seg < m ? t * seg : m, hi = lo + seg < m ? lo + seg : m;
-	uint32_t s = 0;
-	for (uint32_t i = lo; i < hi; i++) s += hist[i];
-	part[t] = s;
-	__syncthreads();
-	for (uint32_t o = 1; o < 1024; o <<= 1)                 // inclusive scan of the segment sums (Hillis-Steele)
+#pragma unroll
+	for (uint32_t o = 1; o < 64; o <<= 1)
 	{
-		const uint32_t v = t >= o ? part[t - o] : 0u;
-		__syncthreads();
-		part[t] += v;
-		__syncthreads();
+		const uint32_t t = (uint32_t) __builtin_amdgcn_ds_bpermute((int) (((lane - o) & 63u) * 4u), (int) v);
+		v += lane >= o ? t : 0u;
 	}
-	uint32_t run = part[t] - s;
-	for (uint32_t i = lo; i < hi; i++)
+	return v;
+}
+
+// row scans: the wave of key k turns its row hist[k * nch .. (k + 1) * nch) into its exclusive scan, in place, and writes the row's
+// sum to tot[k].  Together with the exclusive scan of tot (which every block of the scatter does for itself: P <= 1 024 words) this
+// is the exclusive scan of the whole array.  Grid: ceil(P / 4) blocks of 256 (one wave per key).
+__global__ __launch_bounds__(256) void order_rowscan_kernel(uint32_t *hist, uint32_t P, uint32_t nch, uint32_t *tot)
+{
+	const uint32_t lane = threadIdx.x & 63;
+	const uint32_t k = blockIdx.x * 4u + (threadIdx.x >> 6);
+	if (k >= P) return;                                      // (wave-uniform)
+	uint32_t *row = hist + (size_t) k * nch;
+	uint32_t carry = 0;
+	for (uint32_t c0 = 0; c0 < nch; c0 += 64)
 	{
-		const uint32_t c = hist[i];
-		hist[i] = run;
-		run += c;
+		const uint32_t c = c0 + lane;
+		const uint32_t v = c < nch ? row[c] : 0u;
+		const uint32_t inc = order_wave_scan(v, lane);
+		if (c < nch) row[c] = carry + inc - v;
+		carry += (uint32_t) __builtin_amdgcn_readlane((int) inc, 63);
 	}
+	if (lane == 0) tot[k] = carry;
 }
 
 // scatter: one wave per chunk, 64 queries at a time in query order.  Lanes that hold the same key take consecutive places in the
 // order of their query numbers (ballot of the group, rank = its lanes below this one), so the sort is stable.
+// hist / tot: the row scans and row sums of order_rowscan_kernel; the first place of (key k, chunk b) is the sum of tot below k plus
+// hist[k * nch + b].
 __global__ __launch_bounds__(64) void order_scatter_kernel(const uint32_t *key, uint32_t nq, uint32_t P, uint32_t nch, const uint32_t *hist,
-														   uint32_t *perm)
+														   const uint32_t *tot, uint32_t *perm)
 {
 	extern __shared__ __attribute__((aligned(16))) unsigned char smem[];     // (dynamic LDS: ORDER_TABLE_LDS bytes)
 	uint32_t *off = reinterpret_cast<uint32_t *>(smem);
 	const uint32_t b = blockIdx.x, lane = threadIdx.x;
-	for (uint32_t k = lane; k < P; k += 64) off[k] = hist[(size_t) k * nch + b];
+	{
+		// exclusive scan of tot[0 .. P): lane l owns keys [l * per, (l + 1) * per)
+		constexpr uint32_t per = ORDER_PIVOTS / 64;
+		uint32_t t[per], s = 0;
+#pragma unroll
+		for (uint32_t i = 0; i < per; i++) { const uint32_t k = lane * per + i; t[i] = k < P ? tot[k] : 0u; s += t[i]; }
+		uint32_t run = order_wave_scan(s, lane) - s;
+#pragma unroll
+		for (uint32_t i = 0; i < per; i++) { const uint32_t k = lane * per + i; if (k < P) off[k] = run; run += t[i]; }
+	}
+	__syncthreads();
+	for (uint32_t k = lane; k < P; k += 64) off[k] += hist[(size_t) k * nch + b];
 	__syncthreads();
 	const uint64_t below = (1ull << lane) - 1ull;
 	for (uint32_t s = 0; s < ORDER_CHUNK; s += 64)

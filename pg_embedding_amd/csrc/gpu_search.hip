@@ -75,9 +75,12 @@ uint32_t xcd_chunk_log2(size_t nq)
 }
 
 // keys + stable counting sort of `nq` queries on `stream`, into w->ord (pivots rebuilt first when a writer has touched the rows):
-// returns the permutation (device), or null on an error already reported
-static const uint32_t *build_order(hnsw_gpu_index *ix, SearchWs *w, const float *d_queries, size_t q_stride, size_t nq, hipStream_t stream)
+// returns the permutation (device), or null on an error already reported.  With `tickets`, the key kernel also zeroes those ticket
+// counters for the search launch that follows: *zeroed says whether that kernel is queued (it can be with null returned).
+static const uint32_t *build_order(hnsw_gpu_index *ix, SearchWs *w, const float *d_queries, size_t q_stride, size_t nq, hipStream_t stream,
+								   uint32_t *tickets, bool *zeroed)
 {
+	*zeroed = false;
 	const uint32_t P = (uint32_t) std::min<size_t>(ORDER_PIVOTS, ix->n);
 	const uint32_t kd = std::min<uint32_t>(ORDER_DIMS, (uint32_t) ix->meta.dim);
 	if (!ix->piv)
@@ -95,7 +98,7 @@ static const uint32_t *build_order(hnsw_gpu_index *ix, SearchWs *w, const float 
 	}
 	const uint32_t nch = (uint32_t) ((nq + ORDER_CHUNK - 1) / ORDER_CHUNK);
 	const size_t hist_words = (size_t) P * nch;
-	const size_t words = 2 * nq + hist_words;
+	const size_t words = 2 * nq + hist_words + ORDER_PIVOTS;      // keys | perm | chunk histograms | row totals
 	if (words > w->ord_words)
 	{
 		if (w->ord) (void) hipFree(w->ord);           // (hipFree waits for the launches still using it)
@@ -103,12 +106,14 @@ static const uint32_t *build_order(hnsw_gpu_index *ix, SearchWs *w, const float 
 		if (hipMalloc(&w->ord, words * 4) != hipSuccess) { w->ord = nullptr; fail(HNSW_GPU_ERR_NOMEM, "locality order: no room for %zu keys", nq); return nullptr; }
 		w->ord_words = words;
 	}
-	uint32_t *key = w->ord, *perm = w->ord + nq, *hist = w->ord + 2 * nq;
+	uint32_t *key = w->ord, *perm = w->ord + nq, *hist = w->ord + 2 * nq, *tot = hist + hist_words;
 	hipLaunchKernelGGL(order_key_kernel, dim3((uint32_t) ((nq + ORDER_QT - 1) / ORDER_QT)), dim3(256), ORDER_KEY_LDS, stream, d_queries, (uint32_t) q_stride,
-					   (uint32_t) nq, ix->piv, rank, P, kd, key);
+					   (uint32_t) nq, ix->piv, rank, P, kd, key, tickets, (uint32_t) (XCD_TICKET_BYTES / 4));
+	if (hipGetLastError() != hipSuccess) { fail(HNSW_GPU_ERR_HIP, "locality order: launch failed"); return nullptr; }
+	*zeroed = tickets != nullptr;
 	hipLaunchKernelGGL(order_hist_kernel, dim3(nch), dim3(256), ORDER_TABLE_LDS, stream, key, (uint32_t) nq, P, nch, hist);
-	hipLaunchKernelGGL(order_scan_kernel, dim3(1), dim3(1024), ORDER_TABLE_LDS, stream, hist, (uint32_t) hist_words);
-	hipLaunchKernelGGL(order_scatter_kernel, dim3(nch), dim3(64), ORDER_TABLE_LDS, stream, key, (uint32_t) nq, P, nch, hist, perm);
+	hipLaunchKernelGGL(order_rowscan_kernel, dim3((P + 3) / 4), dim3(256), 0, stream, hist, P, nch, tot);
+	hipLaunchKernelGGL(order_scatter_kernel, dim3(nch), dim3(64), ORDER_TABLE_LDS, stream, key, (uint32_t) nq, P, nch, hist, tot, perm);
 	if (hipGetLastError() != hipSuccess) { fail(HNSW_GPU_ERR_HIP, "locality order: launch failed"); return nullptr; }
 	w->ord_perm_off = nq;
 	return perm;
@@ -491,17 +496,21 @@ int launch_search(hnsw_gpu_index *ix, SearchWs *w, const float *d_queries, size_
 	w->pops_next = nullptr; w->pops_cap_next = 0;
 	a.out_evals = w->evals_next; a.evals_cap = w->evals_cap_next; a.out_times = w->times_next;
 	w->evals_next = nullptr; w->evals_cap_next = 0; w->times_next = nullptr;
-	HIPCHK(hipMemsetAsync(w->ticket, 0, XCD_TICKET_BYTES, stream));        // (the global ticket and the per-XCD counters)
+	// locality order: the beam kernel's plain launches of a large batch (the key and the sort run inside the launch's event pair)
+	const bool want_order = order && rreg < 0 && !stream_launch && a.n > 0 && knob(K_LOCALITY, 1) != 0 &&
+		nq >= (size_t) std::max<long long>(1, knob(K_LOCALITY_MIN_NQ, (long long) ORDER_MIN_NQ));
+	// (the global ticket and the per-XCD counters; an ordered launch's key kernel zeroes them)
+	if (!want_order) HIPCHK(hipMemsetAsync(w->ticket, 0, XCD_TICKET_BYTES, stream));
 
 	const int evi = (int) (w->launches % SearchWs::EV_RING);
 	HIPCHK(hipEventRecord(w->ev0[evi], stream));
-	// locality order: the beam kernel's plain launches of a large batch (the key and the sort run inside the launch's event pair)
 	w->ord_nq = 0; w->ord_evals = nullptr; w->ord_log2c = 0;
-	if (order && rreg < 0 && !stream_launch && a.n > 0 && knob(K_LOCALITY, 1) != 0 &&
-		nq >= (size_t) std::max<long long>(1, knob(K_LOCALITY_MIN_NQ, (long long) ORDER_MIN_NQ)))
+	if (want_order)
 	{
 		// (the order is only an optimisation: where it cannot be built — no memory for its buffers — the launch runs in the caller's order)
-		a.perm = build_order(ix, w, d_queries, q_stride, nq, stream);
+		bool zeroed = false;
+		a.perm = build_order(ix, w, d_queries, q_stride, nq, stream, w->ticket, &zeroed);
+		if (!zeroed) HIPCHK(hipMemsetAsync(w->ticket, 0, XCD_TICKET_BYTES, stream));
 		if (a.perm)
 		{
 			a.xcd_log2c = xcd_chunk_log2(nq);
@@ -516,6 +525,28 @@ int launch_search(hnsw_gpu_index *ix, SearchWs *w, const float *d_queries, size_
 	HIPCHK(hipEventRecord(w->ev1[evi], stream));
 	__atomic_store_n(&w->launches, w->launches + 1, __ATOMIC_SEQ_CST);
 	w->last_slots = (uint32_t) slots;
+	return HNSW_GPU_OK;
+}
+
+// the locality order of a batch without its search (hnsw_gpu_diag.h): the keys and the sort exactly as an ordered launch runs them
+extern "C" int hnsw_gpu_locality_order_dev(hnsw_gpu_index *ix, const coord_t *d_queries, size_t nq, uint32_t *perm, uint32_t *keys)
+{
+	if (!ix || !d_queries || !perm) return fail(HNSW_GPU_ERR_ARG, "NULL argument");
+	std::lock_guard<std::recursive_mutex> g(ix->mu);
+	if (nq == 0) return HNSW_GPU_OK;
+	if (nq >= 0xFFFFFFFFull) return fail(HNSW_GPU_ERR_ARG, "too many queries");
+	if (ix->n == 0) return fail(HNSW_GPU_ERR_ARG, "locality order: the index is empty");
+	knobs_init();
+	HIPCHK(hipSetDevice(ix->device));
+	SearchWs *w = &ix->ws;
+	HIPCHK(hipDeviceSynchronize());                              // (the buffers may hold the order of a launch still running)
+	w->ord_nq = 0; w->ord_evals = nullptr; w->ord_log2c = 0;    // ... and from here on no longer hold the last launch's
+	bool zeroed = false;
+	const uint32_t *d_perm = build_order(ix, w, d_queries, ix->meta.dim, nq, nullptr, nullptr, &zeroed);
+	if (!d_perm) { (void) hipGetLastError(); return HNSW_GPU_ERR_HIP; }
+	HIPCHK(hipDeviceSynchronize());
+	HIPCHK(hipMemcpy(perm, d_perm, nq * 4, hipMemcpyDeviceToHost));
+	if (keys) HIPCHK(hipMemcpy(keys, w->ord, nq * 4, hipMemcpyDeviceToHost));
 	return HNSW_GPU_OK;
 }
 

@@ -584,6 +584,17 @@ class GpuIndex:
         check(self.L.hnsw_gpu_last_search_order(self._h, perm.ctypes.data, key.ctypes.data, n.value, C.byref(n)), "hnsw_gpu_last_search_order")
         return (perm.astype(np.int64), key.astype(np.int64)) if keys else perm.astype(np.int64)
 
+    def locality_order_torch(self, q):
+        """The locality order of a batch without its search (hnsw_gpu_locality_order_dev): q is a contiguous float32 tensor on this
+        index's device; returns (perm, keys) as int64 arrays, perm the stable argsort of keys."""
+        import numpy as np
+        assert q.is_cuda and q.is_contiguous() and q.dim() == 2 and q.shape[1] == self.meta.dim
+        nq = int(q.shape[0])
+        perm = np.empty(nq, np.uint32)
+        key = np.empty(nq, np.uint32)
+        check(self.L.hnsw_gpu_locality_order_dev(self._h, q.data_ptr(), nq, perm.ctypes.data, key.ctypes.data), "hnsw_gpu_locality_order_dev")
+        return perm.astype(np.int64), key.astype(np.int64)
+
     def last_search_chunk(self) -> int:
         """The chunk in which the last search launch of the default workspace dealt its ordered batch per XCD
         (hnsw_gpu_last_search_chunk); 0 = one global ticket."""
