@@ -62,11 +62,26 @@ int hnsw_gpu_index_append_dev(hnsw_gpu_index *ix, const coord_t *d_vectors, cons
 /* Link the stored, still un-linked elements [first, first+count) into the graph; every
  * element below `first` must already be linked (or first == 0).  This is hnsw_bind_point
  * (hnswalg.cpp:279-291 = bindPoint :225-232 + mutuallyConnectNewElement :155-223 +
- * getNeighborsByHeuristic :117-153) for many elements.  Elements are processed in batches of
- * min(max_batch, linked/ratio): members of one batch search the graph as it was before the
- * batch.  max_batch = 1 reproduces the reference's serial inserts exactly (graph bytes equal
- * the oracle's); larger batches give a different, equally valid graph much faster.
- * 0 selects the defaults (max_batch 4096, ratio 8).  Enqueued on `stream`, not synchronised. */
+ * getNeighborsByHeuristic :117-153) for many elements, in batches.  The graph it writes is a
+ * function of the rows and the batch schedule alone:
+ *   - max_batch = 0 means 4096 and ratio = 0 means 8; max_batch is then capped at `count`.
+ *   - Schedule: with end = first + count and linked = max(first, 1) (element 0 is never bound,
+ *     :228), while linked < end the next batch is the b elements [linked, linked + b) with
+ *         b = min(end - linked, max_batch, max(1, linked / ratio))      (integer division),
+ *     and linked += b.
+ *   - Every member of a batch runs searchBaseLayer(ef = efConstruction) on the graph as it
+ *     stood before the batch: it sees no member of its own batch, itself included.
+ *   - Each member then selects <= M neighbours by the heuristic and writes its own list,
+ *     farthest first by (dist, idx).  The selections use vectors only, so their order is free.
+ *   - The reverse links are applied per target in ascending order of the new element: append
+ *     while the target's list holds fewer than maxM, else re-select maxM of {new} + old links
+ *     around the target and rewrite its list farthest first.  Lists of different targets are
+ *     independent.
+ * This equals mutuallyConnectNewElement run for the members in ascending order after all their
+ * searches.  max_batch = 1 is therefore the reference's serial insert, graph bytes equal to the
+ * oracle's; larger batches give a different, equally valid graph much faster, which the host
+ * model of oracle/hnsw_port.c (port_link_batch) restates byte for byte.
+ * Enqueued on `stream`, not synchronised. */
 int hnsw_gpu_index_link(hnsw_gpu_index *ix, size_t first, size_t count, size_t max_batch, size_t ratio,
 						void *stream);
 

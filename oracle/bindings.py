@@ -76,6 +76,10 @@ def _port():
         L.port_set_deleted.argtypes = [C.c_void_p, C.c_uint32, C.c_int]
         L.port_add_many.restype = C.c_long
         L.port_add_many.argtypes = [C.c_void_p, _f32p, _u64p, C.c_size_t]
+        L.port_append_many.restype = C.c_long
+        L.port_append_many.argtypes = [C.c_void_p, _f32p, _u64p, C.c_size_t]
+        L.port_link_batch.restype = C.c_int
+        L.port_link_batch.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32]
         L.port_search.restype = C.c_int
         L.port_search.argtypes = [C.c_void_p, _f32p, C.c_size_t, _u64p, _f32p,
                                   C.POINTER(C.c_size_t), _u32p, _u32p]
@@ -151,6 +155,24 @@ class PortIndex:
         r = self.L.port_add_many(self.h, _ptr(vecs, _f32p), lp, vecs.shape[0])
         if r < 0:
             raise RuntimeError(f"port_add_many failed ({r})")
+
+    def append(self, vecs, labels=None) -> None:
+        """Store zero-linked elements without binding them (the first half of add)."""
+        vecs = _f32(vecs).reshape(-1, self.dim)
+        lp = None
+        if labels is not None:
+            labels = np.ascontiguousarray(labels, dtype=np.uint64)
+            lp = _ptr(labels, _u64p)
+        r = self.L.port_append_many(self.h, _ptr(vecs, _f32p), lp, vecs.shape[0])
+        if r < 0:
+            raise RuntimeError(f"port_append_many failed ({r})")
+
+    def link_batch(self, first: int, count: int) -> None:
+        """One batch of the device's build (hnsw_gpu_index_link, include/hnsw_gpu.h): the stored, un-linked elements
+        [first, first + count), first >= 1, all search the graph as it is, then are connected in ascending order."""
+        r = self.L.port_link_batch(self.h, first, count)
+        if r != 0:
+            raise RuntimeError(f"port_link_batch({first}, {count}) failed ({r})")
 
     def raw(self) -> np.ndarray:
         n = self.count * self.elem_size

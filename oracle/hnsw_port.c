@@ -732,6 +732,59 @@ long port_add_many(PortIndex *ix, const float *vecs, const uint64_t *labels, siz
 }
 
 /* ------------------------------------------------------------------------- */
+/* Host model of the device's batched build (include/hnsw_gpu.h,             */
+/* hnsw_gpu_index_link): the same functions as above, in two phases.         */
+/* ------------------------------------------------------------------------- */
+
+/* The first half of port_add_st: store a zero-linked element without binding it. */
+long port_append(PortIndex *ix, const float *vec, uint64_t label)
+{
+	if (port_reserve(ix, ix->n + 1) != 0) return -1;
+	uint32_t idx = (uint32_t) ix->n;
+	char *p = ix->data + (size_t) idx * ix->elem_size;
+	memset(p, 0, ix->off_data);
+	memcpy(p + ix->off_data, vec, ix->dim * 4);
+	memcpy(p + ix->off_label, &label, 8);
+	ix->n++;
+	return (long) idx;
+}
+
+long port_append_many(PortIndex *ix, const float *vecs, const uint64_t *labels, size_t n)
+{
+	for (size_t i = 0; i < n; i++)
+	{
+		long r = port_append(ix, vecs + i * ix->dim, labels ? labels[i] : (uint64_t) ix->n);
+		if (r < 0) return r;
+	}
+	return (long) ix->n;
+}
+
+/* One batch of the device's build: the stored, zero-linked elements [first, first + count), first >= 1.
+ * Phase A: every member walks the graph as it stands before the batch (searchBaseLayer, ef = efConstruction, :229);
+ * nothing is written.  Phase B: mutuallyConnectNewElement (:230) per member in ascending element order.  No member
+ * can select another (none is reachable in phase A), so the reverse links of different targets never touch the same
+ * list and one target's links arrive in ascending order of the new element: the device's "pairs sorted by
+ * (target, new)". */
+int port_link_batch(PortIndex *ix, uint32_t first, uint32_t count)
+{
+	if (first < 1 || (size_t) first + count > ix->n) return -1;
+	if (count == 0) return 0;
+	Heap *top = (Heap *) calloc(count, sizeof(Heap));
+	if (!top) return -1;
+	PortStats st = PORT_STATS_INIT;
+	for (uint32_t i = 0; i < count; i++)
+		port_search_base_layer(ix, el_vec(ix, first + i), ix->efc, &top[i], &st, NULL);
+	int rc = 0;
+	for (uint32_t i = 0; i < count; i++)
+	{
+		if (rc == 0 && port_mutually_connect(ix, first + i, &top[i], &st, NULL, NULL) != 0) rc = -2;
+		heap_free(&top[i]);
+	}
+	free(top);
+	return rc;
+}
+
+/* ------------------------------------------------------------------------- */
 /* Timed multi-query driver (cpu_baseline kind "port").                      */
 /* ------------------------------------------------------------------------- */
 

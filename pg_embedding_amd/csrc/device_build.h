@@ -13,7 +13,9 @@
 // With batch size 1 this is exactly the reference's serial insert (same candidate order,
 // same pair comparisons, same link order) and the graph is bit-identical to the oracle's;
 // larger batches trade that for parallelism (members of one batch do not see each other
-// in step 1) and are flagged as a different — but equally valid — graph.
+// in step 1) and give a different — but equally valid — graph, which is still a function of the
+// rows and the batch schedule alone (include/hnsw_gpu.h) and equals the host model's byte for
+// byte (oracle/hnsw_port.c port_link_batch, tests/test_gpu_build_batch.py).
 #pragma once
 #include "device_search.h"
 

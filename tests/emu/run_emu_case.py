@@ -408,7 +408,8 @@ def sharded_edges():
 
 def others():
     """the other kernels behind the C-ABI: serial device insert (graph bytes == the oracle's), batched insert (searchable),
-    the walk's pop sequence, vacuum flags, export, the canonical exhaustive scan"""
+    the walk's pop sequence, vacuum flags, export, the canonical exhaustive scan.  The batched insert's bytes are compared with
+    their host model in tests/emu/run_build_batch_case.py (tests/test_build_batch_emu.py); here it is one recall figure."""
     import oracle
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     from test_gpu_build import live_image

@@ -1,5 +1,6 @@
 """Insert path on the device (hnsw_gpu_index_link): serial mode is bit-identical to the
-oracle's graph; batched mode is validated by recall and by CPU/GPU agreement on its bytes."""
+oracle's graph.  The batched mode is compared byte for byte with its host model in test_gpu_build_batch.py
+(tests/build_model.py); here it is checked at full size by recall and by CPU/GPU agreement on its bytes."""
 import numpy as np
 import pytest
 

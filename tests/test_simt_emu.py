@@ -77,7 +77,8 @@ def test_accept_decisions_that_depend_on_each_other(emu_lib):
 
 def test_the_other_kernels_behind_the_c_abi(emu_lib):
     """serial device insert == the oracle's graph bytes, the walk's pop sequence, vacuum flags, a batched build that the
-    search finds its way in; and the distance entry points: the device tier's own test file, unchanged, on the emulated library"""
+    search finds its way in (its bytes against the host model: test_build_batch_emu.py); and the distance entry points: the device
+    tier's own test file, unchanged, on the emulated library"""
     res = run_case("others", emu_lib)
     recall = res.pop("batched_insert_recall_at_10")
     assert all(v == 0 for v in res.values()), res
