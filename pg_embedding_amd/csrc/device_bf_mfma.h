@@ -52,29 +52,21 @@ namespace pgemb {
 typedef float floatx16 __attribute__((ext_vector_type(16)));
 typedef float floatx4 __attribute__((ext_vector_type(4)));       // (a first-class vector: HIP's float4 struct went through scratch here)
 
-#ifndef BF_TK
-#define BF_TK 32                                     // floats of K per step (32 or 64)
-#endif
-#define BF_NBUF 2                                    // LDS buffers: the loads of step ks + 1 fly during the MFMAs of step ks
-#ifndef BF_ABLATE
-#define BF_ABLATE 0                                  // 0 = the product.  1: no barrier in the K loop; 2: one operand read per K step; 3: no tile loads after the first
-#endif
-#ifndef BF_NJ
-#define BF_NJ 2                                      // 32-row MFMA tiles of index rows per wave (2: 64 x 64 per wave, 4: 64 x 128)
-#endif
-#ifndef BF_WM
-#define BF_WM 2                                      // waves along the queries (2: 128-query tiles, 4 waves; 4: 256-query tiles, 8 waves)
-#endif
-#ifndef BF_BIG
-#define BF_BIG 1                                     // 1: launches with enough tiles use 256 x 256 block tiles (8 waves, 64 x 128 per wave, one block per CU)
-#endif
-constexpr int BF_CH = BF_TK / 4;                     // 16-byte chunks of a tile row per K step (8 or 16)
-constexpr int BF_RPI = 64 / BF_CH;                   // tile rows one wave instruction fills (8 x 128 B or 4 x 256 B: whole lines either way)
-constexpr int BF_LS = BF_TK;                         // lane-linear LDS image, no padding: chunk c of row r at slot c ^ swizzle(r)
+// The tile geometry is in 16-byte chunks and 128-byte lines, whatever the operands are: a K step is one line of every tile row
+// (BF_TK = 32 floats in f32, 64 values in 16 bits).
+constexpr int BF_TK = 32;                            // floats of K per step of the f32 form (its query copy is padded to whole steps)
+constexpr int BF_NBUF = 2;                           // LDS buffers: the loads of step ks + 1 fly during the MFMAs of step ks
+constexpr int BF_CH = 8;                             // 16-byte chunks of a tile row per K step
+constexpr int BF_RPI = 64 / BF_CH;                   // tile rows one wave instruction fills (8 whole 128-byte lines)
+constexpr int BF_LS = 32;                            // words per LDS tile row: lane-linear image, no padding, chunk c of row r at slot c ^ bf_swz(r)
 constexpr int BF_PASS_CAP = 508;                     // (query, row) pairs of a block that passed the filter, collected in LDS (+ 4 words of counter: 4 KB)
-// One block tile: WM x 2 waves of 64 queries x (32 NJ) rows each.  Two are instantiated: <BF_WM, BF_NJ> = 128 x 128 (4 waves, two blocks per
-// CU) and <4, 4> = 256 x 256 (8 waves, one block per CU: half the tile loads per flop — 138 against 136 TFLOP/s — for launches with enough tiles).
-template <int WM, int NJ>
+// The two block tiles, as <WM, NJ> = waves along the queries, 32-row MFMA tiles of index rows per wave: 128 x 128 (4 waves, 64 x 64 per
+// wave, two blocks per CU) and 256 x 256 (8 waves, 64 x 128 per wave, one block per CU: half the tile loads per flop — 138 against
+// 136 TFLOP/s in f32 — for launches with enough tiles).  (Other K steps, wave tiles and the ablation builds of round 5 were compile-time
+// switches of this file until the three forms were merged; their measurements are profiles/r5e_* and profiles/r5l_*, the code is in history.)
+constexpr int BF_SMALL_WM = 2, BF_SMALL_NJ = 2, BF_BIG_WM = 4, BF_BIG_NJ = 4;
+// One block tile: WM x 2 waves of 64 queries x (32 NJ) rows each.  P: the operand policy (below), for its epilogue words per query.
+template <class P, int WM, int NJ>
 struct BfTile
 {
 	static constexpr int WAVES = 2 * WM, THREADS = 64 * WAVES;
@@ -82,26 +74,28 @@ struct BfTile
 	static constexpr int RPP = WAVES * BF_RPI;              // tile rows the block fills per pass
 	static constexpr int PASSES = TQ / RPP;                 // load instructions per query tile, thread and K step
 	static constexpr int PASSES_R = TR / RPP;               // ... per row tile
-	static constexpr int TILE_FLOATS = TQ * BF_LS;          // the query tile
-	static constexpr int BUF_FLOATS = (TQ + TR) * BF_LS;    // one buffer: query tile, then row tile
-	static constexpr int EPI_FLOATS = 2 * TQ;               // the tile's per-query bound and |q|^2, staged for the epilogue
-	static constexpr size_t LDS_BYTES = ((size_t) BF_NBUF * BUF_FLOATS + EPI_FLOATS + 4 + 2 * BF_PASS_CAP) * sizeof(float);
+	static constexpr int TILE_WORDS = TQ * BF_LS;           // the query tile
+	static constexpr int BUF_WORDS = (TQ + TR) * BF_LS;     // one buffer: query tile, then row tile
+	static constexpr int EPI_WORDS = P::EPI_Q * TQ;         // the tile's per-query values, staged for the epilogue
+	static constexpr size_t LDS_BYTES = ((size_t) BF_NBUF * BUF_WORDS + EPI_WORDS + 4 + 2 * BF_PASS_CAP) * 4;
 };
-// bank swizzle of a tile row: a ds_read_b128 serves 16 lanes per cycle over a 256-byte bank row.  128-byte rows (BF_TK 32) put two
-// rows in a bank row: slot = c ^ ((r >> 1) & 7) makes (r & 1, (r >> 1) & 7) — all distinct within a lane group — pick 16 distinct
-// slots; 256-byte rows (BF_TK 64) fill one: slot = c ^ (r & 15).
-__device__ __forceinline__ uint32_t bf_swz(uint32_t r) { return BF_TK == 32 ? ((r >> 1) & 7u) : (r & 15u); }
+// bank swizzle of a tile row: a ds_read_b128 serves 16 lanes per cycle over a 256-byte bank row.  128-byte rows put two rows in a bank
+// row: slot = c ^ ((r >> 1) & 7) makes (r & 1, (r >> 1) & 7) — all distinct within a lane group — pick 16 distinct slots.
+__host__ __device__ inline uint32_t bf_swz(uint32_t r) { return (r >> 1) & 7u; }
 
 struct BfArgs
 {
-	const float *queries;      // [nq][qstride] copy, zero padded to whole K steps (qstride = round_up(stride, BF_TK))
-	const float *qnorm;        // |q|^2
+	const uint4 *queries;      // [nq][qchunks] 16-byte chunks, a whole number of K steps: f32 zero padded (pad_queries_kernel), 16-bit in the copy's layout (r16_query_kernel)
+	const uint4 *rows;         // [n][rchunks]: the f32 rows, or the reduced copy
+	const float *qnorm;        // |q|^2 (make_bounds_kernel: halved for L2)
 	const float *qbound;       // L2: squared bound; cosine: threshold on dot / sqrt(|x|^2)
-	const float *vec;          // [n][stride]
-	const float *xnorm;        // |x|^2
-	uint32_t nq, n, stride, qstride, ksteps;
+	const float *xnorm;        // f32: |x|^2
+	const float2 *qterms;      // 16-bit: rq', |q~|'
+	const float4 *xterms;      // 16-bit: |x|^2, |x|', ex'
+	uint32_t nq, n, qchunks, rchunks, ksteps;
 	int func;
 	float xscale;              // L2: (1 - eD) / 2, the filter's |x|^2 factor (make_bounds_kernel: the margin's |x|^2 share, halved)
+	float eabs;                // 16-bit: r16_abs_term(dim)
 	uint32_t *cand;            // [nq][cap]
 	uint32_t *cand_cnt;        // [nq]
 	uint32_t cap;
@@ -109,14 +103,53 @@ struct BfArgs
 	unsigned long long *clocks; // NULL, or 2 words: shader-clock and constant-clock ticks one block spent in its K loop (measurement only)
 };
 
-template <int WM, int NJ>
+// The operand policy of the f32 form (the 16-bit one: Bf16<FMT>, device_bf_mfma16.h).  A policy says
+//   FMT            the ROWS_* format of its operands
+//   CLAMP          whether a row may end inside a K step (then a chunk beyond its end re-reads the row's last chunk)
+//   EPI_Q          LDS words per query of the tile for the epilogue: bound, |q|^2, then its own (query_word)
+//   Row            its own per-row epilogue operands, one per MFMA column of the lane (row_operands, which returns |x|^2)
+//   step           the MFMAs of one 16-byte LDS operand per tile row
+//   value          what the comparisons use in place of the dot product;  keep: a dot that passes whatever the comparison says
+struct BfF32
+{
+	static constexpr int FMT = ROWS_F32;
+	static constexpr bool CLAMP = true;
+	static constexpr int EPI_Q = 2;
+	struct Row {};
+	__device__ static __forceinline__ float query_word(const BfArgs &, uint32_t, int) { return 0.f; }
+	__device__ static __forceinline__ float row_operands(const BfArgs &a, uint32_t r, Row &) { return a.xnorm[r]; }
+	// An MFMA may sum a dot product in any k order as long as both operands use the same one: lane (col, kk) takes the four k of ONE
+	// ds_read_b128 (chunk 2g + kk of its row) and feeds them to four consecutive MFMAs — 16 ds_read_b128 per 64 MFMAs.
+	template <int NJ>
+	__device__ static __forceinline__ void step(const floatx4 (&av)[2], const floatx4 (&bv)[NJ], floatx16 (&acc)[2][NJ])
+	{
+#pragma unroll
+		for (int c = 0; c < 4; c++)
+#pragma unroll
+			for (int i = 0; i < 2; i++)
+#pragma unroll
+				for (int j = 0; j < NJ; j++)
+					acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[i][c], bv[j][c], acc[i][j], 0, 0, 0);
+	}
+	__device__ static __forceinline__ float value(const BfArgs &, float dot, const floatx4 *, int, const Row &) { return dot; }
+	__device__ static __forceinline__ bool keep(float) { return false; }
+};
+
+// a passing (query, row) pair -> the query's candidate list (the host sees a list that overflowed its cap in the count)
+__device__ __forceinline__ void bf_append(const BfArgs &a, uint32_t q, uint32_t r)
+{
+	const uint32_t pos = atomicAdd(&a.cand_cnt[q], 1u);
+	if (pos < a.cap) a.cand[(size_t) q * a.cap + pos] = r;
+}
+
+template <class P, int WM, int NJ>
 __global__ __launch_bounds__(128 * WM, WM == 2 ? 2 : 1) void bf_mfma_filter_kernel(const BfArgs a)
 {
-	using T = BfTile<WM, NJ>;
-	constexpr int BF_THREADS = T::THREADS, BF_TQ = T::TQ, BF_TR = T::TR, BF_RPP = T::RPP, BF_PASSES = T::PASSES, BF_PASSES_R = T::PASSES_R;
-	constexpr int BF_TILE_FLOATS = T::TILE_FLOATS, BF_BUF_FLOATS = T::BUF_FLOATS, BF_EPI_FLOATS = T::EPI_FLOATS;
+	using T = BfTile<P, WM, NJ>;
+	constexpr int THREADS = T::THREADS, TQ = T::TQ, TR = T::TR, RPP = T::RPP, PASSES = T::PASSES, PASSES_R = T::PASSES_R;
+	constexpr int TILE_WORDS = T::TILE_WORDS, BUF_WORDS = T::BUF_WORDS, EPI_WORDS = T::EPI_WORDS;
 	extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-	float *bf_lds = reinterpret_cast<float *>(smem);                    // [buf][A | B][row][BF_LS], then the epilogue's bounds
+	float *lds = reinterpret_cast<float *>(smem);                       // [buf][A | B][row][BF_LS], then the epilogue's per-query values
 	const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
 	// XCD-aware tile order: the nqt query tiles of one row tile share b % 8
 	const uint32_t b = blockIdx.x;
@@ -124,18 +157,15 @@ __global__ __launch_bounds__(128 * WM, WM == 2 ? 2 : 1) void bf_mfma_filter_kern
 	const uint32_t qt = rest % a.nqt, rgrp = rest / a.nqt;
 	const uint32_t rt = rgrp * 8 + xcd;
 	if (rt >= a.nrt) return;
-	const uint32_t q0 = qt * BF_TQ, r0 = rt * BF_TR;
+	const uint32_t q0 = qt * TQ, r0 = rt * TR;
 
-	// staging role: thread owns 16-byte slot `sch` of tile rows srow + BF_RPP * j; a wave instruction moves whole 128-byte lines
+	// staging role: thread owns 16-byte slot `sch` of tile rows srow + RPP * j; a wave instruction moves whole 128-byte lines
 	const uint32_t sch = t & (BF_CH - 1), srow = t / BF_CH;
-	const uint32_t nchunks = a.stride / 4;
-	const floatx4 *qsrc[BF_PASSES], *xsrc[BF_PASSES_R];
+	const uint4 *qsrc[PASSES], *xsrc[PASSES_R];
 #pragma unroll
-	for (int j = 0; j < BF_PASSES; j++)
-		qsrc[j] = reinterpret_cast<const floatx4 *>(a.queries + (size_t) min(q0 + srow + BF_RPP * j, a.nq - 1) * a.qstride);
+	for (int j = 0; j < PASSES; j++) qsrc[j] = a.queries + (size_t) min(q0 + srow + RPP * j, a.nq - 1) * a.qchunks;
 #pragma unroll
-	for (int j = 0; j < BF_PASSES_R; j++)
-		xsrc[j] = reinterpret_cast<const floatx4 *>(a.vec + (size_t) min(r0 + srow + BF_RPP * j, a.n - 1) * a.stride);
+	for (int j = 0; j < PASSES_R; j++) xsrc[j] = a.rows + (size_t) min(r0 + srow + RPP * j, a.n - 1) * a.rchunks;
 
 	floatx16 acc[2][NJ];
 #pragma unroll
@@ -144,81 +174,76 @@ __global__ __launch_bounds__(128 * WM, WM == 2 ? 2 : 1) void bf_mfma_filter_kern
 		for (int j = 0; j < NJ; j++)
 #pragma unroll
 			for (int e = 0; e < 16; e++) acc[i][j][e] = 0.f;
-	const uint32_t wm = wave >> 1, wn = wave & 1;          // 2 x 2 waves over the block tile
+	const uint32_t wm = wave >> 1, wn = wave & 1;          // WM x 2 waves over the block tile
 	const uint32_t kk = lane >> 5, col = lane & 31;
 
 	// What the epilogue compares with is fetched NOW, behind the K loop: every block of a launch takes the same time, so the blocks of
 	// a CU reach their epilogues together, and an epilogue that loads its 32 bounds per lane one dependent L2 round trip after the
-	// other (rounds 1-4) leaves the matrix pipe idle.  The tile's 128 bounds and |q|^2 go to LDS (read back four at a time), the two
-	// |x|^2 of the lane's columns to registers.
-	float *epi = bf_lds + (size_t) BF_NBUF * BF_BUF_FLOATS;
+	// other (rounds 1-4) leaves the matrix pipe idle.  The tile's per-query values go to LDS (read back four at a time), the per-row
+	// values of the lane's columns to registers.
+	float *epi = lds + (size_t) BF_NBUF * BUF_WORDS;
 	// Rows that pass the filter (about twenty per block) are collected in LDS and appended to their queries' candidate lists by the
 	// whole block at once: in rounds 1-4 every passing element was a returning global atomic behind its own `s_waitcnt vmcnt(0)` inside
 	// a divergent branch — a handful of dependent L2 round trips per wave at the end of every block, with the matrix pipe idle.
-	uint32_t *pass_cnt = reinterpret_cast<uint32_t *>(epi + BF_EPI_FLOATS);
-	uint2 *pass_list = reinterpret_cast<uint2 *>(epi + BF_EPI_FLOATS + 4);
+	uint32_t *pass_cnt = reinterpret_cast<uint32_t *>(epi + EPI_WORDS);
+	uint2 *pass_list = reinterpret_cast<uint2 *>(epi + EPI_WORDS + 4);
 	if (t == 0) *pass_cnt = 0u;
-	if (t < BF_TQ)
+	if (t < TQ)
 	{
 		const uint32_t qi = min(q0 + (uint32_t) t, a.nq - 1);
 		epi[t] = a.qbound[qi];
-		epi[BF_TQ + t] = a.qnorm[qi];
+		epi[TQ + t] = a.qnorm[qi];
+#pragma unroll
+		for (int w = 2; w < P::EPI_Q; w++) epi[w * TQ + t] = P::query_word(a, qi, w);
 	}
 	float xs2[NJ];
+	typename P::Row xr[NJ];
 #pragma unroll
 	for (int j = 0; j < NJ; j++)
 	{
-		const float xn = a.xnorm[min(r0 + wn * (32 * NJ) + j * 32 + col, a.n - 1)];
+		const float xn = P::row_operands(a, min(r0 + wn * (32 * NJ) + j * 32 + col, a.n - 1), xr[j]);
 		xs2[j] = !(xn <= __FLT_MAX__) ? __builtin_nanf("") : (a.func == F_COSINE) ? __builtin_sqrtf(xn) : a.xscale * xn;   // (NaN: always passes)
 	}
 
 	// Tiles go global -> LDS directly (global_load_lds_dwordx4: no staging registers, no ds_write).  The LDS image is what the hardware
 	// writes — wave-uniform base + lane * 16: BF_RPI rows of whole lines per instruction, no padding — so bank conflicts are avoided on
 	// the SOURCE side: the lane that fills slot p of row r fetches chunk p ^ swizzle(r).  No select on a loaded value either: the query
-	// copy is zero padded to whole K steps, and a row chunk beyond the row's end re-reads the row's last chunk (times zero: nothing).
-	const uint32_t gch = sch ^ bf_swz(srow);                    // (swizzle(srow + BF_RPP * j) == swizzle(srow): the step is a multiple of 16)
+	// copy is zero padded to whole K steps, and a row chunk beyond the row's end re-reads the row's last chunk (times zero: nothing;
+	// P::CLAMP — a reduced row is a whole number of K steps).
+	const uint32_t gch = sch ^ bf_swz(srow);                    // (swizzle(srow + RPP * j) == swizzle(srow): the step is a multiple of 16)
+	auto load16 = [](const uint4 *src, float *dst)
+	{
+		__builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *) src, (__attribute__((address_space(3))) void *) dst, 16, 0, 0);
+	};
 	auto fetch = [&](uint32_t ks, uint32_t buf)
 	{
 		const uint32_t c = ks * BF_CH + gch;
-		const uint32_t cc = min(c, nchunks - 1);
-		float *As = bf_lds + (size_t) buf * BF_BUF_FLOATS + (wave * BF_RPI) * BF_LS, *Bs = As + BF_TILE_FLOATS;
+		const uint32_t cc = P::CLAMP ? min(c, a.rchunks - 1) : c;
+		float *As = lds + (size_t) buf * BUF_WORDS + (wave * BF_RPI) * BF_LS, *Bs = As + TILE_WORDS;
 #pragma unroll
-		for (int j = 0; j < BF_PASSES; j++)
-			__builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *) (qsrc[j] + c),
-											 (__attribute__((address_space(3))) void *) (As + BF_RPP * j * BF_LS), 16, 0, 0);
+		for (int j = 0; j < PASSES; j++) load16(qsrc[j] + c, As + RPP * j * BF_LS);
 #pragma unroll
-		for (int j = 0; j < BF_PASSES_R; j++)
-			__builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *) (xsrc[j] + cc),
-											 (__attribute__((address_space(3))) void *) (Bs + BF_RPP * j * BF_LS), 16, 0, 0);
+		for (int j = 0; j < PASSES_R; j++) load16(xsrc[j] + cc, Bs + RPP * j * BF_LS);
 	};
-	// An MFMA may sum a dot product in any k order as long as both operands use the same one: lane (col, kk) takes the four k of ONE
-	// ds_read_b128 (chunk 2g + kk of its row) and feeds them to four consecutive MFMAs — 16 ds_read_b128 per 64 MFMAs.
+	// lane (col, kk) reads chunk 2g + kk of its row: A and B use the same chunk per k (P::step says what one ds_read_b128 feeds)
 	const uint32_t swz = bf_swz(col);                           // (the tile rows of this lane are col + 32 * i + 64 * wm: same swizzle)
-	uint32_t roff[BF_TK / 8];                                  // float offset of k-group g's slot in this lane's row
+	uint32_t roff[BF_CH / 2];                                  // word offset of k-group g's slot in this lane's row
 #pragma unroll
-	for (int g = 0; g < BF_TK / 8; g++) roff[g] = ((2 * g + kk) ^ swz) * 4;
+	for (int g = 0; g < BF_CH / 2; g++) roff[g] = ((2 * g + kk) ^ swz) * 4;
 	auto contract = [&](uint32_t buf)
 	{
-		const float *As = bf_lds + (size_t) buf * BF_BUF_FLOATS + (wm * 64 + col) * BF_LS;
-		const float *Bs = bf_lds + (size_t) buf * BF_BUF_FLOATS + BF_TILE_FLOATS + (wn * (32 * NJ) + col) * BF_LS;
+		const float *As = lds + (size_t) buf * BUF_WORDS + (wm * 64 + col) * BF_LS;
+		const float *Bs = lds + (size_t) buf * BUF_WORDS + TILE_WORDS + (wn * (32 * NJ) + col) * BF_LS;
 #pragma unroll
-		for (int g = 0; g < BF_TK / 8; g++)
+		for (int g = 0; g < BF_CH / 2; g++)
 		{
-			const uint32_t o = roff[BF_ABLATE == 2 ? 0 : g];
+			const uint32_t o = roff[g];
 			floatx4 av[2], bv[NJ];
 #pragma unroll
 			for (int i = 0; i < 2; i++) av[i] = *reinterpret_cast<const floatx4 *>(As + i * 32 * BF_LS + o);
 #pragma unroll
 			for (int j = 0; j < NJ; j++) bv[j] = *reinterpret_cast<const floatx4 *>(Bs + j * 32 * BF_LS + o);
-#pragma unroll
-			for (int c = 0; c < 4; c++)
-			{
-#pragma unroll
-				for (int i = 0; i < 2; i++)
-#pragma unroll
-					for (int j = 0; j < NJ; j++)
-						acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[i][c], bv[j][c], acc[i][j], 0, 0, 0);
-			}
+			P::template step<NJ>(av, bv, acc);
 		}
 	};
 
@@ -230,27 +255,20 @@ __global__ __launch_bounds__(128 * WM, WM == 2 ? 2 : 1) void bf_mfma_filter_kern
 	// the last k-group — no LDS or memory round trip exposed inside the loop — 129; three buffers with a counted vmcnt 132.5; the next
 	// step's loads issued between the MFMAs 130 / 124; s_setprio around the MFMAs 131.7; a pipeline across tiles in resident blocks +0.6 % /
 	// -1.5 % (profiles/r5y_*); this plain form 134-136 with 128 x 128 tiles, 138 with 256 x 256.)
-	fetch(0, 0);
 	// The tile loads are LDS-bound DMA (global_load_lds): what orders them before the other waves' LDS reads is vmcnt reaching 0 on the
 	// ISSUING wave before it arrives at the barrier.  hipcc emits that wait today, but nothing obliges it to (gfx950 has back-off
 	// barriers: no automatic waitcnt; a workgroup fence does not wait on vmcnt) — a compiler that dropped it would let a wave read tile
 	// rows another wave's DMA has not landed yet, and the filter would lose true neighbours silently.  Said explicitly (vmcnt(0) only:
 	// expcnt / lgkmcnt left alone); free where the compiler already waits.
-	__builtin_amdgcn_s_waitcnt(0x0F70);
-	__syncthreads();
+	auto landed = [] { __builtin_amdgcn_s_waitcnt(0x0F70); __syncthreads(); };
+	fetch(0, 0);
+	landed();
 	for (uint32_t ks = 0; ks < a.ksteps; ks++)
 	{
-#if BF_ABLATE != 3                                              // (ablation builds — wrong answers, timing only: profiles/r5l_mfma_ablation.txt)
 		fetch(min(ks + 1, a.ksteps - 1), (ks + 1) & 1);            // its readers passed the previous barrier (branch-free: the last step re-reads itself)
-#endif
 		__builtin_amdgcn_sched_barrier(0);
 		contract(ks & 1);
-#if BF_ABLATE == 1
-		__builtin_amdgcn_s_waitcnt(0);                             // the loads are still waited for; only the rendezvous of the four waves is gone
-#else
-		__builtin_amdgcn_s_waitcnt(0x0F70);                        // vmcnt(0): this wave's DMA of step ks + 1 has landed before anybody reads it
-		__syncthreads();
-#endif
+		landed();                                                  // this wave's DMA of step ks + 1 has landed before anybody reads it
 	}
 	if (a.clocks && blockIdx.x == gridDim.x / 2 && t == 0)             // a block from the middle of the launch
 	{
@@ -266,8 +284,9 @@ __global__ __launch_bounds__(128 * WM, WM == 2 ? 2 : 1) void bf_mfma_filter_kern
 		for (int e4 = 0; e4 < 4; e4++)
 		{
 			const uint32_t ql = wm * 64 + i * 32 + 8 * e4 + 4 * kk;          // four consecutive queries of the tile
-			const floatx4 qb = *reinterpret_cast<const floatx4 *>(epi + ql);
-			const floatx4 qn = *reinterpret_cast<const floatx4 *>(epi + BF_TQ + ql);
+			floatx4 qo[P::EPI_Q];                                              // per word: bound, |q|^2, the policy's own
+#pragma unroll
+			for (int w = 0; w < P::EPI_Q; w++) qo[w] = *reinterpret_cast<const floatx4 *>(epi + w * TQ + ql);
 #pragma unroll
 			for (int j = 0; j < NJ; j++)
 			{
@@ -278,32 +297,27 @@ __global__ __launch_bounds__(128 * WM, WM == 2 ? 2 : 1) void bf_mfma_filter_kern
 				{
 					const uint32_t q = q0 + ql + e1;
 					const float dot = acc[i][j][e4 * 4 + e1];
-					bool pass;                                            // (written so that a NaN passes)
+					const float v = P::value(a, dot, qo, e1, xr[j]);
+					bool pass = P::keep(dot);                             // (every comparison written so that a NaN passes)
 					if (a.func == F_COSINE)
-						pass = !(dot < qb[e1] * xs2[j]);                 // 1 - dot/sqrt(nq nx) <= tau (+margin)
+						pass = pass || !(v < qo[0][e1] * xs2[j]);                 // 1 - dot/sqrt(nq nx) <= tau (+margin)
 					else
-						pass = !(qn[e1] + xs2[j] - dot > qb[e1]);        // |q-x|^2 / 2 <= tau^2 / 2 (+margin)
-					if (BF_ABLATE) pass = pass && dot == 12345.678f;      // (timing-only builds compute garbage: keep it out of the lists)
+						pass = pass || !(qo[1][e1] + xs2[j] - v > qo[0][e1]);     // |q-x|^2 / 2 <= tau^2 / 2 (+margin)
 					if (pass && rok && q < a.nq)
 					{
 						const uint32_t slot = atomicAdd(pass_cnt, 1u);      // (LDS)
 						if (slot < (uint32_t) BF_PASS_CAP) pass_list[slot] = make_uint2(q, r);
-						else                                              // a block with more passes than the list holds: straight to the global list
-						{
-							const uint32_t pos = atomicAdd(&a.cand_cnt[q], 1u);
-							if (pos < a.cap) a.cand[(size_t) q * a.cap + pos] = r;
-						}
+						else bf_append(a, q, r);                          // a block with more passes than the list holds: straight to the global list
 					}
 				}
 			}
 		}
 	__syncthreads();
 	const uint32_t npass = min(*pass_cnt, (uint32_t) BF_PASS_CAP);
-	for (uint32_t i = (uint32_t) t; i < npass; i += BF_THREADS)
+	for (uint32_t i = (uint32_t) t; i < npass; i += THREADS)
 	{
 		const uint2 e = pass_list[i];
-		const uint32_t pos = atomicAdd(&a.cand_cnt[e.x], 1u);
-		if (pos < a.cap) a.cand[(size_t) e.x * a.cap + pos] = e.y;
+		bf_append(a, e.x, e.y);
 	}
 }
 
@@ -356,68 +370,4 @@ __global__ void make_bounds_kernel(const float *__restrict__ tau, float *__restr
 		qnorm[q] = 0.5f * nqv;
 	}
 }
-
-// One wave per query: canonical distances of the surviving rows, top-k by (dist, idx).
-template <int FUNC>
-__global__ __launch_bounds__(256) void bf_rescore_kernel(const float *__restrict__ vec, uint32_t dim, uint32_t stride,
-														 uint32_t nchunks, uint32_t kiters, uint32_t qpad_floats,
-														 const float *__restrict__ queries, uint32_t nq,
-														 const uint32_t *__restrict__ cand, const uint32_t *__restrict__ cand_cnt,
-														 uint32_t cap, uint32_t k, uint32_t *__restrict__ out_idx,
-														 float *__restrict__ out_dist, uint32_t *__restrict__ overflow)
-{
-	extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-	const int lane = threadIdx.x & 63;
-	const uint32_t wib = threadIdx.x >> 6;
-	const uint32_t qi = blockIdx.x * 4 + wib;
-	if (qi >= nq) return;
-	const size_t wave_bytes = (size_t) qpad_floats * 4 + (size_t) (k + 1) * 8 + 128 * 4;
-	unsigned char *my = smem + wib * ((wave_bytes + 15) & ~(size_t) 15);
-	float *qf = reinterpret_cast<float *>(my);
-	const float4 *q4 = reinterpret_cast<const float4 *>(my);
-	uint64_t *top = reinterpret_cast<uint64_t *>(my + (size_t) qpad_floats * 4);
-	float *sums = reinterpret_cast<float *>(top + (k + 1));
-	for (uint32_t e = lane; e < qpad_floats; e += 64)
-	{
-		const float t = queries[(size_t) qi * dim + (e < dim ? e : dim - 1)];
-		qf[e] = e < dim ? t : 0.f;
-	}
-	wave_sync();
-	float qnorm = 0.f;
-	if (FUNC == F_COSINE) qnorm = query_norm(q4, nchunks, kiters, lane);
-	uint32_t cnt = cand_cnt[qi];
-	if (cnt > cap) { if (lane == 0) atomicAdd(overflow, 1u); cnt = cap; }
-	const uint32_t *ids = cand + (size_t) qi * cap;
-	uint32_t tsize = 0;
-	uint64_t worst = ~0ull;
-	for (uint32_t base = 0; base < cnt; base += 64)
-	{
-		const uint32_t c64 = min(64u, cnt - base);
-		auto by_id = [ids, base](uint32_t r) { return ids[base + r]; };
-		score_rows<FUNC, 4, 2>(vec, stride, q4, nchunks, kiters, by_id, c64, sums, lane);
-		wave_sync();
-		const float dl = finish_dist<FUNC>(sums[lane], sums[OUT2 + lane], qnorm);
-		const uint64_t kl = ((uint64_t) ord_f32(dl) << 32) | ids[base + ((uint32_t) lane < c64 ? lane : 0)];
-		uint64_t todo = __ballot((uint32_t) lane < c64 && (tsize < k || kl < worst));
-		while (todo)
-		{
-			const uint32_t r = (uint32_t) __builtin_ctzll(todo);
-			todo &= todo - 1;
-			const uint64_t key = readlane_u64(kl, r);
-			if (tsize < k || key < worst)
-			{
-				tsize = sorted_insert(top, tsize, key, k, lane);
-				worst = top[tsize - 1];
-			}
-		}
-		wave_sync();
-	}
-	for (uint32_t i = lane; i < k; i += 64)
-	{
-		const bool ok = i < tsize;
-		out_idx[(size_t) qi * k + i] = ok ? (uint32_t) top[i] : LINK_NONE;
-		if (out_dist) out_dist[(size_t) qi * k + i] = ok ? unord_f32((uint32_t) (top[i] >> 32)) : __builtin_inff();
-	}
-}
-
 }  // namespace pgemb

@@ -45,24 +45,6 @@ namespace pgemb {
 typedef _Float16 halfx8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
-constexpr int R16_CH = 8;                            // 16-byte units of a tile row per K step (128 bytes = 64 values)
-constexpr int R16_RPI = 64 / R16_CH;                 // tile rows one wave instruction fills (8 whole 128-byte lines)
-constexpr int R16_LS = 32;                           // words per LDS tile row (no padding: unit c of row r at slot c ^ r16_swz(r))
-__host__ __device__ inline uint32_t r16_swz(uint32_t r) { return (r >> 1) & 7u; }    // (bf_swz for 128-byte rows)
-
-template <int WM, int NJ>
-struct R16Tile
-{
-	static constexpr int WAVES = 2 * WM, THREADS = 64 * WAVES;
-	static constexpr int TQ = 64 * WM, TR = 64 * NJ;
-	static constexpr int RPP = WAVES * R16_RPI;
-	static constexpr int PASSES = TQ / RPP, PASSES_R = TR / RPP;
-	static constexpr int TILE_WORDS = TQ * R16_LS;
-	static constexpr int BUF_WORDS = (TQ + TR) * R16_LS;
-	static constexpr int EPI_WORDS = 4 * TQ;            // per query of the tile: bound, |q|^2 (halved for L2), rq', |q~|'
-	static constexpr size_t LDS_BYTES = ((size_t) BF_NBUF * BUF_WORDS + EPI_WORDS + 4 + 2 * BF_PASS_CAP) * 4;
-};
-
 // |v|^2 sums in f64 -> f32 rounded up (the bound's norms and residuals; NaN and inf stay what they are)
 __host__ __device__ inline float r16_f32_up(double d)
 {
@@ -189,207 +171,43 @@ __global__ __launch_bounds__(256) void r16_query_kernel(const float *__restrict_
 	}
 }
 
-// one v_mfma_f32_32x32x16_f16 / _bf16: 8 values of A and of B per lane, one 16-byte unit of the copy's layout each
-template <int FMT>
-__device__ __forceinline__ floatx16 r16_mfma(const floatx4 &a, const floatx4 &b, const floatx16 &c)
+// The operand policy of the 16-bit forms for bf_mfma_filter_kernel (device_bf_mfma.h says what a policy is).  A 16-byte chunk is one unit
+// of the copy's layout: 8 values of A and of B per lane, one v_mfma_f32_32x32x16_f16 / _bf16.  The comparisons take dot16 + E (header);
+// a non-finite dot16 passes.
+template <int FMT_>
+struct Bf16
 {
+	static constexpr int FMT = FMT_;
+	static constexpr bool CLAMP = false;                      // a reduced row is a whole number of K steps
+	static constexpr int EPI_Q = 4;                           // bound, |q|^2 (halved for L2), rq', |q~|'
+	struct Row { float xl, ex; };                             // |x|', ex'
+	__device__ static __forceinline__ float query_word(const BfArgs &a, uint32_t qi, int w) { return w == 2 ? a.qterms[qi].x : a.qterms[qi].y; }
+	__device__ static __forceinline__ float row_operands(const BfArgs &a, uint32_t r, Row &x)
+	{
+		const float4 xv = a.xterms[r];
+		x.xl = xv.y; x.ex = xv.z;
+		return xv.x;
+	}
+	template <int NJ>
+	__device__ static __forceinline__ void step(const floatx4 (&av)[2], const floatx4 (&bv)[NJ], floatx16 (&acc)[2][NJ])
+	{
 #if __has_builtin(__builtin_amdgcn_mfma_f32_32x32x16_f16)
-	if (FMT == ROWS_BF16)
-		return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-	return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(halfx8, a), __builtin_bit_cast(halfx8, b), c, 0, 0, 0);
-#else
-	__builtin_trap();          // (a plain host compile of these sources, as the tests' CPU emulator makes, never launches the filter)
-	return c;
-#endif
-}
-
-struct R16Args
-{
-	const uint4 *queries;      // [nq][nunits] (r16_query_kernel)
-	const float *qnorm;        // make_bounds_kernel's |q|^2 (halved for L2)
-	const float *qbound;       // make_bounds_kernel's bound
-	const float2 *qterms;      // rq', |q~|'
-	const uint4 *rows;         // the reduced copy, [n][nunits]
-	const float4 *xterms;      // |x|^2, |x|', ex'
-	uint32_t nq, n, nunits, ksteps;
-	int func;
-	float xscale;              // as BfArgs
-	float eabs;                // r16_abs_term(dim)
-	uint32_t *cand;
-	uint32_t *cand_cnt;
-	uint32_t cap;
-	uint32_t nqt, nrt;
-	unsigned long long *clocks;
-};
-
-template <int FMT, int WM, int NJ>
-__global__ __launch_bounds__(128 * WM, WM == 2 ? 2 : 1) void bf16_filter_kernel(const R16Args a)
-{
-	using T = R16Tile<WM, NJ>;
-	constexpr int THREADS = T::THREADS, TQ = T::TQ, TR = T::TR, RPP = T::RPP, PASSES = T::PASSES, PASSES_R = T::PASSES_R;
-	constexpr int TILE_WORDS = T::TILE_WORDS, BUF_WORDS = T::BUF_WORDS, EPI_WORDS = T::EPI_WORDS;
-	extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-	float *lds = reinterpret_cast<float *>(smem);                       // [buf][A | B][row][R16_LS], then the epilogue's per-query values
-	const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-	const uint32_t b = blockIdx.x;                                       // XCD-aware tile order, as the f32 kernel
-	const uint32_t xcd = b & 7, rest = b >> 3;
-	const uint32_t qt = rest % a.nqt, rgrp = rest / a.nqt;
-	const uint32_t rt = rgrp * 8 + xcd;
-	if (rt >= a.nrt) return;
-	const uint32_t q0 = qt * TQ, r0 = rt * TR;
-
-	const uint32_t sch = t & (R16_CH - 1), srow = t / R16_CH;
-	const uint4 *qsrc[PASSES], *xsrc[PASSES_R];
 #pragma unroll
-	for (int j = 0; j < PASSES; j++) qsrc[j] = a.queries + (size_t) min(q0 + srow + RPP * j, a.nq - 1) * a.nunits;
-#pragma unroll
-	for (int j = 0; j < PASSES_R; j++) xsrc[j] = a.rows + (size_t) min(r0 + srow + RPP * j, a.n - 1) * a.nunits;
-
-	floatx16 acc[2][NJ];
-#pragma unroll
-	for (int i = 0; i < 2; i++)
-#pragma unroll
-		for (int j = 0; j < NJ; j++)
-#pragma unroll
-			for (int e = 0; e < 16; e++) acc[i][j][e] = 0.f;
-	const uint32_t wm = wave >> 1, wn = wave & 1;
-	const uint32_t kk = lane >> 5, col = lane & 31;
-
-	// the epilogue's operands, fetched behind the K loop (device_bf_mfma.h)
-	float *epi = lds + (size_t) BF_NBUF * BUF_WORDS;
-	uint32_t *pass_cnt = reinterpret_cast<uint32_t *>(epi + EPI_WORDS);
-	uint2 *pass_list = reinterpret_cast<uint2 *>(epi + EPI_WORDS + 4);
-	if (t == 0) *pass_cnt = 0u;
-	if (t < TQ)
-	{
-		const uint32_t qi = min(q0 + (uint32_t) t, a.nq - 1);
-		const float2 qv = a.qterms[qi];
-		epi[t] = a.qbound[qi];
-		epi[TQ + t] = a.qnorm[qi];
-		epi[2 * TQ + t] = qv.x;
-		epi[3 * TQ + t] = qv.y;
-	}
-	float xs2[NJ], xl[NJ], ex[NJ];
-#pragma unroll
-	for (int j = 0; j < NJ; j++)
-	{
-		const float4 xv = a.xterms[min(r0 + wn * (32 * NJ) + j * 32 + col, a.n - 1)];
-		xs2[j] = !(xv.x <= __FLT_MAX__) ? __builtin_nanf("") : (a.func == F_COSINE) ? __builtin_sqrtf(xv.x) : a.xscale * xv.x;
-		xl[j] = xv.y;
-		ex[j] = xv.z;
-	}
-
-	// global -> LDS directly, source-side swizzle (device_bf_mfma.h).  A reduced row is a whole number of K steps: no clamp on the unit.
-	const uint32_t gch = sch ^ r16_swz(srow);
-	auto fetch = [&](uint32_t ks, uint32_t buf)
-	{
-		const uint32_t c = ks * R16_CH + gch;
-		float *As = lds + (size_t) buf * BUF_WORDS + (wave * R16_RPI) * R16_LS, *Bs = As + TILE_WORDS;
-#pragma unroll
-		for (int j = 0; j < PASSES; j++)
-			__builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *) (qsrc[j] + c),
-											 (__attribute__((address_space(3))) void *) (As + RPP * j * R16_LS), 16, 0, 0);
-#pragma unroll
-		for (int j = 0; j < PASSES_R; j++)
-			__builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *) (xsrc[j] + c),
-											 (__attribute__((address_space(3))) void *) (Bs + RPP * j * R16_LS), 16, 0, 0);
-	};
-	// lane (col, kk) reads unit 2g + kk of its row: one ds_read_b128 is one MFMA operand (8 k); A and B use the same unit per k
-	const uint32_t swz = r16_swz(col);
-	uint32_t roff[R16_CH / 2];
-#pragma unroll
-	for (int g = 0; g < R16_CH / 2; g++) roff[g] = ((2 * g + kk) ^ swz) * 4;
-	auto contract = [&](uint32_t buf)
-	{
-		const float *As = lds + (size_t) buf * BUF_WORDS + (wm * 64 + col) * R16_LS;
-		const float *Bs = lds + (size_t) buf * BUF_WORDS + TILE_WORDS + (wn * (32 * NJ) + col) * R16_LS;
-#pragma unroll
-		for (int g = 0; g < R16_CH / 2; g++)
-		{
-			const uint32_t o = roff[g];
-			floatx4 av[2], bv[NJ];
-#pragma unroll
-			for (int i = 0; i < 2; i++) av[i] = *reinterpret_cast<const floatx4 *>(As + i * 32 * R16_LS + o);
-#pragma unroll
-			for (int j = 0; j < NJ; j++) bv[j] = *reinterpret_cast<const floatx4 *>(Bs + j * 32 * R16_LS + o);
-#pragma unroll
-			for (int i = 0; i < 2; i++)
-#pragma unroll
-				for (int j = 0; j < NJ; j++)
-				{
-					acc[i][j] = r16_mfma<FMT>(av[i], bv[j], acc[i][j]);
-				}
-		}
-	};
-
-	unsigned long long c0 = 0, r0c = 0;
-	if (a.clocks) { c0 = __builtin_readcyclecounter(); r0c = wall_clock64(); }
-	fetch(0, 0);
-	__builtin_amdgcn_s_waitcnt(0x0F70);                                 // vmcnt(0) before the barrier: the DMA has landed (device_bf_mfma.h)
-	__syncthreads();
-	for (uint32_t ks = 0; ks < a.ksteps; ks++)
-	{
-		fetch(min(ks + 1, a.ksteps - 1), (ks + 1) & 1);
-		__builtin_amdgcn_sched_barrier(0);
-		contract(ks & 1);
-		__builtin_amdgcn_s_waitcnt(0x0F70);
-		__syncthreads();
-	}
-	if (a.clocks && blockIdx.x == gridDim.x / 2 && t == 0)
-	{
-		a.clocks[0] = __builtin_readcyclecounter() - c0;
-		a.clocks[1] = wall_clock64() - r0c;
-	}
-
-	// epilogue: lane holds column r = lane & 31, rows (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5); the comparisons of the f32 kernel with
-	// dot16 + E in place of the dot (header), written so that NaN passes
-#pragma unroll
-	for (int i = 0; i < 2; i++)
-#pragma unroll
-		for (int e4 = 0; e4 < 4; e4++)
-		{
-			const uint32_t ql = wm * 64 + i * 32 + 8 * e4 + 4 * kk;
-			const floatx4 qb = *reinterpret_cast<const floatx4 *>(epi + ql);
-			const floatx4 qn = *reinterpret_cast<const floatx4 *>(epi + TQ + ql);
-			const floatx4 rq = *reinterpret_cast<const floatx4 *>(epi + 2 * TQ + ql);
-			const floatx4 qtl = *reinterpret_cast<const floatx4 *>(epi + 3 * TQ + ql);
+		for (int i = 0; i < 2; i++)
 #pragma unroll
 			for (int j = 0; j < NJ; j++)
-			{
-				const uint32_t r = r0 + wn * (32 * NJ) + j * 32 + col;
-				const bool rok = r < a.n;
-#pragma unroll
-				for (int e1 = 0; e1 < 4; e1++)
-				{
-					const uint32_t q = q0 + ql + e1;
-					const float d16 = acc[i][j][e4 * 4 + e1];
-					const float dot = d16 + __builtin_fmaf(qtl[e1], ex[j], __builtin_fmaf(rq[e1], xl[j], a.eabs));
-					bool pass = !(__builtin_fabsf(d16) <= __FLT_MAX__);
-					if (a.func == F_COSINE)
-						pass = pass || !(dot < qb[e1] * xs2[j]);
-					else
-						pass = pass || !(qn[e1] + xs2[j] - dot > qb[e1]);
-					if (pass && rok && q < a.nq)
-					{
-						const uint32_t slot = atomicAdd(pass_cnt, 1u);
-						if (slot < (uint32_t) BF_PASS_CAP) pass_list[slot] = make_uint2(q, r);
-						else
-						{
-							const uint32_t pos = atomicAdd(&a.cand_cnt[q], 1u);
-							if (pos < a.cap) a.cand[(size_t) q * a.cap + pos] = r;
-						}
-					}
-				}
-			}
-		}
-	__syncthreads();
-	const uint32_t npass = min(*pass_cnt, (uint32_t) BF_PASS_CAP);
-	for (uint32_t i = (uint32_t) t; i < npass; i += THREADS)
-	{
-		const uint2 e = pass_list[i];
-		const uint32_t pos = atomicAdd(&a.cand_cnt[e.x], 1u);
-		if (pos < a.cap) a.cand[(size_t) e.x * a.cap + pos] = e.y;
+				acc[i][j] = FMT == ROWS_BF16
+					? __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, av[i]), __builtin_bit_cast(bf16x8, bv[j]), acc[i][j], 0, 0, 0)
+					: __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(halfx8, av[i]), __builtin_bit_cast(halfx8, bv[j]), acc[i][j], 0, 0, 0);
+#else
+		__builtin_trap();          // (a plain host compile of these sources, as the tests' CPU emulator makes, never launches the filter)
+#endif
 	}
-}
+	__device__ static __forceinline__ float value(const BfArgs &a, float d16, const floatx4 *qo, int e1, const Row &x)
+	{
+		return d16 + __builtin_fmaf(qo[3][e1], x.ex, __builtin_fmaf(qo[2][e1], x.xl, a.eabs));
+	}
+	__device__ static __forceinline__ bool keep(float d16) { return !(__builtin_fabsf(d16) <= __FLT_MAX__); }
+};
 
 }  // namespace pgemb

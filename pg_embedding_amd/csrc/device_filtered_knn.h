@@ -9,18 +9,17 @@
 //                        the total and the longest list go to a pinned host pair (the call's one wait before the scan)
 //      fk_fill_kernel    the count kernel's pass again, writing element numbers: list b = A(b) ascending, lists back to back, 4 bytes
 //                        per entry (CSR: offsets off[b * nseg] .. off[(b + 1) * nseg])
-//   2. fk_scan_kernel    bruteforce_kernel (gpu_scan.hip) with the row functor reading the list: a wave takes a contiguous slice of its
-//                        query's list, 64 entries per step (loaded coalesced, once, into the wave's LDS), scores them with the canonical
-//                        score_rows<FUNC, 4, 2> + finish_dist and keeps a sorted top-k of (ord(dist) << 32 | ELEMENT) keys.  A query
+//   2. fk_scan_kernel    bruteforce_kernel (device_topk_scan.h) with the rows read from the list: a wave takes a contiguous slice of its
+//                        query's list, 64 entries per step (loaded coalesced, once, into the wave's LDS: StagedRows), scores them with the
+//                        canonical scan (scan_topk) and keeps a sorted top-k of (ord(dist) << 32 | ELEMENT) keys.  A query
 //                        uses as many waves as its own list is long (FK_WAVE_ROWS rows each at least, at most the launch's splits * 4).
-//   3. fk_emit_kernel    one wave per query: merges the query's partial lists (ranks by binary search: keys are unique), gathers the
+//   3. fk_emit_kernel    one wave per query: merges the query's partial lists (merge_ranks: keys are unique), gathers the
 //                        labels of the <= k winners, ranks them by (dist, label, element) — hnsw_search's order — and writes labels,
 //                        distances, element numbers, the count and the padded tails.
 //
 // Selection by (dist, element), emission by (dist, label): the reference's two steps (topResults, then the sort of searchKnn's output).
 #pragma once
-#include "device_dist.h"
-#include "device_search.h"
+#include "device_topk_scan.h"
 
 namespace pgemb {
 
@@ -181,10 +180,8 @@ __global__ __launch_bounds__(256) void fk_scan_kernel(const FkScan a)
 	fk_list_of(a, qi, list, len);
 	const uint32_t nw = fk_waves(len, a.splits);
 	if (sp * 4u >= nw) return;                                        // (block-uniform) a short list leaves the later splits idle
-	float *qf = reinterpret_cast<float *>(smem);
+	stage_query_block(reinterpret_cast<float *>(smem), a.queries + (size_t) qi * a.dim, a.dim, a.qpad_floats);
 	const float4 *q4 = reinterpret_cast<const float4 *>(smem);
-	for (uint32_t e = threadIdx.x; e < a.qpad_floats; e += blockDim.x) qf[e] = (e < a.dim) ? a.queries[(size_t) qi * a.dim + e] : 0.f;
-	__syncthreads();
 	const int lane = threadIdx.x & 63;
 	const uint32_t wib = threadIdx.x >> 6, w = sp * 4u + wib, k = a.k;
 	if (w >= nw) return;                                              // (wave-uniform; no block barrier below)
@@ -193,38 +190,8 @@ __global__ __launch_bounds__(256) void fk_scan_kernel(const FkScan a)
 	float *sums = reinterpret_cast<float *>(wbase + (size_t) 4 * (k + 1) * 8) + wib * 128;
 	uint32_t *ids = reinterpret_cast<uint32_t *>(wbase + (size_t) 4 * (k + 1) * 8 + 4 * 128 * 4) + wib * 64;
 	const uint32_t lo = (uint32_t) ((uint64_t) len * w / nw), hi = (uint32_t) ((uint64_t) len * (w + 1) / nw);
-	float qnorm = 0.f;
-	if (FUNC == F_COSINE) qnorm = query_norm(q4, a.nchunks, a.kiters, lane);
-	uint32_t tsize = 0;
-	uint64_t worst = ~0ull;
-	for (uint32_t base = lo; base < hi; base += 64)
-	{
-		const uint32_t cnt = min(64u, hi - base);
-		const uint32_t id = list[base + min((uint32_t) lane, cnt - 1u)];      // one coalesced load per step; the tail re-reads its last entry
-		ids[lane] = id;
-		wave_sync();
-		auto listed = [ids](uint32_t r) { return ids[r]; };
-		score_rows<FUNC, 4, 2>(a.vec, a.stride, q4, a.nchunks, a.kiters, listed, cnt, sums, lane);
-		wave_sync();
-		const float dl = finish_dist<FUNC>(sums[lane], sums[OUT2 + lane], qnorm);
-		const uint64_t kl = ((uint64_t) ord_f32(dl) << 32) | id;
-		// only rows that can enter the current top-k are visited one by one
-		uint64_t todo = __ballot((uint32_t) lane < cnt && (tsize < k || kl < worst));
-		while (todo)
-		{
-			const uint32_t r = (uint32_t) __builtin_ctzll(todo);
-			todo &= todo - 1;
-			const uint64_t key = readlane_u64(kl, r);
-			if (tsize < k || key < worst)
-			{
-				tsize = sorted_insert(top, tsize, key, k, lane);
-				worst = top[tsize - 1];
-			}
-		}
-		wave_sync();
-	}
-	uint64_t *dst = a.part + ((size_t) qi * a.splits * 4u + w) * k;
-	for (uint32_t i = lane; i < k; i += 64) dst[i] = (i < tsize) ? top[i] : ~0ull;
+	const uint32_t tsize = scan_topk<FUNC>(a.vec, a.stride, q4, a.nchunks, a.kiters, StagedRows{list, ids}, lo, hi, top, sums, k, lane);
+	store_partial(a.part + ((size_t) qi * a.splits * 4u + w) * k, top, tsize, k, lane);
 	if (lane == 0) atomicAdd(a.scored, (unsigned long long) (hi - lo));
 }
 
@@ -245,25 +212,8 @@ __global__ __launch_bounds__(64) void fk_emit_kernel(const FkEmit a)
 	fk_list_of(a.s, qi, list, len);
 	const uint32_t nlists = fk_waves(len, a.s.splits);
 	const uint32_t cnt = min(k, len);                                 // every listed row was scored: the merge finds min(k, |A|) keys
-	const uint64_t *src = a.s.part + (size_t) qi * a.s.splits * 4u * k;
-	// 1. the key merge (key_merge_kernel's ranks) over the lists this query's waves wrote
-	const uint32_t total = nlists * k;
-	for (uint32_t x = lane; x < total; x += 64)
-	{
-		const uint32_t l = x / k;
-		const uint64_t key = src[x];
-		if (key == ~0ull) continue;
-		uint32_t rank = x - l * k;
-		for (uint32_t m = 0; m < nlists && rank < k; m++)
-		{
-			if (m == l) continue;
-			const uint64_t *o = src + (size_t) m * k;
-			uint32_t lo = 0, hi = k;                                  // number of keys in list m below `key` (keys are unique: one element, one key)
-			while (lo < hi) { uint32_t mid = (lo + hi) >> 1; if (o[mid] < key) lo = mid + 1; else hi = mid; }
-			rank += lo;
-		}
-		if (rank < k) win[rank] = key;
-	}
+	// 1. the key merge over the lists this query's waves wrote (one element, one key: merge_ranks)
+	merge_ranks(a.s.part + (size_t) qi * a.s.splits * 4u * k, nlists, k, (int) lane, [win](uint32_t rank, uint64_t key) { win[rank] = key; });
 	wave_sync();
 	// 2. the winners' labels
 	for (uint32_t i = lane; i < cnt; i += 64) lab[i] = a.labels[min((uint32_t) win[i], a.n - 1u)];

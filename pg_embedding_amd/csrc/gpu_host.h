@@ -5,7 +5,7 @@
 //   hnsw_gpu.hip      errors, configuration, workspaces + watchdog, the mirror (create / import / export / append / reserve)
 //   gpu_search.hip    launch planning (launch_search), the search entry points, traces of one walk, search contexts
 //   gpu_stream.hip    streams: one resident launch fed by the host
-//   gpu_scan.hip      batched distances, exhaustive k-NN (canonical scan, MFMA filter), exact filtered k-NN over allowed lists
+//   gpu_scan.hip      batched distances, exhaustive k-NN (canonical scan, MFMA filter in three operand forms), exact filtered k-NN over allowed lists
 //   gpu_build.hip     insert path: batched link step, single inserts
 //   gpu_sharded.hip   top-k merge, shards in one process, the exchange buffer shared between processes
 //   gpu_diag.hip      measurement only (include/hnsw_gpu_diag.h): traced launches, replay / gather roofs, clocks, placement
@@ -20,6 +20,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <mutex>
 #include <thread>
 #include <chrono>
@@ -112,8 +113,13 @@ struct SearchWs
 
 // ---- the batched index scan (device_indexscan.h, hnsw_gpu_scan_batch_dev) ------------------------
 // Buffers of one mirror's scan calls.  Each is reused from call to call and from round to round while it is large enough; what a late,
-// wide round made larger than SCAN_KEEP_BYTES is freed when its call ends.
+// wide round made larger than BUF_KEEP_BYTES is freed when its call ends.
 struct ScanBuf { void *p = nullptr; size_t bytes = 0; };
+static const size_t BUF_KEEP_BYTES = (size_t) 64 << 20;  // a grow-on-demand buffer larger than this does not outlive its call
+// at least `bytes` in *b (contents are not kept); on failure "<who>: no room for <what> (<bytes> bytes)" and an empty buffer (hnsw_gpu.hip)
+int buf_reserve(ScanBuf *b, size_t bytes, const char *who, const char *what);
+// free those of `bufs` that are larger than `keep` bytes (0: all that hold memory)
+void buf_trim(std::initializer_list<ScanBuf *> bufs, size_t keep = BUF_KEEP_BYTES);
 struct ScanWs
 {
 	static const int MAX_ROUNDS = 40;                    // (ef doubles per round and stays below 2^32)

@@ -1,10 +1,26 @@
-// gpu_scan.hip — batched distances (hnsw_dist_func over many rows), exhaustive k-NN: canonical scan, MFMA filter (csrc/device_bf_mfma.h), and exact
-// filtered k-NN: the canonical scan over lists of allowed rows (csrc/device_filtered_knn.h)
+// gpu_scan.hip — batched distances (hnsw_dist_func over many rows), exhaustive k-NN: canonical scan (csrc/device_topk_scan.h), MFMA filter over
+// the f32 rows or the reduced copy (csrc/device_bf_mfma.h, csrc/device_bf_mfma16.h), and exact filtered k-NN: the canonical scan over lists of
+// allowed rows (csrc/device_filtered_knn.h)
 // One translation unit of libhnsw_gpu.so (csrc/gpu_host.h lists them); gfx950 only, plain HIP runtime, no framework types in any signature.
 #include "gpu_host.h"
+#include "device_topk_scan.h"
 #include "device_bf_mfma.h"
 #include "device_bf_mfma16.h"
 #include "device_filtered_knn.h"
+
+#include <type_traits>
+
+// the runtime hnsw_dist_func as a compile-time constant: f(std::integral_constant<int, F_L2 | F_COSINE | F_MANHATTAN>{})
+template <class F>
+static void with_func(int func, F &&f)
+{
+	switch (func)
+	{
+		case F_L2: f(std::integral_constant<int, F_L2>{}); break;
+		case F_COSINE: f(std::integral_constant<int, F_COSINE>{}); break;
+		default: f(std::integral_constant<int, F_MANHATTAN>{}); break;
+	}
+}
 
 // ------------------------------------------------------------------------------------
 // batched distances (hnsw_dist_func over many rows)
@@ -15,15 +31,9 @@ __global__ __launch_bounds__(256) void dist_batch_kernel(const float *__restrict
 														 uint32_t kiters, uint32_t qpad_floats, float *__restrict__ out)
 {
 	extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-	float *qf = reinterpret_cast<float *>(smem);
 	const float4 *q4 = reinterpret_cast<const float4 *>(smem);
 	float *sums = reinterpret_cast<float *>(smem + (size_t) qpad_floats * 4) + (threadIdx.x >> 6) * 128;   // per wave
-	for (uint32_t e = threadIdx.x; e < qpad_floats; e += blockDim.x)
-	{
-		const float t = q[e < dim ? e : dim - 1];
-		qf[e] = (e < dim) ? t : 0.f;
-	}
-	__syncthreads();
+	stage_query_block(reinterpret_cast<float *>(smem), q, dim, qpad_floats);
 	const int lane = threadIdx.x & 63;
 	const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
 	const uint32_t nwaves = (gridDim.x * blockDim.x) >> 6;
@@ -56,21 +66,10 @@ extern "C" int hnsw_gpu_dist_batch_dev(dist_func_t func, const coord_t *d_q, con
 	if (lds > 64 * 1024) return fail(HNSW_GPU_ERR_ARG, "dim %zu too large", dim);
 	const uint32_t blocks = (uint32_t) std::min<size_t>((nrows + 255) / 256, 256 * 8);
 	hipStream_t s = (hipStream_t) stream;
-	switch ((int) func)
-	{
-		case F_L2:
-			hipLaunchKernelGGL(dist_batch_kernel<F_L2>, dim3(blocks), dim3(256), lds, s, d_q, d_rows, (uint32_t) nrows,
-							   (uint32_t) dim, (uint32_t) row_stride, nchunks, kiters, qpad, d_out);
-			break;
-		case F_COSINE:
-			hipLaunchKernelGGL(dist_batch_kernel<F_COSINE>, dim3(blocks), dim3(256), lds, s, d_q, d_rows, (uint32_t) nrows,
-							   (uint32_t) dim, (uint32_t) row_stride, nchunks, kiters, qpad, d_out);
-			break;
-		default:
-			hipLaunchKernelGGL(dist_batch_kernel<F_MANHATTAN>, dim3(blocks), dim3(256), lds, s, d_q, d_rows, (uint32_t) nrows,
-							   (uint32_t) dim, (uint32_t) row_stride, nchunks, kiters, qpad, d_out);
-			break;
-	}
+	with_func((int) func, [&](auto F) {
+		hipLaunchKernelGGL(dist_batch_kernel<decltype(F)::value>, dim3(blocks), dim3(256), lds, s, d_q, d_rows, (uint32_t) nrows, (uint32_t) dim,
+						   (uint32_t) row_stride, nchunks, kiters, qpad, d_out);
+	});
 	HIPCHK(hipGetLastError());
 	return HNSW_GPU_OK;
 }
@@ -139,89 +138,8 @@ extern "C" int hnsw_gpu_dist_batch(dist_func_t func, const coord_t *q, const coo
 }
 
 // ------------------------------------------------------------------------------------
-// exhaustive k-NN with the same distance code (recall ground truth)
+// exhaustive k-NN with the same distance code (recall ground truth): bruteforce_kernel + key_merge_kernel, device_topk_scan.h
 // ------------------------------------------------------------------------------------
-// grid = (splits, nq); each wave scans a contiguous slice of the rows for one query and keeps a
-// sorted top-k of (ord(dist)<<32 | idx) keys in LDS; partial lists are merged by topk_merge_kernel.
-template <int FUNC>
-__global__ __launch_bounds__(256) void bruteforce_kernel(const float *__restrict__ vec, uint32_t n, uint32_t dim,
-														 uint32_t stride, uint32_t nchunks, uint32_t kiters,
-														 uint32_t qpad_floats, const float *__restrict__ queries,
-														 uint32_t k, uint64_t *__restrict__ part /* [nq][splits*4][k] */)
-{
-	extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-	const uint32_t qi = blockIdx.y;
-	float *qf = reinterpret_cast<float *>(smem);
-	const float4 *q4 = reinterpret_cast<const float4 *>(smem);
-	for (uint32_t e = threadIdx.x; e < qpad_floats; e += blockDim.x) qf[e] = (e < dim) ? queries[(size_t) qi * dim + e] : 0.f;
-	__syncthreads();
-	const int lane = threadIdx.x & 63;
-	const uint32_t wib = threadIdx.x >> 6;
-	uint64_t *top = reinterpret_cast<uint64_t *>(smem + (size_t) qpad_floats * 4) + (size_t) wib * (k + 1);
-	float *sums = reinterpret_cast<float *>(smem + (size_t) qpad_floats * 4 + (size_t) 4 * (k + 1) * 8) + wib * 128;
-	const uint32_t nw = gridDim.x * 4, w = blockIdx.x * 4 + wib;
-	const uint32_t lo = (uint32_t) ((uint64_t) n * w / nw), hi = (uint32_t) ((uint64_t) n * (w + 1) / nw);
-	float qnorm = 0.f;
-	if (FUNC == F_COSINE) qnorm = query_norm(q4, nchunks, kiters, lane);
-	uint32_t tsize = 0;
-	uint64_t worst = ~0ull;
-	for (uint32_t base = lo; base < hi; base += 64)
-	{
-		const uint32_t cnt = min(64u, hi - base);
-		auto direct = [base](uint32_t r) { return base + r; };
-		score_rows<FUNC, 4, 2>(vec, stride, q4, nchunks, kiters, direct, cnt, sums, lane);
-		wave_sync();
-		const float dl = finish_dist<FUNC>(sums[lane], sums[OUT2 + lane], qnorm);
-		const uint64_t kl = ((uint64_t) ord_f32(dl) << 32) | (base + lane);
-		// only rows that can enter the current top-k are visited one by one
-		uint64_t todo = __ballot((uint32_t) lane < cnt && (tsize < k || kl < worst));
-		while (todo)
-		{
-			const uint32_t r = (uint32_t) __builtin_ctzll(todo);
-			todo &= todo - 1;
-			const uint64_t key = readlane_u64(kl, r);
-			if (tsize < k || key < worst)
-			{
-				tsize = sorted_insert(top, tsize, key, k, lane);
-				worst = top[tsize - 1];
-			}
-		}
-		wave_sync();
-	}
-	uint64_t *dst = part + ((size_t) qi * nw + w) * k;
-	for (uint32_t i = lane; i < k; i += 64) dst[i] = (i < tsize) ? top[i] : ~0ull;
-}
-
-// One wave per query: merge `nlists` ascending key lists of length k into the k smallest.
-__global__ __launch_bounds__(64) void key_merge_kernel(const uint64_t *__restrict__ part, uint32_t nlists, uint32_t k,
-													   uint32_t *__restrict__ out_idx, float *__restrict__ out_dist)
-{
-	const uint32_t qi = blockIdx.x;
-	const int lane = threadIdx.x;
-	const uint64_t *src = part + (size_t) qi * nlists * k;
-	const uint32_t total = nlists * k;
-	for (uint32_t x = lane; x < total; x += 64)
-	{
-		const uint32_t l = x / k;
-		const uint64_t key = src[x];
-		if (key == ~0ull) continue;
-		uint32_t rank = x - l * k;
-		for (uint32_t m = 0; m < nlists && rank < k; m++)
-		{
-			if (m == l) continue;
-			const uint64_t *o = src + (size_t) m * k;
-			uint32_t lo = 0, hi = k;                       // number of keys in list m below `key` (keys are unique)
-			while (lo < hi) { uint32_t mid = (lo + hi) >> 1; if (o[mid] < key) lo = mid + 1; else hi = mid; }
-			rank += lo;
-		}
-		if (rank < k)
-		{
-			out_idx[(size_t) qi * k + rank] = (uint32_t) key;
-			if (out_dist) out_dist[(size_t) qi * k + rank] = unord_f32((uint32_t) (key >> 32));
-		}
-	}
-}
-
 __global__ void fill_u32_kernel(uint32_t *p, size_t n, uint32_t v)
 {
 	size_t i = (size_t) blockIdx.x * blockDim.x + threadIdx.x;
@@ -255,16 +173,10 @@ static int bruteforce_prefix(hnsw_gpu_index *ix, size_t nrows, const coord_t *d_
 		hipLaunchKernelGGL(fill_u32_kernel, dim3((uint32_t) ((tot + 255) / 256)), dim3(256), 0, s, (uint32_t *) d_dists, tot,
 						   0x7F800000u);
 	dim3 grid(splits, (uint32_t) nq);
-#define BF_LAUNCH(F)                                                                                                   \
-	hipLaunchKernelGGL(bruteforce_kernel<F>, grid, dim3(256), lds, s, ix->vec, (uint32_t) nrows, (uint32_t) ix->meta.dim, \
-					   ix->stride, nchunks, kiters, qpad, d_queries, (uint32_t) k, part)
-	switch ((int) ix->meta.dist_func)
-	{
-		case F_L2: BF_LAUNCH(F_L2); break;
-		case F_COSINE: BF_LAUNCH(F_COSINE); break;
-		default: BF_LAUNCH(F_MANHATTAN); break;
-	}
-#undef BF_LAUNCH
+	with_func((int) ix->meta.dist_func, [&](auto F) {
+		hipLaunchKernelGGL(bruteforce_kernel<decltype(F)::value>, grid, dim3(256), lds, s, ix->vec, (uint32_t) nrows, (uint32_t) ix->meta.dim, ix->stride,
+						   nchunks, kiters, qpad, d_queries, (uint32_t) k, part);
+	});
 	hipLaunchKernelGGL(key_merge_kernel, dim3((uint32_t) nq), dim3(64), 0, s, part, nlists, (uint32_t) k, d_idx, d_dists);
 	HIPCHK(hipGetLastError());
 	return HNSW_GPU_OK;
@@ -281,158 +193,24 @@ extern "C" int hnsw_gpu_bruteforce_dev(hnsw_gpu_index *ix, const coord_t *d_quer
 }
 
 // ------------------------------------------------------------------------------------
-// exhaustive k-NN with the dense part on the matrix cores (device_bf_mfma.h)
+// exhaustive k-NN with the dense part on the matrix cores: a filter over the f32 rows (device_bf_mfma.h) or over the reduced copy on the
+// 16-bit matrix cores (device_bf_mfma16.h), then the canonical re-score of the survivors
 // ------------------------------------------------------------------------------------
 static float g_last_bf_gemm_ms = 0.f;
 static unsigned long long g_last_bf_clocks[2] = { 0, 0 };
 static int g_last_bf_tile = 0;
+static const size_t BF_MIN_LDS = (size_t) 72 * 1024;          // every form's 128 x 128 tile fits in this (69 - 70 KB; 256 x 256: 134 - 136 KB)
 
-// the filter launch for one tile shape (LDS per block: 69 KB for 128 x 128 tiles, 134 KB for 256 x 256; set per call: the attribute is per device)
-template <int WM, int NJ>
-static int bf_filter_launch(BfArgs &a, uint32_t nq, uint32_t n, hipStream_t s)
+// the operand policy of a form: ROWS_F32 = the f32 rows, ROWS_F16 / ROWS_BF16 = the reduced copy
+template <class F>
+static int with_form(int format, F &&f)
 {
-	using T = BfTile<WM, NJ>;
-	a.nqt = (nq + T::TQ - 1) / T::TQ;
-	a.nrt = (n + T::TR - 1) / T::TR;
-	const uint32_t rgroups = (a.nrt + 7) / 8;
-	HIPCHK(hipFuncSetAttribute((const void *) bf_mfma_filter_kernel<WM, NJ>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) T::LDS_BYTES));
-	hipLaunchKernelGGL((bf_mfma_filter_kernel<WM, NJ>), dim3(rgroups * a.nqt * 8), dim3(T::THREADS), T::LDS_BYTES, s, a);
-	return HNSW_GPU_OK;
+	if (format == ROWS_F16) return f(Bf16<ROWS_F16>{});
+	if (format == ROWS_BF16) return f(Bf16<ROWS_BF16>{});
+	return f(BfF32{});
 }
 
-extern "C" int hnsw_gpu_bruteforce_mfma_dev(hnsw_gpu_index *ix, const coord_t *d_queries, size_t nq, size_t k,
-											idx_t *d_idx, dist_t *d_dists, void *stream_)
-{
-	std::unique_lock<std::recursive_mutex> lock_;
-	if (ix) lock_ = std::unique_lock<std::recursive_mutex>(ix->mu);
-	if (!ix || !d_queries || !d_idx) return fail(HNSW_GPU_ERR_ARG, "NULL argument");
-	if (nq == 0) return HNSW_GPU_OK;
-	if (k == 0 || k > 1024) return fail(HNSW_GPU_ERR_ARG, "k %zu out of range [1, 1024]", k);
-	if (nq > 65535) return fail(HNSW_GPU_ERR_ARG, "at most 65535 queries per call");
-	ix->bf_cnt_nq = 0;
-	const int func = (int) ix->meta.dist_func;
-	if (func == F_MANHATTAN || ix->n < 4096)          // not a contraction / too small to matter
-		return hnsw_gpu_bruteforce_dev(ix, d_queries, nq, k, d_idx, d_dists, stream_);
-	HIPCHK(hipSetDevice(ix->device));
-	{
-		// The filter kernel is written for gfx950: 16-byte direct-to-LDS loads and 69 / 134 KB of LDS per block.  Anything else gets the
-		// canonical scan — the same answer, bit for bit (the filter's survivors are re-scored by that code anyway).
-		if (!ix->gfx950 || ix->max_lds < (size_t) 72 * 1024)
-			return hnsw_gpu_bruteforce_dev(ix, d_queries, nq, k, d_idx, d_dists, stream_);
-	}
-	hipStream_t s = (hipStream_t) stream_;
-	const uint32_t n = (uint32_t) ix->n, stride = ix->stride, dim = (uint32_t) ix->meta.dim;
-	const uint32_t nchunks = stride / 4, kiters = (nchunks + 15) / 16;
-	// the re-score step holds a query image and a k-list per wave in LDS; where that does not fit, the scan's answer (before any launch)
-	const uint32_t qpadf = (uint32_t) round_up(kiters, 4) * 64;
-	const size_t wave_bytes = round_up((size_t) qpadf * 4 + (k + 1) * 8 + 128 * 4, 16);
-	const size_t lds = wave_bytes * 4;
-	if (lds > 64 * 1024) return hnsw_gpu_bruteforce_dev(ix, d_queries, nq, k, d_idx, d_dists, stream_);
-
-	// |row|^2 cache
-	if (ix->xnorm_cap < ix->n)
-	{
-		if (ix->xnorm) (void) hipFree(ix->xnorm);
-		ix->xnorm = nullptr; ix->xnorm_cap = 0; ix->xnorm_n = 0;
-		HIPCHK(hipMalloc(&ix->xnorm, ix->cap * sizeof(float)));
-		ix->xnorm_cap = ix->cap;
-	}
-	if (ix->xnorm_n != ix->n)
-	{
-		hipLaunchKernelGGL(row_norm2_kernel, dim3((n + 3) / 4), dim3(256), 0, s, ix->vec, n, stride, ix->xnorm);
-		ix->xnorm_n = ix->n;
-	}
-
-	const uint32_t cap = 16384;
-	const size_t sample = std::min<size_t>(ix->n, std::max<size_t>(8192, (size_t) k * ix->n / 2048));
-	// scratch carve
-	const size_t o_q = 0;
-	const uint32_t qstride = (uint32_t) round_up(stride, BF_TK);        // the filter's query copy: zero padded to whole K steps
-	const size_t o_qn = o_q + round_up(nq * qstride * 4, 256);
-	const size_t o_sidx = o_qn + round_up(nq * 4, 256);
-	const size_t o_sdist = o_sidx + round_up(nq * k * 4, 256);
-	const size_t o_bound = o_sdist + round_up(nq * k * 4, 256);
-	const size_t o_cnt = o_bound + round_up(nq * 4, 256);
-	const size_t o_cand = o_cnt + round_up(nq * 4 + 64, 256);
-	const size_t o_clk = o_cand + round_up(nq * (size_t) cap * 4, 256);
-	const size_t total = o_clk + 256;
-	if (total > ix->bf_bytes)
-	{
-		if (ix->bf) (void) hipFree(ix->bf);
-		ix->bf = nullptr; ix->bf_bytes = 0;
-		HIPCHK(hipMalloc(&ix->bf, total));
-		ix->bf_bytes = total;
-	}
-	char *B = (char *) ix->bf;
-	float *qpad = (float *) (B + o_q), *qn = (float *) (B + o_qn), *sdist = (float *) (B + o_sdist), *bound = (float *) (B + o_bound);
-	uint32_t *sidx = (uint32_t *) (B + o_sidx), *cnt = (uint32_t *) (B + o_cnt), *cand = (uint32_t *) (B + o_cand);
-	uint32_t *overflow = cnt + nq;
-
-	// 1. bound per query from a canonical scan of the sample rows
-	int rc = bruteforce_prefix(ix, sample, d_queries, nq, k, sidx, sdist, s);
-	if (rc) return rc;
-	const size_t qtot = nq * (size_t) qstride;
-	hipLaunchKernelGGL(pad_queries_kernel, dim3((uint32_t) ((qtot + 255) / 256)), dim3(256), 0, s, d_queries, (uint32_t) nq, dim, qstride, qpad);
-	hipLaunchKernelGGL(row_norm2_kernel, dim3((uint32_t) ((nq + 3) / 4)), dim3(256), 0, s, qpad, (uint32_t) nq, qstride, qn);
-	// tau_q = sdist[q*k + k-1]: gather with a strided view
-	{
-		// reuse make_bounds on a compacted tau array: write tau into `bound` first
-		hipLaunchKernelGGL(fill_u32_kernel, dim3(1), dim3(1), 0, s, overflow, (size_t) 1, 0u);
-		HIPCHK(hipMemcpy2DAsync(bound, 4, sdist + (k - 1), k * 4, 4, nq, hipMemcpyDeviceToDevice, s));
-		hipLaunchKernelGGL(make_bounds_kernel, dim3((uint32_t) ((nq + 255) / 256)), dim3(256), 0, s, bound, qn, (uint32_t) nq, func, dim, bound);
-	}
-	HIPCHK(hipMemsetAsync(cnt, 0, nq * 4, s));
-	ix->bf_cnt_off = o_cnt; ix->bf_cnt_nq = nq;
-
-	// 2. the dense contraction + filter
-	BfArgs a;
-	memset(&a, 0, sizeof(a));
-	a.queries = qpad; a.qnorm = qn; a.qbound = bound; a.vec = ix->vec; a.xnorm = ix->xnorm;
-	a.nq = (uint32_t) nq; a.n = n; a.stride = stride; a.qstride = qstride; a.ksteps = qstride / BF_TK; a.func = func;
-	a.xscale = 0.5f * (1.f - 2.f * ((float) dim + 32.f) * 0x1p-24f);          // (1 - eD) / 2: make_bounds_kernel
-	a.cand = cand; a.cand_cnt = cnt; a.cap = cap; a.clocks = (unsigned long long *) (B + o_clk);
-	HIPCHK(hipMemsetAsync(a.clocks, 0, 16, s));                  // (written only by a block from the middle of the launch that does not exit early: a small table must not leave stale ticks behind)
-	if (!ix->bf_e0) { HIPCHK(hipEventCreate(&ix->bf_e0)); HIPCHK(hipEventCreate(&ix->bf_e1)); }
-	hipEvent_t e0 = ix->bf_e0, e1 = ix->bf_e1;
-	HIPCHK(hipEventRecord(e0, s));
-	// 256 x 256 tiles when they compute no more padding than 128 x 128 tiles would (an even number of 128-query tiles) and there are
-	// tiles enough to fill the device several times over; the same dot products in the same k order either way: the same survivors
-	{
-		using Big = BfTile<4, 4>;
-		const uint64_t nqt_s = (nq + BfTile<BF_WM, BF_NJ>::TQ - 1) / BfTile<BF_WM, BF_NJ>::TQ;
-		const uint64_t big_blocks = ((nq + Big::TQ - 1) / Big::TQ) * ((n + Big::TR - 1) / Big::TR);
-		// (test knob: 0 = never, < 0 = always, n = at least n blocks; the tests run every case through both tiles)
-		const long long min_blocks = knob(K_BF_BIG_MIN_BLOCKS, 2048);
-		const bool big = BF_BIG && BF_WM == 2 && BF_NJ == 2 && min_blocks != 0 &&
-						 (min_blocks < 0 || (nqt_s % 2 == 0 && big_blocks >= (uint64_t) min_blocks));
-		rc = big ? bf_filter_launch<4, 4>(a, (uint32_t) nq, n, s) : bf_filter_launch<BF_WM, BF_NJ>(a, (uint32_t) nq, n, s);
-		if (rc) return rc;
-		g_last_bf_tile = big ? Big::TQ : BfTile<BF_WM, BF_NJ>::TQ;
-	}
-	HIPCHK(hipEventRecord(e1, s));
-
-	// 3. canonical re-score of the survivors
-#define RS_LAUNCH(F)                                                                                                      \
-	hipLaunchKernelGGL(bf_rescore_kernel<F>, dim3((uint32_t) ((nq + 3) / 4)), dim3(256), lds, s, ix->vec, dim, stride,      \
-					   nchunks, kiters, qpadf, d_queries, (uint32_t) nq, cand, cnt, cap, (uint32_t) k, d_idx, d_dists, overflow)
-	if (func == F_L2) RS_LAUNCH(F_L2); else RS_LAUNCH(F_COSINE);
-#undef RS_LAUNCH
-	HIPCHK(hipGetLastError());
-	uint32_t ovf = 0;
-	HIPCHK(hipMemcpyAsync(&ovf, overflow, 4, hipMemcpyDeviceToHost, s));
-	HIPCHK(hipMemcpyAsync(g_last_bf_clocks, a.clocks, 16, hipMemcpyDeviceToHost, s));
-	HIPCHK(hipStreamSynchronize(s));
-	(void) hipEventElapsedTime(&g_last_bf_gemm_ms, e0, e1);
-	if (ovf)      // a candidate list overflowed (bound far too loose for some query): canonical scan instead
-		return hnsw_gpu_bruteforce_dev(ix, d_queries, nq, k, d_idx, d_dists, stream_);
-	ix->bf_form = HNSW_GPU_BF_FORM_F32;
-	return HNSW_GPU_OK;
-}
-
-// ------------------------------------------------------------------------------------
-// exhaustive k-NN with the filter on the 16-bit matrix cores, over the reduced copy (device_bf_mfma16.h)
-// ------------------------------------------------------------------------------------
-// The per-row terms of the bound, brought up to date on `s` after rows16_sync: rows never computed for this format, and rows written since
+// The per-row terms of the 16-bit bound, brought up to date on `s` after rows16_sync: rows never computed for this format, and rows written since
 // (rows16_mark widens r16x_lo / r16x_hi as it widens the copy's dirty range; a reduced search clears only the latter)
 static int r16x_sync(hnsw_gpu_index *ix, hipStream_t s)
 {
@@ -459,55 +237,82 @@ static int r16x_sync(hnsw_gpu_index *ix, hipStream_t s)
 	return HNSW_GPU_OK;
 }
 
-template <int FMT, int WM, int NJ>
-static int bf16_filter_launch(R16Args &a, uint32_t nq, uint32_t n, hipStream_t s)
+// the filter launch for one form and tile shape (LDS per block set per call: the attribute is per device)
+template <class P, int WM, int NJ>
+static int bf_filter_launch(BfArgs &a, hipStream_t s)
 {
-	using T = R16Tile<WM, NJ>;
-	a.nqt = (nq + T::TQ - 1) / T::TQ;
-	a.nrt = (n + T::TR - 1) / T::TR;
+	using T = BfTile<P, WM, NJ>;
+	a.nqt = (a.nq + T::TQ - 1) / T::TQ;
+	a.nrt = (a.n + T::TR - 1) / T::TR;
 	const uint32_t rgroups = (a.nrt + 7) / 8;
-	HIPCHK(hipFuncSetAttribute((const void *) bf16_filter_kernel<FMT, WM, NJ>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) T::LDS_BYTES));
-	hipLaunchKernelGGL((bf16_filter_kernel<FMT, WM, NJ>), dim3(rgroups * a.nqt * 8), dim3(T::THREADS), T::LDS_BYTES, s, a);
+	HIPCHK(hipFuncSetAttribute((const void *) bf_mfma_filter_kernel<P, WM, NJ>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) T::LDS_BYTES));
+	hipLaunchKernelGGL((bf_mfma_filter_kernel<P, WM, NJ>), dim3(rgroups * a.nqt * 8), dim3(T::THREADS), T::LDS_BYTES, s, a);
+	g_last_bf_tile = T::TQ;
 	return HNSW_GPU_OK;
 }
 
-extern "C" int hnsw_gpu_bruteforce_reduced_dev(hnsw_gpu_index *ix, int format, const coord_t *d_queries, size_t nq, size_t k,
-											   idx_t *d_idx, dist_t *d_dists, void *stream_)
+// Both forms of the call: a bound per query from a canonical scan of a sample, the filter over the f32 rows (reduced == false) or over the
+// reduced copy of `format`, the canonical re-score of the survivors.  A form that cannot answer hands the call down: the 16-bit filter to
+// the f32 filter, that one to the canonical scan — the same answer, bit for bit (the filter's survivors are re-scored by that code anyway).
+static int bruteforce_filter(hnsw_gpu_index *ix, bool reduced, int format, const coord_t *d_queries, size_t nq, size_t k, idx_t *d_idx,
+							 dist_t *d_dists, void *stream_)
 {
 	std::unique_lock<std::recursive_mutex> lock_;
 	if (ix) lock_ = std::unique_lock<std::recursive_mutex>(ix->mu);
 	if (!ix || !d_queries || !d_idx) return fail(HNSW_GPU_ERR_ARG, "NULL argument");
-	if ((format != ROWS_F16 && format != ROWS_BF16) || ix->rows_fmt != format || !ix->rows16)
+	if (reduced && ((format != ROWS_F16 && format != ROWS_BF16) || ix->rows_fmt != format || !ix->rows16))
 		return fail(HNSW_GPU_ERR_ARG, "reduced rows: format %d is not the copy this index holds (%d; hnsw_gpu_index_set_reduced_rows)", format, ix->rows_fmt);
 	if (nq == 0) return HNSW_GPU_OK;
 	if (k == 0 || k > 1024) return fail(HNSW_GPU_ERR_ARG, "k %zu out of range [1, 1024]", k);
 	if (nq > 65535) return fail(HNSW_GPU_ERR_ARG, "at most 65535 queries per call");
 	ix->bf_cnt_nq = 0;
 	const int func = (int) ix->meta.dist_func;
-	using Small = R16Tile<BF_WM, BF_NJ>;
-	using Big = R16Tile<4, 4>;
-	// the cases the f32 form answers with the scan get the scan here too (before any launch)
-	if (func == F_MANHATTAN || ix->n < 4096) return hnsw_gpu_bruteforce_dev(ix, d_queries, nq, k, d_idx, d_dists, stream_);
+	auto scan = [&] { return hnsw_gpu_bruteforce_dev(ix, d_queries, nq, k, d_idx, d_dists, stream_); };
+	// the scan's answer, before any launch: not a contraction / too small to matter; a device the filter kernel is not written for (gfx950:
+	// 16-byte direct-to-LDS loads and 69 / 134 KB of LDS per block); a re-score step — a query image and a k-list per wave in LDS — that does not fit
+	if (func == F_MANHATTAN || ix->n < 4096) return scan();
 	HIPCHK(hipSetDevice(ix->device));
-	if (!ix->gfx950 || ix->max_lds < Small::LDS_BYTES) return hnsw_gpu_bruteforce_dev(ix, d_queries, nq, k, d_idx, d_dists, stream_);
+	if (!ix->gfx950 || ix->max_lds < BF_MIN_LDS) return scan();
 	hipStream_t s = (hipStream_t) stream_;
 	const uint32_t n = (uint32_t) ix->n, stride = ix->stride, dim = (uint32_t) ix->meta.dim;
 	const uint32_t nchunks = stride / 4, kiters = (nchunks + 15) / 16;
 	const uint32_t qpadf = (uint32_t) round_up(kiters, 4) * 64;
 	const size_t wave_bytes = round_up((size_t) qpadf * 4 + (k + 1) * 8 + 128 * 4, 16);
 	const size_t lds = wave_bytes * 4;
-	if (lds > 64 * 1024) return hnsw_gpu_bruteforce_dev(ix, d_queries, nq, k, d_idx, d_dists, stream_);
+	if (lds > 64 * 1024) return scan();
 
-	// the copy and the bound's per-row terms, current on this stream
-	int rc = rows16_sync(ix, s);
-	if (!rc) rc = r16x_sync(ix, s);
-	if (rc) return rc;
-	const uint32_t nunits = ix->rows16_bytes / 16;
+	// the rows' side, current on this stream: the reduced copy and the bound's per-row terms, or the |row|^2 cache
+	int rc = HNSW_GPU_OK;
+	if (reduced)
+	{
+		rc = rows16_sync(ix, s);
+		if (!rc) rc = r16x_sync(ix, s);
+		if (rc) return rc;
+	}
+	else
+	{
+		if (ix->xnorm_cap < ix->n)
+		{
+			if (ix->xnorm) (void) hipFree(ix->xnorm);
+			ix->xnorm = nullptr; ix->xnorm_cap = 0; ix->xnorm_n = 0;
+			HIPCHK(hipMalloc(&ix->xnorm, ix->cap * sizeof(float)));
+			ix->xnorm_cap = ix->cap;
+		}
+		if (ix->xnorm_n != ix->n)
+		{
+			hipLaunchKernelGGL(row_norm2_kernel, dim3((n + 3) / 4), dim3(256), 0, s, ix->vec, n, stride, ix->xnorm);
+			ix->xnorm_n = ix->n;
+		}
+	}
+	// 16-byte chunks of the filter's query copy (f32: zero padded to whole K steps; 16-bit: the copy's row) and of a row
+	const uint32_t qchunks = reduced ? ix->rows16_bytes / 16 : (uint32_t) round_up(stride, BF_TK) / 4;
+	const uint32_t rchunks = reduced ? ix->rows16_bytes / 16 : nchunks;
 
 	const uint32_t cap = 16384;
 	const size_t sample = std::min<size_t>(ix->n, std::max<size_t>(8192, (size_t) k * ix->n / 2048));
+	// scratch carve
 	const size_t o_q = 0;
-	const size_t o_qn = o_q + round_up(nq * (size_t) ix->rows16_bytes, 256);
+	const size_t o_qn = o_q + round_up(nq * (size_t) qchunks * 16, 256);
 	const size_t o_qt = o_qn + round_up(nq * 4, 256);
 	const size_t o_sidx = o_qt + round_up(nq * 8, 256);
 	const size_t o_sdist = o_sidx + round_up(nq * k * 4, 256);
@@ -524,107 +329,107 @@ extern "C" int hnsw_gpu_bruteforce_reduced_dev(hnsw_gpu_index *ix, int format, c
 		ix->bf_bytes = total;
 	}
 	char *B = (char *) ix->bf;
-	uint4 *q16 = (uint4 *) (B + o_q);
+	uint4 *qcopy = (uint4 *) (B + o_q);
 	float *qn = (float *) (B + o_qn), *sdist = (float *) (B + o_sdist), *bound = (float *) (B + o_bound);
 	float2 *qterms = (float2 *) (B + o_qt);
 	uint32_t *sidx = (uint32_t *) (B + o_sidx), *cnt = (uint32_t *) (B + o_cnt), *cand = (uint32_t *) (B + o_cand);
 	uint32_t *overflow = cnt + nq;
 
-	// 1. the same bound per query as the f32 form: a canonical scan of the sample rows, then make_bounds_kernel's margin
+	// 1. bound per query from a canonical scan of the sample rows, then make_bounds_kernel's margin (the same in every form)
 	rc = bruteforce_prefix(ix, sample, d_queries, nq, k, sidx, sdist, s);
 	if (rc) return rc;
+	// the queries' side: the filter's copy and |q|^2 (16-bit: and the queries' terms of the bound)
 	const dim3 qgrid((uint32_t) ((nq + 3) / 4));
-	if (format == ROWS_BF16)
-		hipLaunchKernelGGL(r16_query_kernel<ROWS_BF16>, qgrid, dim3(256), 0, s, d_queries, (uint32_t) nq, dim, nunits, q16, qn, qterms);
+	if (!reduced)
+	{
+		const size_t qtot = nq * (size_t) qchunks * 4;
+		hipLaunchKernelGGL(pad_queries_kernel, dim3((uint32_t) ((qtot + 255) / 256)), dim3(256), 0, s, d_queries, (uint32_t) nq, dim, qchunks * 4, (float *) qcopy);
+		hipLaunchKernelGGL(row_norm2_kernel, qgrid, dim3(256), 0, s, (const float *) qcopy, (uint32_t) nq, qchunks * 4, qn);
+	}
+	else if (format == ROWS_BF16)
+		hipLaunchKernelGGL(r16_query_kernel<ROWS_BF16>, qgrid, dim3(256), 0, s, d_queries, (uint32_t) nq, dim, qchunks, qcopy, qn, qterms);
 	else
-		hipLaunchKernelGGL(r16_query_kernel<ROWS_F16>, qgrid, dim3(256), 0, s, d_queries, (uint32_t) nq, dim, nunits, q16, qn, qterms);
+		hipLaunchKernelGGL(r16_query_kernel<ROWS_F16>, qgrid, dim3(256), 0, s, d_queries, (uint32_t) nq, dim, qchunks, qcopy, qn, qterms);
+	// tau_q = sdist[q*k + k-1], gathered with a strided copy into `bound`, which make_bounds_kernel then rewrites in place
 	hipLaunchKernelGGL(fill_u32_kernel, dim3(1), dim3(1), 0, s, overflow, (size_t) 1, 0u);
 	HIPCHK(hipMemcpy2DAsync(bound, 4, sdist + (k - 1), k * 4, 4, nq, hipMemcpyDeviceToDevice, s));
 	hipLaunchKernelGGL(make_bounds_kernel, dim3((uint32_t) ((nq + 255) / 256)), dim3(256), 0, s, bound, qn, (uint32_t) nq, func, dim, bound);
 	HIPCHK(hipMemsetAsync(cnt, 0, nq * 4, s));
 	ix->bf_cnt_off = o_cnt; ix->bf_cnt_nq = nq;
 
-	// 2. the 16-bit contraction + filter
-	R16Args a;
+	// 2. the dense contraction + filter
+	BfArgs a;
 	memset(&a, 0, sizeof(a));
-	a.queries = q16; a.qnorm = qn; a.qbound = bound; a.qterms = qterms; a.rows = (const uint4 *) ix->rows16; a.xterms = ix->r16x;
-	a.nq = (uint32_t) nq; a.n = n; a.nunits = nunits; a.ksteps = nunits / R16_CH; a.func = func;
+	a.queries = qcopy; a.qnorm = qn; a.qbound = bound; a.qterms = qterms;
+	a.rows = reduced ? (const uint4 *) ix->rows16 : (const uint4 *) ix->vec; a.xnorm = ix->xnorm; a.xterms = ix->r16x;
+	a.nq = (uint32_t) nq; a.n = n; a.qchunks = qchunks; a.rchunks = rchunks; a.ksteps = qchunks / BF_CH; a.func = func;
 	a.xscale = 0.5f * (1.f - 2.f * ((float) dim + 32.f) * 0x1p-24f);          // (1 - eD) / 2: make_bounds_kernel
 	a.eabs = r16_abs_term(dim);
 	a.cand = cand; a.cand_cnt = cnt; a.cap = cap; a.clocks = (unsigned long long *) (B + o_clk);
-	HIPCHK(hipMemsetAsync(a.clocks, 0, 16, s));
+	HIPCHK(hipMemsetAsync(a.clocks, 0, 16, s));                  // (written only by a block from the middle of the launch that does not exit early: a small table must not leave stale ticks behind)
 	if (!ix->bf_e0) { HIPCHK(hipEventCreate(&ix->bf_e0)); HIPCHK(hipEventCreate(&ix->bf_e1)); }
 	hipEvent_t e0 = ix->bf_e0, e1 = ix->bf_e1;
 	HIPCHK(hipEventRecord(e0, s));
-	{
-		// the f32 form's rule for the 256 x 256 tile (and its test knob), where the device has the LDS for it
+	// 256 x 256 tiles when they compute no more padding than 128 x 128 tiles would (an even number of 128-query tiles), there are tiles
+	// enough to fill the device several times over and the device has the LDS for them; the same dot products in the same k order either
+	// way: the same survivors
+	rc = with_form(format, [&](auto p) {
+		using P = decltype(p);
+		using Small = BfTile<P, BF_SMALL_WM, BF_SMALL_NJ>;
+		using Big = BfTile<P, BF_BIG_WM, BF_BIG_NJ>;
+		static_assert(Small::LDS_BYTES <= BF_MIN_LDS, "the 128 x 128 tile must fit where the call does not fall back");
 		const uint64_t nqt_s = (nq + Small::TQ - 1) / Small::TQ;
 		const uint64_t big_blocks = ((nq + Big::TQ - 1) / Big::TQ) * ((n + Big::TR - 1) / Big::TR);
+		// (test knob: 0 = never, < 0 = always, n = at least n blocks; the tests run every case through both tiles)
 		const long long min_blocks = knob(K_BF_BIG_MIN_BLOCKS, 2048);
-		const bool big = ix->max_lds >= Big::LDS_BYTES && min_blocks != 0 &&
-						 (min_blocks < 0 || (nqt_s % 2 == 0 && big_blocks >= (uint64_t) min_blocks));
-		if (format == ROWS_BF16)
-			rc = big ? bf16_filter_launch<ROWS_BF16, 4, 4>(a, (uint32_t) nq, n, s) : bf16_filter_launch<ROWS_BF16, BF_WM, BF_NJ>(a, (uint32_t) nq, n, s);
-		else
-			rc = big ? bf16_filter_launch<ROWS_F16, 4, 4>(a, (uint32_t) nq, n, s) : bf16_filter_launch<ROWS_F16, BF_WM, BF_NJ>(a, (uint32_t) nq, n, s);
-		if (rc) return rc;
-		g_last_bf_tile = big ? Big::TQ : Small::TQ;
-	}
+		const bool big = ix->max_lds >= Big::LDS_BYTES && min_blocks != 0 && (min_blocks < 0 || (nqt_s % 2 == 0 && big_blocks >= (uint64_t) min_blocks));
+		return big ? bf_filter_launch<P, BF_BIG_WM, BF_BIG_NJ>(a, s) : bf_filter_launch<P, BF_SMALL_WM, BF_SMALL_NJ>(a, s);
+	});
+	if (rc) return rc;
 	HIPCHK(hipEventRecord(e1, s));
 
 	// 3. canonical re-score of the survivors against the fp32 rows
-#define RS_LAUNCH(F)                                                                                                      \
-	hipLaunchKernelGGL(bf_rescore_kernel<F>, dim3((uint32_t) ((nq + 3) / 4)), dim3(256), lds, s, ix->vec, dim, stride,      \
-					   nchunks, kiters, qpadf, d_queries, (uint32_t) nq, cand, cnt, cap, (uint32_t) k, d_idx, d_dists, overflow)
-	if (func == F_L2) RS_LAUNCH(F_L2); else RS_LAUNCH(F_COSINE);
-#undef RS_LAUNCH
+	with_func(func, [&](auto F) {
+		if constexpr (decltype(F)::value != F_MANHATTAN)           // (answered by the scan above: no re-score kernel is compiled for it)
+			hipLaunchKernelGGL(bf_rescore_kernel<decltype(F)::value>, dim3((uint32_t) ((nq + 3) / 4)), dim3(256), lds, s, ix->vec, dim, stride, nchunks, kiters,
+							   qpadf, d_queries, (uint32_t) nq, cand, cnt, cap, (uint32_t) k, d_idx, d_dists, overflow);
+	});
 	HIPCHK(hipGetLastError());
 	uint32_t ovf = 0;
 	HIPCHK(hipMemcpyAsync(&ovf, overflow, 4, hipMemcpyDeviceToHost, s));
 	HIPCHK(hipMemcpyAsync(g_last_bf_clocks, a.clocks, 16, hipMemcpyDeviceToHost, s));
 	HIPCHK(hipStreamSynchronize(s));
 	(void) hipEventElapsedTime(&g_last_bf_gemm_ms, e0, e1);
-	if (ovf)      // the 16-bit bound is looser: a list that overflowed here may not in f32 (which falls back to the scan in turn)
-		return hnsw_gpu_bruteforce_mfma_dev(ix, d_queries, nq, k, d_idx, d_dists, stream_);
-	ix->bf_form = format == ROWS_BF16 ? HNSW_GPU_BF_FORM_BF16 : HNSW_GPU_BF_FORM_F16;
+	// a candidate list overflowed (bound far too loose for some query).  The 16-bit bound is looser: a list that overflowed there may not
+	// in f32, which ends in the canonical scan in turn
+	if (ovf) return reduced ? bruteforce_filter(ix, false, ROWS_F32, d_queries, nq, k, d_idx, d_dists, stream_) : scan();
+	ix->bf_form = !reduced ? HNSW_GPU_BF_FORM_F32 : format == ROWS_BF16 ? HNSW_GPU_BF_FORM_BF16 : HNSW_GPU_BF_FORM_F16;
 	return HNSW_GPU_OK;
+}
+
+extern "C" int hnsw_gpu_bruteforce_mfma_dev(hnsw_gpu_index *ix, const coord_t *d_queries, size_t nq, size_t k,
+											idx_t *d_idx, dist_t *d_dists, void *stream)
+{
+	return bruteforce_filter(ix, false, ROWS_F32, d_queries, nq, k, d_idx, d_dists, stream);
+}
+
+extern "C" int hnsw_gpu_bruteforce_reduced_dev(hnsw_gpu_index *ix, int format, const coord_t *d_queries, size_t nq, size_t k,
+											   idx_t *d_idx, dist_t *d_dists, void *stream)
+{
+	return bruteforce_filter(ix, true, format, d_queries, nq, k, d_idx, d_dists, stream);
 }
 
 // ------------------------------------------------------------------------------------
 // exact filtered k-NN: the canonical scan over the allowed rows only (device_filtered_knn.h)
 // ------------------------------------------------------------------------------------
-static const size_t FK_KEEP_BYTES = (size_t) 64 << 20;        // a buffer larger than this does not outlive its call (as the index scan's)
 static const size_t FK_PART_BYTES = (size_t) 1 << 30;         // the partial lists of a call: more splits are not worth more memory than this
 
 void fk_ws_free(FkWs *s)
 {
-	ScanBuf *all[] = {&s->cells, &s->list, &s->part};
-	for (ScanBuf *b : all) { if (b->p) (void) hipFree(b->p); b->p = nullptr; b->bytes = 0; }
+	buf_trim({&s->cells, &s->list, &s->part}, 0);
 	if (s->host) (void) hipHostFree(s->host);
 	s->host = nullptr;
 	for (hipEvent_t &e : s->ev) { if (e) (void) hipEventDestroy(e); e = nullptr; }
-}
-
-static int fk_buf(ScanBuf *b, size_t bytes, const char *what)
-{
-	if (bytes <= b->bytes) return HNSW_GPU_OK;
-	if (b->p) (void) hipFree(b->p);
-	b->p = nullptr; b->bytes = 0;
-	if (hipMalloc(&b->p, bytes) != hipSuccess)
-	{
-		b->p = nullptr;
-		(void) hipGetLastError();
-		return fail(HNSW_GPU_ERR_NOMEM, "filtered k-NN: no room for %s (%zu bytes)", what, bytes);
-	}
-	b->bytes = bytes;
-	return HNSW_GPU_OK;
-}
-
-static void fk_trim(FkWs *s)
-{
-	ScanBuf *all[] = {&s->cells, &s->list, &s->part};
-	for (ScanBuf *b : all)
-		if (b->bytes > FK_KEEP_BYTES) { (void) hipFree(b->p); b->p = nullptr; b->bytes = 0; }
 }
 
 // the caller's contract, checked before anything is launched or copied (the outputs stay untouched)
@@ -655,7 +460,7 @@ extern "C" int hnsw_gpu_filtered_knn_dev(hnsw_gpu_index *ix, const coord_t *d_qu
 	HIPCHK(hipSetDevice(ix->device));
 	hipStream_t s = (hipStream_t) stream;
 	FkWs *fw = &ix->fk;
-	struct Trim { FkWs *w; ~Trim() { fk_trim(w); } } trim_{fw};   // on EVERY way out, errors included: no buffer above 64 MiB outlives its call
+	struct Trim { FkWs *w; ~Trim() { buf_trim({&w->cells, &w->list, &w->part}); } } trim_{fw};   // on EVERY way out, errors included: no buffer above 64 MiB outlives its call
 	if (!fw->host) HIPCHK(hipHostMalloc((void **) &fw->host, 64, hipHostMallocDefault));
 	for (hipEvent_t &e : fw->ev)
 		if (!e) HIPCHK(hipEventCreate(&e));
@@ -667,7 +472,7 @@ extern "C" int hnsw_gpu_filtered_knn_dev(hnsw_gpu_index *ix, const coord_t *d_qu
 	const size_t ncells = (size_t) nseg * nfilters, nsb = (nseg + 3) / 4;
 	if (nsb * nfilters >= 0x7FFFFFFFull) return fail(HNSW_GPU_ERR_ARG, "filtered k-NN: %zu filters over %zu rows are too many for one call", nfilters, n);
 	const size_t o_off = round_up(ncells * 4, 256), o_scored = o_off + round_up((ncells + 1) * 8, 256);
-	int rc = fk_buf(&fw->cells, o_scored + 256, "the list offsets");
+	int rc = buf_reserve(&fw->cells, o_scored + 256, "filtered k-NN", "the list offsets");
 	if (rc) return rc;
 	uint32_t *cells = (uint32_t *) fw->cells.p;
 	uint64_t *off = (uint64_t *) ((char *) fw->cells.p + o_off);
@@ -684,7 +489,7 @@ extern "C" int hnsw_gpu_filtered_knn_dev(hnsw_gpu_index *ix, const coord_t *d_qu
 	HIPCHK(hipStreamSynchronize(s));                              // the one wait before the scan: the lists are sized exactly
 	const size_t total = fw->host[0], longest = fw->host[1];
 	if (longest > n || total > n * nfilters) return fail(HNSW_GPU_ERR_INTERNAL, "filtered k-NN: %zu listed rows, longest list %zu, of %zu rows", total, longest, n);
-	if ((rc = fk_buf(&fw->list, total * 4, "the lists of allowed rows"))) return rc;
+	if ((rc = buf_reserve(&fw->list, total * 4, "filtered k-NN", "the lists of allowed rows"))) return rc;
 	if (total) hipLaunchKernelGGL(fk_fill_kernel, dim3((uint32_t) (nsb * nfilters)), dim3(256), 0, s, fl, (const uint64_t *) off, (uint32_t *) fw->list.p);
 	HIPCHK(hipMemsetAsync(scored, 0, 8, s));
 	HIPCHK(hipEventRecord(fw->ev[1], s));
@@ -695,7 +500,7 @@ extern "C" int hnsw_gpu_filtered_knn_dev(hnsw_gpu_index *ix, const coord_t *d_qu
 	if (FK_XCD_REMAP && longest >= 8192) splits = std::max(splits, 8u);
 	splits = (uint32_t) std::min<size_t>(splits, std::max<size_t>(1, longest / (4 * FK_WAVE_ROWS)));
 	while (splits > 1 && nq * splits * 4 * k * 8 > FK_PART_BYTES) splits /= 2;
-	if (longest && (rc = fk_buf(&fw->part, nq * splits * 4 * k * 8, "the partial result lists"))) return rc;   // (no list, no scan: the emit kernel reads no partial list)
+	if (longest && (rc = buf_reserve(&fw->part, nq * splits * 4 * k * 8, "filtered k-NN", "the partial result lists"))) return rc;   // (no list, no scan: the emit kernel reads no partial list)
 	const uint32_t nchunks = ix->stride / 4, kiters = (nchunks + 15) / 16;
 	FkEmit fe;
 	memset(&fe, 0, sizeof(fe));
@@ -710,12 +515,7 @@ extern "C" int hnsw_gpu_filtered_knn_dev(hnsw_gpu_index *ix, const coord_t *d_qu
 	const size_t lds = (size_t) fs.qpad_floats * 4 + (size_t) 4 * (k + 1) * 8 + 4 * 128 * 4 + 4 * 64 * 4;
 	const dim3 grid((uint32_t) round_up((size_t) splits * nq, 8));
 	if (longest)
-		switch ((int) ix->meta.dist_func)
-		{
-			case F_L2: hipLaunchKernelGGL(fk_scan_kernel<F_L2>, grid, dim3(256), lds, s, fs); break;
-			case F_COSINE: hipLaunchKernelGGL(fk_scan_kernel<F_COSINE>, grid, dim3(256), lds, s, fs); break;
-			default: hipLaunchKernelGGL(fk_scan_kernel<F_MANHATTAN>, grid, dim3(256), lds, s, fs); break;
-		}
+		with_func((int) ix->meta.dist_func, [&](auto F) { hipLaunchKernelGGL(fk_scan_kernel<decltype(F)::value>, grid, dim3(256), lds, s, fs); });
 	// 3. merge + emit
 	hipLaunchKernelGGL(fk_emit_kernel, dim3((uint32_t) nq), dim3(64), k * 16, s, fe);
 	hipError_t e = hipGetLastError();
@@ -806,4 +606,3 @@ extern "C" double hnsw_gpu_last_bruteforce_clock_mhz(void)
 		khz = 100000;
 	return g_last_bf_clocks[1] ? khz * 1e-3 * (double) g_last_bf_clocks[0] / (double) g_last_bf_clocks[1] : 0.0;
 }
-

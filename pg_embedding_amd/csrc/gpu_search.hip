@@ -1133,37 +1133,12 @@ extern "C" int hnsw_gpu_search_batch_ctx_flags(hnsw_gpu_ctx *c, const coord_t *d
 // plain batch path, locality order of large batches included), the hand-out kernel takes each row into the query's scan state, the
 // compaction kernel lists the queries that go on, the host reads their number (the one wait of a round) and the next round searches
 // only those, gathered, at twice the width.  The walk kernels are the search's own; nothing here changes what a search returns.
-static const size_t SCAN_KEEP_BYTES = (size_t) 64 << 20;      // a buffer larger than this does not outlive its call
-
 void scan_ws_free(ScanWs *s)
 {
-	ScanBuf *all[] = {&s->rows, &s->tab[0], &s->tab[1], &s->q, &s->state, &s->act[0], &s->act[1]};
-	for (ScanBuf *b : all) { if (b->p) (void) hipFree(b->p); b->p = nullptr; b->bytes = 0; }
+	buf_trim({&s->rows, &s->tab[0], &s->tab[1], &s->q, &s->state, &s->act[0], &s->act[1]}, 0);
 	if (s->host) (void) hipHostFree(s->host);
 	s->host = nullptr;
 	for (hipEvent_t &e : s->ev) { if (e) (void) hipEventDestroy(e); e = nullptr; }
-}
-
-static int scan_buf(ScanBuf *b, size_t bytes, const char *what)
-{
-	if (bytes <= b->bytes) return HNSW_GPU_OK;
-	if (b->p) (void) hipFree(b->p);                           // (waits for the launches still using it)
-	b->p = nullptr; b->bytes = 0;
-	if (hipMalloc(&b->p, bytes) != hipSuccess)
-	{
-		b->p = nullptr;
-		(void) hipGetLastError();
-		return fail(HNSW_GPU_ERR_NOMEM, "index scan: no room for %s (%zu bytes)", what, bytes);
-	}
-	b->bytes = bytes;
-	return HNSW_GPU_OK;
-}
-
-static void scan_trim(ScanWs *s)
-{
-	ScanBuf *all[] = {&s->rows, &s->tab[0], &s->tab[1], &s->q, &s->state, &s->act[0], &s->act[1]};
-	for (ScanBuf *b : all)
-		if (b->bytes > SCAN_KEEP_BYTES) { (void) hipFree(b->p); b->p = nullptr; b->bytes = 0; }
 }
 
 // the caller's contract, checked before anything is launched or copied (the outputs stay untouched)
@@ -1197,7 +1172,7 @@ extern "C" int hnsw_gpu_scan_batch_dev(hnsw_gpu_index *ix, const coord_t *d_quer
 	const size_t dim = ix->meta.dim, n = std::max<size_t>(ix->n, 1);
 	if (!sw->host) HIPCHK(hipHostMalloc((void **) &sw->host, 64, hipHostMallocDefault));
 	// state of the call: hlen | slot_of | finished | the device's copy of the active count | the stats when the caller wants none
-	int rc = scan_buf(&sw->state, (3 * nq + 64 + (d_scan_stats ? 0 : 4 * nq)) * 4, "the scan state");
+	int rc = buf_reserve(&sw->state, (3 * nq + 64 + (d_scan_stats ? 0 : 4 * nq)) * 4, "index scan", "the scan state");
 	if (rc) return rc;
 	uint32_t *hlen = (uint32_t *) sw->state.p, *slot_of = hlen + nq, *finished = slot_of + nq, *d_count = finished + nq;
 	uint32_t *stats = d_scan_stats ? d_scan_stats : d_count + 64;
@@ -1224,9 +1199,9 @@ extern "C" int hnsw_gpu_scan_batch_dev(hnsw_gpu_index *ix, const coord_t *d_quer
 		if (cap > 0x80000000ull) { rc = fail(HNSW_GPU_ERR_NOMEM, "index scan: a membership table of %zu slots", cap); break; }
 		const size_t lb = round_up(nact * ef * 8, 256), db = round_up(nact * ef * 4, 256), cb = round_up(nact * 4, 256);
 		ScanBuf *tb = &sw->tab[round & 1], *ab = &sw->act[round & 1];
-		if ((rc = scan_buf(&sw->rows, lb + db + cb, "a round's result rows"))) break;
-		if ((rc = scan_buf(tb, nact * cap * 8, "a round's membership tables"))) break;
-		if ((rc = scan_buf(ab, nact * 4, "the list of active queries"))) break;
+		if ((rc = buf_reserve(&sw->rows, lb + db + cb, "index scan", "a round's result rows"))) break;
+		if ((rc = buf_reserve(tb, nact * cap * 8, "index scan", "a round's membership tables"))) break;
+		if ((rc = buf_reserve(ab, nact * 4, "index scan", "the list of active queries"))) break;
 		uint64_t *rl = (uint64_t *) sw->rows.p;
 		float *rd = (float *) ((char *) sw->rows.p + lb);
 		uint32_t *rcnt = (uint32_t *) ((char *) sw->rows.p + lb + db);
@@ -1258,7 +1233,7 @@ extern "C" int hnsw_gpu_scan_batch_dev(hnsw_gpu_index *ix, const coord_t *d_quer
 		if (next == 0) break;
 		if (next > nact) { rc = fail(HNSW_GPU_ERR_INTERNAL, "index scan: %zu active queries out of %zu", next, nact); break; }
 		if (ef * 2 >= 0xFFFFFFFFull) { rc = fail(HNSW_GPU_ERR_ARG, "index scan: the doubled ef %zu is out of range", ef * 2); break; }
-		if ((rc = scan_buf(&sw->q, next * dim * 4, "the active queries"))) break;
+		if ((rc = buf_reserve(&sw->q, next * dim * 4, "index scan", "the active queries"))) break;
 		hipLaunchKernelGGL(scan_gather_kernel, dim3((uint32_t) ((next + SCAN_WPB - 1) / SCAN_WPB)), dim3(SCAN_WPB * 64), 0, s, d_queries, (uint32_t) dim,
 						   (const uint32_t *) ab->p, (uint32_t) next, (float *) sw->q.p);
 		act = (const uint32_t *) ab->p; qs = (const float *) sw->q.p;
@@ -1272,7 +1247,7 @@ extern "C" int hnsw_gpu_scan_batch_dev(hnsw_gpu_index *ix, const coord_t *d_quer
 		(void) hipEventElapsedTime(&sw->r_search_ms[r], sw->ev[3 * r], sw->ev[3 * r + 1]);
 		(void) hipEventElapsedTime(&sw->r_handout_ms[r], sw->ev[3 * r + 1], sw->ev[3 * r + 2]);
 	}
-	scan_trim(sw);
+	buf_trim({&sw->rows, &sw->tab[0], &sw->tab[1], &sw->q, &sw->state, &sw->act[0], &sw->act[1]});
 	return rc;
 }
 

@@ -252,6 +252,28 @@ int ensure_scratch(hnsw_gpu_index *ix, size_t bytes)
 	return HNSW_GPU_OK;
 }
 
+// grow-on-demand buffers of the batched index scan and of filtered k-NN (gpu_host.h)
+int buf_reserve(ScanBuf *b, size_t bytes, const char *who, const char *what)
+{
+	if (bytes <= b->bytes) return HNSW_GPU_OK;
+	if (b->p) (void) hipFree(b->p);                           // (waits for the launches still using it)
+	b->p = nullptr; b->bytes = 0;
+	if (hipMalloc(&b->p, bytes) != hipSuccess)
+	{
+		b->p = nullptr;
+		(void) hipGetLastError();
+		return fail(HNSW_GPU_ERR_NOMEM, "%s: no room for %s (%zu bytes)", who, what, bytes);
+	}
+	b->bytes = bytes;
+	return HNSW_GPU_OK;
+}
+
+void buf_trim(std::initializer_list<ScanBuf *> bufs, size_t keep)
+{
+	for (ScanBuf *b : bufs)
+		if (b->p && b->bytes > keep) { (void) hipFree(b->p); b->p = nullptr; b->bytes = 0; }
+}
+
 static int check_meta(const HnswMetadata *m)
 {
 	if (!m) return fail(HNSW_GPU_ERR_ARG, "meta is NULL");
