@@ -248,6 +248,24 @@ int hnsw_gpu_filtered_knn(hnsw_gpu_index *ix, const coord_t *queries, size_t nq,
 						  const uint32_t *allow, size_t allow_bits, size_t nfilters, const uint32_t *allow_of,
 						  label_t *labels, dist_t *dists, idx_t *idx, uint32_t *counts);
 
+/* hnsw_gpu_filtered_knn_dev's answer, bit for bit, for LOOSE filters (a pass rate of about 1/10 and looser: DESIGN 4.11b has the measured
+ * table): the Q x N part runs on the matrix cores (csrc/device_filtered_knn_mfma.h).  Every row is scored against every query by the MFMA
+ * filter of hnsw_gpu_bruteforce_mfma_dev (format = HNSW_GPU_ROWS_F32) or of hnsw_gpu_bruteforce_reduced_dev (format = HNSW_GPU_ROWS_F16 /
+ * _BF16: the reduced copy the index holds, else HNSW_GPU_ERR_ARG before any launch), against a bound from a canonical scan of the first
+ * rows of the query's OWN allowed list; a pair within the bound is kept only if the row is in A(b); the survivors are re-scored and ranked
+ * by the canonical code.  Same filter convention, selection, order, counts, tails and argument rules as hnsw_gpu_filtered_knn_dev.
+ * Manhattan, fewer than 4096 rows, a device other than gfx950, a (dim, k) whose re-score does not fit, a call whose lists are all short
+ * enough to be scanned whole, and a candidate list that overflows (16-bit -> f32 -> listed) are answered by the listed form: the same
+ * bytes.  hnsw_gpu_last_filtered_knn_form (hnsw_gpu_diag.h) names the form that answered.  There is no automatic choice between the two
+ * calls.  Memory: one bit per row and bitmap, and 64 KiB of candidates per query, kept in the mirror up to 64 MiB each. */
+int hnsw_gpu_filtered_knn_mfma_dev(hnsw_gpu_index *ix, int format, const coord_t *d_queries, size_t nq, size_t k,
+								   const uint32_t *d_allow, size_t allow_bits, size_t nfilters, const uint32_t *d_allow_of,
+								   label_t *d_labels, dist_t *d_dists, idx_t *d_idx, uint32_t *d_counts, void *stream);
+/* Host-pointer form: copies in, runs on the default stream, copies out. */
+int hnsw_gpu_filtered_knn_mfma(hnsw_gpu_index *ix, int format, const coord_t *queries, size_t nq, size_t k,
+							   const uint32_t *allow, size_t allow_bits, size_t nfilters, const uint32_t *allow_of,
+							   label_t *labels, dist_t *dists, idx_t *idx, uint32_t *counts);
+
 /* Milliseconds the most recent search kernel of this index spent on the device,
  * from HIP events recorded on its stream around the launch (waits for it). */
 int hnsw_gpu_last_search_ms(hnsw_gpu_index *ix, float *ms);

@@ -110,8 +110,21 @@ int hnsw_gpu_last_scan_rounds(hnsw_gpu_index *ix, uint32_t *rounds, uint32_t *ac
 /* The mirror's last hnsw_gpu_filtered_knn[_dev] call: out[0] = entries of all allowed lists together (sum over the bitmaps b of |A(b)|),
  * out[1] = rows the scan kernel scored (every wave adds its slice's length: equal to the sum over the queries q of |A(b(q))|, and NOT
  * nq * n — the call reads the allowed rows only), out[2] = the list build and out[3] = scan + merge + emit, both in MICROSECONDS from
- * HIP events on the call's stream (the list build includes the call's wait for the lists' total size).  Zeros before the first call. */
+ * HIP events on the call's stream (the list build includes the call's wait for the lists' total size).  Zeros before the first call.
+ * After a call that the matrix-core form answered: out[1] = the rows of the sample scans, out[2] includes the row masks, out[3] = the rest. */
 int hnsw_gpu_last_filtered_knn(hnsw_gpu_index *ix, uint64_t out[4]);
+
+/* The form that answered the mirror's last filtered k-NN call of either entry point (hnsw_gpu_filtered_knn[_dev], _mfma[_dev]): the listed
+ * scan, or the MFMA filter over f32 / fp16 / bf16 operands.  -1 before the first such call (and for a NULL index). */
+enum { HNSW_GPU_FK_FORM_LISTED = 0, HNSW_GPU_FK_FORM_F32 = 1, HNSW_GPU_FK_FORM_F16 = 2, HNSW_GPU_FK_FORM_BF16 = 3 };
+int hnsw_gpu_last_filtered_knn_form(hnsw_gpu_index *ix);
+/* The last filter launch of the mirror's last hnsw_gpu_filtered_knn_mfma[_dev] call (zeros when that call, or a listed call since, ran no
+ * filter; the last attempt's figures when a candidate list overflowed and another form answered): out[0] = sum over the bitmaps b of
+ * |A(b)|, out[1] = rows scored canonically for the bounds (the sample scans), out[2] = dist_pass: (query, row) pairs with q < nq and
+ * r < n that passed the filter's distance comparison, counted BEFORE the allow test, out[3] = appended: those that also passed the allow
+ * test and went to a candidate list, out[4] = list build + row masks, out[5] = the filter kernel, out[6] = the whole call, all three
+ * in MICROSECONDS from HIP events on the call's stream. */
+int hnsw_gpu_last_filtered_knn_mfma(hnsw_gpu_index *ix, uint64_t out[7]);
 
 #ifdef __cplusplus
 }

@@ -101,6 +101,10 @@ struct BfArgs
 	uint32_t cap;
 	uint32_t nqt, nrt;         // tiles
 	unsigned long long *clocks; // NULL, or 2 words: shader-clock and constant-clock ticks one block spent in its K loop (measurement only)
+	// policies with ALLOW (exact filtered k-NN, device_filtered_knn_mfma.h): one bit per row and mask row, mwords words apart; the mask row
+	// of every query; two launch-wide counters: pairs that passed the comparison, pairs that passed the allow test as well
+	const uint32_t *mask, *mask_of; uint32_t mwords;
+	unsigned long long *fcnt;
 };
 
 // The operand policy of the f32 form (the 16-bit one: Bf16<FMT>, device_bf_mfma16.h).  A policy says
@@ -110,9 +114,11 @@ struct BfArgs
 //   Row            its own per-row epilogue operands, one per MFMA column of the lane (row_operands, which returns |x|^2)
 //   step           the MFMAs of one 16-byte LDS operand per tile row
 //   value          what the comparisons use in place of the dot product;  keep: a dot that passes whatever the comparison says
+//   ALLOW          whether a passing pair is tested against the query's row mask before it is appended (BfAllow<P>, device_filtered_knn_mfma.h)
 struct BfF32
 {
 	static constexpr int FMT = ROWS_F32;
+	static constexpr bool ALLOW = false;
 	static constexpr bool CLAMP = true;
 	static constexpr int EPI_Q = 2;
 	struct Row {};
@@ -135,11 +141,25 @@ struct BfF32
 	__device__ static __forceinline__ bool keep(float) { return false; }
 };
 
-// a passing (query, row) pair -> the query's candidate list (the host sees a list that overflowed its cap in the count)
-__device__ __forceinline__ void bf_append(const BfArgs &a, uint32_t q, uint32_t r)
+// a passing (query, row) pair -> the query's candidate list (the host sees a list that overflowed its cap in the count).  ALLOW: only if
+// the row's bit is set in the query's mask row (q < nq, r < n: one bit of one word); returns whether the pair went to the list
+template <bool ALLOW>
+__device__ __forceinline__ bool bf_append(const BfArgs &a, uint32_t q, uint32_t r)
 {
+	if (ALLOW)
+	{
+		const uint32_t w = a.mask[(size_t) a.mask_of[q] * a.mwords + (r >> 5)];
+		if (!((w >> (r & 31u)) & 1u)) return false;
+	}
 	const uint32_t pos = atomicAdd(&a.cand_cnt[q], 1u);
 	if (pos < a.cap) a.cand[(size_t) q * a.cap + pos] = r;
+	return true;
+}
+// a block's or a wave's share of the two counters of an ALLOW launch: one vector atomic each, by one lane, at its end
+__device__ __forceinline__ void bf_count(const BfArgs &a, uint32_t dist_pass, uint32_t appended)
+{
+	atomicAdd(a.fcnt, (unsigned long long) dist_pass);
+	atomicAdd(a.fcnt + 1, (unsigned long long) appended);
 }
 
 template <class P, int WM, int NJ>
@@ -188,6 +208,8 @@ __global__ __launch_bounds__(128 * WM, WM == 2 ? 2 : 1) void bf_mfma_filter_kern
 	uint32_t *pass_cnt = reinterpret_cast<uint32_t *>(epi + EPI_WORDS);
 	uint2 *pass_list = reinterpret_cast<uint2 *>(epi + EPI_WORDS + 4);
 	if (t == 0) *pass_cnt = 0u;
+	if constexpr (P::ALLOW)
+		if (t == 0) pass_cnt[1] = 0u;                                   // pairs of the block that passed the allow test
 	if (t < TQ)
 	{
 		const uint32_t qi = min(q0 + (uint32_t) t, a.nq - 1);
@@ -307,7 +329,7 @@ __global__ __launch_bounds__(128 * WM, WM == 2 ? 2 : 1) void bf_mfma_filter_kern
 					{
 						const uint32_t slot = atomicAdd(pass_cnt, 1u);      // (LDS)
 						if (slot < (uint32_t) BF_PASS_CAP) pass_list[slot] = make_uint2(q, r);
-						else bf_append(a, q, r);                          // a block with more passes than the list holds: straight to the global list
+						else if (bf_append<P::ALLOW>(a, q, r) && P::ALLOW) atomicAdd(pass_cnt + 1, 1u);   // a block with more passes than the list holds: straight to the global list
 					}
 				}
 			}
@@ -317,7 +339,12 @@ __global__ __launch_bounds__(128 * WM, WM == 2 ? 2 : 1) void bf_mfma_filter_kern
 	for (uint32_t i = (uint32_t) t; i < npass; i += THREADS)
 	{
 		const uint2 e = pass_list[i];
-		bf_append(a, e.x, e.y);
+		if (bf_append<P::ALLOW>(a, e.x, e.y) && P::ALLOW) atomicAdd(pass_cnt + 1, 1u);
+	}
+	if constexpr (P::ALLOW)
+	{
+		__syncthreads();
+		if (t == 0) bf_count(a, pass_cnt[0], pass_cnt[1]);              // (pass_cnt[0] counts every pair that passed the comparison, listed in LDS or not)
 	}
 }
 

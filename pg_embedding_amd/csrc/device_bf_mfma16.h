@@ -178,6 +178,7 @@ template <int FMT_>
 struct Bf16
 {
 	static constexpr int FMT = FMT_;
+	static constexpr bool ALLOW = false;
 	static constexpr bool CLAMP = false;                      // a reduced row is a whole number of K steps
 	static constexpr int EPI_Q = 4;                           // bound, |q|^2 (halved for L2), rq', |q~|'
 	struct Row { float xl, ex; };                             // |x|', ex'

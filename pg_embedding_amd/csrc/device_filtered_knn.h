@@ -136,6 +136,14 @@ __global__ __launch_bounds__(256) void fk_fill_kernel(const FkLists a, const uin
 	}
 }
 
+// The sample of a list of `len` entries (the matrix-core form's bound, device_filtered_knn_mfma.h): its first min(len, max(smin, k len / 2048))
+// entries — the exhaustive filter's sample rule (bruteforce_filter, gpu_scan.hip) applied to the list
+__host__ __device__ inline uint32_t fk_sample_len(uint32_t len, uint32_t smin, uint32_t k)
+{
+	const uint64_t prop = (uint64_t) k * len / 2048u, s = prop > smin ? prop : smin;
+	return s < len ? (uint32_t) s : len;
+}
+
 struct FkScan
 {
 	const float *vec; uint32_t dim, stride, nchunks, kiters, qpad_floats;
@@ -143,6 +151,7 @@ struct FkScan
 	const uint32_t *list; const uint64_t *off; uint32_t nseg; const uint32_t *allow_of;
 	uint64_t *part;                  // [nq][splits * 4][k] ascending keys, ~0 = none
 	unsigned long long *scored;      // rows scored by the call (one atomic per wave)
+	uint32_t smin;                   // 0: a query's whole list; else only its sample (fk_sample_len)
 };
 
 // the waves query qi scans with, out of the launch's splits * 4, from the length of its own list
@@ -157,6 +166,7 @@ __device__ __forceinline__ void fk_list_of(const FkScan &a, uint32_t qi, const u
 	const uint64_t o = a.off[(size_t) b * a.nseg];
 	list = a.list + o;
 	len = (uint32_t) (a.off[(size_t) (b + 1) * a.nseg] - o);          // (a list is a subset of the < 2^32 elements)
+	if (a.smin) len = fk_sample_len(len, a.smin, a.k);
 }
 
 // grid = splits * nq blocks (rounded up to 8), 4 waves each.  Block order: query number fastest within a split, so the blocks resident at
@@ -198,6 +208,7 @@ __global__ __launch_bounds__(256) void fk_scan_kernel(const FkScan a)
 struct FkEmit
 {
 	FkScan s;
+	const uint64_t *single;          // NULL, or [nq][k]: every query's keys as ONE ascending list (~0 = none) in place of its partial lists
 	const uint64_t *labels; uint32_t n;
 	uint64_t *out_labels; float *out_dists; uint32_t *out_idx; uint32_t *out_counts;
 };
@@ -210,10 +221,11 @@ __global__ __launch_bounds__(64) void fk_emit_kernel(const FkEmit a)
 	uint64_t *win = reinterpret_cast<uint64_t *>(smem), *lab = win + k;
 	const uint32_t *list; uint32_t len;
 	fk_list_of(a.s, qi, list, len);
-	const uint32_t nlists = fk_waves(len, a.s.splits);
+	const uint32_t nlists = a.single ? 1u : fk_waves(len, a.s.splits);
+	const uint64_t *src = a.single ? a.single + (size_t) qi * k : a.s.part + (size_t) qi * a.s.splits * 4u * k;
 	const uint32_t cnt = min(k, len);                                 // every listed row was scored: the merge finds min(k, |A|) keys
 	// 1. the key merge over the lists this query's waves wrote (one element, one key: merge_ranks)
-	merge_ranks(a.s.part + (size_t) qi * a.s.splits * 4u * k, nlists, k, (int) lane, [win](uint32_t rank, uint64_t key) { win[rank] = key; });
+	merge_ranks(src, nlists, k, (int) lane, [win](uint32_t rank, uint64_t key) { win[rank] = key; });
 	wave_sync();
 	// 2. the winners' labels
 	for (uint32_t i = lane; i < cnt; i += 64) lab[i] = a.labels[min((uint32_t) win[i], a.n - 1u)];

@@ -5,7 +5,7 @@
 //   hnsw_gpu.hip      errors, configuration, workspaces + watchdog, the mirror (create / import / export / append / reserve)
 //   gpu_search.hip    launch planning (launch_search), the search entry points, traces of one walk, search contexts
 //   gpu_stream.hip    streams: one resident launch fed by the host
-//   gpu_scan.hip      batched distances, exhaustive k-NN (canonical scan, MFMA filter in three operand forms), exact filtered k-NN over allowed lists
+//   gpu_scan.hip      batched distances, exhaustive k-NN (canonical scan, MFMA filter in three operand forms), exact filtered k-NN (listed scan, MFMA filter with an allow test)
 //   gpu_build.hip     insert path: batched link step, single inserts
 //   gpu_sharded.hip   top-k merge, shards in one process, the exchange buffer shared between processes
 //   gpu_diag.hip      measurement only (include/hnsw_gpu_diag.h): traced launches, replay / gather roofs, clocks, placement
@@ -57,6 +57,7 @@ enum Knob : int
 	K_BLOCKS_PER_CU, K_STREAM_LIGHT, K_LOCALITY, K_XCD_TICKETS,
 	// test knobs (hnsw_gpu_config_set only)
 	K_BEAM16, K_NARROW5, K_LEAN, K_HASH_ENTRIES, K_LDS_SET_MIN_WAVES, K_TEAM_SPEC, K_TEAM_WPB, K_NARROW_WPB, K_ABORT_POLL_LOG2, K_MAX_BLOCKS, K_SHARDED_NO_PEER, K_BF_BIG_MIN_BLOCKS, K_LOCALITY_MIN_NQ,
+	K_FK_SAMPLE_MIN, K_FK_MFMA_STANDIN,
 #ifdef HNSW_EXPERIMENT
 	K_WIDE_WAVES, K_SHAPE_12X1, K_TEAM_MAINS, K_TEAM_COUNTERS,
 #endif
@@ -137,10 +138,13 @@ void scan_ws_free(ScanWs *s);
 struct FkWs
 {
 	ScanBuf cells, list, part;                           // per-(bitmap, segment) counts | offsets | rows-scored word; the lists; the partial top-k lists
-	uint64_t *host = nullptr;                            // pinned: [0] entries of all lists, [1] the longest list, [2] rows scored
-	hipEvent_t ev[3] = {};                               // before the list build | after it | after the emit kernel
+	ScanBuf mask, bfs, cand;                             // matrix-core form (device_filtered_knn_mfma.h): row masks; per-query scratch; candidate lists
+	uint64_t *host = nullptr;                            // pinned: [0] entries of all lists, [1] the longest list, [2] rows scored, [3] pairs that passed the filter's comparison, [4] pairs appended, [5] candidate lists that overflowed
+	hipEvent_t ev[6] = {};                               // before the list build | after it | after the emit kernel | before the filter | after it | before a listed scan that follows a filter
 	uint64_t listed = 0, scored = 0;                     // the last call (hnsw_gpu_last_filtered_knn)
 	float build_ms = 0.f, scan_ms = 0.f;
+	int form = -1;                                       // the form that answered it (HNSW_GPU_FK_FORM_*, hnsw_gpu_last_filtered_knn_form)
+	struct Mfma { uint64_t listed = 0, scored = 0, dist_pass = 0, appended = 0; float build_ms = 0.f, filter_ms = 0.f, call_ms = 0.f; } m;   // its last filter launch (hnsw_gpu_last_filtered_knn_mfma)
 };
 void fk_ws_free(FkWs *s);
 

@@ -1,12 +1,13 @@
 // gpu_scan.hip — batched distances (hnsw_dist_func over many rows), exhaustive k-NN: canonical scan (csrc/device_topk_scan.h), MFMA filter over
 // the f32 rows or the reduced copy (csrc/device_bf_mfma.h, csrc/device_bf_mfma16.h), and exact filtered k-NN: the canonical scan over lists of
-// allowed rows (csrc/device_filtered_knn.h)
+// allowed rows (csrc/device_filtered_knn.h) or, for loose filters, the MFMA filter with the allow test at its append (csrc/device_filtered_knn_mfma.h)
 // One translation unit of libhnsw_gpu.so (csrc/gpu_host.h lists them); gfx950 only, plain HIP runtime, no framework types in any signature.
 #include "gpu_host.h"
 #include "device_topk_scan.h"
 #include "device_bf_mfma.h"
 #include "device_bf_mfma16.h"
 #include "device_filtered_knn.h"
+#include "device_filtered_knn_mfma.h"
 
 #include <type_traits>
 
@@ -251,6 +252,63 @@ static int bf_filter_launch(BfArgs &a, hipStream_t s)
 	return HNSW_GPU_OK;
 }
 
+// 256 x 256 tiles when they compute no more padding than 128 x 128 tiles would (an even number of 128-query tiles), there are tiles
+// enough to fill the device several times over and the device has the LDS for them; the same dot products in the same k order either
+// way: the same survivors
+template <class P>
+static int bf_filter_pick(hnsw_gpu_index *ix, BfArgs &a, hipStream_t s)
+{
+	using Small = BfTile<P, BF_SMALL_WM, BF_SMALL_NJ>;
+	using Big = BfTile<P, BF_BIG_WM, BF_BIG_NJ>;
+	static_assert(Small::LDS_BYTES <= BF_MIN_LDS, "the 128 x 128 tile must fit where the call does not fall back");
+	const uint64_t nqt_s = ((uint64_t) a.nq + Small::TQ - 1) / Small::TQ;
+	const uint64_t big_blocks = (((uint64_t) a.nq + Big::TQ - 1) / Big::TQ) * (((uint64_t) a.n + Big::TR - 1) / Big::TR);
+	// (test knob: 0 = never, < 0 = always, n = at least n blocks; the tests run every case through both tiles)
+	const long long min_blocks = knob(K_BF_BIG_MIN_BLOCKS, 2048);
+	const bool big = ix->max_lds >= Big::LDS_BYTES && min_blocks != 0 && (min_blocks < 0 || (nqt_s % 2 == 0 && big_blocks >= (uint64_t) min_blocks));
+	return big ? bf_filter_launch<P, BF_BIG_WM, BF_BIG_NJ>(a, s) : bf_filter_launch<P, BF_SMALL_WM, BF_SMALL_NJ>(a, s);
+}
+
+// the rows' side of a filter launch, current on `s`: the reduced copy and the bound's per-row terms, or the |row|^2 cache
+static int bf_rows_side(hnsw_gpu_index *ix, bool reduced, hipStream_t s)
+{
+	if (reduced)
+	{
+		const int rc = rows16_sync(ix, s);
+		return rc ? rc : r16x_sync(ix, s);
+	}
+	if (ix->xnorm_cap < ix->n)
+	{
+		if (ix->xnorm) (void) hipFree(ix->xnorm);
+		ix->xnorm = nullptr; ix->xnorm_cap = 0; ix->xnorm_n = 0;
+		HIPCHK(hipMalloc(&ix->xnorm, ix->cap * sizeof(float)));
+		ix->xnorm_cap = ix->cap;
+	}
+	if (ix->xnorm_n != ix->n)
+	{
+		hipLaunchKernelGGL(row_norm2_kernel, dim3(((uint32_t) ix->n + 3) / 4), dim3(256), 0, s, ix->vec, (uint32_t) ix->n, ix->stride, ix->xnorm);
+		ix->xnorm_n = ix->n;
+	}
+	return HNSW_GPU_OK;
+}
+
+// the queries' side: the filter's copy and |q|^2 (16-bit: and the queries' terms of the bound)
+static void bf_queries_side(bool reduced, int format, const coord_t *d_queries, size_t nq, uint32_t dim, uint32_t qchunks, uint4 *qcopy, float *qn,
+							float2 *qterms, hipStream_t s)
+{
+	const dim3 qgrid((uint32_t) ((nq + 3) / 4));
+	if (!reduced)
+	{
+		const size_t qtot = nq * (size_t) qchunks * 4;
+		hipLaunchKernelGGL(pad_queries_kernel, dim3((uint32_t) ((qtot + 255) / 256)), dim3(256), 0, s, d_queries, (uint32_t) nq, dim, qchunks * 4, (float *) qcopy);
+		hipLaunchKernelGGL(row_norm2_kernel, qgrid, dim3(256), 0, s, (const float *) qcopy, (uint32_t) nq, qchunks * 4, qn);
+	}
+	else if (format == ROWS_BF16)
+		hipLaunchKernelGGL(r16_query_kernel<ROWS_BF16>, qgrid, dim3(256), 0, s, d_queries, (uint32_t) nq, dim, qchunks, qcopy, qn, qterms);
+	else
+		hipLaunchKernelGGL(r16_query_kernel<ROWS_F16>, qgrid, dim3(256), 0, s, d_queries, (uint32_t) nq, dim, qchunks, qcopy, qn, qterms);
+}
+
 // Both forms of the call: a bound per query from a canonical scan of a sample, the filter over the f32 rows (reduced == false) or over the
 // reduced copy of `format`, the canonical re-score of the survivors.  A form that cannot answer hands the call down: the 16-bit filter to
 // the f32 filter, that one to the canonical scan — the same answer, bit for bit (the filter's survivors are re-scored by that code anyway).
@@ -282,28 +340,8 @@ static int bruteforce_filter(hnsw_gpu_index *ix, bool reduced, int format, const
 	if (lds > 64 * 1024) return scan();
 
 	// the rows' side, current on this stream: the reduced copy and the bound's per-row terms, or the |row|^2 cache
-	int rc = HNSW_GPU_OK;
-	if (reduced)
-	{
-		rc = rows16_sync(ix, s);
-		if (!rc) rc = r16x_sync(ix, s);
-		if (rc) return rc;
-	}
-	else
-	{
-		if (ix->xnorm_cap < ix->n)
-		{
-			if (ix->xnorm) (void) hipFree(ix->xnorm);
-			ix->xnorm = nullptr; ix->xnorm_cap = 0; ix->xnorm_n = 0;
-			HIPCHK(hipMalloc(&ix->xnorm, ix->cap * sizeof(float)));
-			ix->xnorm_cap = ix->cap;
-		}
-		if (ix->xnorm_n != ix->n)
-		{
-			hipLaunchKernelGGL(row_norm2_kernel, dim3((n + 3) / 4), dim3(256), 0, s, ix->vec, n, stride, ix->xnorm);
-			ix->xnorm_n = ix->n;
-		}
-	}
+	int rc = bf_rows_side(ix, reduced, s);
+	if (rc) return rc;
 	// 16-byte chunks of the filter's query copy (f32: zero padded to whole K steps; 16-bit: the copy's row) and of a row
 	const uint32_t qchunks = reduced ? ix->rows16_bytes / 16 : (uint32_t) round_up(stride, BF_TK) / 4;
 	const uint32_t rchunks = reduced ? ix->rows16_bytes / 16 : nchunks;
@@ -339,17 +377,7 @@ static int bruteforce_filter(hnsw_gpu_index *ix, bool reduced, int format, const
 	rc = bruteforce_prefix(ix, sample, d_queries, nq, k, sidx, sdist, s);
 	if (rc) return rc;
 	// the queries' side: the filter's copy and |q|^2 (16-bit: and the queries' terms of the bound)
-	const dim3 qgrid((uint32_t) ((nq + 3) / 4));
-	if (!reduced)
-	{
-		const size_t qtot = nq * (size_t) qchunks * 4;
-		hipLaunchKernelGGL(pad_queries_kernel, dim3((uint32_t) ((qtot + 255) / 256)), dim3(256), 0, s, d_queries, (uint32_t) nq, dim, qchunks * 4, (float *) qcopy);
-		hipLaunchKernelGGL(row_norm2_kernel, qgrid, dim3(256), 0, s, (const float *) qcopy, (uint32_t) nq, qchunks * 4, qn);
-	}
-	else if (format == ROWS_BF16)
-		hipLaunchKernelGGL(r16_query_kernel<ROWS_BF16>, qgrid, dim3(256), 0, s, d_queries, (uint32_t) nq, dim, qchunks, qcopy, qn, qterms);
-	else
-		hipLaunchKernelGGL(r16_query_kernel<ROWS_F16>, qgrid, dim3(256), 0, s, d_queries, (uint32_t) nq, dim, qchunks, qcopy, qn, qterms);
+	bf_queries_side(reduced, format, d_queries, nq, dim, qchunks, qcopy, qn, qterms, s);
 	// tau_q = sdist[q*k + k-1], gathered with a strided copy into `bound`, which make_bounds_kernel then rewrites in place
 	hipLaunchKernelGGL(fill_u32_kernel, dim3(1), dim3(1), 0, s, overflow, (size_t) 1, 0u);
 	HIPCHK(hipMemcpy2DAsync(bound, 4, sdist + (k - 1), k * 4, 4, nq, hipMemcpyDeviceToDevice, s));
@@ -370,21 +398,7 @@ static int bruteforce_filter(hnsw_gpu_index *ix, bool reduced, int format, const
 	if (!ix->bf_e0) { HIPCHK(hipEventCreate(&ix->bf_e0)); HIPCHK(hipEventCreate(&ix->bf_e1)); }
 	hipEvent_t e0 = ix->bf_e0, e1 = ix->bf_e1;
 	HIPCHK(hipEventRecord(e0, s));
-	// 256 x 256 tiles when they compute no more padding than 128 x 128 tiles would (an even number of 128-query tiles), there are tiles
-	// enough to fill the device several times over and the device has the LDS for them; the same dot products in the same k order either
-	// way: the same survivors
-	rc = with_form(format, [&](auto p) {
-		using P = decltype(p);
-		using Small = BfTile<P, BF_SMALL_WM, BF_SMALL_NJ>;
-		using Big = BfTile<P, BF_BIG_WM, BF_BIG_NJ>;
-		static_assert(Small::LDS_BYTES <= BF_MIN_LDS, "the 128 x 128 tile must fit where the call does not fall back");
-		const uint64_t nqt_s = (nq + Small::TQ - 1) / Small::TQ;
-		const uint64_t big_blocks = ((nq + Big::TQ - 1) / Big::TQ) * ((n + Big::TR - 1) / Big::TR);
-		// (test knob: 0 = never, < 0 = always, n = at least n blocks; the tests run every case through both tiles)
-		const long long min_blocks = knob(K_BF_BIG_MIN_BLOCKS, 2048);
-		const bool big = ix->max_lds >= Big::LDS_BYTES && min_blocks != 0 && (min_blocks < 0 || (nqt_s % 2 == 0 && big_blocks >= (uint64_t) min_blocks));
-		return big ? bf_filter_launch<P, BF_BIG_WM, BF_BIG_NJ>(a, s) : bf_filter_launch<P, BF_SMALL_WM, BF_SMALL_NJ>(a, s);
-	});
+	rc = with_form(format, [&](auto p) { return bf_filter_pick<decltype(p)>(ix, a, s); });
 	if (rc) return rc;
 	HIPCHK(hipEventRecord(e1, s));
 
@@ -426,7 +440,7 @@ static const size_t FK_PART_BYTES = (size_t) 1 << 30;         // the partial lis
 
 void fk_ws_free(FkWs *s)
 {
-	buf_trim({&s->cells, &s->list, &s->part}, 0);
+	buf_trim({&s->cells, &s->list, &s->part, &s->mask, &s->bfs, &s->cand}, 0);
 	if (s->host) (void) hipHostFree(s->host);
 	s->host = nullptr;
 	for (hipEvent_t &e : s->ev) { if (e) (void) hipEventDestroy(e); e = nullptr; }
@@ -448,26 +462,43 @@ static int fk_check(hnsw_gpu_index *ix, const void *queries, size_t nq, size_t k
 	if (lds > 64 * 1024) return fail(HNSW_GPU_ERR_ARG, "k/dim too large for filtered k-NN");
 	return HNSW_GPU_OK;
 }
-
-extern "C" int hnsw_gpu_filtered_knn_dev(hnsw_gpu_index *ix, const coord_t *d_queries, size_t nq, size_t k, const uint32_t *d_allow,
-										 size_t allow_bits, size_t nfilters, const uint32_t *d_allow_of, label_t *d_labels, dist_t *d_dists,
-										 idx_t *d_idx, uint32_t *d_counts, void *stream)
+// the matrix-core form's operands: the f32 rows, or the reduced copy the index holds (hnsw_gpu_bruteforce_reduced_dev's rule)
+static int fk_check_format(hnsw_gpu_index *ix, int format)
 {
-	std::unique_lock<std::recursive_mutex> lock_;
-	if (ix) lock_ = std::unique_lock<std::recursive_mutex>(ix->mu);
-	if (int rc0 = fk_check(ix, d_queries, nq, k, d_allow, allow_bits, nfilters, d_labels, d_counts)) return rc0;
-	if (nq == 0) return HNSW_GPU_OK;
-	HIPCHK(hipSetDevice(ix->device));
-	hipStream_t s = (hipStream_t) stream;
-	FkWs *fw = &ix->fk;
-	struct Trim { FkWs *w; ~Trim() { buf_trim({&w->cells, &w->list, &w->part}); } } trim_{fw};   // on EVERY way out, errors included: no buffer above 64 MiB outlives its call
+	if (format == ROWS_F32) return HNSW_GPU_OK;
+	if ((format != ROWS_F16 && format != ROWS_BF16) || ix->rows_fmt != format || !ix->rows16)
+		return fail(HNSW_GPU_ERR_ARG, "filtered k-NN: format %d is neither f32 nor the reduced copy this index holds (%d; hnsw_gpu_index_set_reduced_rows)", format, ix->rows_fmt);
+	return HNSW_GPU_OK;
+}
+
+// one call: its arguments, and what its list build found
+struct FkCall
+{
+	hnsw_gpu_index *ix; const coord_t *queries; size_t nq, k; const uint32_t *allow; size_t allow_bits, nfilters; const uint32_t *allow_of;
+	label_t *labels; dist_t *dists; idx_t *idx; uint32_t *counts; hipStream_t s;
+	FkLists fl; uint64_t *off; unsigned long long *scored; size_t nsb, total, longest;
+};
+struct FkTrim { FkWs *w; ~FkTrim() { buf_trim({&w->cells, &w->list, &w->part, &w->mask, &w->bfs, &w->cand}); } };   // on EVERY way out, errors included: no buffer above 64 MiB outlives its call
+
+static int fk_begin(FkCall &c)
+{
+	HIPCHK(hipSetDevice(c.ix->device));
+	FkWs *fw = &c.ix->fk;
 	if (!fw->host) HIPCHK(hipHostMalloc((void **) &fw->host, 64, hipHostMallocDefault));
 	for (hipEvent_t &e : fw->ev)
 		if (!e) HIPCHK(hipEventCreate(&e));
 	fw->listed = fw->scored = 0; fw->build_ms = fw->scan_ms = 0.f;
+	fw->m = FkWs::Mfma();
+	return HNSW_GPU_OK;
+}
 
-	// 1. the allowed lists: count per (bitmap, segment), offsets, fill
-	const size_t n = ix->n;
+// 1. the allowed lists: count per (bitmap, segment), offsets, fill
+static int fk_lists(FkCall &c)
+{
+	hnsw_gpu_index *ix = c.ix;
+	FkWs *fw = &ix->fk;
+	hipStream_t s = c.s;
+	const size_t n = ix->n, nfilters = c.nfilters;
 	const uint32_t nseg = (uint32_t) std::max<size_t>(1, (n + FK_SEG - 1) / FK_SEG);
 	const size_t ncells = (size_t) nseg * nfilters, nsb = (nseg + 3) / 4;
 	if (nsb * nfilters >= 0x7FFFFFFFull) return fail(HNSW_GPU_ERR_ARG, "filtered k-NN: %zu filters over %zu rows are too many for one call", nfilters, n);
@@ -477,10 +508,10 @@ extern "C" int hnsw_gpu_filtered_knn_dev(hnsw_gpu_index *ix, const coord_t *d_qu
 	uint32_t *cells = (uint32_t *) fw->cells.p;
 	uint64_t *off = (uint64_t *) ((char *) fw->cells.p + o_off);
 	unsigned long long *scored = (unsigned long long *) ((char *) fw->cells.p + o_scored);
-	FkLists fl;
+	FkLists &fl = c.fl;
 	memset(&fl, 0, sizeof(fl));
 	fl.labels = ix->labels; fl.n = (uint32_t) n; fl.nseg = nseg;
-	fl.allow = d_allow; fl.allow_bits = allow_bits; fl.allow_words = (uint32_t) ((allow_bits + 31) / 32); fl.nfilters = (uint32_t) nfilters;
+	fl.allow = c.allow; fl.allow_bits = c.allow_bits; fl.allow_words = (uint32_t) ((c.allow_bits + 31) / 32); fl.nfilters = (uint32_t) nfilters;
 	fw->host[0] = fw->host[1] = fw->host[2] = 0;
 	HIPCHK(hipEventRecord(fw->ev[0], s));
 	hipLaunchKernelGGL(fk_count_kernel, dim3((uint32_t) (nsb * nfilters)), dim3(256), 0, s, fl, cells);
@@ -493,49 +524,275 @@ extern "C" int hnsw_gpu_filtered_knn_dev(hnsw_gpu_index *ix, const coord_t *d_qu
 	if (total) hipLaunchKernelGGL(fk_fill_kernel, dim3((uint32_t) (nsb * nfilters)), dim3(256), 0, s, fl, (const uint64_t *) off, (uint32_t *) fw->list.p);
 	HIPCHK(hipMemsetAsync(scored, 0, 8, s));
 	HIPCHK(hipEventRecord(fw->ev[1], s));
+	c.off = off; c.scored = scored; c.nsb = nsb; c.total = total; c.longest = longest;
+	return HNSW_GPU_OK;
+}
 
-	// 2. the listed scan.  Splits as the exhaustive scan chooses them, from the longest list (a query with a shorter one uses fewer
-	// waves: fk_waves).  (FK_XCD_REMAP variant builds: a list long enough for it gets at least one slice per XCD to keep apart.)
-	uint32_t splits = (uint32_t) std::max<size_t>(1, std::min<size_t>(64, (size_t) (4 * ix->num_cu) / nq));
-	if (FK_XCD_REMAP && longest >= 8192) splits = std::max(splits, 8u);
-	splits = (uint32_t) std::min<size_t>(splits, std::max<size_t>(1, longest / (4 * FK_WAVE_ROWS)));
-	while (splits > 1 && nq * splits * 4 * k * 8 > FK_PART_BYTES) splits /= 2;
-	if (longest && (rc = buf_reserve(&fw->part, nq * splits * 4 * k * 8, "filtered k-NN", "the partial result lists"))) return rc;   // (no list, no scan: the emit kernel reads no partial list)
+// what the scan and emit kernels of a call share (splits, the partial lists and the sample are the caller's)
+static FkEmit fk_kernel_args(const FkCall &c)
+{
+	hnsw_gpu_index *ix = c.ix;
 	const uint32_t nchunks = ix->stride / 4, kiters = (nchunks + 15) / 16;
 	FkEmit fe;
 	memset(&fe, 0, sizeof(fe));
 	FkScan &fs = fe.s;
 	fs.vec = ix->vec; fs.dim = (uint32_t) ix->meta.dim; fs.stride = ix->stride; fs.nchunks = nchunks; fs.kiters = kiters;
 	fs.qpad_floats = (uint32_t) round_up(kiters, 4) * 64;
-	fs.queries = d_queries; fs.nq = (uint32_t) nq; fs.k = (uint32_t) k; fs.splits = splits;
-	fs.list = (const uint32_t *) fw->list.p; fs.off = off; fs.nseg = nseg; fs.allow_of = d_allow_of;
-	fs.part = (uint64_t *) fw->part.p; fs.scored = scored;
-	fe.labels = ix->labels; fe.n = (uint32_t) n;
-	fe.out_labels = d_labels; fe.out_dists = d_dists; fe.out_idx = d_idx; fe.out_counts = d_counts;
-	const size_t lds = (size_t) fs.qpad_floats * 4 + (size_t) 4 * (k + 1) * 8 + 4 * 128 * 4 + 4 * 64 * 4;
-	const dim3 grid((uint32_t) round_up((size_t) splits * nq, 8));
-	if (longest)
-		with_func((int) ix->meta.dist_func, [&](auto F) { hipLaunchKernelGGL(fk_scan_kernel<decltype(F)::value>, grid, dim3(256), lds, s, fs); });
-	// 3. merge + emit
-	hipLaunchKernelGGL(fk_emit_kernel, dim3((uint32_t) nq), dim3(64), k * 16, s, fe);
+	fs.queries = c.queries; fs.nq = (uint32_t) c.nq; fs.k = (uint32_t) c.k;
+	fs.list = (const uint32_t *) ix->fk.list.p; fs.off = c.off; fs.nseg = c.fl.nseg; fs.allow_of = c.allow_of;
+	fs.scored = c.scored;
+	fe.labels = ix->labels; fe.n = (uint32_t) ix->n;
+	fe.out_labels = c.labels; fe.out_dists = c.dists; fe.out_idx = c.idx; fe.out_counts = c.counts;
+	return fe;
+}
+// Splits as the exhaustive scan chooses them, from the longest list a query scans (a query with a shorter one uses fewer waves: fk_waves),
+// and room for the partial lists.  (FK_XCD_REMAP variant builds: a list long enough for it gets at least one slice per XCD to keep apart.)
+static int fk_splits(const FkCall &c, size_t longest, uint32_t *out)
+{
+	hnsw_gpu_index *ix = c.ix;
+	const size_t nq = c.nq, k = c.k;
+	uint32_t splits = (uint32_t) std::max<size_t>(1, std::min<size_t>(64, (size_t) (4 * ix->num_cu) / nq));
+	if (FK_XCD_REMAP && longest >= 8192) splits = std::max(splits, 8u);
+	splits = (uint32_t) std::min<size_t>(splits, std::max<size_t>(1, longest / (4 * FK_WAVE_ROWS)));
+	while (splits > 1 && nq * splits * 4 * k * 8 > FK_PART_BYTES) splits /= 2;
+	*out = splits;
+	if (!longest) return HNSW_GPU_OK;                             // (no list, no scan: the emit kernel reads no partial list)
+	return buf_reserve(&ix->fk.part, nq * splits * 4 * k * 8, "filtered k-NN", "the partial result lists");
+}
+static void fk_scan_launch(const FkCall &c, const FkScan &fs)
+{
+	const size_t lds = (size_t) fs.qpad_floats * 4 + (size_t) 4 * (c.k + 1) * 8 + 4 * 128 * 4 + 4 * 64 * 4;
+	const dim3 grid((uint32_t) round_up((size_t) fs.splits * c.nq, 8));
+	with_func((int) c.ix->meta.dist_func, [&](auto F) { hipLaunchKernelGGL(fk_scan_kernel<decltype(F)::value>, grid, dim3(256), lds, c.s, fs); });
+}
+
+// 2. the listed scan over the whole lists, 3. merge + emit; `start`: the event the scan's time counts from
+static int fk_listed_scan(FkCall &c, hipEvent_t start)
+{
+	FkWs *fw = &c.ix->fk;
+	hipStream_t s = c.s;
+	uint32_t splits = 1;
+	int rc = fk_splits(c, c.longest, &splits);
+	if (rc) return rc;
+	FkEmit fe = fk_kernel_args(c);
+	fe.s.splits = splits; fe.s.part = (uint64_t *) fw->part.p;
+	if (c.longest) fk_scan_launch(c, fe.s);
+	hipLaunchKernelGGL(fk_emit_kernel, dim3((uint32_t) c.nq), dim3(64), c.k * 16, s, fe);
 	hipError_t e = hipGetLastError();
 	if (e == hipSuccess) e = hipEventRecord(fw->ev[2], s);
-	if (e == hipSuccess) e = hipMemcpyAsync(&fw->host[2], scored, 8, hipMemcpyDeviceToHost, s);
+	if (e == hipSuccess) e = hipMemcpyAsync(&fw->host[2], c.scored, 8, hipMemcpyDeviceToHost, s);
 	const hipError_t e2 = hipStreamSynchronize(s);
 	if (e == hipSuccess) e = e2;
 	if (e != hipSuccess) return fail(HNSW_GPU_ERR_HIP, "filtered k-NN: %s", hipGetErrorString(e));
-	fw->listed = total; fw->scored = fw->host[2];
+	fw->listed = c.total; fw->scored = fw->host[2];
 	(void) hipEventElapsedTime(&fw->build_ms, fw->ev[0], fw->ev[1]);
-	(void) hipEventElapsedTime(&fw->scan_ms, fw->ev[1], fw->ev[2]);
+	(void) hipEventElapsedTime(&fw->scan_ms, start, fw->ev[2]);
+	fw->form = HNSW_GPU_FK_FORM_LISTED;
 	return HNSW_GPU_OK;
 }
 
-extern "C" int hnsw_gpu_filtered_knn(hnsw_gpu_index *ix, const coord_t *queries, size_t nq, size_t k, const uint32_t *allow, size_t allow_bits,
-									 size_t nfilters, const uint32_t *allow_of, label_t *labels, dist_t *dists, idx_t *idx, uint32_t *counts)
+static int fk_listed_call(FkCall &c)
+{
+	FkTrim trim_{&c.ix->fk};
+	int rc = fk_begin(c);
+	if (!rc) rc = fk_lists(c);
+	if (!rc) rc = fk_listed_scan(c, c.ix->fk.ev[1]);
+	return rc;
+}
+
+extern "C" int hnsw_gpu_filtered_knn_dev(hnsw_gpu_index *ix, const coord_t *d_queries, size_t nq, size_t k, const uint32_t *d_allow,
+										 size_t allow_bits, size_t nfilters, const uint32_t *d_allow_of, label_t *d_labels, dist_t *d_dists,
+										 idx_t *d_idx, uint32_t *d_counts, void *stream)
+{
+	std::unique_lock<std::recursive_mutex> lock_;
+	if (ix) lock_ = std::unique_lock<std::recursive_mutex>(ix->mu);
+	if (int rc0 = fk_check(ix, d_queries, nq, k, d_allow, allow_bits, nfilters, d_labels, d_counts)) return rc0;
+	if (nq == 0) return HNSW_GPU_OK;
+	FkCall c = { ix, d_queries, nq, k, d_allow, allow_bits, nfilters, d_allow_of, d_labels, d_dists, d_idx, d_counts, (hipStream_t) stream };
+	return fk_listed_call(c);
+}
+
+// ------------------------------------------------------------------------------------
+// exact filtered k-NN for loose filters: the Q x N part on the matrix cores, the allow test where a pair is appended
+// (device_filtered_knn_mfma.h)
+// ------------------------------------------------------------------------------------
+// One pass over the built lists and masks with the operands of `format`: sample scan -> bounds -> filter (or its stand-in) -> re-score ->
+// emit.  *ovf = candidate lists that overflowed (then the outputs are not the answer: the caller hands the call down).
+static int fk_mfma_pass(FkCall &c, int format, bool standin, uint32_t smin, uint32_t mwords, uint64_t *ovf)
+{
+	hnsw_gpu_index *ix = c.ix;
+	FkWs *fw = &ix->fk;
+	hipStream_t s = c.s;
+	const bool reduced = format != ROWS_F32;
+	const size_t nq = c.nq, k = c.k;
+	const int func = (int) ix->meta.dist_func;
+	const uint32_t n = (uint32_t) ix->n, stride = ix->stride, dim = (uint32_t) ix->meta.dim;
+	const uint32_t nchunks = stride / 4, kiters = (nchunks + 15) / 16;
+	const uint32_t qpadf = (uint32_t) round_up(kiters, 4) * 64;
+	const size_t wave_bytes = round_up((size_t) qpadf * 4 + (k + 1) * 8 + 128 * 4, 16);
+	int rc = bf_rows_side(ix, reduced, s);
+	if (rc) return rc;
+	const uint32_t qchunks = reduced ? ix->rows16_bytes / 16 : (uint32_t) round_up(stride, BF_TK) / 4;
+	const uint32_t rchunks = reduced ? ix->rows16_bytes / 16 : nchunks;
+	const uint32_t cap = 16384;
+	// scratch carve
+	const size_t o_q = 0;
+	const size_t o_qn = o_q + round_up(nq * (size_t) qchunks * 16, 256);
+	const size_t o_qt = o_qn + round_up(nq * 4, 256);
+	const size_t o_tau = o_qt + round_up(nq * 8, 256);
+	const size_t o_bound = o_tau + round_up(nq * 4, 256);
+	const size_t o_mof = o_bound + round_up(nq * 4, 256);
+	const size_t o_cnt = o_mof + round_up(nq * 4, 256);
+	const size_t o_fcnt = o_cnt + round_up(nq * 4 + 64, 256);
+	const size_t o_ridx = o_fcnt + 256;
+	const size_t o_rdist = o_ridx + round_up(nq * k * 4, 256);
+	const size_t o_keys = o_rdist + round_up(nq * k * 4, 256);
+	const size_t total = o_keys + round_up(nq * k * 8, 256);
+	if ((rc = buf_reserve(&fw->bfs, total, "filtered k-NN", "the filter's scratch"))) return rc;
+	if ((rc = buf_reserve(&fw->cand, nq * (size_t) cap * 4, "filtered k-NN", "the candidate lists"))) return rc;
+	char *B = (char *) fw->bfs.p;
+	uint4 *qcopy = (uint4 *) (B + o_q);
+	float *qn = (float *) (B + o_qn), *tau = (float *) (B + o_tau), *bound = (float *) (B + o_bound), *rdist = (float *) (B + o_rdist);
+	float2 *qterms = (float2 *) (B + o_qt);
+	uint32_t *mask_of = (uint32_t *) (B + o_mof), *cnt = (uint32_t *) (B + o_cnt), *ridx = (uint32_t *) (B + o_ridx), *cand = (uint32_t *) fw->cand.p;
+	uint32_t *overflow = cnt + nq;
+	unsigned long long *fcnt = (unsigned long long *) (B + o_fcnt);
+	uint64_t *keys = (uint64_t *) (B + o_keys);
+
+	// 3. the sample scan: the listed scan core over the first S(b) entries of every query's list, then tau_q, the sample's keys and the mask rows
+	const uint32_t slongest = fk_sample_len((uint32_t) c.longest, smin, (uint32_t) k);
+	uint32_t splits = 1;
+	if ((rc = fk_splits(c, slongest, &splits))) return rc;
+	FkEmit fe = fk_kernel_args(c);
+	FkmBounds fb;
+	memset(&fb, 0, sizeof(fb));
+	fb.s = fe.s;
+	fb.s.splits = splits; fb.s.part = (uint64_t *) fw->part.p; fb.s.smin = smin;
+	fb.nfilters = (uint32_t) c.nfilters; fb.keys = keys; fb.tau = tau; fb.mask_of = mask_of;
+	HIPCHK(hipMemsetAsync(c.scored, 0, 8, s));
+	fk_scan_launch(c, fb.s);
+	hipLaunchKernelGGL(fkm_bounds_kernel, dim3((uint32_t) nq), dim3(64), k * 8, s, fb);
+	bf_queries_side(reduced, format, c.queries, nq, dim, qchunks, qcopy, qn, qterms, s);
+	hipLaunchKernelGGL(make_bounds_kernel, dim3((uint32_t) ((nq + 255) / 256)), dim3(256), 0, s, (const float *) tau, qn, (uint32_t) nq, func, dim, bound);
+	HIPCHK(hipMemsetAsync(cnt, 0, nq * 4 + 64, s));               // (the candidate counts and the overflow word behind them)
+	HIPCHK(hipMemsetAsync(fcnt, 0, 16, s));
+
+	// 4. the filter over all rows, the allow test at its append
+	BfArgs a;
+	memset(&a, 0, sizeof(a));
+	a.queries = qcopy; a.qnorm = qn; a.qbound = bound; a.qterms = qterms;
+	a.rows = reduced ? (const uint4 *) ix->rows16 : (const uint4 *) ix->vec; a.xnorm = ix->xnorm; a.xterms = ix->r16x;
+	a.nq = (uint32_t) nq; a.n = n; a.qchunks = qchunks; a.rchunks = rchunks; a.ksteps = qchunks / BF_CH; a.func = func;
+	a.xscale = 0.5f * (1.f - 2.f * ((float) dim + 32.f) * 0x1p-24f);          // (1 - eD) / 2: make_bounds_kernel
+	a.eabs = r16_abs_term(dim);
+	a.cand = cand; a.cand_cnt = cnt; a.cap = cap;
+	a.mask = (const uint32_t *) fw->mask.p; a.mask_of = mask_of; a.mwords = mwords; a.fcnt = fcnt;
+	HIPCHK(hipEventRecord(fw->ev[3], s));
+	if (standin)
+		with_func(func, [&](auto F) {
+			hipLaunchKernelGGL(fkm_standin_kernel<decltype(F)::value>, dim3((uint32_t) nq), dim3(256), (size_t) qpadf * 4 + 4 * 128 * 4, s, a, ix->vec, dim, stride,
+							   nchunks, kiters, qpadf, c.queries, (const float *) tau);
+		});
+	else if ((rc = with_form(format, [&](auto p) { return bf_filter_pick<BfAllow<decltype(p)>>(ix, a, s); })))
+		return rc;
+	HIPCHK(hipEventRecord(fw->ev[4], s));
+
+	// 5. canonical re-score of the candidates, 6. one key list per query -> emit
+	with_func(func, [&](auto F) {
+		if constexpr (decltype(F)::value != F_MANHATTAN)           // (answered by the listed form: no re-score kernel is compiled for it)
+			hipLaunchKernelGGL(bf_rescore_kernel<decltype(F)::value>, dim3((uint32_t) ((nq + 3) / 4)), dim3(256), wave_bytes * 4, s, ix->vec, dim, stride, nchunks,
+							   kiters, qpadf, c.queries, (uint32_t) nq, cand, cnt, cap, (uint32_t) k, ridx, rdist, overflow);
+	});
+	hipLaunchKernelGGL(fkm_keys_kernel, dim3((uint32_t) ((nq * k + 255) / 256)), dim3(256), 0, s, (const uint32_t *) ridx, (const float *) rdist,
+					   (const uint32_t *) mask_of, (uint32_t) c.nfilters, (uint32_t) nq, (uint32_t) k, keys);
+	fe.single = keys;
+	hipLaunchKernelGGL(fk_emit_kernel, dim3((uint32_t) nq), dim3(64), k * 16, s, fe);
+	hipError_t e = hipGetLastError();
+	if (e == hipSuccess) e = hipEventRecord(fw->ev[2], s);
+	fw->host[5] = 0;
+	if (e == hipSuccess) e = hipMemcpyAsync(&fw->host[2], c.scored, 8, hipMemcpyDeviceToHost, s);
+	if (e == hipSuccess) e = hipMemcpyAsync(&fw->host[3], fcnt, 16, hipMemcpyDeviceToHost, s);
+	if (e == hipSuccess) e = hipMemcpyAsync(&fw->host[5], overflow, 4, hipMemcpyDeviceToHost, s);
+	const hipError_t e2 = hipStreamSynchronize(s);
+	if (e == hipSuccess) e = e2;
+	if (e != hipSuccess) return fail(HNSW_GPU_ERR_HIP, "filtered k-NN: %s", hipGetErrorString(e));
+	*ovf = fw->host[5];
+	FkWs::Mfma &m = fw->m;
+	m.listed = c.total; m.scored = fw->host[2]; m.dist_pass = fw->host[3]; m.appended = fw->host[4];
+	(void) hipEventElapsedTime(&m.build_ms, fw->ev[0], fw->ev[1]);
+	(void) hipEventElapsedTime(&m.filter_ms, fw->ev[3], fw->ev[4]);
+	(void) hipEventElapsedTime(&m.call_ms, fw->ev[0], fw->ev[2]);
+	return HNSW_GPU_OK;
+}
+
+extern "C" int hnsw_gpu_filtered_knn_mfma_dev(hnsw_gpu_index *ix, int format, const coord_t *d_queries, size_t nq, size_t k, const uint32_t *d_allow,
+											  size_t allow_bits, size_t nfilters, const uint32_t *d_allow_of, label_t *d_labels, dist_t *d_dists,
+											  idx_t *d_idx, uint32_t *d_counts, void *stream)
+{
+	std::unique_lock<std::recursive_mutex> lock_;
+	if (ix) lock_ = std::unique_lock<std::recursive_mutex>(ix->mu);
+	if (int rc0 = fk_check(ix, d_queries, nq, k, d_allow, allow_bits, nfilters, d_labels, d_counts)) return rc0;
+	if (int rc0 = fk_check_format(ix, format)) return rc0;
+	if (nq == 0) return HNSW_GPU_OK;
+	FkCall c = { ix, d_queries, nq, k, d_allow, allow_bits, nfilters, d_allow_of, d_labels, d_dists, d_idx, d_counts, (hipStream_t) stream };
+	// The listed form's answer, before any launch: not a contraction; a re-score step — a query image and a k-list per wave in LDS — that does
+	// not fit; and, unless the stand-in takes the filter's place (test knob: then the operands are f32 whatever `format` says), a table too
+	// small to matter or a device the filter kernel is not written for (bruteforce_filter's rules; the tests' emulator has no such kernel)
+	const bool standin = knob(K_FK_MFMA_STANDIN, 0) != 0;
+	const int func = (int) ix->meta.dist_func;
+	const uint32_t kiters = (ix->stride / 4 + 15) / 16;
+	const size_t wave_bytes = round_up(round_up(kiters, 4) * 64 * 4 + (k + 1) * 8 + 128 * 4, 16);
+#ifdef PGEMB_SIMT_EMULATOR
+	const bool have_filter = false;
+#else
+	const bool have_filter = ix->n >= 4096 && ix->gfx950 && ix->max_lds >= BF_MIN_LDS;
+#endif
+	if (func == F_MANHATTAN || wave_bytes * 4 > 64 * 1024 || !(standin || have_filter)) return fk_listed_call(c);
+	if (standin) format = ROWS_F32;
+
+	FkWs *fw = &ix->fk;
+	FkTrim trim_{fw};
+	int rc = fk_begin(c);
+	if (!rc) rc = fk_lists(c);
+	if (rc) return rc;
+	// a list no longer than S_min is its own sample: with no longer list in the call, every query is answered by the listed scan
+	const uint32_t smin = (uint32_t) std::min<long long>(0xFFFFFFFFll, std::max<long long>(1, knob(K_FK_SAMPLE_MIN, FKM_SAMPLE_MIN)));
+	if (c.longest <= smin) return fk_listed_scan(c, fw->ev[1]);
+	// 2. the row masks (counted with the list build), and a row of zeros behind them
+	const uint32_t mwords = fkm_mask_words((uint32_t) ix->n);
+	if ((rc = buf_reserve(&fw->mask, (nfilters + 1) * (size_t) mwords * 4, "filtered k-NN", "the row masks"))) return rc;
+	hipLaunchKernelGGL(fkm_mask_kernel, dim3((uint32_t) (c.nsb * nfilters)), dim3(256), 0, c.s, c.fl, mwords, (uint32_t *) fw->mask.p);
+	HIPCHK(hipMemsetAsync((uint32_t *) fw->mask.p + nfilters * (size_t) mwords, 0, (size_t) mwords * 4, c.s));
+	HIPCHK(hipEventRecord(fw->ev[1], c.s));
+	// a candidate list that overflows sends a 16-bit call to the f32 operands (its bound is looser: a list that overflowed there may not
+	// in f32), and an f32 call to the listed scan
+	for (;;)
+	{
+		uint64_t ovf = 0;
+		if ((rc = fk_mfma_pass(c, format, standin, smin, mwords, &ovf))) return rc;
+		if (!ovf) break;
+		if (format == ROWS_F32)
+		{
+			HIPCHK(hipEventRecord(fw->ev[5], c.s));
+			HIPCHK(hipMemsetAsync(c.scored, 0, 8, c.s));
+			return fk_listed_scan(c, fw->ev[5]);
+		}
+		format = ROWS_F32;
+	}
+	fw->listed = fw->m.listed; fw->scored = fw->m.scored; fw->build_ms = fw->m.build_ms; fw->scan_ms = fw->m.call_ms - fw->m.build_ms;
+	fw->form = format == ROWS_F32 ? HNSW_GPU_FK_FORM_F32 : format == ROWS_BF16 ? HNSW_GPU_FK_FORM_BF16 : HNSW_GPU_FK_FORM_F16;
+	return HNSW_GPU_OK;
+}
+
+// the host-pointer forms: copy in, run on the default stream, copy out.  format < 0: the listed form
+static int fk_host(hnsw_gpu_index *ix, int format, const coord_t *queries, size_t nq, size_t k, const uint32_t *allow, size_t allow_bits,
+				   size_t nfilters, const uint32_t *allow_of, label_t *labels, dist_t *dists, idx_t *idx, uint32_t *counts)
 {
 	std::unique_lock<std::recursive_mutex> lock_;
 	if (ix) lock_ = std::unique_lock<std::recursive_mutex>(ix->mu);
 	if (int rc0 = fk_check(ix, queries, nq, k, allow, allow_bits, nfilters, labels, counts)) return rc0;
+	if (format >= 0)
+		if (int rc0 = fk_check_format(ix, format)) return rc0;
 	if (nq == 0) return HNSW_GPU_OK;
 	HIPCHK(hipSetDevice(ix->device));
 	const size_t dim = ix->meta.dim, words = (allow_bits + 31) / 32;
@@ -550,13 +807,28 @@ extern "C" int hnsw_gpu_filtered_knn(hnsw_gpu_index *ix, const coord_t *queries,
 	HIPCHK(hipMemcpy(dq, queries, nq * dim * 4, hipMemcpyHostToDevice));
 	HIPCHK(hipMemcpy(df, allow, nfilters * words * 4, hipMemcpyHostToDevice));
 	if (allow_of) HIPCHK(hipMemcpy(dof, allow_of, nq * 4, hipMemcpyHostToDevice));
-	rc = hnsw_gpu_filtered_knn_dev(ix, dq, nq, k, df, allow_bits, nfilters, allow_of ? dof : nullptr, dl, dd, di, dc, nullptr);
+	rc = format < 0 ? hnsw_gpu_filtered_knn_dev(ix, dq, nq, k, df, allow_bits, nfilters, allow_of ? dof : nullptr, dl, dd, di, dc, nullptr)
+					: hnsw_gpu_filtered_knn_mfma_dev(ix, format, dq, nq, k, df, allow_bits, nfilters, allow_of ? dof : nullptr, dl, dd, di, dc, nullptr);
 	if (rc) return rc;
 	HIPCHK(hipMemcpy(labels, dl, nq * k * 8, hipMemcpyDeviceToHost));
 	if (dists) HIPCHK(hipMemcpy(dists, dd, nq * k * 4, hipMemcpyDeviceToHost));
 	if (idx) HIPCHK(hipMemcpy(idx, di, nq * k * 4, hipMemcpyDeviceToHost));
 	HIPCHK(hipMemcpy(counts, dc, nq * 4, hipMemcpyDeviceToHost));
 	return HNSW_GPU_OK;
+}
+
+extern "C" int hnsw_gpu_filtered_knn(hnsw_gpu_index *ix, const coord_t *queries, size_t nq, size_t k, const uint32_t *allow, size_t allow_bits,
+									 size_t nfilters, const uint32_t *allow_of, label_t *labels, dist_t *dists, idx_t *idx, uint32_t *counts)
+{
+	return fk_host(ix, -1, queries, nq, k, allow, allow_bits, nfilters, allow_of, labels, dists, idx, counts);
+}
+
+extern "C" int hnsw_gpu_filtered_knn_mfma(hnsw_gpu_index *ix, int format, const coord_t *queries, size_t nq, size_t k, const uint32_t *allow,
+										  size_t allow_bits, size_t nfilters, const uint32_t *allow_of, label_t *labels, dist_t *dists, idx_t *idx,
+										  uint32_t *counts)
+{
+	if (format < 0) return fail(HNSW_GPU_ERR_ARG, "filtered k-NN: bad format %d", format);
+	return fk_host(ix, format, queries, nq, k, allow, allow_bits, nfilters, allow_of, labels, dists, idx, counts);
 }
 
 extern "C" int hnsw_gpu_last_filtered_knn(hnsw_gpu_index *ix, uint64_t out[4])
@@ -567,6 +839,25 @@ extern "C" int hnsw_gpu_last_filtered_knn(hnsw_gpu_index *ix, uint64_t out[4])
 	out[1] = ix->fk.scored;
 	out[2] = (uint64_t) std::llround((double) ix->fk.build_ms * 1000.0);
 	out[3] = (uint64_t) std::llround((double) ix->fk.scan_ms * 1000.0);
+	return HNSW_GPU_OK;
+}
+
+extern "C" int hnsw_gpu_last_filtered_knn_form(hnsw_gpu_index *ix)
+{
+	if (!ix) return -1;
+	std::lock_guard<std::recursive_mutex> lock_(ix->mu);
+	return ix->fk.form;
+}
+
+extern "C" int hnsw_gpu_last_filtered_knn_mfma(hnsw_gpu_index *ix, uint64_t out[7])
+{
+	if (!ix || !out) return fail(HNSW_GPU_ERR_ARG, "NULL argument");
+	std::lock_guard<std::recursive_mutex> lock_(ix->mu);
+	const FkWs::Mfma &m = ix->fk.m;
+	out[0] = m.listed; out[1] = m.scored; out[2] = m.dist_pass; out[3] = m.appended;
+	out[4] = (uint64_t) std::llround((double) m.build_ms * 1000.0);
+	out[5] = (uint64_t) std::llround((double) m.filter_ms * 1000.0);
+	out[6] = (uint64_t) std::llround((double) m.call_ms * 1000.0);
 	return HNSW_GPU_OK;
 }
 

@@ -410,13 +410,27 @@ class GpuIndex:
         return [{"active": int(act[r]), "ef": int(ef[r]), "search_ms": float(sm[r]), "handout_ms": float(hm[r])} for r in range(min(n.value, cap))]
 
     # ---------------------------------------------------------------- exact filtered k-NN
-    def filtered_knn(self, queries: np.ndarray, k: int, allow, allow_of=None, return_idx: bool = False):
+    @staticmethod
+    def _fk_form(form, rows) -> Optional[int]:
+        """None for the listed form, else the matrix-core form's operand code"""
+        if form in (None, "listed"):
+            if rows is not None:
+                raise ValueError("rows= names the operands of form=\"mfma\"")
+            return None
+        if form != "mfma":
+            raise ValueError('form is None, "listed" or "mfma"')
+        return _rows_code(rows)
+
+    def filtered_knn(self, queries: np.ndarray, k: int, allow, allow_of=None, return_idx: bool = False, form=None, rows=None):
         """Exact k nearest ALLOWED elements per query, host buffers (hnsw_gpu_filtered_knn): a canonical scan over the rows whose label
         passes the query's filter and that are not vacuumed — |allowed| rows of work per query, not the table.  allow (required) and
         allow_of as in scan().  Returns a dict: labels [nq, k] u64 in ascending (distance, label) order (tail ~0), dists [nq, k] f32
-        (tail +inf), counts [nq] u32 = min(k, allowed rows), and with return_idx=True idx [nq, k] u32 element numbers (tail 0xFFFFFFFF)."""
+        (tail +inf), counts [nq] u32 = min(k, allowed rows), and with return_idx=True idx [nq, k] u32 element numbers (tail 0xFFFFFFFF).
+        form="mfma": the same answer with the Q x N part on the matrix cores, for loose filters (hnsw_gpu_filtered_knn_mfma); rows=None |
+        "f16" | "bf16" names its operands (the f32 rows, or the reduced copy of set_reduced_rows)."""
         if allow is None:
             raise ValueError("filtered_knn needs an allow filter (bruteforce_torch takes none)")
+        code = self._fk_form(form, rows)
         queries = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, self.meta.dim)
         nq, k = queries.shape[0], int(k)
         words, bits, nf = _pack_allow_numpy(allow)
@@ -424,18 +438,22 @@ class GpuIndex:
         out = {"labels": np.empty((nq, k), np.uint64), "dists": np.empty((nq, k), np.float32), "counts": np.empty(nq, np.uint32)}
         if return_idx:
             out["idx"] = np.empty((nq, k), np.uint32)
-        check(self.L.hnsw_gpu_filtered_knn(self._h, queries.ctypes.data, nq, k, words.ctypes.data, bits, nf, None if of is None else of.ctypes.data,
-                                           out["labels"].ctypes.data, out["dists"].ctypes.data, out["idx"].ctypes.data if return_idx else None,
-                                           out["counts"].ctypes.data), "hnsw_gpu_filtered_knn")
+        tail = (queries.ctypes.data, nq, k, words.ctypes.data, bits, nf, None if of is None else of.ctypes.data, out["labels"].ctypes.data,
+                out["dists"].ctypes.data, out["idx"].ctypes.data if return_idx else None, out["counts"].ctypes.data)
+        if code is None:
+            check(self.L.hnsw_gpu_filtered_knn(self._h, *tail), "hnsw_gpu_filtered_knn")
+        else:
+            check(self.L.hnsw_gpu_filtered_knn_mfma(self._h, code, *tail), "hnsw_gpu_filtered_knn_mfma")
         return out
 
-    def filtered_knn_torch(self, queries, k: int, allow, allow_of=None, return_idx: bool = False):
+    def filtered_knn_torch(self, queries, k: int, allow, allow_of=None, return_idx: bool = False, form=None, rows=None):
         """filtered_knn() with everything resident in HBM (hnsw_gpu_filtered_knn_dev on torch's current stream, which the call
         synchronises).  allow: a bool tensor [allow_bits] / [nfilters, allow_bits] or an already packed int32 tensor; allow_of: an integer
         tensor [nq].  Returns a dict: labels [nq, k] int64 (tail -1), dists [nq, k] (tail +inf), counts [nq] int32, idx [nq, k] int32
-        (tail -1) with return_idx=True."""
+        (tail -1) with return_idx=True.  form / rows as in filtered_knn() (hnsw_gpu_filtered_knn_mfma_dev)."""
         if allow is None:
             raise ValueError("filtered_knn_torch needs an allow filter (bruteforce_torch takes none)")
+        code = self._fk_form(form, rows)
         torch = _torch()
         assert queries.is_cuda and queries.dtype == torch.float32 and queries.is_contiguous()
         nq, k, dev = queries.shape[0], int(k), queries.device
@@ -449,9 +467,12 @@ class GpuIndex:
         if return_idx:
             out["idx"] = torch.empty((nq, k), dtype=torch.int32, device=dev)
         s = torch.cuda.current_stream(dev).cuda_stream
-        check(self.L.hnsw_gpu_filtered_knn_dev(self._h, queries.data_ptr(), nq, k, words.data_ptr(), bits, nf, _dptr(of), out["labels"].data_ptr(),
-                                               out["dists"].data_ptr(), _dptr(out.get("idx")), out["counts"].data_ptr(), s),
-              "hnsw_gpu_filtered_knn_dev")
+        tail = (queries.data_ptr(), nq, k, words.data_ptr(), bits, nf, _dptr(of), out["labels"].data_ptr(), out["dists"].data_ptr(), _dptr(out.get("idx")),
+                out["counts"].data_ptr(), s)
+        if code is None:
+            check(self.L.hnsw_gpu_filtered_knn_dev(self._h, *tail), "hnsw_gpu_filtered_knn_dev")
+        else:
+            check(self.L.hnsw_gpu_filtered_knn_mfma_dev(self._h, code, *tail), "hnsw_gpu_filtered_knn_mfma_dev")
         return out
 
     def last_filtered_knn(self) -> dict:
@@ -460,6 +481,20 @@ class GpuIndex:
         v = (C.c_uint64 * 4)()
         check(self.L.hnsw_gpu_last_filtered_knn(self._h, v), "hnsw_gpu_last_filtered_knn")
         return {"listed": int(v[0]), "rows_scored": int(v[1]), "build_ms": v[2] / 1000.0, "scan_ms": v[3] / 1000.0}
+
+    def last_filtered_knn_form(self) -> Optional[str]:
+        """The form that answered the last filtered_knn call of either form on this mirror: "listed", "f32", "f16" or "bf16" (the MFMA
+        filters), or None before the first one (hnsw_gpu_last_filtered_knn_form)."""
+        return {0: "listed", 1: "f32", 2: "f16", 3: "bf16"}.get(int(self.L.hnsw_gpu_last_filtered_knn_form(self._h)))
+
+    def last_filtered_knn_mfma(self) -> dict:
+        """The last filter launch of a form="mfma" call on this mirror (hnsw_gpu_last_filtered_knn_mfma): entries of all allowed lists, rows
+        scored canonically for the bounds, (query, row) pairs that passed the distance comparison — before the allow test — and pairs
+        appended to a candidate list; list-build, filter and whole-call ms.  Zeros when the last call ran no filter."""
+        v = (C.c_uint64 * 7)()
+        check(self.L.hnsw_gpu_last_filtered_knn_mfma(self._h, v), "hnsw_gpu_last_filtered_knn_mfma")
+        return {"listed": int(v[0]), "rows_scored": int(v[1]), "dist_pass": int(v[2]), "appended": int(v[3]), "build_ms": v[4] / 1000.0,
+                "filter_ms": v[5] / 1000.0, "call_ms": v[6] / 1000.0}
 
     def last_search_ms(self, back: int = 0) -> float:
         """Device time of the search kernel launched `back` launches ago (HIP events recorded on
