@@ -16,8 +16,8 @@ extern "C" {
 #endif
 
 /* Diagnostics of the team form of the search kernel (launches with fewer queries than resident waves: idle
- * waves of a block pre-fetch link lists and distances for a sibling's walk).  With HNSW_GPU_TEAM_COUNTERS=1 in
- * the environment the last launch of the mirror's default workspace counted, over all its queries:
+ * waves of a block pre-fetch link lists and distances for a sibling's walk).  In a diagnostic
+ * build of the library (-DHNSW_TEAM_COUNTERS; all zero otherwise) the last launch of the mirror's default workspace counted, over all its queries:
  * out[0] hops that had helpers, [1] link lists served from a helper's cache, [2] neighbour ids looked up,
  * [3] distances served from a cache, [4] hops that still scored rows themselves, [5] all hops, [6] polls spent
  * waiting for a helper that had the element in flight, [10] hops that waited, [7]/[8]/[9] shader cycles of the
@@ -60,7 +60,7 @@ int hnsw_gpu_last_search_clock_mhz(hnsw_gpu_index *ix, double *mhz);
 
 /* Where the mirror and its default search workspace sit in the device's address space: out[2*i] = device address, out[2*i+1] =
  * bytes, for i = 0 arena (one allocation holding rows | links | labels, each on a 2 MiB boundary), 1 rows, 2 links, 3 labels,
- * 4 visited bitmaps, 5 bitmap logs, 6 prune scratch of the beam form, 7 ticket words.  `out` holds 16 values. */
+ * 4 visited bitmaps, 5 bitmap logs, 6 unused (0, 0: the beam form's prune needs no scratch), 7 ticket words.  `out` holds 16 values. */
 int hnsw_gpu_index_placement(hnsw_gpu_index *ix, uint64_t *out16);
 
 /* Shader clock (MHz) a block of the MFMA filter kernel of the last hnsw_gpu_bruteforce_mfma_dev call saw over its K loop:

@@ -291,5 +291,5 @@ def sync_env(force: bool = False) -> None:
             rc = L.hnsw_gpu_config_set(k.encode(), None if v is None else v.encode())
             if rc != 0 and v is not None:
                 msg = L.hnsw_gpu_last_error()
-                raise RuntimeError(f"{k}={v}: {msg.decode() if msg else rc} (knobs of rejected experiments exist only in -DHNSW_EXPERIMENT builds)")
+                raise RuntimeError(f"{k}={v}: {msg.decode() if msg else rc} (the library has no such knob, or refuses the value)")
     _env_seen = now

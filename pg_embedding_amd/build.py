@@ -84,10 +84,9 @@ HOST_UNITS = ("hnsw_gpu", "gpu_search", "gpu_stream", "gpu_scan", "gpu_build", "
 # libhnsw_gpu.so = these translation units, compiled in parallel and linked: the host code + its small kernels, the pair sort,
 # and the search kernels of one load shape each (csrc/search_inst.hip, -DSEARCH_INST_SHAPE=n) — as one unit the 220 search
 # kernel instantiations took hipcc five and a half minutes, like this the library builds in about two.
-def _gpu_units(defines):
+def _gpu_units():
     units = [(u, u + ".hip", []) for u in HOST_UNITS] + [("sort_pairs", "sort_pairs.hip", [])]
-    shapes = range(1, 7) if "HNSW_EXPERIMENT" in defines else range(1, 6)
-    return units + [(f"search_inst_{k}", "search_inst.hip", [f"-DSEARCH_INST_SHAPE={k}"]) for k in shapes]
+    return units + [(f"search_inst_{k}", "search_inst.hip", [f"-DSEARCH_INST_SHAPE={k}"]) for k in range(1, 6)]
 
 
 def _build_gpu_lib(target, sources, defines, force=False, verbose=False):
@@ -98,7 +97,7 @@ def _build_gpu_lib(target, sources, defines, force=False, verbose=False):
     objdir = os.path.join(LIBDIR, "obj", os.path.basename(target))
     os.makedirs(objdir, exist_ok=True)
     procs = []
-    for name, src, extra in _gpu_units(defines):
+    for name, src, extra in _gpu_units():
         obj = os.path.join(objdir, name + ".o")
         cmd = [_hipcc()] + flags + extra + ["-I", INC, "-I", CSRC, "-c", os.path.join(CSRC, src), "-o", obj]
         ud = _digest(sources, flags + extra + [src])         # per-object stamp: an unchanged unit is not recompiled
@@ -159,8 +158,6 @@ def build_variant(tag: str, defines) -> str:
     os.makedirs(vdir, exist_ok=True)
     out = os.path.join(vdir, f"libhnsw_gpu_{tag}.so")
     defines = list(defines)
-    if any(d.split("=")[0] in ("HNSW_TEAM_COUNTERS", "HNSW_HOP_STAMPS") for d in defines) and "HNSW_EXPERIMENT" not in defines:
-        defines.append("HNSW_EXPERIMENT")                   # diagnostic builds read every knob from the environment
     hdrs = [os.path.join(INC, h) for h in ("hnsw_abi.h", "hnsw_gpu.h", "hnsw_gpu_diag.h", "hnsw_gpu_shim.h", "hnsw_gpu_server.h")]
     host_only = ("hgs_io.h", "host_walk.h", "host_dist.h", "shim_cache.h")
     gpu_src = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h")) and f not in host_only] + hdrs

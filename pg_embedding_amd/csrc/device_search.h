@@ -13,9 +13,7 @@
 //                           elements in registers, every decision of the reference restated as a count
 //                           over it (banner further down); visited set = exact bucketed tag set in LDS
 //                           (banner at tagset_split) with the HBM bitmap behind it;
-//   hnsw_search_kernel_reg  (ef <= 256, fallback): result set sorted + candidate set unsorted, both in
-//                           registers;
-//   hnsw_search_kernel_lds  (any ef): both sets as unsorted arrays, in LDS or (large ef) in HBM;
+//   hnsw_search_kernel_lds  (any ef; device_search_generic.h): both sets as unsorted arrays, in LDS or (large ef) in HBM;
 //                           visited set = bitmap.
 //
 // Heaps.  The reference keeps two std::priority_queue<pair<float,idx>>:
@@ -36,12 +34,8 @@
 //   * beam form: bucketed tag set in LDS — 16-byte buckets of eight 16-bit tags, bucket and tag together are
 //     the id; one ds_read_b128 tests, one ds_cmpst inserts, whatever the fill; an id whose bucket is full
 //     lives in the HBM bitmap instead (exact, see the banner at tagset_split);
-//   * two-set register form: LDS hash set of 32-bit ids, open addressing, lock-free ds_cmpst insert = the
-//     test and the set of :91-93 in one LDS operation;
 //   * per-slot bitmap in HBM: returning atomic OR (safe when two neighbours share a word), bits
-//     undone through a log after the query.  It is the only set of the generic form; in the two-set
-//     register form it takes over from the hash set once that is 3/4 full (wide rows: both are consulted
-//     from then on; narrow rows: the hash set is flushed into the bitmap once).
+//     undone through a log after the query.  It is the only set of the generic form.
 // Link lists are de-duplicated at upload (first occurrence kept), which is behaviour-preserving
 // because a repeated id is always already visited when reached again in pass 2 (:89-93).
 #pragma once
@@ -86,11 +80,10 @@ struct SearchArgs
 	uint32_t *ticket;           // zeroed before every launch
 	// LDS carve (bytes, per wave)
 	uint32_t qpad_floats, off_res, off_cand, off_newid, off_newdist, wave_bytes;
-	// register form only: exact visited hash set in LDS (power-of-two entries, 0 = off); ids that
-	// arrive after it is hmax full go to the HBM bitmap instead
+	// beam form: its visited set in LDS at off_hash, hcap 16-bit tags (0 = off: the HBM bitmap alone).  hmax is unused (the removed two-set
+	// register form's fill limit): it keeps hmagic where it was — without it every team instantiation spills one more SGPR
 	uint32_t off_hash, hcap, hmax;
 	uint32_t hmagic;            // beam form: ceil(2^38 / buckets) of the bucketed set (hcap / 4 buckets of eight 16-bit tags)
-	uint64_t *beam_scratch;     // (unused since round 6: the beam form's prune compacts in registers; rounds 1-5: a per-slot HBM scratch line)
 	uint64_t *set_scratch;      // generic form with its sets in HBM: per-slot area, set_stride keys apart
 	uint32_t out_stride;        // result slots per query in the output arrays (the caller's ef; a.ef may be clamped to n)
 	size_t set_stride;
@@ -187,6 +180,36 @@ __device__ __forceinline__ void signal_done(uint32_t *flag, int lane, bool writt
 	if (lane == 0) __hip_atomic_store(flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
+// ---- phases every kernel form shares (`args` = the kernel's SearchArgs by address, or the beam kernel's ColdArgs) ----------
+
+// out_counts[qi] of a query that an aborted launch took a ticket for and did not answer
+template <typename Args>
+__device__ __forceinline__ void mark_aborted(Args args, uint32_t qi, int lane)
+{
+	if (lane == 0) args->out_counts[qi] = ABORTED_COUNT;
+}
+
+// Restore the slot's all-zero bitmap for its next query: through the undo log, or (log overflowed) word by word.  The next query's
+// atomics must see the zeros, so the stores are drained — always (generic and wide forms), or only when the walk put anything into
+// the bitmap at all (beam form: the result stores need no wait, the next query touches none of them).
+template <typename Args>
+__device__ __forceinline__ void restore_bitmap(uint32_t *vis, const uint32_t *vlog, uint32_t logn, uint32_t logcap, Args args, bool always_wait, int lane)
+{
+	if (logn <= logcap)
+	{
+		for (uint32_t i = lane; i < logn; i += 64) vis[vlog[i] >> 5] = 0u;
+	}
+	else
+	{
+		for (uint64_t w = lane, nw = args->vis_words; w < nw; w += 64) vis[w] = 0u;
+	}
+	if (always_wait || logn)
+	{
+		__builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+		__builtin_amdgcn_s_waitcnt(0);
+	}
+}
+
 __device__ __forceinline__ uint32_t ord_f32(float f)
 {
 	uint32_t u = __float_as_uint(f);
@@ -235,21 +258,7 @@ __device__ __forceinline__ uint32_t sorted_insert(uint64_t *A, uint32_t sz, uint
 
 
 
-// =====================================================================================
-// Register-resident form (ef <= 64*RREG, RREG in {2,4}): the hot configuration.
-//
-//   results    : SORTED ascending in RREG 64-bit registers per lane (index = reg*64 + lane,
-//                unused slots = ~0).  Insert = ballot-count for the position + one DPP
-//                wave_shr:1 shift; the worst element falls off the end.  No LDS, no waits.
-//   candidates : UNSORTED in 2*RREG registers per lane (capacity 128*RREG >= 2*ef, which the
-//                header comment proves sufficient).  Append = one lane write; pop-best = a
-//                per-lane min + a DPP wave-min of the distance word (ties on the distance
-//                resolved by a second min over ~idx).
-//   accept loop: lane r holds (dist, id) of new row r; rows that cannot beat the bound as
-//                it stood at the start of the hop are masked out with one ballot (the bound
-//                only decreases, so they would be rejected at their turn anyway) and the
-//                survivors are visited in link order via v_readlane.
-// =====================================================================================
+// ---- lane exchanges shared by every form -----------------------------------------------
 
 template <int CTRL, int ROW_MASK = 0xF>
 __device__ __forceinline__ uint32_t dpp_u32(uint32_t old, uint32_t v)
@@ -279,157 +288,11 @@ __device__ __forceinline__ uint64_t readlane_u64(uint64_t v, uint32_t l)
 	return ((uint64_t) hi << 32) | lo;
 }
 
-#ifdef HNSW_EXPERIMENT      // (helpers of the two-set register form: experiment builds only, see hnsw_search_kernel_reg)
-// value of lane-1 (lane 0 receives `fill`)
-__device__ __forceinline__ uint64_t wave_shr1_u64(uint64_t v, uint64_t fill)
-{
-	const uint32_t lo = dpp_u32<0x138>((uint32_t) fill, (uint32_t) v);              // wave_shr:1
-	const uint32_t hi = dpp_u32<0x138>((uint32_t) (fill >> 32), (uint32_t) (v >> 32));
-	return ((uint64_t) hi << 32) | lo;
-}
-
-// Insert into the sorted result registers.  Only registers at or above the insert position
-// change.  Capacity is 64*R >= ef: elements pushed past index ef-1 are not cleared — they were the
-// maximum when they fell off and the valid maximum only decreases afterwards, so they stay above
-// every valid key, never count in `p` for an accepted key, and are never read (rsize bounds all reads).
-template <int R>
-__device__ __forceinline__ void res_insert(uint64_t (&rk)[R], uint64_t key, int lane)
-{
-	uint32_t p = 0;
-#pragma unroll
-	for (int k = 0; k < R; k++) p += (uint32_t) __builtin_popcountll(__ballot(rk[k] < key));
-#pragma unroll
-	for (int k = R - 1; k >= 0; k--)
-	{
-		if (p < (uint32_t) (k + 1) * 64)          // wave-uniform: registers below the position are untouched
-		{
-			const uint64_t fill = (k > 0) ? readlane_u64(rk[k > 0 ? k - 1 : 0], 63) : 0ull;
-			const uint64_t prev = wave_shr1_u64(rk[k], fill);
-			const uint32_t i = (uint32_t) k * 64 + lane;
-			rk[k] = (i < p) ? rk[k] : ((i == p) ? key : prev);
-		}
-	}
-}
-
-// NOTE: every access below touches ALL registers of the array with compile-time indices and
-// picks by select.  Writing `if (k == sel) a[k] = ...` lets the optimiser fold the unrolled
-// chain back into a dynamically indexed a[sel], which forces the array into scratch memory.
-template <int R>
-__device__ __forceinline__ uint64_t res_at(const uint64_t (&rk)[R], uint32_t i)
-{
-	uint64_t out = 0;
-#pragma unroll
-	for (int k = 0; k < R; k++)
-	{
-		const uint64_t t = readlane_u64(rk[k], i & 63);
-		out = ((i >> 6) == (uint32_t) k) ? t : out;
-	}
-	return out;
-}
-
-template <int C>
-__device__ __forceinline__ void cand_set(uint64_t (&ck)[C], uint32_t slot, uint64_t key, int lane)
-{
-#pragma unroll
-	for (int k = 0; k < C; k++)
-	{
-		const bool hit = slot == ((uint32_t) k * 64 + (uint32_t) lane);
-		ck[k] = hit ? key : ck[k];
-	}
-}
-
-// Smallest key of the set; returns its slot through `slot`.  Set must be non-empty.
-template <int C>
-__device__ __forceinline__ uint64_t cand_min(const uint64_t (&ck)[C], uint32_t &slot)
-{
-	uint64_t m = ck[0];
-	uint32_t mk = 0;
-#pragma unroll
-	for (int k = 1; k < C; k++)
-	{
-		const bool lt = ck[k] < m;
-		m = lt ? ck[k] : m;
-		mk = lt ? (uint32_t) k : mk;
-	}
-	const uint32_t h = (uint32_t) (m >> 32);
-	const uint32_t hmin = wave_min_u32(h);
-	uint64_t eq = __ballot(h == hmin);
-	if (__builtin_popcountll(eq) > 1)                      // equal distances: larger idx first
-	{
-		const uint32_t lo = (h == hmin) ? (uint32_t) m : 0xFFFFFFFFu;
-		const uint32_t lomin = wave_min_u32(lo);
-		eq = __ballot(h == hmin && lo == lomin);
-	}
-	const uint32_t L = (uint32_t) __builtin_ctzll(eq);
-	slot = ((uint32_t) __builtin_amdgcn_readlane((int) mk, (int) L) << 6) | L;
-	return readlane_u64(m, L);
-}
-
-// Largest real key (set full): used only to make room when the candidate set overflows.
-template <int C>
-__device__ __forceinline__ uint64_t cand_max(const uint64_t (&ck)[C], uint32_t &slot)
-{
-	uint64_t m = ck[0];
-	uint32_t mk = 0;
-#pragma unroll
-	for (int k = 1; k < C; k++)
-	{
-		const bool gt = ck[k] > m;
-		m = gt ? ck[k] : m;
-		mk = gt ? (uint32_t) k : mk;
-	}
-	const uint32_t h = ~(uint32_t) (m >> 32);
-	const uint32_t hmin = wave_min_u32(h);
-	uint64_t eq = __ballot(h == hmin);
-	if (__builtin_popcountll(eq) > 1)
-	{
-		const uint32_t lo = (h == hmin) ? ~(uint32_t) m : 0xFFFFFFFFu;
-		const uint32_t lomin = wave_min_u32(lo);
-		eq = __ballot(h == hmin && lo == lomin);
-	}
-	const uint32_t L = (uint32_t) __builtin_ctzll(eq);
-	slot = ((uint32_t) __builtin_amdgcn_readlane((int) mk, (int) L) << 6) | L;
-	return readlane_u64(m, L);
-}
-
-
-#endif
-
-// ---- exact visited set in LDS: open addressing, linear probing, lock-free insert ------------
-constexpr uint32_t HASH_EMPTY = 0xFFFFFFFFu;     // never a valid element number (LINK_NONE)
-
+// hash of an element number into a power-of-two table (the helpers' distance memo, dc_lookup / dc_insert)
 __device__ __forceinline__ uint32_t hash_slot(uint32_t id, uint32_t mask)
 {
 	return ((id * 2654435761u) >> 7) & mask;
 }
-
-#ifdef HNSW_EXPERIMENT
-// true if `id` was not in the table (and is now); per-lane, lanes may collide on a slot
-__device__ __forceinline__ bool hash_test_and_set(uint32_t *tab, uint32_t mask, uint32_t id)
-{
-	uint32_t s = hash_slot(id, mask);
-	for (;;)
-	{
-		const uint32_t old = atomicCAS(&tab[s], HASH_EMPTY, id);
-		if (old == HASH_EMPTY) return true;
-		if (old == id) return false;
-		s = (s + 1) & mask;
-	}
-}
-
-__device__ __forceinline__ bool hash_contains(const uint32_t *tab, uint32_t mask, uint32_t id)
-{
-	uint32_t s = hash_slot(id, mask);
-	for (;;)
-	{
-		const uint32_t v = tab[s];
-		if (v == id) return true;
-		if (v == HASH_EMPTY) return false;
-		s = (s + 1) & mask;
-	}
-}
-
-#endif
 
 // ---- exact visited set in LDS, bucketed (beam form): 16-byte buckets of eight 16-bit tags ---------------
 // bucket = id % nb, tag = id / nb + 1 (0 = free slot): bucket and tag together ARE the id, so the set is
@@ -489,653 +352,6 @@ __device__ __forceinline__ bool tagset_contains(const uint32_t *tab, uint32_t nb
 	return tag_match(w, tag * 0x00010001u) != 0u;
 }
 
-// The two-set register form was the hot kernel of round 1; the beam form (further down) has dominated it since (40 % fewer VALU
-// instructions at 128 dims, 0.76 -> 0.62 ms for one query at 768 dims: profiles/r1i_beam_form.txt) and it had survived only as the
-// HNSW_GPU_BEAM=0 fallback and for mirrors of >= 2^31 elements.  Since round 5 those run the generic form below and this kernel is
-// compiled in experiment builds only (-DHNSW_EXPERIMENT): 30 instantiations fewer in the shipped library.
-#ifdef HNSW_EXPERIMENT
-template <int FUNC, typename SH, int RREG>
-__global__ __launch_bounds__(256, SH::MIN_WAVES) void hnsw_search_kernel_reg(const SearchArgs a)
-{
-	constexpr int CREG = 2 * RREG;
-	constexpr uint32_t CCAP = 64u * CREG;
-	extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-	const int lane = threadIdx.x & 63;
-	const uint32_t wib = threadIdx.x >> 6;
-	unsigned char *my = smem + (size_t) wib * a.wave_bytes;
-	float        *qf      = reinterpret_cast<float *>(my);
-	const float4 *q4      = reinterpret_cast<const float4 *>(my);
-	uint64_t     *tie_key = reinterpret_cast<uint64_t *>(my + a.off_res);     // tie path of the emit only
-	uint64_t     *tie_lab = reinterpret_cast<uint64_t *>(my + a.off_cand);    // (both overlay the hash set)
-	uint32_t     *htab    = reinterpret_cast<uint32_t *>(my + a.off_hash);
-	const uint32_t hmask  = a.hcap - 1;
-	uint32_t     *newid   = reinterpret_cast<uint32_t *>(my + a.off_newid);
-	float        *newdist = reinterpret_cast<float *>(my + a.off_newdist);
-
-	const uint32_t slot = blockIdx.x * (blockDim.x >> 6) + wib;
-	uint32_t *vis  = a.vis + (size_t) slot * a.vis_words;
-	uint32_t *vlog = a.vlog + (size_t) slot * a.logcap;
-	const uint32_t ef = a.ef;
-	bool aborted = false;              // the host asked this launch to end (abort word)
-
-	for (;;)
-	{
-		uint32_t qi = 0;
-		if (lane == 0) qi = atomicAdd(a.ticket, 1u);
-		qi = __builtin_amdgcn_readfirstlane(qi);
-		if (qi >= a.nq) break;
-		// (an abort request is sticky for this wave: it takes the remaining tickets without walking and marks every query it does not
-		// answer with count 0xFFFFFFFF, so that the caller of an interrupted launch can tell which rows of its outputs are results)
-		if (!aborted && (qi & a.abort_mask) == 0u && abort_requested(a)) aborted = true;
-		if (__builtin_amdgcn_readfirstlane((int) aborted)) { if (lane == 0) a.out_counts[qi] = ABORTED_COUNT; continue; }   // (wave-uniform by construction; said explicitly)
-		if (a.out_times && lane == 0) a.out_times[2 * (size_t) qi] = __builtin_amdgcn_s_memrealtime();
-
-		const float *qsrc = a.queries + (size_t) qi * a.q_stride;
-		for (uint32_t e = lane; e < a.qpad_floats; e += 64)
-		{
-			const float t = qsrc[e < a.dim ? e : a.dim - 1];
-			qf[e] = (e < a.dim) ? t : 0.f;
-		}
-		wave_sync();
-		float qnorm = 0.f;
-		if (FUNC == F_COSINE) qnorm = query_norm(q4, a.nchunks, a.kiters, lane);
-
-		uint64_t rk[RREG], ck[CREG];
-#pragma unroll
-		for (int k = 0; k < RREG; k++) rk[k] = ~0ull;
-#pragma unroll
-		for (int k = 0; k < CREG; k++) ck[k] = ~0ull;
-		uint32_t rsize = 0, csize = 0, logn = 0, evals = 0, hops = 0;
-		uint32_t hcount = 0;
-		bool spill = a.hcap == 0;            // true: visited ids go to the HBM bitmap
-		if (a.hcap)
-		{
-			uint4 *h4 = reinterpret_cast<uint4 *>(htab);
-			for (uint32_t i = lane; i < a.hcap / 4; i += 64) h4[i] = make_uint4(HASH_EMPTY, HASH_EMPTY, HASH_EMPTY, HASH_EMPTY);
-			wave_sync();
-		}
-
-		if (a.n > 0)
-		{
-			const uint32_t ep = a.entry;                                   // hnswalg.cpp:55-65
-			{
-				auto one = [ep](uint32_t) { return ep; };
-				score_rows<FUNC, SH::KB, 1>(a.vec, a.stride, q4, a.nchunks, a.kiters, one, 1u, newdist, lane);
-			}
-			wave_sync();
-			float lowerBound = finish_dist<FUNC>(newdist[0], newdist[OUT2], qnorm);
-			evals = 1;
-			if (a.out_evals && a.evals_cap && lane == 0) a.out_evals[(size_t) qi * a.evals_cap] = ep;
-			{
-				const uint64_t hi = (uint64_t) ord_f32(lowerBound) << 32;
-				res_insert<RREG>(rk, hi | ep, lane);
-				cand_set<CREG>(ck, 0, hi | (uint32_t) ~ep, lane);
-			}
-			if (lane == 0)
-			{
-				if (spill) { vis[ep >> 5] = 1u << (ep & 31); vlog[0] = ep; }
-				else htab[hash_slot(ep, hmask)] = ep;
-			}
-			rsize = csize = 1;
-			logn = spill ? 1 : 0;
-			hcount = 1;
-			wave_sync();
-
-			while (csize > 0)                                               // hnswalg.cpp:67-112
-			{
-				uint32_t cslot;
-				const uint64_t ckey = cand_min<CREG>(ck, cslot);
-				if (unord_f32((uint32_t) (ckey >> 32)) > lowerBound)        // :70-71
-					break;
-				const uint32_t cur = ~(uint32_t) ckey;
-				{                                                           // :73 pop = move last into the hole
-					const uint32_t last = csize - 1;
-					const uint64_t lastkey = res_at<CREG>(ck, last);
-					cand_set<CREG>(ck, cslot, lastkey, lane);
-					cand_set<CREG>(ck, last, ~0ull, lane);
-					csize = last;
-				}
-				if (a.out_pops && hops < a.pops_cap && lane == 0)       // (system scope: a host that polls the sequence sees it as the walk goes)
-					__hip_atomic_store(a.out_pops + (size_t) qi * a.pops_cap + hops, cur, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-				hops++;
-				if ((hops & 255u) == 0u && abort_requested(a)) { aborted = true; break; }
-
-				for (uint32_t j0 = 0; j0 < a.maxM; j0 += 64)               // :76-77
-				{
-					const uint32_t j = j0 + lane;
-					const uint32_t t = a.links[(size_t) cur * a.lstride + (j < a.lstride ? j : a.lstride - 1)];
-					bool isnew = false;
-					if (j < a.lstride && t != LINK_NONE)                    // :91-93 test-and-set
-					{
-						if (!spill)
-							isnew = hash_test_and_set(htab, hmask, t);
-						else if (!(a.hcap && hash_contains(htab, hmask, t)))
-						{
-							const uint32_t bit = 1u << (t & 31);
-							const uint32_t old = atomicOr(&vis[t >> 5], bit);
-							isnew = !(old & bit);
-						}
-					}
-					const uint64_t mask = __ballot(isnew);
-					const uint32_t nnew = (uint32_t) __builtin_popcountll(mask);
-					if (nnew == 0) continue;
-					const uint32_t rank = lane_rank(mask);
-					if (isnew)
-					{
-						newid[rank] = t;
-						if (a.out_evals && evals + rank < a.evals_cap) a.out_evals[(size_t) qi * a.evals_cap + evals + rank] = t;   // (measurement: the rows this walk scores, in order)
-						if (spill)                                          // only bitmap bits need undoing
-						{
-							const uint32_t lp = logn + rank;
-							if (lp < a.logcap) vlog[lp] = t;
-						}
-					}
-					if (spill) logn += nnew;
-					else
-					{
-						hcount += nnew;
-						if (hcount + 64 > a.hmax) spill = true;             // keep probe chains short: later ids -> bitmap
-					}
-					wave_sync();
-					{                                                       // :95-97, batched
-						const uint32_t *ids = newid;
-						auto by_id = [ids](uint32_t r) { return ids[r]; };
-						score_rows_fit<FUNC, SH::KB, SH::RPG>(a.vec, a.stride, q4, a.nchunks, a.kiters, by_id, nnew, newdist, lane);
-					}
-					evals += nnew;
-					wave_sync();
-					const float    d_mine = finish_dist<FUNC>(newdist[lane], newdist[OUT2 + lane], qnorm);   // lane r <- row r
-					const uint32_t t_mine = newid[lane];
-					uint64_t todo = __ballot((uint32_t) lane < nnew && (rsize < ef || lowerBound > d_mine));
-					while (todo)                                            // :99-108, in link order
-					{
-						const uint32_t r = (uint32_t) __builtin_ctzll(todo);
-						todo &= todo - 1;
-						const float d = __uint_as_float((uint32_t) __builtin_amdgcn_readlane((int) __float_as_uint(d_mine), (int) r));
-						if (rsize < ef || lowerBound > d)
-						{
-							const uint32_t t2 = (uint32_t) __builtin_amdgcn_readlane((int) t_mine, (int) r);
-							const uint64_t hi = (uint64_t) ord_f32(d) << 32;
-							if (csize == CCAP)                              // make room: the largest key is dead
-							{
-								uint32_t ms;
-								const uint64_t mx = cand_max<CREG>(ck, ms);
-								if ((hi | (uint32_t) ~t2) < mx) cand_set<CREG>(ck, ms, hi | (uint32_t) ~t2, lane);
-							}
-							else
-							{
-								cand_set<CREG>(ck, csize, hi | (uint32_t) ~t2, lane);   // :100
-								csize++;
-							}
-							res_insert<RREG>(rk, hi | t2, lane);            // :102-105
-							rsize = rsize < ef ? rsize + 1 : ef;
-							lowerBound = unord_f32((uint32_t) (res_at<RREG>(rk, rsize - 1) >> 32));   // :107
-						}
-					}
-					wave_sync();
-				}
-			}
-		}
-
-		if (__builtin_amdgcn_readfirstlane((int) aborted)) { if (lane == 0) a.out_counts[qi] = ABORTED_COUNT; continue; }      // interrupted inside its walk
-		if (a.out_times && lane == 0) a.out_times[2 * (size_t) qi + 1] = __builtin_amdgcn_s_memrealtime();
-		// ---- emit -------------------------------------------------------------------------
-		const size_t obase = (size_t) qi * a.out_stride;
-		uint32_t nout = 0;
-		if (a.mode == 1)
-		{
-#pragma unroll
-			for (int k = 0; k < RREG; k++)
-			{
-				const uint32_t i = (uint32_t) k * 64 + lane;
-				if (i < ef)
-				{
-					const bool ok = i < rsize;
-					a.out_idx[obase + i] = ok ? (uint32_t) rk[k] : LINK_NONE;
-					if (a.out_dists) a.out_dists[obase + i] = ok ? unord_f32((uint32_t) (rk[k] >> 32)) : __builtin_inff();
-				}
-			}
-			for (uint32_t i = ef + lane; i < a.out_stride; i += 64)     // caller's ef larger than the index
-			{
-				a.out_idx[obase + i] = LINK_NONE;
-				if (a.out_dists) a.out_dists[obase + i] = __builtin_inff();
-			}
-			nout = rsize;
-		}
-		else
-		{
-			// searchKnn, hnswalg.cpp:241-249
-			uint64_t lab[RREG];
-			bool tie = false;
-#pragma unroll
-			for (int k = 0; k < RREG; k++)
-			{
-				const uint32_t i = (uint32_t) k * 64 + lane;
-				lab[k] = a.labels[(i < rsize) ? (uint32_t) rk[k] : 0];
-				const uint64_t fill = (k > 0) ? readlane_u64(rk[k > 0 ? k - 1 : 0], 63) : 0ull;
-				const uint64_t prev = wave_shr1_u64(rk[k], fill);
-				if (i > 0 && i < rsize && (uint32_t) (prev >> 32) == (uint32_t) (rk[k] >> 32)) tie = true;
-			}
-			if (__ballot(tie) == 0)
-			{
-#pragma unroll
-				for (int k = 0; k < RREG; k++)
-				{
-					const uint32_t i = (uint32_t) k * 64 + lane;
-					const bool keep = i < rsize && !((lab[k] >> 48) & 1);
-					const uint64_t kmask = __ballot(keep);
-					if (keep)
-					{
-						const uint32_t rank = nout + lane_rank(kmask);
-						a.out_labels[obase + rank] = lab[k];
-						if (a.out_dists) a.out_dists[obase + rank] = unord_f32((uint32_t) (rk[k] >> 32));
-					}
-					nout += (uint32_t) __builtin_popcountll(kmask);
-				}
-			}
-			else
-			{
-				// equal distances present: order by (dist, label) through LDS (hnswalg.cpp:236,246)
-#pragma unroll
-				for (int k = 0; k < RREG; k++)
-				{
-					const uint32_t i = (uint32_t) k * 64 + lane;
-					if (i < rsize) { tie_key[i] = rk[k]; tie_lab[i] = lab[k]; }
-				}
-				wave_sync();
-#pragma unroll
-				for (int k = 0; k < RREG; k++)
-				{
-					const uint32_t i = (uint32_t) k * 64 + lane;
-					const bool keep = i < rsize && !((lab[k] >> 48) & 1);
-					const uint32_t di = (uint32_t) (rk[k] >> 32);
-					uint32_t rank = 0;
-					for (uint32_t jx = 0; jx < rsize; jx++)
-					{
-						const uint64_t lj = tie_lab[jx];
-						const uint32_t dj = (uint32_t) (tie_key[jx] >> 32);
-						const bool kj = !((lj >> 48) & 1);
-						rank += (kj && (dj < di || (dj == di && lj < lab[k]))) ? 1u : 0u;
-					}
-					if (keep)
-					{
-						a.out_labels[obase + rank] = lab[k];
-						if (a.out_dists) a.out_dists[obase + rank] = unord_f32(di);
-					}
-					nout += (uint32_t) __builtin_popcountll(__ballot(keep));
-				}
-			}
-			for (uint32_t i = nout + lane; i < a.out_stride; i += 64)
-			{
-				a.out_labels[obase + i] = ~0ull;
-				if (a.out_dists) a.out_dists[obase + i] = __builtin_inff();
-			}
-		}
-		if (lane == 0)
-		{
-			a.out_counts[qi] = nout;
-			if (a.out_stats) { a.out_stats[2 * (size_t) qi] = evals; a.out_stats[2 * (size_t) qi + 1] = hops; }
-		}
-		if (a.done) signal_done(a.done + qi, lane);
-
-		// ---- restore the all-zero bitmap ---------------------------------------------------
-		wave_sync();
-		if (logn <= a.logcap)
-		{
-			for (uint32_t i = lane; i < logn; i += 64) vis[vlog[i] >> 5] = 0u;
-		}
-		else
-		{
-			for (uint64_t w = lane; w < a.vis_words; w += 64) vis[w] = 0u;
-		}
-		__builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-		__builtin_amdgcn_s_waitcnt(0);
-		wave_sync();
-	}
-	if (aborted && lane == 0) atomicAdd(a.health + HEALTH_ABORTED_WAVES, 1u);
-}
-
-
-#endif      // HNSW_EXPERIMENT (two-set register form)
-
-// =====================================================================================
-// Generic form (any ef; used when ef > 256): both sets as UNSORTED arrays in LDS.
-//   results    : res[0..rsize) + the position of the largest key kept wave-uniformly.  Insert while
-//                not full = append; when full = overwrite the largest and rescan for the new largest
-//                (ceil(ef/64) LDS reads per lane + one DPP wave-min).
-//   candidates : cand[0..csize), capacity 2*ef (exact, see the header).  Append = one LDS write;
-//                pop-best = scan for the smallest key, move the last entry into the hole.
-//   emit       : rank sort by (dist, idx) or (dist, label) — O(ef^2/64) per query, a few percent
-//                of a traversal that long.
-// Visited set = the per-slot HBM bitmap.  Same pre-filtered accept loop as the register form.
-// =====================================================================================
-
-// Set-array accessors.  G = false: LDS, plain accesses.  G = true: HBM scratch, accessed with relaxed
-// agent-scope atomics = L1-bypassing loads/stores, so that a wave always reads back its own writes from L2
-// (loads still pipeline: the scans below issue four before the first use).
-template <bool G>
-__device__ __forceinline__ uint64_t ldk(const uint64_t *p)
-{
-	if (G) return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-	return *p;
-}
-template <bool G>
-__device__ __forceinline__ void stk(uint64_t *p, uint64_t v)
-{
-	if (G) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-	else *p = v;
-}
-
-// Smallest (MIN=true) or largest key of A[0..n) and its position; n > 0; wave-uniform result.
-template <bool MIN, bool G>
-__device__ __forceinline__ uint64_t lds_extreme(const uint64_t *A, uint32_t n, uint32_t &pos, int lane)
-{
-	uint64_t best = MIN ? ~0ull : 0ull;
-	uint32_t bpos = 0;
-	for (uint32_t i0 = 0; i0 < n; i0 += 256)
-	{
-		uint64_t k[4];
-#pragma unroll
-		for (int u = 0; u < 4; u++)
-		{
-			const uint32_t i = i0 + 64u * u + lane;
-			k[u] = ldk<G>(&A[i < n ? i : n - 1]);
-		}
-#pragma unroll
-		for (int u = 0; u < 4; u++)
-		{
-			const uint32_t i = i0 + 64u * u + lane;
-			const bool better = i < n && (MIN ? (k[u] < best) : (k[u] > best));
-			best = better ? k[u] : best;
-			bpos = better ? i : bpos;
-		}
-	}
-	// reduce on the distance word, then on the low word among the lanes that tie on it
-	const uint32_t h = MIN ? (uint32_t) (best >> 32) : ~(uint32_t) (best >> 32);
-	const uint32_t hmin = wave_min_u32(h);
-	uint64_t eq = __ballot(h == hmin);
-	if (__builtin_popcountll(eq) > 1)
-	{
-		const uint32_t lo = (h == hmin) ? (MIN ? (uint32_t) best : ~(uint32_t) best) : 0xFFFFFFFFu;
-		const uint32_t lomin = wave_min_u32(lo);
-		eq = __ballot(h == hmin && lo == lomin);
-	}
-	const uint32_t L = (uint32_t) __builtin_ctzll(eq);
-	pos = (uint32_t) __builtin_amdgcn_readlane((int) bpos, (int) L);
-	return readlane_u64(best, L);
-}
-
-// Make this wave's own writes to the set arrays visible to its own later reads.  LDS: program order +
-// lgkmcnt.  HBM (G): the accesses bypass L1 (ldk/stk), so draining vmcnt is enough.
-template <bool G>
-__device__ __forceinline__ void set_sync()
-{
-	if (G)
-	{
-		__builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-		__builtin_amdgcn_s_waitcnt(0);
-	}
-	wave_sync();
-}
-
-// G = false: result/candidate arrays in LDS (ef up to what 160 KB hold).  G = true: the same arrays in a
-// per-slot HBM scratch area — any ef the API admits (the reference's scan doubles efSearch until the
-// index is exhausted, embedding.c:329-343), at L2 latency per scan instead of LDS latency.
-template <int FUNC, typename SH, bool G>
-__global__ __launch_bounds__(256) void hnsw_search_kernel_lds(const SearchArgs a)
-{
-	extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-	const int lane = threadIdx.x & 63;
-	const uint32_t wib = threadIdx.x >> 6;
-	unsigned char *my = smem + (size_t) wib * a.wave_bytes;
-	float        *qf      = reinterpret_cast<float *>(my);
-	const float4 *q4      = reinterpret_cast<const float4 *>(my);
-	uint32_t     *newid   = reinterpret_cast<uint32_t *>(my + a.off_newid);
-	float        *newdist = reinterpret_cast<float *>(my + a.off_newdist);
-
-	const uint32_t slot = blockIdx.x * (blockDim.x >> 6) + wib;
-	uint64_t *res, *cand;
-	if (G)
-	{
-		res  = a.set_scratch + (size_t) slot * a.set_stride;
-		cand = res + a.off_cand;                        // G: off_cand counts keys inside the slot's area
-	}
-	else
-	{
-		res  = reinterpret_cast<uint64_t *>(my + a.off_res);
-		cand = reinterpret_cast<uint64_t *>(my + a.off_cand);
-	}
-	uint32_t *vis  = a.vis + (size_t) slot * a.vis_words;
-	uint32_t *vlog = a.vlog + (size_t) slot * a.logcap;
-	const uint32_t ef = a.ef;
-	bool aborted = false;              // the host asked this launch to end (abort word)
-
-	for (;;)
-	{
-		uint32_t qi = 0;
-		if (lane == 0) qi = atomicAdd(a.ticket, 1u);
-		qi = __builtin_amdgcn_readfirstlane(qi);
-		if (qi >= a.nq) break;
-		// (an abort request is sticky for this wave: it takes the remaining tickets without walking and marks every query it does not
-		// answer with count 0xFFFFFFFF, so that the caller of an interrupted launch can tell which rows of its outputs are results)
-		if (!aborted && (qi & a.abort_mask) == 0u && abort_requested(a)) aborted = true;
-		if (__builtin_amdgcn_readfirstlane((int) aborted)) { if (lane == 0) a.out_counts[qi] = ABORTED_COUNT; continue; }   // (wave-uniform by construction; said explicitly)
-		if (a.out_times && lane == 0) a.out_times[2 * (size_t) qi] = __builtin_amdgcn_s_memrealtime();
-
-		const float *qsrc = a.queries + (size_t) qi * a.q_stride;
-		for (uint32_t e = lane; e < a.qpad_floats; e += 64)
-		{
-			const float t = qsrc[e < a.dim ? e : a.dim - 1];     // unconditional load, then select
-			qf[e] = (e < a.dim) ? t : 0.f;
-		}
-		set_sync<G>();
-		float qnorm = 0.f;
-		if (FUNC == F_COSINE) qnorm = query_norm(q4, a.nchunks, a.kiters, lane);
-
-		uint32_t rsize = 0, csize = 0, logn = 0, evals = 0, hops = 0;
-		uint32_t rmax_pos = 0;
-
-		if (a.n > 0)      // empty index: hnsw_begin_read(entry) fails, hnswalg.cpp:56-57
-		{
-			const uint32_t ep = a.entry;                                   // hnswalg.cpp:55-65
-			{
-				auto one = [ep](uint32_t) { return ep; };
-				score_rows<FUNC, SH::KB, 1>(a.vec, a.stride, q4, a.nchunks, a.kiters, one, 1u, newdist, lane);
-			}
-			set_sync<G>();
-			float lowerBound = finish_dist<FUNC>(newdist[0], newdist[OUT2], qnorm);
-			evals = 1;
-			if (a.out_evals && a.evals_cap && lane == 0) a.out_evals[(size_t) qi * a.evals_cap] = ep;
-			if (lane == 0)
-			{
-				const uint32_t o = ord_f32(lowerBound);
-				stk<G>(&res[0], ((uint64_t) o << 32) | ep);
-				stk<G>(&cand[0], ((uint64_t) o << 32) | (uint32_t) ~ep);
-				vis[ep >> 5] = 1u << (ep & 31);       // slot bitmap is all-zero here
-				vlog[0] = ep;
-			}
-			rsize = csize = logn = 1;
-			set_sync<G>();
-
-			while (csize > 0)                                               // hnswalg.cpp:67-112
-			{
-				uint32_t cpos;
-				const uint64_t ck = lds_extreme<true, G>(cand, csize, cpos, lane);
-				if (unord_f32((uint32_t) (ck >> 32)) > lowerBound)         // :70-71
-					break;
-				const uint32_t cur = ~(uint32_t) ck;
-				csize--;                                                    // :73 pop = last entry into the hole
-				if (lane == 0) stk<G>(&cand[cpos], ldk<G>(&cand[csize]));
-				set_sync<G>();
-				if (a.out_pops && hops < a.pops_cap && lane == 0)       // (system scope: a host that polls the sequence sees it as the walk goes)
-					__hip_atomic_store(a.out_pops + (size_t) qi * a.pops_cap + hops, cur, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-				hops++;
-				if ((hops & 255u) == 0u && abort_requested(a)) { aborted = true; break; }
-
-				for (uint32_t j0 = 0; j0 < a.maxM; j0 += 64)               // :76-77
-				{
-					const uint32_t j = j0 + lane;
-					const uint32_t t = a.links[(size_t) cur * a.lstride + (j < a.lstride ? j : a.lstride - 1)];
-					bool isnew = false;
-					if (j < a.lstride && t != LINK_NONE)                    // :91-93 test-and-set
-					{
-						const uint32_t bit = 1u << (t & 31);
-						const uint32_t old = atomicOr(&vis[t >> 5], bit);
-						isnew = !(old & bit);
-					}
-					const uint64_t mask = __ballot(isnew);
-					const uint32_t nnew = (uint32_t) __builtin_popcountll(mask);
-					if (nnew == 0) continue;
-					const uint32_t rank = lane_rank(mask);
-					if (isnew)
-					{
-						newid[rank] = t;
-						if (a.out_evals && evals + rank < a.evals_cap) a.out_evals[(size_t) qi * a.evals_cap + evals + rank] = t;   // (measurement: the rows this walk scores, in order)
-						const uint32_t lp = logn + rank;
-						if (lp < a.logcap) vlog[lp] = t;
-					}
-					logn += nnew;
-					set_sync<G>();
-					{                                                       // :95-97, batched
-						const uint32_t *ids = newid;
-						auto by_id = [ids](uint32_t r) { return ids[r]; };
-						score_rows_fit<FUNC, SH::KB, SH::RPG>(a.vec, a.stride, q4, a.nchunks, a.kiters, by_id, nnew, newdist, lane);
-					}
-					evals += nnew;
-					set_sync<G>();
-					const float    d_mine = finish_dist<FUNC>(newdist[lane], newdist[OUT2 + lane], qnorm);
-					const uint32_t t_mine = newid[lane];
-					uint64_t todo = __ballot((uint32_t) lane < nnew && (rsize < ef || lowerBound > d_mine));
-					while (todo)                                            // :99-108, in link order
-					{
-						const uint32_t r = (uint32_t) __builtin_ctzll(todo);
-						todo &= todo - 1;
-						const float d = __uint_as_float((uint32_t) __builtin_amdgcn_readlane((int) __float_as_uint(d_mine), (int) r));
-						if (!(rsize < ef || lowerBound > d)) continue;
-						const uint32_t t2 = (uint32_t) __builtin_amdgcn_readlane((int) t_mine, (int) r);
-						const uint64_t hi = (uint64_t) ord_f32(d) << 32;
-						const uint64_t ckey = hi | (uint32_t) ~t2, rkey = hi | t2;
-						if (csize == a.ccap)                                // :100; make room: the largest key is dead
-						{
-							uint32_t mp;
-							const uint64_t mx = lds_extreme<false, G>(cand, csize, mp, lane);
-							if (ckey < mx && lane == 0) stk<G>(&cand[mp], ckey);
-						}
-						else
-						{
-							if (lane == 0) stk<G>(&cand[csize], ckey);
-							csize++;
-						}
-						if (rsize < ef)                                     // :102
-						{
-							if (lane == 0) stk<G>(&res[rsize], rkey);
-							rsize++;
-							set_sync<G>();
-							if (rsize == 1 || rkey > ldk<G>(&res[rmax_pos])) rmax_pos = rsize - 1;
-						}
-						else                                                // :104-105 evict the largest
-						{
-							if (lane == 0) stk<G>(&res[rmax_pos], rkey);
-							set_sync<G>();
-							(void) lds_extreme<false, G>(res, rsize, rmax_pos, lane);
-						}
-						set_sync<G>();
-						lowerBound = unord_f32((uint32_t) (ldk<G>(&res[rmax_pos]) >> 32));   // :107
-					}
-					set_sync<G>();
-				}
-			}
-		}
-
-		if (__builtin_amdgcn_readfirstlane((int) aborted)) { if (lane == 0) a.out_counts[qi] = ABORTED_COUNT; continue; }      // interrupted inside its walk
-		if (a.out_times && lane == 0) a.out_times[2 * (size_t) qi + 1] = __builtin_amdgcn_s_memrealtime();
-		// ---- emit: rank-sort the unsorted result array ----------------------------------------
-		// (G: the arrays are final now; drop this CU's L1 copies of them once — an earlier query of this slot
-		// read them through L1 here — and read them with plain, freely pipelined loads)
-		if (G) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-		const size_t obase = (size_t) qi * a.out_stride;
-		uint32_t nout = 0;
-		if (a.mode == 1)
-		{
-			for (uint32_t b = 0; b < rsize; b += 64)
-			{
-				const uint32_t i = b + lane;
-				if (i < rsize)
-				{
-					const uint64_t k = res[i];
-					uint32_t rank = 0;
-					for (uint32_t jx = 0; jx < rsize; jx++) rank += (res[jx] < k) ? 1u : 0u;
-					a.out_idx[obase + rank] = (uint32_t) k;
-					if (a.out_dists) a.out_dists[obase + rank] = unord_f32((uint32_t) (k >> 32));
-				}
-			}
-			nout = rsize;
-			for (uint32_t i = nout + lane; i < a.out_stride; i += 64)
-			{
-				a.out_idx[obase + i] = LINK_NONE;
-				if (a.out_dists) a.out_dists[obase + i] = __builtin_inff();
-			}
-		}
-		else
-		{
-			// searchKnn, hnswalg.cpp:241-249: label lookup, vacuum filter, order by (dist, label)
-			uint64_t *lab = cand;                       // candidate array is dead now (capacity 2*ef)
-			for (uint32_t i = lane; i < rsize; i += 64) lab[i] = a.labels[(uint32_t) res[i]];
-			set_sync<G>();
-			if (G) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");     // lab[] is read through L1 below
-			for (uint32_t b = 0; b < rsize; b += 64)
-			{
-				const uint32_t i = b + lane;
-				const bool in = i < rsize;
-				const uint64_t li = in ? lab[i] : 0;
-				const uint32_t di = in ? (uint32_t) (res[i] >> 32) : 0;
-				const bool keep = in && !((li >> 48) & 1);           // hnsw_is_deleted, embedding.c:948-953
-				uint32_t rank = 0;
-				for (uint32_t jx = 0; jx < rsize; jx++)              // rank by (dist, label), hnswalg.cpp:236,246
-				{
-					const uint64_t lj = lab[jx];
-					const uint32_t dj = (uint32_t) (res[jx] >> 32);
-					const bool kj = !((lj >> 48) & 1);
-					rank += (kj && (dj < di || (dj == di && lj < li))) ? 1u : 0u;
-				}
-				if (keep)
-				{
-					a.out_labels[obase + rank] = li;
-					if (a.out_dists) a.out_dists[obase + rank] = unord_f32(di);
-				}
-				nout += (uint32_t) __builtin_popcountll(__ballot(keep));
-			}
-			for (uint32_t i = nout + lane; i < a.out_stride; i += 64)          // pad the tail
-			{
-				a.out_labels[obase + i] = ~0ull;
-				if (a.out_dists) a.out_dists[obase + i] = __builtin_inff();
-			}
-		}
-		if (lane == 0)
-		{
-			a.out_counts[qi] = nout;
-			if (a.out_stats) { a.out_stats[2 * (size_t) qi] = evals; a.out_stats[2 * (size_t) qi + 1] = hops; }
-		}
-		if (a.done) signal_done(a.done + qi, lane);
-
-		// ---- restore the all-zero bitmap for the next query of this slot --------------
-		set_sync<G>();
-		if (logn <= a.logcap)
-		{
-			for (uint32_t i = lane; i < logn; i += 64) vis[vlog[i] >> 5] = 0u;
-		}
-		else
-		{
-			for (uint64_t w = lane; w < a.vis_words; w += 64) vis[w] = 0u;
-		}
-		__builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-		__builtin_amdgcn_s_waitcnt(0);   // drain: the next query's atomics must see the zeros
-		set_sync<G>();
-	}
-	if (aborted && lane == 0) atomicAdd(a.health + HEALTH_ABORTED_WAVES, 1u);
-}
-
-
 // =====================================================================================
 // Beam form (ef <= 64*UREG/2): ONE unsorted set of accepted elements, acceptance by counting.
 //
@@ -1155,7 +371,7 @@ __global__ __launch_bounds__(256) void hnsw_search_kernel_lds(const SearchArgs a
 // slot, and NO sorted insert and NO second set:
 //   accept test = UREG compares + ballots; append = one slot write; pop = masked min-scan;
 //   prune (when the 64*UREG slots are full): 32-step radix select of the ef-th smallest distance word,
-//   compaction in registers (ds_permute; rounds 1-5: through a per-slot HBM scratch line), once per ~ef accepts.
+//   compaction in registers (ds_permute), once per ~ef accepts.
 // Output order is produced at the end by a rank sort over the <= ef survivors.
 // =====================================================================================
 
@@ -1261,10 +477,6 @@ __device__ __forceinline__ uint32_t wave_or_u32(uint32_t v)
 template <int U>
 __device__ __forceinline__ uint32_t beam_select(const uint64_t (&uk)[U], uint32_t ef)
 {
-#ifdef HNSW_OLD_SELECT
-	int top = 31;
-	uint32_t prefix = 0, need = ef;
-#else
 	const uint32_t ref = (uint32_t) __builtin_amdgcn_readlane((int) (uint32_t) (uk[0] >> 32), 0);     // slot 0 is always in use
 	uint32_t diff = 0;
 #pragma unroll
@@ -1277,7 +489,6 @@ __device__ __forceinline__ uint32_t beam_select(const uint64_t (&uk)[U], uint32_
 	if (diff == 0u) return ref;                                     // every used slot holds the same distance word
 	const int top = 31 - __builtin_clz(diff);
 	uint32_t prefix = top == 31 ? 0u : ref & ~((2u << top) - 1u), need = ef;
-#endif
 	for (int bit = top; bit >= 0; bit--)
 	{
 		uint32_t c = 0;
@@ -1291,15 +502,12 @@ __device__ __forceinline__ uint32_t beam_select(const uint64_t (&uk)[U], uint32_
 
 // Drop every element whose distance word exceeds `v`; survivors keep their expanded bits and are
 // compacted to slots 0..n-1.  Returns n.
-#ifndef HNSW_OLD_COMPACT
-// (round 6: in registers.  Register k's survivors go to slots base .. base + n - 1: every lane pushes its key with ds_permute — a survivor to the
+// (In registers.  Register k's survivors go to slots base .. base + n - 1: every lane pushes its key with ds_permute — a survivor to the
 // lane that owns its slot, the others to the lanes behind, a permutation — and a lane keeps what it received if that is one of the n survivors, in
-// the register its slot belongs to (two candidates per source register).  Rounds 1-5 went through a per-slot HBM scratch line: two memory round
-// trips per prune, ~5 prunes per walk.  `scratch` is unused.)
+// the register its slot belongs to (two candidates per source register).)
 template <int U>
-__device__ __forceinline__ uint32_t beam_compact(uint64_t (&uk)[U], uint32_t &ex, uint32_t v, uint64_t *scratch, int lane)
+__device__ __forceinline__ uint32_t beam_compact(uint64_t (&uk)[U], uint32_t &ex, uint32_t v, int lane)
 {
-	(void) scratch;
 	uint64_t nk[U];
 #pragma unroll
 	for (int k = 0; k < U; k++) nk[k] = ~0ull;
@@ -1336,38 +544,6 @@ __device__ __forceinline__ uint32_t beam_compact(uint64_t (&uk)[U], uint32_t &ex
 	}
 	return base;
 }
-#else
-template <int U>
-__device__ __forceinline__ uint32_t beam_compact(uint64_t (&uk)[U], uint32_t &ex, uint32_t v, uint64_t *scratch, int lane)
-{
-	uint32_t base = 0;
-#pragma unroll
-	for (int k = 0; k < U; k++)
-	{
-		const bool keep = (uint32_t) (uk[k] >> 32) <= v && (uint32_t) (uk[k] >> 32) != 0xFFFFFFFFu;
-		const uint64_t mask = __ballot(keep);
-		// expanded bit travels in bit 31 of the idx word (element numbers stay below 2^31 in this form)
-		if (keep) scratch[base + lane_rank(mask)] = uk[k] | ((uint64_t) ((ex >> k) & 1u) << 31);
-		base += (uint32_t) __builtin_popcountll(mask);
-	}
-	// same wave, same L2: the stores are acknowledged by L2 once vmcnt drains, and the loads below
-	// bypass L1 — no cache writeback needed (an agent-scope release costs a full L2 writeback on gfx950)
-	__builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-	__builtin_amdgcn_s_waitcnt(0);
-	ex = 0;
-#pragma unroll
-	for (int k = 0; k < U; k++)
-	{
-		const uint32_t i = (uint32_t) k * 64 + lane;
-		uint64_t t = ~0ull;
-		if (i < base) t = __hip_atomic_load(&scratch[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // L1-bypassing load
-		const bool used = i < base;
-		ex |= (used && ((t >> 31) & 1u)) ? (1u << k) : 0u;
-		uk[k] = used ? (t & ~(1ull << 31)) : ~0ull;
-	}
-	return base;
-}
-#endif
 
 template <int U>
 __device__ __forceinline__ void beam_set(uint64_t (&uk)[U], uint32_t slot, uint64_t key, int lane)
@@ -1406,7 +582,8 @@ __device__ __forceinline__ void beam_set(uint64_t (&uk)[U], uint32_t slot, uint6
 // only makes a helper fetch something useless.  Outputs, E_q and H_q equal the one-wave form
 // (tests/test_gpu_search.py::test_every_kernel_variant_is_exact, ::test_team_form_is_exact_at_every_launch_size).
 // =====================================================================================
-// launch-wide diagnostics of the team form (hnsw_gpu_team_counters): compiled in only with -DHNSW_TEAM_COUNTERS —
+// launch-wide diagnostics of the team form (hnsw_gpu_team_counters): compiled in only with -DHNSW_TEAM_COUNTERS (a variant build of its own:
+// both write team_dbg[0..12], so one build takes one of the two) —
 // the cycle stamps and global atomics cost ~15 % of a single-query walk
 #ifdef HNSW_TEAM_COUNTERS
 constexpr bool TEAM_COUNT = true;
@@ -1414,7 +591,7 @@ constexpr bool TEAM_COUNT = true;
 constexpr bool TEAM_COUNT = false;
 #endif
 // per-section cycle stamps of the walking wave (any beam kernel): compiled in only with -DHNSW_HOP_STAMPS
-// (scripts/build_variant.sh); sums in units of 64 cycles land in team_dbg[0..7]
+// (python pg_embedding_amd/build.py variant <tag> HNSW_HOP_STAMPS); HopDiag below.  A diagnostic build always has team_dbg (launch_search).
 #ifdef HNSW_HOP_STAMPS
 constexpr bool HOP_STAMPS = true;
 #else
@@ -1427,6 +604,46 @@ __device__ __forceinline__ uint32_t hop_stamp()
 	__builtin_amdgcn_sched_barrier(0);
 	return t;
 }
+// What a -DHNSW_HOP_STAMPS build measures on a walking wave: cycles per section of a hop (a section ends at its mark) and what the
+// accept section does per hop.  flush() adds one query's sums to team_dbg: [0] hops, [1..5] the sections in units of 64 cycles,
+// [6] query start .. walk over (incl. set-up and entry point), [7] emit + bitmap clean-up, [8..15] the counters in the order below
+// (pg_embedding_amd/index.py debug_counters, profiles/r5_hop_budget.md).  The product's HopDiag<false> is empty.
+enum : int { HS_POP, HS_LINK, HS_VIS, HS_SCORE, HS_ACC, HS_SECTIONS };
+enum : int { HC_NEW, HC_TODO, HC_ITER, HC_ACC, HC_FAST, HC_PRUNE, HC_PASS2, HC_ACC_LOOP, HC_COUNTERS };
+template <bool ON>
+struct HopDiag
+{
+	__device__ __forceinline__ void query_start() {}
+	__device__ __forceinline__ void hop_start() {}
+	__device__ __forceinline__ void drain() {}
+	__device__ __forceinline__ void mark(int) {}
+	__device__ __forceinline__ void count(int, uint32_t) {}
+	__device__ __forceinline__ void walk_over() {}
+	__device__ __forceinline__ void flush(uint32_t *, uint32_t, int) {}
+};
+template <>
+struct HopDiag<true>
+{
+	uint32_t sec[HS_SECTIONS] = {}, cnt[HC_COUNTERS] = {}, q0 = 0, t0 = 0, walk = 0;
+	__device__ __forceinline__ void query_start() { q0 = hop_stamp(); }
+	__device__ __forceinline__ void hop_start() { t0 = hop_stamp(); }
+	__device__ __forceinline__ void drain() { __builtin_amdgcn_s_waitcnt(0); }      // (a section that ends when its loads have arrived)
+	__device__ __forceinline__ void mark(int section) { const uint32_t t1 = hop_stamp(); sec[section] += t1 - t0; t0 = t1; }
+	__device__ __forceinline__ void count(int counter, uint32_t n) { cnt[counter] += n; }
+	__device__ __forceinline__ void walk_over() { walk = hop_stamp(); }
+	__device__ __forceinline__ void flush(uint32_t *team_dbg, uint32_t hops, int lane)
+	{
+		if (!team_dbg || lane != 0) return;
+		const uint32_t end = hop_stamp();
+		atomicAdd(team_dbg + 0, hops);
+#pragma unroll
+		for (int i = 0; i < HS_SECTIONS; i++) atomicAdd(team_dbg + 1 + i, sec[i] >> 6);
+		atomicAdd(team_dbg + 6, (walk - q0) >> 6);
+		atomicAdd(team_dbg + 7, (end - walk) >> 6);
+#pragma unroll
+		for (int i = 0; i < HC_COUNTERS; i++) atomicAdd(team_dbg + 8 + i, cnt[i]);
+	}
+};
 
 constexpr uint32_t SLICE_ROWS = 16;             // rows of the widest scoring pass (4 * RPG, RPG <= 4) = the largest slice
 struct TeamCtl
@@ -1766,11 +983,7 @@ template <int FUNC, typename SH, int UREG, bool TEAM = false, bool LEAN = false>
 __global__ __launch_bounds__(TEAM ? 512 : 256, (UREG >= 16 && SH::MIN_WAVES > 2) ? 2 : SH::MIN_WAVES) void hnsw_search_kernel_beam(const SearchArgs a)
 {
 	constexpr uint32_t UCAP = 64u * UREG;
-#ifdef HNSW_NO_EARLY_POP
-	constexpr bool EARLY_POP = false;
-#else
 	constexpr bool EARLY_POP = !TEAM;              // banner "Early pop" at the hop loop
-#endif
 	extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 	const int lane = threadIdx.x & 63;
 	const uint32_t wib = threadIdx.x >> 6;
@@ -1786,7 +999,6 @@ __global__ __launch_bounds__(TEAM ? 512 : 256, (UREG >= 16 && SH::MIN_WAVES > 2)
 	clock_stamp(cold_args(a)->health, slot, lane, 0);
 	uint32_t *vis  = a.vis + (size_t) slot * cold_args(a)->vis_words;
 	uint32_t *vlog = a.vlog + (size_t) slot * a.logcap;
-	uint64_t *scratch = a.beam_scratch + (size_t) slot * UCAP;
 	const uint32_t ef = a.ef;
 	bool aborted = false;              // the host asked this launch to end (abort word)
 	TeamCtl *ctl = reinterpret_cast<TeamCtl *>(smem + a.off_ctl);
@@ -1812,6 +1024,7 @@ __global__ __launch_bounds__(TEAM ? 512 : 256, (UREG >= 16 && SH::MIN_WAVES > 2)
 	if (stream && blockIdx.x == 0)
 	{
 		if (wib != 0) return;
+		// (in the kernel body: as a function the doorbell costs team instantiations two more spilled SGPRs)
 		const uint32_t *stream_host = cold_args(a)->stream_host;
 		uint32_t *stream_dev = cold_args(a)->stream_dev;
 		for (;;)
@@ -1885,7 +1098,7 @@ __global__ __launch_bounds__(TEAM ? 512 : 256, (UREG >= 16 && SH::MIN_WAVES > 2)
 		}
 		if (__builtin_amdgcn_readfirstlane((int) aborted))
 		{
-			if (lane == 0) c->out_counts[qi] = ABORTED_COUNT;
+			mark_aborted(c, qi, lane);
 			if (stream) break;                                            // (a stream has no last ticket to run to)
 			continue;
 		}
@@ -1893,6 +1106,7 @@ __global__ __launch_bounds__(TEAM ? 512 : 256, (UREG >= 16 && SH::MIN_WAVES > 2)
 
 		const float *qsrc = c->queries + (size_t) qi * c->q_stride;
 		const uint32_t qdim = c->dim, qpad = c->qpad_floats;
+		// (staged in the kernel body, not through stage_query: as a function the copy costs every beam instantiation two more spilled SGPRs)
 		if (stream)
 		{
 			// the ring lives in pinned host memory and this slot held another query a ring ago: system-scope loads, so that no cache of
@@ -1922,10 +1136,9 @@ __global__ __launch_bounds__(TEAM ? 512 : 256, (UREG >= 16 && SH::MIN_WAVES > 2)
 		uint32_t usize = 0, logn = 0, evals = 0, hops = 0, hcount = 0;
 		uint32_t bstale = 0xFFFFFFFFu;       // ord() of a valid upper bound of the reference's lowerBound
 		bool spill = a.hcap == 0;
-		uint32_t hs_pop = 0, hs_link = 0, hs_vis = 0, hs_score = 0, hs_acc = 0, hs_q0 = 0;
-		uint32_t hc_new = 0, hc_todo = 0, hc_iter = 0, hc_acc = 0, hc_fast = 0, hc_prune = 0, hc_pass2 = 0, hc_acc_loop = 0;   // (diagnostic build: what the accept section does per hop)
+		HopDiag<HOP_STAMPS> diag;            // (empty in the product)
 		uint32_t jobseq = TEAM ? (uint32_t) __builtin_amdgcn_readfirstlane(lds_load_u32(&ctl[wib].jobseq)) : 0u;   // scoring jobs posted by this wave so far
-		if (HOP_STAMPS && a.team_dbg) hs_q0 = hop_stamp();
+		diag.query_start();
 		const uint32_t hnb = a.hcap / 4u;                                  // buckets of the visited set
 		if (a.hcap)
 		{
@@ -1979,8 +1192,7 @@ __global__ __launch_bounds__(TEAM ? 512 : 256, (UREG >= 16 && SH::MIN_WAVES > 2)
 				if (TEAM) hm = __builtin_amdgcn_readfirstlane(ctl[wib].helpers);
 				uint32_t cslot;
 				uint64_t ckey;
-				uint32_t hs0 = 0, hs1 = 0;
-				if (HOP_STAMPS && a.team_dbg) hs0 = hop_stamp();
+				diag.hop_start();
 				uint32_t n_lt = 0;                                          // elements of the set below the popped distance (the stop test's count)
 				if (EARLY_POP && nx_valid)
 				{
@@ -1990,17 +1202,7 @@ __global__ __launch_bounds__(TEAM ? 512 : 256, (UREG >= 16 && SH::MIN_WAVES > 2)
 					cd = (uint32_t) __builtin_amdgcn_readfirstlane((int) cd); // a 32-bit scalar of its own: hipcc otherwise compares (key >> 32) with (ckey >> 32) as 64-bit pairs
 					n_lt = beam_count_lt<UREG>(uk, cd);
 				}
-#ifdef HNSW_OLD_POP_COUNT
-				else
-				{
-					if (!beam_next<UREG>(uk, ex, cslot, ckey)) break;
-					uint32_t cd = (uint32_t) (ckey >> 32);
-					cd = (uint32_t) __builtin_amdgcn_readfirstlane((int) cd);
-					n_lt = beam_count_lt<UREG>(uk, cd);
-				}
-#else
 				else if (!beam_next<UREG, true>(uk, ex, cslot, ckey, &n_lt)) break;     // candidateSet empty
-#endif
 				nx_valid = false;
 				bool nx_taken = false, nx_beaten = false;                   // this hop: the scan was made / an accepted row lies below its result
 				if (n_lt >= ef) break;                                      // :70-71  best candidate > lowerBound
@@ -2016,7 +1218,7 @@ __global__ __launch_bounds__(TEAM ? 512 : 256, (UREG >= 16 && SH::MIN_WAVES > 2)
 				}
 				hops++;
 				if (!LEAN && (hops & 255u) == 0u && abort_word_set(cold_args(a)->abort_word)) { aborted = true; break; }
-				if (HOP_STAMPS && a.team_dbg) { hs1 = hop_stamp(); hs_pop += hs1 - hs0; hs0 = hs1; }
+				diag.mark(HS_POP);
 				TeamView h0v = {};
 				if (TEAM && (TEAM_COUNT && a.team_dbg) && lane == 0) { atomicAdd(a.team_dbg + 5, 1u); if (hm) atomicAdd(a.team_dbg + 0, 1u); }
 				uint64_t tc0 = 0, tc1 = 0, tc2 = 0, tc3 = 0;
@@ -2078,7 +1280,7 @@ __global__ __launch_bounds__(TEAM ? 512 : 256, (UREG >= 16 && SH::MIN_WAVES > 2)
 					}
 					if (TEAM && (TEAM_COUNT && a.team_dbg) && lhit && lane == 0) atomicAdd(a.team_dbg + 1, 1u);
 					if (TEAM && (TEAM_COUNT && a.team_dbg)) { __builtin_amdgcn_s_waitcnt(0); tc1 = __builtin_amdgcn_s_memtime(); }
-					if (HOP_STAMPS && a.team_dbg) { __builtin_amdgcn_s_waitcnt(0); hs1 = hop_stamp(); hs_link += hs1 - hs0; hs0 = hs1; }
+					diag.drain(); diag.mark(HS_LINK);
 					bool isnew = false;
 					bool tobits = false;                                    // this id lives in the HBM bitmap (bucket full, or no LDS set)
 					if (j < a.lstride && t != LINK_NONE)                    // :91-93
@@ -2108,11 +1310,7 @@ __global__ __launch_bounds__(TEAM ? 512 : 256, (UREG >= 16 && SH::MIN_WAVES > 2)
 					}
 					const uint64_t mask = __ballot(isnew);
 					const uint32_t nnew = (uint32_t) __builtin_popcountll(mask);
-					if (nnew == 0)
-					{
-						if (HOP_STAMPS && a.team_dbg) { hs1 = hop_stamp(); hs_vis += hs1 - hs0; hs0 = hs1; }
-						continue;
-					}
+					if (nnew == 0) { diag.mark(HS_VIS); continue; }
 					const uint32_t rank = lane_rank(mask);
 					uint32_t *ev_out = nullptr;                             // (cold arguments are read in uniform control flow only)
 					uint32_t ev_cap = 0;
@@ -2152,7 +1350,7 @@ __global__ __launch_bounds__(TEAM ? 512 : 256, (UREG >= 16 && SH::MIN_WAVES > 2)
 						sids = h0v.miss;
 					}
 					uint32_t od_mine = od_c;
-					if (HOP_STAMPS && a.team_dbg) { hs1 = hop_stamp(); hs_vis += hs1 - hs0; hs0 = hs1; }
+					diag.mark(HS_VIS);
 					if (nscore)
 					{
 						const uint32_t *ids = sids;
@@ -2225,10 +1423,10 @@ __global__ __launch_bounds__(TEAM ? 512 : 256, (UREG >= 16 && SH::MIN_WAVES > 2)
 					evals += nnew;
 					if (TEAM && (TEAM_COUNT && a.team_dbg)) { __builtin_amdgcn_s_waitcnt(0); tc2 = __builtin_amdgcn_s_memtime(); }
 					const uint32_t t_mine = newid[lane];
-					if (HOP_STAMPS && a.team_dbg) { hs1 = hop_stamp(); hs_score += hs1 - hs0; hs0 = hs1; }
+					diag.mark(HS_SCORE);
 					// rows at or above a valid upper bound of lowerBound cannot be accepted (:99)
 					uint64_t todo = __ballot((uint32_t) lane < nnew && od_mine < bstale);
-					if (HOP_STAMPS && a.team_dbg) { hc_new += nnew; hc_todo += (uint32_t) __builtin_popcountll(todo); if (nscore > 4u * SH::RPG) hc_pass2++; }
+					diag.count(HC_NEW, nnew); diag.count(HC_TODO, (uint32_t) __builtin_popcountll(todo)); diag.count(HC_PASS2, nscore > 4u * SH::RPG ? 1u : 0u);
 					// While the accepted set is below ef every row is accepted whatever its distance (hnswalg.cpp:99: size < ef), one by
 					// one in the reference; the set is unordered here, so a hop whose rows ALL fit below ef is appended in one step:
 					// row r goes to slot usize + r, fetched by the lane that owns that slot (ds_bpermute), no count, no per-row loop.
@@ -2251,9 +1449,8 @@ __global__ __launch_bounds__(TEAM ? 512 : 256, (UREG >= 16 && SH::MIN_WAVES > 2)
 						usize += nnew;
 						todo = 0;
 						if (EARLY_POP) nx_beaten = nx_beaten || !nx_has || __ballot((uint32_t) lane < nnew && (((uint64_t) od_mine << 32) | (uint32_t) ~t_mine) < nx_key) != 0;
-						if (HOP_STAMPS && a.team_dbg) { hc_fast++; hc_acc += nnew; }
+						diag.count(HC_FAST, 1u); diag.count(HC_ACC, nnew);
 					}
-#ifndef HNSW_SERIAL_ACCEPT
 					// Batch form of the accept loop (round 6).  A hop leaves ~4 rows below the stale bound and nearly all of them are accepted
 					// (profiles/r6u_*: 3.5 loop iterations, 3.3 accepts per hop), and an accept used to cost a slot write over all UREG
 					// registers — 12 of the ~19 VALU instructions of an iteration.  The decisions are still taken one by one in link order,
@@ -2271,7 +1468,7 @@ __global__ __launch_bounds__(TEAM ? 512 : 256, (UREG >= 16 && SH::MIN_WAVES > 2)
 						{
 							const uint32_t r = (uint32_t) __builtin_ctzll(todo);
 							todo &= todo - 1;
-							if (HOP_STAMPS && a.team_dbg) hc_iter++;
+							diag.count(HC_ITER, 1u);
 							const uint32_t od = (uint32_t) __builtin_amdgcn_readlane((int) od_mine, (int) r);
 							const uint32_t c = beam_count_le<UREG>(uk, od) + (uint32_t) __builtin_popcountll(acc & __ballot(od_mine <= od));
 							if (c >= ef)                                    // rejected, and od is a fresh upper bound of lowerBound
@@ -2299,16 +1496,15 @@ __global__ __launch_bounds__(TEAM ? 512 : 256, (UREG >= 16 && SH::MIN_WAVES > 2)
 								uk[k] = kreg == (uint32_t) k ? (((uint64_t) od_p << 32) | id_p) : uk[k];
 							usize += na;
 							if (EARLY_POP) nx_beaten = nx_beaten || !nx_has || __ballot(mine_acc && (((uint64_t) od_mine << 32) | (uint32_t) ~t_mine) < nx_key) != 0;
-							if (HOP_STAMPS && a.team_dbg) { hc_acc += na; hc_acc_loop += na; }
+							diag.count(HC_ACC, na); diag.count(HC_ACC_LOOP, na);
 						}
 					}
-#endif
 					if (EARLY_POP && todo) nx_beaten = true;                // (rare: the one-by-one loop may prune, and then slots move)
 					while (todo)                                            // :99-108, in link order, one by one (a hop that may need the prune)
 					{
 						const uint32_t r = (uint32_t) __builtin_ctzll(todo);
 						todo &= todo - 1;
-						if (HOP_STAMPS && a.team_dbg) hc_iter++;
+						diag.count(HC_ITER, 1u);
 						const uint32_t od = (uint32_t) __builtin_amdgcn_readlane((int) od_mine, (int) r);
 						if (beam_count_le<UREG>(uk, od) >= ef)              // top().first <= dist and full: rejected,
 						{                                                   // and od is a fresh upper bound of lowerBound
@@ -2320,16 +1516,16 @@ __global__ __launch_bounds__(TEAM ? 512 : 256, (UREG >= 16 && SH::MIN_WAVES > 2)
 						if (usize == UCAP)                                  // make room: drop what lies above the bound
 						{
 							const uint32_t v = beam_select<UREG>(uk, ef);
-							usize = beam_compact<UREG>(uk, ex, v, scratch, lane);
+							usize = beam_compact<UREG>(uk, ex, v, lane);
 							bstale = v;                                     // lowerBound right now
-							if (HOP_STAMPS && a.team_dbg) hc_prune++;
+							diag.count(HC_PRUNE, 1u);
 						}
 						beam_set<UREG>(uk, usize, ((uint64_t) od << 32) | t2, lane);   // :100,:102
 						usize++;
-						if (HOP_STAMPS && a.team_dbg) { hc_acc++; hc_acc_loop++; }
+						diag.count(HC_ACC, 1u); diag.count(HC_ACC_LOOP, 1u);
 					}
 					wave_sync();
-					if (HOP_STAMPS && a.team_dbg) { hs1 = hop_stamp(); hs_acc += hs1 - hs0; hs0 = hs1; }
+					diag.mark(HS_ACC);
 					if (TEAM && (TEAM_COUNT && a.team_dbg) && lane == 0)
 					{
 						tc3 = __builtin_amdgcn_s_memtime();
@@ -2346,21 +1542,20 @@ __global__ __launch_bounds__(TEAM ? 512 : 256, (UREG >= 16 && SH::MIN_WAVES > 2)
 		c = cold_args(a);                                                  // the emit step's cold arguments
 		if (__builtin_amdgcn_readfirstlane((int) aborted))                 // interrupted inside its walk
 		{
-			if (lane == 0) c->out_counts[qi] = ABORTED_COUNT;
+			mark_aborted(c, qi, lane);
 			if (stream) break;
 			continue;
 		}
 		if (!LEAN && (opt_out & 4u) && lane == 0) c->out_times[2 * (size_t) qi + 1] = __builtin_amdgcn_s_memrealtime();
+		diag.walk_over();
 		uint64_t *srt_key = reinterpret_cast<uint64_t *>(my + c->off_res);     // emit scratch (overlays the visited set)
 		uint64_t *srt_lab = reinterpret_cast<uint64_t *>(my + c->off_cand);
-		uint32_t hs_walk = 0;
-		if (HOP_STAMPS && a.team_dbg) hs_walk = hop_stamp();
 		// ---- emit: the ef smallest (dist, idx) keys of the set, then the reference's output order ----
 		uint32_t rsize = usize;
 		if (usize > ef)
 		{
 			const uint32_t v = beam_select<UREG>(uk, ef);
-			rsize = beam_compact<UREG>(uk, ex, v, scratch, lane);          // >= ef, more only with ties at v
+			rsize = beam_compact<UREG>(uk, ex, v, lane);          // >= ef, more only with ties at v
 		}
 #pragma unroll
 		for (int k = 0; k < UREG; k++)
@@ -2392,7 +1587,6 @@ __global__ __launch_bounds__(TEAM ? 512 : 256, (UREG >= 16 && SH::MIN_WAVES > 2)
 		}
 		// ... and the survivors sit in slots 0 .. rsize - 1, so with rsize <= 32 * UREG (the usual case: rsize = ef, the set's capacity 2 ef) the
 		// upper half of the registers is empty and stays out of the loop
-#ifndef HNSW_OLD_EMIT
 		if (UREG >= 2 && rsize <= 32u * UREG)
 		{
 			for (uint32_t jx = 0; jx < rsize; jx += 4)
@@ -2404,7 +1598,6 @@ __global__ __launch_bounds__(TEAM ? 512 : 256, (UREG >= 16 && SH::MIN_WAVES > 2)
 			}
 		}
 		else
-#endif
 		for (uint32_t jx = 0; jx < rsize; jx += 4)
 		{
 			const uint64_t k0 = srt_key[jx], k1 = srt_key[jx + 1], k2 = srt_key[jx + 2], k3 = srt_key[jx + 3];
@@ -2517,38 +1710,9 @@ __global__ __launch_bounds__(TEAM ? 512 : 256, (UREG >= 16 && SH::MIN_WAVES > 2)
 		}
 
 		wave_sync();
-		if (logn <= a.logcap)
-		{
-			for (uint32_t i = lane; i < logn; i += 64) vis[vlog[i] >> 5] = 0u;
-		}
-		else
-		{
-			for (uint64_t w = lane, nw = c->vis_words; w < nw; w += 64) vis[w] = 0u;
-		}
-#ifdef HNSW_ALWAYS_END_WAIT
-		if (true)
-#else
-		if (logn)                                                          // (nothing in the bitmap to wait for: the result stores need no wait, the next query touches none of them)
-#endif
-		{
-			__builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-			__builtin_amdgcn_s_waitcnt(0);
-		}
+		restore_bitmap(vis, vlog, logn, a.logcap, c, false, lane);
 		wave_sync();
-		if (HOP_STAMPS && a.team_dbg && lane == 0)
-		{
-			const uint32_t hs_end = hop_stamp();
-			atomicAdd(a.team_dbg + 0, hops);
-			atomicAdd(a.team_dbg + 1, hs_pop >> 6);
-			atomicAdd(a.team_dbg + 2, hs_link >> 6);
-			atomicAdd(a.team_dbg + 3, hs_vis >> 6);
-			atomicAdd(a.team_dbg + 4, hs_score >> 6);
-			atomicAdd(a.team_dbg + 5, hs_acc >> 6);
-			atomicAdd(a.team_dbg + 6, (hs_walk - hs_q0) >> 6);      // query start .. walk over (incl. set-up and entry point)
-			atomicAdd(a.team_dbg + 7, (hs_end - hs_walk) >> 6);     // emit + bitmap clean-up
-			atomicAdd(a.team_dbg + 8, hc_new); atomicAdd(a.team_dbg + 9, hc_todo); atomicAdd(a.team_dbg + 10, hc_iter); atomicAdd(a.team_dbg + 11, hc_acc);
-			atomicAdd(a.team_dbg + 12, hc_fast); atomicAdd(a.team_dbg + 13, hc_prune); atomicAdd(a.team_dbg + 14, hc_pass2); atomicAdd(a.team_dbg + 15, hc_acc_loop);
-		}
+		diag.flush(a.team_dbg, hops, lane);
 	}
 	if (__builtin_amdgcn_readfirstlane((int) aborted)) { uint32_t *hw = cold_args(a)->health; if (lane == 0) atomicAdd(hw + HEALTH_ABORTED_WAVES, 1u); }
 	clock_stamp(cold_args(a)->health, slot, lane, 1);

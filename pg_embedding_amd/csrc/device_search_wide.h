@@ -21,7 +21,7 @@
 // a walk with a beam of 200 000 is a chain of 200 000 hops whatever the container — this form makes each of them cost
 // microseconds, not the better part of a millisecond.
 #pragma once
-#include "device_search.h"
+#include "device_search_generic.h"
 
 namespace pgemb {
 
@@ -95,15 +95,11 @@ __global__ __launch_bounds__(256) void hnsw_search_kernel_wide(const SearchArgs 
 		// (an abort request is sticky for this wave: it takes the remaining tickets without walking and marks every query it does not
 		// answer with count 0xFFFFFFFF, so that the caller of an interrupted launch can tell which rows of its outputs are results)
 		if (!aborted && (qi & a.abort_mask) == 0u && abort_requested(a)) aborted = true;
-		if (__builtin_amdgcn_readfirstlane((int) aborted)) { if (lane == 0) a.out_counts[qi] = ABORTED_COUNT; continue; }   // (wave-uniform by construction; said explicitly)
+		if (__builtin_amdgcn_readfirstlane((int) aborted)) { mark_aborted(&a, qi, lane); continue; }   // (wave-uniform by construction; said explicitly)
 		if (a.out_times && lane == 0) a.out_times[2 * (size_t) qi] = __builtin_amdgcn_s_memrealtime();
 
 		const float *qsrc = a.queries + (size_t) qi * a.q_stride;
-		for (uint32_t e = lane; e < a.qpad_floats; e += 64)
-		{
-			const float t = qsrc[e < a.dim ? e : a.dim - 1];
-			qf[e] = (e < a.dim) ? t : 0.f;
-		}
+		stage_query(qf, qsrc, a.dim, a.qpad_floats, lane);
 		for (uint32_t i = lane; i < a.wide_nr; i += 64) rmax[i] = 0ull;
 		for (uint32_t i = lane; i < a.wide_nc; i += 64) cmin[i] = ~0ull;
 		wave_sync();
@@ -262,7 +258,7 @@ __global__ __launch_bounds__(256) void hnsw_search_kernel_wide(const SearchArgs 
 			}
 		}
 
-		if (__builtin_amdgcn_readfirstlane((int) aborted)) { if (lane == 0) a.out_counts[qi] = ABORTED_COUNT; continue; }      // interrupted inside its walk
+		if (__builtin_amdgcn_readfirstlane((int) aborted)) { mark_aborted(&a, qi, lane); continue; }      // interrupted inside its walk
 		if (a.out_times && lane == 0) a.out_times[2 * (size_t) qi + 1] = __builtin_amdgcn_s_memrealtime();
 		// ---- emit: (key, label) pairs sorted by a bitonic network in the slot's scratch ----------------------------------
 		const size_t obase = (size_t) qi * a.out_stride;
@@ -312,16 +308,7 @@ __global__ __launch_bounds__(256) void hnsw_search_kernel_wide(const SearchArgs 
 
 		// ---- restore the all-zero bitmap for the next query of this slot --------------
 		set_sync<true>();
-		if (logn <= a.logcap)
-		{
-			for (uint32_t i = lane; i < logn; i += 64) vis[vlog[i] >> 5] = 0u;
-		}
-		else
-		{
-			for (uint64_t w = lane; w < a.vis_words; w += 64) vis[w] = 0u;
-		}
-		__builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-		__builtin_amdgcn_s_waitcnt(0);
+		restore_bitmap(vis, vlog, logn, a.logcap, &a, true, lane);       // (always drained: the next query's atomics must see the zeros)
 		set_sync<true>();
 	}
 	if (aborted && lane == 0) atomicAdd(a.health + HEALTH_ABORTED_WAVES, 1u);

@@ -217,7 +217,7 @@ extern "C" int hnsw_gpu_index_placement(hnsw_gpu_index *ix, uint64_t *out16)
 		(uint64_t) (uintptr_t) ix->labels, ix->cap * sizeof(uint64_t),
 		(uint64_t) (uintptr_t) w.vis, w.vis_slots * w.vis_words * 4,
 		(uint64_t) (uintptr_t) w.vlog, w.vis_slots * (size_t) w.logcap * 4,
-		(uint64_t) (uintptr_t) w.beam, w.beam_keys * 8,
+		0, 0,                                               // (was the beam form's prune scratch: the prune compacts in registers)
 		(uint64_t) (uintptr_t) w.ticket, XCD_TICKET_BYTES };
 	memcpy(out16, v, sizeof(v));
 	return HNSW_GPU_OK;

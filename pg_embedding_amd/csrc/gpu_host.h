@@ -58,9 +58,6 @@ enum Knob : int
 	// test knobs (hnsw_gpu_config_set only)
 	K_BEAM16, K_NARROW5, K_LEAN, K_HASH_ENTRIES, K_LDS_SET_MIN_WAVES, K_TEAM_SPEC, K_TEAM_WPB, K_NARROW_WPB, K_ABORT_POLL_LOG2, K_MAX_BLOCKS, K_SHARDED_NO_PEER, K_BF_BIG_MIN_BLOCKS, K_LOCALITY_MIN_NQ,
 	K_FK_SAMPLE_MIN, K_FK_MFMA_STANDIN,
-#ifdef HNSW_EXPERIMENT
-	K_WIDE_WAVES, K_SHAPE_12X1, K_TEAM_MAINS, K_TEAM_COUNTERS,
-#endif
 	K_COUNT
 };
 struct KnobVal { std::atomic<long long> v{0}; std::atomic<bool> set{false}; };
@@ -83,7 +80,6 @@ struct SearchWs
 	static const int EV_RING = 64;
 	uint32_t *vis = nullptr;  size_t vis_slots = 0, vis_words = 0;
 	uint32_t *vlog = nullptr; uint32_t logcap = 0;
-	uint64_t *beam = nullptr; size_t beam_keys = 0;      // beam form: prune scratch, 64*UREG keys per slot
 	uint64_t *sets = nullptr; size_t set_keys = 0;       // generic form with its sets in HBM: 3*ef+2 keys per slot
 	uint32_t *ticket = nullptr;
 	hipEvent_t ev0[EV_RING] = {}, ev1[EV_RING] = {};
@@ -96,7 +92,7 @@ struct SearchWs
 	uint32_t *pops_next = nullptr; uint32_t pops_cap_next = 0;   // pop-sequence output for the next launch only
 	uint32_t *evals_next = nullptr; uint32_t evals_cap_next = 0; uint64_t *times_next = nullptr;   // evaluation trace, next launch only
 	char kname[96] = "";                                 // symbol of the kernel the last launch used (as rocprofv3 prints it)
-	uint32_t *team_dbg = nullptr;                        // 8 launch-wide counters of the team form (HNSW_GPU_TEAM_COUNTERS=1)
+	uint32_t *team_dbg = nullptr;                        // 16 launch-wide counters of a diagnostic build (-DHNSW_HOP_STAMPS / -DHNSW_TEAM_COUNTERS), else null
 	// abort word (pinned host memory) + health counters (device memory): device_search.h, banner at abort_requested
 	uint32_t *abort_host = nullptr;
 	uint32_t *health = nullptr;

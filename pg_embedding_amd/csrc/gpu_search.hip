@@ -17,11 +17,7 @@ static search_kernel_t pick_search_kernel(int func, uint32_t kiters, int rreg, b
 			return pick_kernel_shape2x4(func, rreg, team);
 		case 1:  return pick_kernel_shape4x2(func, rreg, team);
 		case 2:  return pick_kernel_shape8x2(func, rreg, team);
-		default:
-#ifdef HNSW_EXPERIMENT
-			if (knob(K_SHAPE_12X1, 0)) return pick_kernel_shape12x1(func, rreg, team);
-#endif
-			return pick_kernel_shape12x2(func, rreg, team);
+		default: return pick_kernel_shape12x2(func, rreg, team);
 	}
 }
 
@@ -158,8 +154,7 @@ int launch_search(hnsw_gpu_index *ix, SearchWs *w, const float *d_queries, size_
 	//     beat the LDS form there (+22-28 %, profiles/r1i_beam_form.txt); narrow rows keep the LDS form
 	//     above 256 (it holds 4 waves/SIMD).  Its prune packs the "expanded" bit into bit 31 of the idx.
 	//   LDS (generic) form: everything else — also HNSW_GPU_BEAM=0 and mirrors of >= 2^31 elements (HNSW_GPU_FORCE_LDS_HEAPS=1 forces it).
-	//   (two-set register form, round 1's hot kernel: experiment builds only since round 5.)
-	// The register forms use their LDS "res"/"cand" areas only as scratch of the emit step.
+	// The beam form uses its LDS "res"/"cand" areas only as scratch of the emit step.
 	knobs_init();
 	const bool use_beam = knob(K_BEAM, 1) != 0 && ix->cap < 0x80000000ull;
 	const bool beam16 = use_beam && ef > 256 && ef <= 512 && (knob_is_set(K_BEAM16) ? knob(K_BEAM16, 0) > 0 : shape_index(a.kiters) >= 2);
@@ -183,11 +178,7 @@ int launch_search(hnsw_gpu_index *ix, SearchWs *w, const float *d_queries, size_
 	else if (ef > wide_min) rreg = 3;
 	else if (knob(K_FORCE_LDS_HEAPS, 0) > 0) rreg = 0;
 	else if (use_beam && (ef <= 256 || beam16)) rreg = ef <= 64 ? -2 : (ef <= 128 ? -4 : (ef <= 256 ? -8 : -16));
-#ifdef HNSW_EXPERIMENT
-	else rreg = ef <= 128 ? 2 : (ef <= 256 ? 4 : 0);         // two-set register form (experiment builds)
-#else
 	else rreg = 0;                                           // HNSW_GPU_BEAM=0, or a mirror of >= 2^31 elements: the generic form
-#endif
 	// Reduced-row walk (device_rows16.h; hnsw_gpu_search_batch_reduced_dev): the one-wave beam form only — no team, no narrow-row or
 	// LEAN kernels, no wide-beam / generic forms, no reference-order arithmetic, no streams or traces.  Refused here, before anything is
 	// launched or allocated.
@@ -237,45 +228,33 @@ int launch_search(hnsw_gpu_index *ix, SearchWs *w, const float *d_queries, size_
 		if (3 * P * 8 > SET_BUDGET_BYTES)
 			return fail(HNSW_GPU_ERR_NOMEM, "ef %zu needs %zu bytes of scratch per query slot (more than the %zu-byte budget)", ef, 3 * P * 8, SET_BUDGET_BYTES);
 	}
-	else if (rreg)
+	else if (rreg < 0)
 	{
-		// [query | hash set (overlaid by the emit step's tie scratch) | newid | newdist]
+		// [query | visited set (overlaid by the emit step's tie scratch) | newid | newdist]
 		const size_t fixed = off + 64 * 4 + 128 * 4 + (team_wanted ? sizeof(TeamCtl) : 0);   // (+ the wave's control block behind the regions)
 		// Rows of >= 1.25 KiB make the traversal HBM-bound, and there the LDS set pays (no L2
 		// atomics, ~10 % less HBM traffic; measured 5.4 -> 7.5 TB/s at 768 dims) at 8 waves per CU.
 		// Narrow rows are latency-bound and want 16-20 waves per CU: the beam form gives them a bucketed set of
-		// 3456-4096 16-bit tags (ids whose bucket is full go to the bitmap); the two-set register form keeps the
-		// bitmap only (profiles/r1g_visited_set_by_dim.txt, profiles/r1i_beam_form.md, profiles/r2m_*).
+		// 3456-4096 16-bit tags (ids whose bucket is full go to the bitmap)
+		// (profiles/r1g_visited_set_by_dim.txt, profiles/r1i_beam_form.md, profiles/r2m_*).
 		// (rows of up to 128 floats in the beam form with ef <= 128, L2 / Manhattan, launches that will not run as
 		// teams: 5 waves/SIMD with the 8-rows-per-pass shape — measured +6-10 % over 4 waves, profiles/r2m_*)
 		const bool wide = ix->stride > 320;
 		size_t want_waves = wide ? 8 : (narrow5 ? 20 : 16);
-#ifdef HNSW_EXPERIMENT
-		if (wide && knob(K_WIDE_WAVES, 0) >= 4) want_waves = (size_t) knob(K_WIDE_WAVES, 0);   // (experiment builds at 3 waves/SIMD)
-#endif
-		uint32_t hcap = wide ? 4096 : (rreg < 0 ? 2048 : 0);
+		uint32_t hcap = wide ? 4096 : 2048;
 		if (knob_is_set(K_HASH_ENTRIES)) hcap = (uint32_t) knob(K_HASH_ENTRIES, 0);
 		// emit scratch: [keys | labels]; the beam form sorts up to `ucap` survivors (ties at the bound)
-		const size_t nkeys = ucap ? ucap : ef;
+		const size_t nkeys = ucap;
 		const size_t emit = round_up(nkeys * 8, 16) + round_up(ef * 8, 16);
-		if (rreg < 0)
-		{
-			// beam form: hcap/4 buckets (any count, 128-byte steps of LDS) of eight 16-bit tags (device_search.h,
-			// "bucketed"); tag = id / buckets + 1 must fit 16 bits and the 38-bit reciprocal must be exact (ids below
-			// 2^28), else the kernel runs on the HBM bitmap alone
-			hcap = std::min<uint32_t>(hcap, 4096);
-			while (hcap >= 512 && want_waves * (fixed + std::max<size_t>(hcap * 4, emit)) > LDS_PER_CU) hcap -= 128;
-			hcap &= ~31u;
-			if (hcap < 512 || (uint64_t) ix->cap > (uint64_t) 65535 * (hcap / 4) || ix->cap >= (1u << 28)) hcap = 0;
-			a.hmagic = hcap ? (uint32_t) ((((uint64_t) 1 << 38) + hcap / 4 - 1) / (hcap / 4)) : 0;
-		}
-		else
-		{
-			while (hcap >= 512 && want_waves * (fixed + std::max<size_t>(hcap * 4, emit)) > LDS_PER_CU) hcap >>= 1;
-			if (hcap < 512 || (hcap & (hcap - 1))) hcap = 0;
-		}
+		// hcap/4 buckets (any count, 128-byte steps of LDS) of eight 16-bit tags (device_search.h, "bucketed");
+		// tag = id / buckets + 1 must fit 16 bits and the 38-bit reciprocal must be exact (ids below 2^28), else the
+		// kernel runs on the HBM bitmap alone
+		hcap = std::min<uint32_t>(hcap, 4096);
+		while (hcap >= 512 && want_waves * (fixed + std::max<size_t>(hcap * 4, emit)) > LDS_PER_CU) hcap -= 128;
+		hcap &= ~31u;
+		if (hcap < 512 || (uint64_t) ix->cap > (uint64_t) 65535 * (hcap / 4) || ix->cap >= (1u << 28)) hcap = 0;
+		a.hmagic = hcap ? (uint32_t) ((((uint64_t) 1 << 38) + hcap / 4 - 1) / (hcap / 4)) : 0;
 		a.hcap = hcap;
-		a.hmax = hcap - hcap / 4;
 		a.off_hash = (uint32_t) off;
 		a.off_res = (uint32_t) off;
 		a.off_cand = (uint32_t) (off + round_up(nkeys * 8, 16));
@@ -372,15 +351,11 @@ int launch_search(hnsw_gpu_index *ix, SearchWs *w, const float *d_queries, size_
 	{
 		static const char *const shapes[4] = { "Shape2x4", "Shape4x2", "Shape8x2", "Shape12x2" };
 		const char *shp = shapes[shape_index(a.kiters)];
-#ifdef HNSW_EXPERIMENT
-		if (shape_index(a.kiters) == 3 && knob(K_SHAPE_12X1, 0)) shp = "Shape12x1";
-#endif
 		if (narrow5 && !team) shp = "Shape2x2";
 		static const char *const rshapes[4] = { "1, 4, 4", "2, 4, 4", "4, 2, 4", "6, 2, 2" };
 		if (rows) snprintf(w->kname, sizeof(w->kname), "pgemb::hnsw_search_kernel_beam<%d, pgemb::ShapeR16<%d, %s>, %d, false, false>", func_code, rows, rshapes[shape_index(a.kiters)], -rreg);
 		else if (rreg < 0) snprintf(w->kname, sizeof(w->kname), "pgemb::hnsw_search_kernel_beam<%d, pgemb::%s, %d, %s, %s>", func_code, shp, -rreg, team ? "true" : "false", lean ? "true" : "false");
 		else if (rreg == 3) snprintf(w->kname, sizeof(w->kname), "pgemb::hnsw_search_kernel_wide<%d, pgemb::%s>", (int) ix->meta.dist_func, shp);
-		else if (rreg >= 2) snprintf(w->kname, sizeof(w->kname), "pgemb::hnsw_search_kernel_reg<%d, pgemb::%s, %d>", (int) ix->meta.dist_func, shp, rreg);
 		else snprintf(w->kname, sizeof(w->kname), "pgemb::hnsw_search_kernel_lds<%d, pgemb::%s, %s>", (int) ix->meta.dist_func, shp, rreg == 1 ? "true" : "false");
 	}
 	if (lds > 48 * 1024)
@@ -406,10 +381,6 @@ int launch_search(hnsw_gpu_index *ix, SearchWs *w, const float *d_queries, size_
 			blocks = std::min<size_t>((nq + a.team_mains - 1) / a.team_mains, (size_t) per_cu * ix->num_cu);
 		}
 	}
-	// (experiment knob: walking waves per block of a team launch — the others help from the start; scripts/exp_spec_ab.py)
-#ifdef HNSW_EXPERIMENT
-	if (team && knob(K_TEAM_MAINS, 0) > 0) a.team_mains = std::min<uint32_t>(a.team_mains, (uint32_t) knob(K_TEAM_MAINS, 0));
-#endif
 	if (stream_launch)
 	{
 		// a resident launch fed by the host (device_search.h, "Stream mode"): exactly the blocks the device holds at once — block 0 is the
@@ -460,15 +431,6 @@ int launch_search(hnsw_gpu_index *ix, SearchWs *w, const float *d_queries, size_
 	// abort_requested in device_search.h)
 	a.abort_mask = (1u << (uint32_t) std::min<long long>(16, std::max<long long>(0, knob(K_ABORT_POLL_LOG2, 4)))) - 1u;
 	a.vis = w->vis; a.vis_words = words; a.vlog = w->vlog; a.logcap = w->logcap;
-	// (the beam form's prune scratch: read only by -DHNSW_OLD_COMPACT builds since round 6 — the shipped kernels compact in registers; 2 KB per slot)
-	if (ucap && slots * ucap > w->beam_keys)
-	{
-		if (w->beam) (void) hipFree(w->beam);
-		w->beam = nullptr; w->beam_keys = 0;
-		HIPCHK(hipMalloc(&w->beam, slots * ucap * 8));
-		w->beam_keys = slots * ucap;
-	}
-	a.beam_scratch = w->beam;
 	if (rreg == 1 || rreg == 3)
 	{
 		const size_t keys = slots * a.set_stride;
@@ -482,13 +444,10 @@ int launch_search(hnsw_gpu_index *ix, SearchWs *w, const float *d_queries, size_
 		a.set_scratch = w->sets;
 	}
 	a.ticket = w->ticket;
-#ifdef HNSW_EXPERIMENT
-	if (knob(K_TEAM_COUNTERS, 0))                           // (diagnostic builds only: build.py variant ... HNSW_HOP_STAMPS / HNSW_TEAM_COUNTERS)
-	{
-		if (!w->team_dbg) HIPCHK(hipMalloc(&w->team_dbg, 64));
-		HIPCHK(hipMemsetAsync(w->team_dbg, 0, 64, stream));
-		a.team_dbg = w->team_dbg;
-	}
+#if defined(HNSW_HOP_STAMPS) || defined(HNSW_TEAM_COUNTERS)      // diagnostic builds (build.py variant <tag> HNSW_HOP_STAMPS / HNSW_TEAM_COUNTERS): 16 launch-wide counters
+	if (!w->team_dbg) HIPCHK(hipMalloc(&w->team_dbg, 64));
+	HIPCHK(hipMemsetAsync(w->team_dbg, 0, 64, stream));
+	a.team_dbg = w->team_dbg;
 #endif
 	a.done = w->done_next;
 	w->done_next = nullptr;

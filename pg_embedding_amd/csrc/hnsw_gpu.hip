@@ -36,8 +36,7 @@ extern "C" int hnsw_gpu_device_count(void)
 // INTEGRATION.md "environment") — and after that a launch reads plain words: no getenv, no parsing, no locale on the path of
 // a 0.4 ms call.  A host that wants another value later says so explicitly (hnsw_gpu_config_set; hnsw_gpu_config_reload re-reads
 // the environment): that is how the test tiers flip kernel forms inside one process.  TEST knobs (forms and shapes the host code
-// never picks by itself, forced so that every compiled kernel is exercised) can only be set through that call; experiment knobs
-// of rejected variants exist only in -DHNSW_EXPERIMENT builds, where the whole table is read from the environment.
+// never picks by itself, forced so that every compiled kernel is exercised) can only be set through that call.
 struct KnobDef { const char *name; bool env; };
 static const KnobDef g_knob_def[K_COUNT] = {
 	{ "HNSW_GPU_BEAM", true }, { "HNSW_GPU_FORCE_LDS_HEAPS", true }, { "HNSW_GPU_TEAM", true }, { "HNSW_GPU_TEAM_MAX_NQ", true },
@@ -47,9 +46,6 @@ static const KnobDef g_knob_def[K_COUNT] = {
 	{ "HNSW_GPU_TEAM_SPEC", false }, { "HNSW_GPU_TEAM_WPB", false }, { "HNSW_GPU_NARROW_WPB", false }, { "HNSW_GPU_ABORT_POLL_LOG2", false }, { "HNSW_GPU_MAX_BLOCKS", false }, { "HNSW_GPU_SHARDED_NO_PEER", false },
 	{ "HNSW_GPU_BF_BIG_MIN_BLOCKS", false }, { "HNSW_GPU_LOCALITY_MIN_NQ", false },
 	{ "HNSW_GPU_FK_SAMPLE_MIN", false }, { "HNSW_GPU_FK_MFMA_STANDIN", false },
-#ifdef HNSW_EXPERIMENT
-	{ "HNSW_GPU_WIDE_WAVES", false }, { "HNSW_GPU_SHAPE_12X1", false }, { "HNSW_GPU_TEAM_MAINS", false }, { "HNSW_GPU_TEAM_COUNTERS", false },
-#endif
 };
 KnobVal g_knob[K_COUNT];
 static std::once_flag g_knob_once;
@@ -63,14 +59,7 @@ static void knob_store(int k, const char *text)
 static void knobs_from_env(bool all)
 {
 	for (int k = 0; k < K_COUNT; k++)
-	{
-#ifdef HNSW_EXPERIMENT
-		(void) all;
-		knob_store(k, getenv(g_knob_def[k].name));
-#else
 		if (g_knob_def[k].env || all) knob_store(k, g_knob_def[k].env ? getenv(g_knob_def[k].name) : nullptr);
-#endif
-	}
 }
 
 void knobs_init() { std::call_once(g_knob_once, [] { knobs_from_env(false); }); }
@@ -228,7 +217,6 @@ void ws_free(SearchWs *w)
 	if (w->health) (void) hipFree(w->health);
 	if (w->abort_host) (void) hipHostFree(w->abort_host);
 	if (w->vis) (void) hipFree(w->vis);
-	if (w->beam) (void) hipFree(w->beam);
 	if (w->sets) (void) hipFree(w->sets);
 	if (w->vlog) (void) hipFree(w->vlog);
 	if (w->team_dbg) (void) hipFree(w->team_dbg);

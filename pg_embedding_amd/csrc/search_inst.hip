@@ -1,5 +1,5 @@
-// search_inst.hip — the search kernels of ONE load shape (-DSEARCH_INST_SHAPE=1..6), a translation unit each: build.py compiles
-// the six in parallel with hnsw_gpu.hip and links the objects into libhnsw_gpu.so.
+// search_inst.hip — the search kernels of ONE load shape (-DSEARCH_INST_SHAPE=1..5), a translation unit each: build.py compiles
+// the five in parallel with hnsw_gpu.hip and links the objects into libhnsw_gpu.so.
 #include <hip/hip_runtime.h>
 #include "search_kernels.h"
 
@@ -39,8 +39,6 @@ search_kernel_t pick_kernel_shape2x2(int func, int rreg, bool lean)
 		default:   return rreg == -2 ? hnsw_search_kernel_beam<F_MANHATTAN, Shape2x2, 2, false> : hnsw_search_kernel_beam<F_MANHATTAN, Shape2x2, 4, false>;
 	}
 }
-#elif SEARCH_INST_SHAPE == 6 && defined(HNSW_EXPERIMENT)
-search_kernel_t pick_kernel_shape12x1(int func, int rreg, bool team) { return pick_search_kernel_s<Shape12x1>(func, rreg, team); }
 #endif
 
 }  // namespace pgemb

@@ -4,6 +4,7 @@
 #pragma once
 #include "device_dist.h"
 #include "device_search.h"
+#include "device_search_generic.h"
 #include "device_search_wide.h"
 #include "device_rerank.h"
 
@@ -12,8 +13,7 @@ namespace pgemb {
 typedef void (*search_kernel_t)(const SearchArgs);
 typedef void (*rerank_kernel_t)(const RerankArgs);
 
-// rreg: 0 = generic form, sets in LDS; 1 = generic form, sets in HBM (any ef); 2 / 4 = two-set register form for ef <= 128 / 256
-//       (experiment builds only),
+// rreg: 0 = generic form, sets in LDS; 1 = generic form, sets in HBM (any ef);
 //       -2 / -4 / -8 / -16 = beam form (counting acceptance) with that many set registers, ef <= 64 / 128 / 256 / 512
 template <typename SH, int RREG>
 inline search_kernel_t pick_search_kernel_f(int func, bool team)
@@ -52,24 +52,12 @@ inline search_kernel_t pick_search_kernel_f(int func, bool team)
 			case F_COSINE: return hnsw_search_kernel_lds<F_COSINE, SH, true>;
 			default:       return hnsw_search_kernel_lds<F_MANHATTAN, SH, true>;
 		}
-	if (RREG == 0)
-		switch (func)
-		{
-			case F_L2:     return hnsw_search_kernel_lds<F_L2, SH, false>;
-			case F_COSINE: return hnsw_search_kernel_lds<F_COSINE, SH, false>;
-			default:       return hnsw_search_kernel_lds<F_MANHATTAN, SH, false>;
-		}
-#ifdef HNSW_EXPERIMENT
-	constexpr int R = (RREG <= 1 || RREG == 3) ? 2 : RREG;
-	switch (func)
+	switch (func)               // RREG == 0: generic form, sets in LDS
 	{
-		case F_L2:     return hnsw_search_kernel_reg<F_L2, SH, R>;
-		case F_COSINE: return hnsw_search_kernel_reg<F_COSINE, SH, R>;
-		default:       return hnsw_search_kernel_reg<F_MANHATTAN, SH, R>;
+		case F_L2:     return hnsw_search_kernel_lds<F_L2, SH, false>;
+		case F_COSINE: return hnsw_search_kernel_lds<F_COSINE, SH, false>;
+		default:       return hnsw_search_kernel_lds<F_MANHATTAN, SH, false>;
 	}
-#else
-	return nullptr;          // (the two-set register form exists in experiment builds only; the host never asks for it otherwise)
-#endif
 }
 
 template <typename SH>
@@ -77,10 +65,6 @@ inline search_kernel_t pick_search_kernel_s(int func, int rreg, bool team)
 {
 	switch (rreg)
 	{
-#ifdef HNSW_EXPERIMENT
-		case 2:  return pick_search_kernel_f<SH, 2>(func, false);
-		case 4:  return pick_search_kernel_f<SH, 4>(func, false);
-#endif
 		case -2: return pick_search_kernel_f<SH, -2>(func, team);
 		case -4: return pick_search_kernel_f<SH, -4>(func, team);
 		case -8: return pick_search_kernel_f<SH, -8>(func, team);
@@ -149,8 +133,5 @@ rerank_kernel_t pick_rerank_kernel_shape8x2(int func);
 rerank_kernel_t pick_rerank_kernel_shape12x2(int func);
 // the hot narrow-row form (rows of <= 128 floats, beam form with 2 / 4 set registers, L2 / Manhattan, one wave per query)
 search_kernel_t pick_kernel_shape2x2(int func, int rreg, bool lean);
-#ifdef HNSW_EXPERIMENT
-search_kernel_t pick_kernel_shape12x1(int func, int rreg, bool team);
-#endif
 
 }  // namespace pgemb

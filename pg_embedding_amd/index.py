@@ -522,7 +522,7 @@ class GpuIndex:
         return buf.value.decode()
 
     def team_counters(self):
-        """Launch-wide counters of the team form (needs HNSW_GPU_TEAM_COUNTERS=1): dict."""
+        """Launch-wide counters of the team form (all zero unless the library is a -DHNSW_TEAM_COUNTERS variant build): dict."""
         v = (C.c_uint32 * 16)()
         check(self.L.hnsw_gpu_team_counters(self._h, v), "hnsw_gpu_team_counters")
         names = ("hops_with_helpers", "link_hits", "ids_looked_up", "dist_hits", "hops_that_scored", "hops", "wait_polls",
@@ -530,7 +530,7 @@ class GpuIndex:
         return {k: int(v[i]) for i, k in enumerate(names)}
 
     def debug_counters(self):
-        """The 16 raw launch-wide debug counters (HNSW_GPU_TEAM_COUNTERS=1; -DHNSW_HOP_STAMPS builds put the per-section
+        """The 16 raw launch-wide debug counters of a diagnostic variant build (all zero in the product; -DHNSW_HOP_STAMPS builds put the per-section
         cycle sums of the walking waves there: hops, then pop / link wait / visited / scoring / accept / walk / emit in
         units of 64 cycles)."""
         v = (C.c_uint32 * 16)()
@@ -601,7 +601,7 @@ class GpuIndex:
         {"rows": (address, bytes), ...} plus "aligned_2MiB": do the three arrays start on 2 MiB boundaries."""
         v = (C.c_uint64 * 16)()
         check(self.L.hnsw_gpu_index_placement(self._h, v), "hnsw_gpu_index_placement")
-        names = ("arena", "rows", "links", "labels", "visited_bitmaps", "bitmap_logs", "prune_scratch", "ticket")
+        names = ("arena", "rows", "links", "labels", "visited_bitmaps", "bitmap_logs", "unused", "ticket")       # slot 6 is (0, 0): the beam form's prune needs no scratch
         out = {k: (int(v[2 * i]), int(v[2 * i + 1])) for i, k in enumerate(names)}
         out["aligned_2MiB"] = all(out[k][0] % (2 << 20) == 0 for k in ("rows", "links", "labels"))
         return out

@@ -30,13 +30,6 @@ if mode == "full":
         run(nq, 0)
     for bpc in (1, 2, 3, 4, 5):
         run(40000, bpc)
-elif mode == "shape":
-    for sh in ("12x2", "12x1"):
-        if sh == "12x1": os.environ["HNSW_GPU_SHAPE_12X1"] = "1"
-        else: os.environ.pop("HNSW_GPU_SHAPE_12X1", None)
-        print("shape", sh, flush=True)
-        for nq in (1, 2048, 10000, 40000, 160000):
-            run(nq, 0, reps=5)
 elif mode == "beam":
     efs = [int(x) for x in (sys.argv[7].split(",") if len(sys.argv) > 7 else [str(ef)])]
     for e in efs:

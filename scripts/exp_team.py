@@ -61,8 +61,8 @@ for nq in [int(x) for x in os.environ.get("EXP_NQS", "1,16,256,1024,2560,10000,4
         else:
             same = all((x == y).all() for x, y in zip(ref[nq], cur))
         cnt = ""
-        if os.environ.get("HNSW_GPU_TEAM_COUNTERS") and name != "one-wave":
-            c = ix.team_counters()
+        c = ix.team_counters()                                 # (all zero unless the library is a -DHNSW_TEAM_COUNTERS build)
+        if c["hops"] and name != "one-wave":
             cnt = (f" | hops {c['hops']} with helpers {c['hops_with_helpers']} link hits {c['link_hits']} ids {c['ids_looked_up']} "
                    f"dist hits {c['dist_hits']} hops that scored {c['hops_that_scored']} waited {c['hops_that_waited']} polls {c['wait_polls']} "
                    f"cyc pop+links {c['cyc_pop_links']} dists {c['cyc_dists']} accept {c['cyc_accept']} | helpers: {c['helper_elements']} elements, "

@@ -1,4 +1,4 @@
-"""Team-form counters of a launch (needs a -DHNSW_TEAM_COUNTERS build: PGEMB_GPU_LIB=.../libhnsw_gpu_teamcnt.so, HNSW_GPU_TEAM_COUNTERS=1):
+"""Team-form counters of a launch (needs a -DHNSW_TEAM_COUNTERS build: build.py variant teamcnt HNSW_TEAM_COUNTERS, PGEMB_GPU_LIB=.../libhnsw_gpu_teamcnt.so):
 how many hops found a helper's package, how many waited for one and for how long, how many still scored rows themselves, and what a
 helper's package costs.   usage: exp_team_counters.py <dim> <m> [metric] [nqs]"""
 import os, sys

@@ -10,7 +10,6 @@ mkdir -p $(dirname $OUT)
 : > $OUT
 for tag in "$@"; do
   if [ "$tag" = base ]; then unset PGEMB_GPU_LIB; else export PGEMB_GPU_LIB=$R/pg_embedding_amd/lib/variants/libhnsw_gpu_$tag.so; fi
-  case $tag in stamps*) export HNSW_GPU_TEAM_COUNTERS=1;; *) unset HNSW_GPU_TEAM_COUNTERS;; esac
   echo "## variant $tag: exp_cfg.py $ARGS" >> $OUT
   timeout 300 python $R/scripts/exp_cfg.py $ARGS >> $OUT 2>&1 || echo "variant $tag failed ($?)" >> $OUT
 done

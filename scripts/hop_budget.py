@@ -37,7 +37,7 @@ def sections():
     L = lambda s, a=0: find_line(ds, s, a)
     k0 = L("void hnsw_search_kernel_beam(const SearchArgs a)")
     hop0 = L("// hnswalg.cpp:67-112", k0)
-    pop_end = L("if (HOP_STAMPS && a.team_dbg) { hs1 = hop_stamp(); hs_pop += hs1 - hs0; hs0 = hs1; }", hop0)
+    pop_end = L("diag.mark(HS_POP);", hop0)
     link0 = L("for (uint32_t j0 = 0; j0 < a.maxM; j0 += 64)", hop0)
     vis0 = L("bool isnew = false;", link0)
     comp0 = L("const uint64_t mask = __ballot(isnew);", vis0)
@@ -54,6 +54,9 @@ def sections():
         while not ds[b - 1].startswith("}"):
             b += 1
         rng.append((a - 2, b, sec))
+    # the phases outside the hop are functions of their own (their lines lie in front of the kernel)
+    helper("__device__ __forceinline__ void mark_aborted(", "query set-up")
+    helper("__device__ __forceinline__ void restore_bitmap(", "emit")
     helper("__device__ __forceinline__ bool beam_next(", "pop")
     helper("__device__ __forceinline__ uint32_t wave_min_u32(", "pop")
     helper("__device__ __forceinline__ uint32_t beam_count_lt(", "stop test")

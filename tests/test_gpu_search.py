@@ -329,7 +329,7 @@ def test_many_queries_reuse_slots():
     {"HNSW_GPU_HASH_ENTRIES": "512"},        # tiny LDS visited set: most ids spill to the HBM bitmap
     {"HNSW_GPU_HASH_ENTRIES": "0"},          # bitmap only
     {"HNSW_GPU_FORCE_LDS_HEAPS": "1"},       # generic kernel (sorted arrays in LDS) at small ef
-    {"HNSW_GPU_BEAM": "0"},                  # no beam form: the generic kernel (the two-set register form lives in experiment builds only)
+    {"HNSW_GPU_BEAM": "0"},                  # no beam form: the generic kernel
     {"HNSW_GPU_BEAM": "0", "HNSW_GPU_HASH_ENTRIES": "512"},
     {"HNSW_GPU_BEAM16": "0"},                # ef in (256, 512]: LDS form instead of 16 set registers
     {"HNSW_GPU_TEAM": "1"},                  # team form: idle waves of a block feed a sibling's walk from LDS caches
