@@ -2,10 +2,13 @@
 Run as a subprocess by tests/test_reduced_rows_emu.py (the library is chosen by environment before pg_embedding_amd is imported).
 Prints one JSON line.
 
-    python tests/emu/run_reduced_rows_case.py parity|inexact [emulated-library]
+    python tests/emu/run_reduced_rows_case.py parity|inexact|middle [emulated-library]
 
 parity : rows that the 16-bit format represents exactly -> the walk over the copy IS the fp32 walk, so labels, distance bits, counts
          and the walk's evaluation / hop counts equal oracle.PortIndex.search_many's
+middle : the two middle load shapes at widths that end a load batch inside the row (130 dims: Shape4x2 / ShapeR16<., 2, 4, 4>, an odd kiters;
+         260 dims: Shape8x2 / ShapeR16<., 4, 2, 4>, a short second batch) — rows exact in both formats, the fp32 search and both reduced searches
+         against the oracle
 inexact: plain GMM rows -> every returned distance equals oracle.port_dist_many of the returned label's fp32 row, bitwise, in ascending
          (distance, label) order
 """
@@ -102,6 +105,31 @@ def compare(want, lab, dst, cnt, st, ef):
     return dict(wrong=wrong, stats_wrong=stats_wrong)
 
 
+def middle():
+    out = []
+    for dim in (130, 260):
+        for func in (pg.DIST_L2, pg.DIST_COSINE):
+            n, nq = 500, 4
+            X = (np.clip(np.rint(gmm(n, dim, k=6, seed=dim + func) * 32), -255, 255) / 32).astype(np.float32)     # exact in f16 and in bf16
+            assert (representable(X, "f16") == X).all() and (representable(X, "bf16") == X).all()
+            Q = gmm(nq, dim, k=6, seed=dim + func + 1, stream=1)
+            port, ix = build(n, dim, 8, func, X)
+            for ef in (16, 100):
+                want = port.search_many(Q, ef, nthreads=4)
+                fl, fd, fc = ix.search(Q, ef)
+                st0 = np.stack([want["evals"], want["hops"]], axis=1)
+                fp32 = dict(kernel=ix.last_search_kernel(), **compare(want, fl, fd, fc, st0, ef))
+                for fmt in ("f16", "bf16"):
+                    ix.set_reduced_rows(fmt)
+                    lab, dst, cnt, st = reduced_dev(ix, fmt, Q, ef)
+                    hl, hd, hc = ix.search(Q, ef, rows=fmt)
+                    out.append(dict(dim=dim, func=int(func), fmt=fmt, ef=ef, kernel=ix.last_search_kernel(), fp32_kernel=fp32["kernel"],
+                                    fp32_wrong=fp32["wrong"], **compare(want, lab, dst, cnt, st, ef),
+                                    host_same=bool((hl == lab).all() and (hd.view(np.uint32) == dst.view(np.uint32)).all() and (hc == cnt).all())))
+            ix.close()
+    return out
+
+
 def inexact():
     out = []
     for func in (pg.DIST_L2, pg.DIST_COSINE, pg.DIST_MANHATTAN):
@@ -131,4 +159,4 @@ def inexact():
 
 if __name__ == "__main__":
     case = sys.argv[1]
-    print(json.dumps({"parity": parity, "inexact": inexact}[case]()))
+    print(json.dumps({"parity": parity, "inexact": inexact, "middle": middle}[case]()))
