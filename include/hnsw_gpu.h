@@ -266,6 +266,43 @@ int hnsw_gpu_filtered_knn_mfma(hnsw_gpu_index *ix, int format, const coord_t *qu
 							   const uint32_t *allow, size_t allow_bits, size_t nfilters, const uint32_t *allow_of,
 							   label_t *labels, dist_t *dists, idx_t *idx, uint32_t *counts);
 
+/* Exact radius search: the k nearest elements WITHIN a distance, and how many elements are that close (csrc/device_range_knn.h) — the exact
+ * plan of  WHERE emb <-> q <= r [AND pred] ORDER BY emb <-> q LIMIT k.  Per query q with radius r_q = d_radius[q] and, with a filter, bitmap b:
+ * R(q) = the elements that are not vacuumed (bit 48 of the label word), whose label passes b (two elements holding one label both belong),
+ * and whose canonical fp32 distance d — the one the search and hnsw_dist_func compute, bit for bit — has d <= r_q.  The comparison is IEEE
+ * <= on the fp32 values, not bit-pattern order, and the boundary is inclusive (for <, pass nextafterf(r, -inf)).  The result is the
+ * min(k, |R|) elements of R with the smallest (distance, element number), written in ascending order of (distance, label), equal pairs by
+ * element number, tails padded exactly as hnsw_gpu_filtered_knn_dev pads them:
+ *   d_labels  nq*k, unused tail = ~0     d_dists  nq*k or NULL, tail = +inf     d_idx  nq*k element numbers or NULL, tail = 0xFFFFFFFF
+ *   d_counts  nq: min(k, |R(q)|)          d_totals nq or NULL: |R(q)|, the exact number of elements in range, whatever k is
+ * r_q = +inf: R is the whole allowed set and the answer is hnsw_gpu_filtered_knn_dev's bytes.  A NaN radius selects nothing (count 0,
+ * total 0).  A negative radius is legal (cosine distances can be slightly negative).  A NaN distance (a zero row under cosine) is outside
+ * the contract.  The filter convention is hnsw_gpu_scan_batch_dev's, d_allow == NULL meaning every label passes: then allow_bits, nfilters
+ * and d_allow_of are ignored and R is cut by the vacuum flag and the radius only (one implicit bitmap: a list of 4 bytes, or a mask of 1
+ * bit, per row).
+ * form: HNSW_GPU_RANGE_LISTED = the threshold scan over each query's list of allowed rows (|A(b)| rows of work per query); HNSW_GPU_RANGE_MFMA
+ * = every row against every query on the matrix cores, operands `format` (HNSW_GPU_ROWS_F32, or _F16 / _BF16: the reduced copy the index
+ * holds, else HNSW_GPU_ERR_ARG; ignored by the listed form), with the radius as the filter's bound — min(r_q, the k-th distance over a
+ * sample of the query's list) when d_totals is NULL, r_q itself when totals are asked for (every element in range must be re-scored to be
+ * counted) — and a canonical re-score of what passes.  The same bytes either way; there is no automatic choice.  The matrix-core form
+ * hands the call to the listed form where hnsw_gpu_filtered_knn_mfma_dev does (Manhattan, fewer than 4096 rows, a device other than gfx950,
+ * a (dim, k) whose re-score does not fit, a call whose lists are all short enough to be scanned whole) and when a query's candidate list
+ * passes its 16 384 entries (16-bit -> f32 -> listed, call-wide).  With totals every element in range is a candidate, so a radius that
+ * holds more than about 16 000 allowed elements for some query is answered by the listed form, by design; without totals the bound is
+ * never looser than the sample's k-th distance, and only thousands of ties at that distance overflow a list.
+ * hnsw_gpu_last_range_knn_form (hnsw_gpu_diag.h) names the form that answered.
+ * Argument rules as filtered k-NN: k outside [1, 1024], nq > 65535, a NULL d_queries / d_radius / d_labels / d_counts, a form that is
+ * neither, with a filter allow_bits == 0 or nfilters == 0, k and dim too large for one block's LDS: HNSW_GPU_ERR_ARG before anything is
+ * launched (outputs untouched); nq == 0: OK, nothing touched.  The call synchronises `stream`. */
+enum { HNSW_GPU_RANGE_LISTED = 0, HNSW_GPU_RANGE_MFMA = 1 };
+int hnsw_gpu_range_knn_dev(hnsw_gpu_index *ix, int form, int format, const coord_t *d_queries, size_t nq, const dist_t *d_radius, size_t k,
+						   const uint32_t *d_allow, size_t allow_bits, size_t nfilters, const uint32_t *d_allow_of,
+						   label_t *d_labels, dist_t *d_dists, idx_t *d_idx, uint32_t *d_counts, uint32_t *d_totals, void *stream);
+/* Host-pointer form: copies in, runs on the default stream, copies out. */
+int hnsw_gpu_range_knn(hnsw_gpu_index *ix, int form, int format, const coord_t *queries, size_t nq, const dist_t *radius, size_t k,
+					   const uint32_t *allow, size_t allow_bits, size_t nfilters, const uint32_t *allow_of,
+					   label_t *labels, dist_t *dists, idx_t *idx, uint32_t *counts, uint32_t *totals);
+
 /* Milliseconds the most recent search kernel of this index spent on the device,
  * from HIP events recorded on its stream around the launch (waits for it). */
 int hnsw_gpu_last_search_ms(hnsw_gpu_index *ix, float *ms);

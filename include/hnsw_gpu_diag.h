@@ -126,6 +126,20 @@ int hnsw_gpu_last_filtered_knn_form(hnsw_gpu_index *ix);
  * in MICROSECONDS from HIP events on the call's stream. */
 int hnsw_gpu_last_filtered_knn_mfma(hnsw_gpu_index *ix, uint64_t out[7]);
 
+/* The form that answered the mirror's last hnsw_gpu_range_knn[_dev] call that ended well: the listed scan, or the MFMA filter over f32 /
+ * fp16 / bf16 operands.  -1 before the first such call (and for a NULL index). */
+enum { HNSW_GPU_RK_FORM_LISTED = 0, HNSW_GPU_RK_FORM_F32 = 1, HNSW_GPU_RK_FORM_F16 = 2, HNSW_GPU_RK_FORM_BF16 = 3 };
+int hnsw_gpu_last_range_knn_form(hnsw_gpu_index *ix);
+/* The last pass of the mirror's last hnsw_gpu_range_knn[_dev] call (the pass that answered; the filtered k-NN figures above are not
+ * touched): out[0] = entries of all lists together (without a filter: the elements that are not vacuumed), out[1] = rows the threshold
+ * scan scored canonically (listed form: the sum of the queries' own list lengths; a NaN radius, or a negative one under L2, scans nothing; matrix-core form: the lists
+ * scanned whole and, without totals, the samples), out[2] = dist_pass: (query, row) pairs that passed the filter's comparison, before the
+ * allow test, out[3] = appended: pairs that went to a candidate list, out[4] = the sum over the queries of the in-range rows counted
+ * (listed form, or with totals: the sum of |R(q)|; matrix-core form without totals: in-range candidates, at least min(k, |R(q)|) each),
+ * out[5] = list build (+ row masks), out[6] = the filter kernel, out[7] = the whole call, all three in MICROSECONDS from HIP events on the
+ * call's stream.  out[2], out[3] and out[6] are zero after a listed answer. */
+int hnsw_gpu_last_range_knn(hnsw_gpu_index *ix, uint64_t out[8]);
+
 #ifdef __cplusplus
 }
 #endif

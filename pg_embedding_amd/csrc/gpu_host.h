@@ -141,6 +141,9 @@ struct FkWs
 	float build_ms = 0.f, scan_ms = 0.f;
 	int form = -1;                                       // the form that answered it (HNSW_GPU_FK_FORM_*, hnsw_gpu_last_filtered_knn_form)
 	struct Mfma { uint64_t listed = 0, scored = 0, dist_pass = 0, appended = 0; float build_ms = 0.f, filter_ms = 0.f, call_ms = 0.f; } m;   // its last filter launch (hnsw_gpu_last_filtered_knn_mfma)
+	// the last radius search (device_range_knn.h, hnsw_gpu_last_range_knn): it uses the buffers above (bfs: its per-query scratch in both forms;
+	// host[6]: the sum of its totals) and keeps figures of its own, so the filtered k-NN diagnostics stay those of the last filtered k-NN call
+	struct Range { uint64_t listed = 0, scored = 0, dist_pass = 0, appended = 0, totals = 0; float build_ms = 0.f, filter_ms = 0.f, call_ms = 0.f; int form = -1; } r;
 };
 void fk_ws_free(FkWs *s);
 

@@ -1,6 +1,7 @@
 // gpu_scan.hip — batched distances (hnsw_dist_func over many rows), exhaustive k-NN: canonical scan (csrc/device_topk_scan.h), MFMA filter over
 // the f32 rows or the reduced copy (csrc/device_bf_mfma.h, csrc/device_bf_mfma16.h), and exact filtered k-NN: the canonical scan over lists of
-// allowed rows (csrc/device_filtered_knn.h) or, for loose filters, the MFMA filter with the allow test at its append (csrc/device_filtered_knn_mfma.h)
+// allowed rows (csrc/device_filtered_knn.h) or, for loose filters, the MFMA filter with the allow test at its append (csrc/device_filtered_knn_mfma.h),
+// and exact radius search over the same lists, masks and filter (csrc/device_range_knn.h)
 // One translation unit of libhnsw_gpu.so (csrc/gpu_host.h lists them); gfx950 only, plain HIP runtime, no framework types in any signature.
 #include "gpu_host.h"
 #include "device_topk_scan.h"
@@ -8,6 +9,7 @@
 #include "device_bf_mfma16.h"
 #include "device_filtered_knn.h"
 #include "device_filtered_knn_mfma.h"
+#include "device_range_knn.h"
 
 #include <type_traits>
 
@@ -477,7 +479,9 @@ struct FkCall
 	hnsw_gpu_index *ix; const coord_t *queries; size_t nq, k; const uint32_t *allow; size_t allow_bits, nfilters; const uint32_t *allow_of;
 	label_t *labels; dist_t *dists; idx_t *idx; uint32_t *counts; hipStream_t s;
 	FkLists fl; uint64_t *off; unsigned long long *scored; size_t nsb, total, longest;
+	const char *who;                                              // the call's name in a message; NULL: filtered k-NN
 };
+static const char *fk_who(const FkCall &c) { return c.who ? c.who : "filtered k-NN"; }
 struct FkTrim { FkWs *w; ~FkTrim() { buf_trim({&w->cells, &w->list, &w->part, &w->mask, &w->bfs, &w->cand}); } };   // on EVERY way out, errors included: no buffer above 64 MiB outlives its call
 
 static int fk_begin(FkCall &c)
@@ -492,7 +496,8 @@ static int fk_begin(FkCall &c)
 	return HNSW_GPU_OK;
 }
 
-// 1. the allowed lists: count per (bitmap, segment), offsets, fill
+// 1. the allowed lists: count per (bitmap, segment), offsets, fill.  c.allow == NULL (radius search without a filter: nfilters == 1): the one
+// list of the rows that are not vacuumed (rk_live_kernel)
 static int fk_lists(FkCall &c)
 {
 	hnsw_gpu_index *ix = c.ix;
@@ -501,9 +506,9 @@ static int fk_lists(FkCall &c)
 	const size_t n = ix->n, nfilters = c.nfilters;
 	const uint32_t nseg = (uint32_t) std::max<size_t>(1, (n + FK_SEG - 1) / FK_SEG);
 	const size_t ncells = (size_t) nseg * nfilters, nsb = (nseg + 3) / 4;
-	if (nsb * nfilters >= 0x7FFFFFFFull) return fail(HNSW_GPU_ERR_ARG, "filtered k-NN: %zu filters over %zu rows are too many for one call", nfilters, n);
+	if (nsb * nfilters >= 0x7FFFFFFFull) return fail(HNSW_GPU_ERR_ARG, "%s: %zu filters over %zu rows are too many for one call", fk_who(c), nfilters, n);
 	const size_t o_off = round_up(ncells * 4, 256), o_scored = o_off + round_up((ncells + 1) * 8, 256);
-	int rc = buf_reserve(&fw->cells, o_scored + 256, "filtered k-NN", "the list offsets");
+	int rc = buf_reserve(&fw->cells, o_scored + 256, fk_who(c), "the list offsets");
 	if (rc) return rc;
 	uint32_t *cells = (uint32_t *) fw->cells.p;
 	uint64_t *off = (uint64_t *) ((char *) fw->cells.p + o_off);
@@ -514,14 +519,16 @@ static int fk_lists(FkCall &c)
 	fl.allow = c.allow; fl.allow_bits = c.allow_bits; fl.allow_words = (uint32_t) ((c.allow_bits + 31) / 32); fl.nfilters = (uint32_t) nfilters;
 	fw->host[0] = fw->host[1] = fw->host[2] = 0;
 	HIPCHK(hipEventRecord(fw->ev[0], s));
-	hipLaunchKernelGGL(fk_count_kernel, dim3((uint32_t) (nsb * nfilters)), dim3(256), 0, s, fl, cells);
+	if (c.allow) hipLaunchKernelGGL(fk_count_kernel, dim3((uint32_t) (nsb * nfilters)), dim3(256), 0, s, fl, cells);
+	else hipLaunchKernelGGL(rk_live_kernel<RK_LIVE_COUNT>, dim3((uint32_t) nsb), dim3(256), 0, s, fl, (const uint64_t *) nullptr, cells);
 	hipLaunchKernelGGL(fk_offsets_kernel, dim3(1), dim3(FK_SCAN_THREADS), FK_SCAN_THREADS * 8, s, (const uint32_t *) cells, nseg, (uint32_t) nfilters, off, fw->host);
 	HIPCHK(hipGetLastError());
 	HIPCHK(hipStreamSynchronize(s));                              // the one wait before the scan: the lists are sized exactly
 	const size_t total = fw->host[0], longest = fw->host[1];
-	if (longest > n || total > n * nfilters) return fail(HNSW_GPU_ERR_INTERNAL, "filtered k-NN: %zu listed rows, longest list %zu, of %zu rows", total, longest, n);
-	if ((rc = buf_reserve(&fw->list, total * 4, "filtered k-NN", "the lists of allowed rows"))) return rc;
-	if (total) hipLaunchKernelGGL(fk_fill_kernel, dim3((uint32_t) (nsb * nfilters)), dim3(256), 0, s, fl, (const uint64_t *) off, (uint32_t *) fw->list.p);
+	if (longest > n || total > n * nfilters) return fail(HNSW_GPU_ERR_INTERNAL, "%s: %zu listed rows, longest list %zu, of %zu rows", fk_who(c), total, longest, n);
+	if ((rc = buf_reserve(&fw->list, total * 4, fk_who(c), "the lists of allowed rows"))) return rc;
+	if (total && c.allow) hipLaunchKernelGGL(fk_fill_kernel, dim3((uint32_t) (nsb * nfilters)), dim3(256), 0, s, fl, (const uint64_t *) off, (uint32_t *) fw->list.p);
+	else if (total) hipLaunchKernelGGL(rk_live_kernel<RK_LIVE_FILL>, dim3((uint32_t) nsb), dim3(256), 0, s, fl, (const uint64_t *) off, (uint32_t *) fw->list.p);
 	HIPCHK(hipMemsetAsync(scored, 0, 8, s));
 	HIPCHK(hipEventRecord(fw->ev[1], s));
 	c.off = off; c.scored = scored; c.nsb = nsb; c.total = total; c.longest = longest;
@@ -557,7 +564,7 @@ static int fk_splits(const FkCall &c, size_t longest, uint32_t *out)
 	while (splits > 1 && nq * splits * 4 * k * 8 > FK_PART_BYTES) splits /= 2;
 	*out = splits;
 	if (!longest) return HNSW_GPU_OK;                             // (no list, no scan: the emit kernel reads no partial list)
-	return buf_reserve(&ix->fk.part, nq * splits * 4 * k * 8, "filtered k-NN", "the partial result lists");
+	return buf_reserve(&ix->fk.part, nq * splits * 4 * k * 8, fk_who(c), "the partial result lists");
 }
 static void fk_scan_launch(const FkCall &c, const FkScan &fs)
 {
@@ -858,6 +865,286 @@ extern "C" int hnsw_gpu_last_filtered_knn_mfma(hnsw_gpu_index *ix, uint64_t out[
 	out[4] = (uint64_t) std::llround((double) m.build_ms * 1000.0);
 	out[5] = (uint64_t) std::llround((double) m.filter_ms * 1000.0);
 	out[6] = (uint64_t) std::llround((double) m.call_ms * 1000.0);
+	return HNSW_GPU_OK;
+}
+
+// ------------------------------------------------------------------------------------
+// exact radius search: the k nearest within a distance, with totals (device_range_knn.h)
+// ------------------------------------------------------------------------------------
+struct RkCall { FkCall c; const dist_t *radius; uint32_t *totals; };
+
+static int rk_check(hnsw_gpu_index *ix, int form, const void *queries, size_t nq, const void *radius, size_t k, const void *allow, size_t allow_bits,
+					size_t nfilters, const void *labels, const void *counts)
+{
+	if (!ix) return fail(HNSW_GPU_ERR_ARG, "index is NULL");
+	if (nq == 0) return HNSW_GPU_OK;
+	if (form != HNSW_GPU_RANGE_LISTED && form != HNSW_GPU_RANGE_MFMA) return fail(HNSW_GPU_ERR_ARG, "radius search: form %d is neither listed (0) nor matrix cores (1)", form);
+	if (!queries || !radius || !labels || !counts) return fail(HNSW_GPU_ERR_ARG, "radius search: NULL buffer");
+	if (k == 0 || k > 1024) return fail(HNSW_GPU_ERR_ARG, "k %zu out of range [1, 1024]", k);
+	if (nq > 65535) return fail(HNSW_GPU_ERR_ARG, "at most 65535 queries per call");
+	if (allow && (allow_bits == 0 || nfilters == 0)) return fail(HNSW_GPU_ERR_ARG, "radius search: an allow filter of no bits");
+	if (allow && ((allow_bits + 31) / 32 >= 0xFFFFFFFFull || nfilters >= 0xFFFFFFFFull)) return fail(HNSW_GPU_ERR_ARG, "radius search: allow filter too large");
+	const uint32_t kiters = (ix->stride / 4 + 15) / 16;
+	const size_t lds = round_up(kiters, 4) * 64 * 4 + (size_t) 4 * (k + 1) * 8 + 4 * 128 * 4 + 4 * 64 * 4;
+	if (lds > 64 * 1024) return fail(HNSW_GPU_ERR_ARG, "k/dim too large for radius search");
+	return HNSW_GPU_OK;
+}
+
+static int rk_begin(FkCall &c)
+{
+	HIPCHK(hipSetDevice(c.ix->device));
+	FkWs *fw = &c.ix->fk;
+	if (!fw->host) HIPCHK(hipHostMalloc((void **) &fw->host, 64, hipHostMallocDefault));
+	for (hipEvent_t &e : fw->ev)
+		if (!e) HIPCHK(hipEventCreate(&e));
+	const int form = fw->r.form;
+	fw->r = FkWs::Range();
+	fw->r.form = form;                                            // (the form that answered the last call that ended well)
+	return HNSW_GPU_OK;
+}
+
+// One pass over the built lists (and masks).  format < 0: the listed form — the threshold scan over every query's whole list, merge,
+// emit.  Else the matrix-core form with the operands of `format`: the scan over the lists no longer than their sample and (without totals)
+// over the samples of the others -> merge + bounds -> filter (or its stand-in) -> threshold re-score -> emit.  *ovf = candidate lists
+// that overflowed (then the outputs are not the answer: the caller hands the call down).
+static int rk_pass(RkCall &r, int format, bool standin, uint32_t smin, uint32_t mwords, uint64_t *ovf)
+{
+	FkCall &c = r.c;
+	hnsw_gpu_index *ix = c.ix;
+	FkWs *fw = &ix->fk;
+	hipStream_t s = c.s;
+	const bool listed = format < 0, reduced = !listed && format != ROWS_F32, skip = !listed && r.totals;
+	const size_t nq = c.nq, k = c.k;
+	const int func = (int) ix->meta.dist_func;
+	const uint32_t n = (uint32_t) ix->n, stride = ix->stride, dim = (uint32_t) ix->meta.dim;
+	const uint32_t nchunks = stride / 4, kiters = (nchunks + 15) / 16;
+	const uint32_t qpadf = (uint32_t) round_up(kiters, 4) * 64;
+	const size_t wave_bytes = round_up((size_t) qpadf * 4 + (k + 1) * 8 + 128 * 4, 16);
+	int rc = listed ? HNSW_GPU_OK : bf_rows_side(ix, reduced, s);
+	if (rc) return rc;
+	const uint32_t qchunks = listed ? 0 : reduced ? ix->rows16_bytes / 16 : (uint32_t) round_up(stride, BF_TK) / 4;
+	const uint32_t rchunks = reduced ? ix->rows16_bytes / 16 : nchunks;
+	const uint32_t cap = 16384;
+	// the longest run of list entries a query scans: its whole list, its sample, or (totals) a list no longer than its sample
+	const size_t slongest = listed ? c.longest : skip ? std::min<size_t>(c.longest, smin) : fk_sample_len((uint32_t) c.longest, smin, (uint32_t) k);
+	uint32_t splits = 1;
+	if ((rc = fk_splits(c, slongest, &splits))) return rc;
+	// scratch carve
+	const size_t o_keys = 0;
+	const size_t o_rcnt = o_keys + round_up(nq * k * 8, 256);
+	const size_t o_off = o_rcnt + round_up(nq * 4, 256);
+	const size_t o_aof = o_off + round_up(nq * 16, 256);
+	const size_t o_pcnt = o_aof + round_up(nq * 4, 256);
+	const size_t o_sum = o_pcnt + round_up(nq * (size_t) splits * 16, 256);
+	const size_t o_q = o_sum + 256;
+	const size_t o_qn = o_q + round_up(nq * (size_t) qchunks * 16, 256);
+	const size_t o_qt = o_qn + round_up(nq * 4, 256);
+	const size_t o_tau = o_qt + round_up(nq * 8, 256);
+	const size_t o_bound = o_tau + round_up(nq * 4, 256);
+	const size_t o_mof = o_bound + round_up(nq * 4, 256);
+	const size_t o_cnt = o_mof + round_up(nq * 4, 256);
+	const size_t o_fcnt = o_cnt + round_up(nq * 4 + 64, 256);
+	const size_t total = o_fcnt + 256;
+	if ((rc = buf_reserve(&fw->bfs, total, "radius search", "the per-query scratch"))) return rc;
+	if (!listed && (rc = buf_reserve(&fw->cand, nq * (size_t) cap * 4, "radius search", "the candidate lists"))) return rc;
+	char *B = (char *) fw->bfs.p;
+	uint64_t *keys = (uint64_t *) (B + o_keys), *off2 = (uint64_t *) (B + o_off);
+	uint32_t *rcount = (uint32_t *) (B + o_rcnt), *aof2 = (uint32_t *) (B + o_aof), *pcount = (uint32_t *) (B + o_pcnt);
+	unsigned long long *sum = (unsigned long long *) (B + o_sum), *fcnt = (unsigned long long *) (B + o_fcnt);
+	uint4 *qcopy = (uint4 *) (B + o_q);
+	float *qn = (float *) (B + o_qn), *tau = (float *) (B + o_tau), *bound = (float *) (B + o_bound);
+	float2 *qterms = (float2 *) (B + o_qt);
+	uint32_t *mask_of = (uint32_t *) (B + o_mof), *cnt = (uint32_t *) (B + o_cnt), *cand = (uint32_t *) fw->cand.p;
+	uint32_t *overflow = cnt + nq;
+
+	// the threshold scan, then per query: its keys, its in-range count and (matrix-core form) its bound and mask row
+	FkEmit fe = fk_kernel_args(c);
+	RkMerge rm;
+	memset(&rm, 0, sizeof(rm));
+	rm.r.s = fe.s;
+	rm.r.s.splits = splits; rm.r.s.part = (uint64_t *) fw->part.p; rm.r.s.smin = listed ? 0u : smin;
+	rm.r.radius = r.radius; rm.r.pcount = pcount; rm.r.skip_samples = skip ? 1u : 0u; rm.r.func = func;
+	rm.nfilters = (uint32_t) c.nfilters; rm.keys = keys; rm.rcount = rcount; rm.tau = listed ? nullptr : tau; rm.mask_of = mask_of;
+	HIPCHK(hipMemsetAsync(c.scored, 0, 8, s));
+	HIPCHK(hipMemsetAsync(sum, 0, 8, s));
+	if (slongest)
+	{
+		const size_t lds = (size_t) qpadf * 4 + (size_t) 4 * (k + 1) * 8 + 4 * 128 * 4 + 4 * 64 * 4;
+		const dim3 grid((uint32_t) round_up((size_t) splits * nq, 8));
+		with_func(func, [&](auto F) { hipLaunchKernelGGL(rk_scan_kernel<decltype(F)::value>, grid, dim3(256), lds, s, rm.r); });
+	}
+	hipLaunchKernelGGL(rk_merge_kernel, dim3((uint32_t) nq), dim3(64), k * 8, s, rm);
+	if (!listed)
+	{
+		bf_queries_side(reduced, format, c.queries, nq, dim, qchunks, qcopy, qn, qterms, s);
+		hipLaunchKernelGGL(make_bounds_kernel, dim3((uint32_t) ((nq + 255) / 256)), dim3(256), 0, s, (const float *) tau, qn, (uint32_t) nq, func, dim, bound);
+		HIPCHK(hipMemsetAsync(cnt, 0, nq * 4 + 64, s));               // (the candidate counts and the overflow word behind them)
+		HIPCHK(hipMemsetAsync(fcnt, 0, 16, s));
+		// the filter over all rows, the allow test (the mask of allowed, or of live, rows) at its append
+		BfArgs a;
+		memset(&a, 0, sizeof(a));
+		a.queries = qcopy; a.qnorm = qn; a.qbound = bound; a.qterms = qterms;
+		a.rows = reduced ? (const uint4 *) ix->rows16 : (const uint4 *) ix->vec; a.xnorm = ix->xnorm; a.xterms = ix->r16x;
+		a.nq = (uint32_t) nq; a.n = n; a.qchunks = qchunks; a.rchunks = rchunks; a.ksteps = qchunks / BF_CH; a.func = func;
+		a.xscale = 0.5f * (1.f - 2.f * ((float) dim + 32.f) * 0x1p-24f);          // (1 - eD) / 2: make_bounds_kernel
+		a.eabs = r16_abs_term(dim);
+		a.cand = cand; a.cand_cnt = cnt; a.cap = cap;
+		a.mask = (const uint32_t *) fw->mask.p; a.mask_of = mask_of; a.mwords = mwords; a.fcnt = fcnt;
+		HIPCHK(hipEventRecord(fw->ev[3], s));
+		if (standin)
+			with_func(func, [&](auto F) {
+				hipLaunchKernelGGL(fkm_standin_kernel<decltype(F)::value>, dim3((uint32_t) nq), dim3(256), (size_t) qpadf * 4 + 4 * 128 * 4, s, a, ix->vec, dim, stride,
+								   nchunks, kiters, qpadf, c.queries, (const float *) tau);
+			});
+		else if ((rc = with_form(format, [&](auto p) { return bf_filter_pick<BfAllow<decltype(p)>>(ix, a, s); })))
+			return rc;
+		HIPCHK(hipEventRecord(fw->ev[4], s));
+		with_func(func, [&](auto F) {
+			if constexpr (decltype(F)::value != F_MANHATTAN)           // (answered by the listed form: no re-score kernel is compiled for it)
+				hipLaunchKernelGGL(rk_rescore_kernel<decltype(F)::value>, dim3((uint32_t) ((nq + 3) / 4)), dim3(256), wave_bytes * 4, s, ix->vec, dim, stride, nchunks,
+								   kiters, qpadf, c.queries, (uint32_t) nq, r.radius, (const uint32_t *) mask_of, (uint32_t) c.nfilters, (const uint32_t *) cand,
+								   (const uint32_t *) cnt, cap, (uint32_t) k, keys, rcount, overflow);
+		});
+	}
+	// counts as list lengths, totals -> the emit kernel over one key list per query
+	hipLaunchKernelGGL(rk_finish_kernel, dim3((uint32_t) ((nq + 255) / 256)), dim3(256), 0, s, (const uint32_t *) rcount, (uint32_t) nq, (uint32_t) k, off2, aof2,
+					   r.totals, sum);
+	fe.s.off = off2; fe.s.allow_of = aof2; fe.s.nseg = 1; fe.s.smin = 0;
+	fe.single = keys;
+	hipLaunchKernelGGL(fk_emit_kernel, dim3((uint32_t) nq), dim3(64), k * 16, s, fe);
+	hipError_t e = hipGetLastError();
+	if (e == hipSuccess) e = hipEventRecord(fw->ev[2], s);
+	fw->host[3] = fw->host[4] = fw->host[5] = 0;
+	if (e == hipSuccess) e = hipMemcpyAsync(&fw->host[2], c.scored, 8, hipMemcpyDeviceToHost, s);
+	if (e == hipSuccess) e = hipMemcpyAsync(&fw->host[6], sum, 8, hipMemcpyDeviceToHost, s);
+	if (e == hipSuccess && !listed) e = hipMemcpyAsync(&fw->host[3], fcnt, 16, hipMemcpyDeviceToHost, s);
+	if (e == hipSuccess && !listed) e = hipMemcpyAsync(&fw->host[5], overflow, 4, hipMemcpyDeviceToHost, s);
+	const hipError_t e2 = hipStreamSynchronize(s);
+	if (e == hipSuccess) e = e2;
+	if (e != hipSuccess) return fail(HNSW_GPU_ERR_HIP, "radius search: %s", hipGetErrorString(e));
+	*ovf = fw->host[5];
+	FkWs::Range &m = fw->r;
+	m.listed = c.total; m.scored = fw->host[2]; m.dist_pass = fw->host[3]; m.appended = fw->host[4]; m.totals = fw->host[6];
+	m.filter_ms = 0.f;
+	(void) hipEventElapsedTime(&m.build_ms, fw->ev[0], fw->ev[1]);
+	if (!listed) (void) hipEventElapsedTime(&m.filter_ms, fw->ev[3], fw->ev[4]);
+	(void) hipEventElapsedTime(&m.call_ms, fw->ev[0], fw->ev[2]);
+	return HNSW_GPU_OK;
+}
+
+extern "C" int hnsw_gpu_range_knn_dev(hnsw_gpu_index *ix, int form, int format, const coord_t *d_queries, size_t nq, const dist_t *d_radius, size_t k,
+									  const uint32_t *d_allow, size_t allow_bits, size_t nfilters, const uint32_t *d_allow_of, label_t *d_labels,
+									  dist_t *d_dists, idx_t *d_idx, uint32_t *d_counts, uint32_t *d_totals, void *stream)
+{
+	std::unique_lock<std::recursive_mutex> lock_;
+	if (ix) lock_ = std::unique_lock<std::recursive_mutex>(ix->mu);
+	if (int rc0 = rk_check(ix, form, d_queries, nq, d_radius, k, d_allow, allow_bits, nfilters, d_labels, d_counts)) return rc0;
+	if (nq == 0) return HNSW_GPU_OK;
+	if (form == HNSW_GPU_RANGE_MFMA)
+		if (int rc0 = fk_check_format(ix, format)) return rc0;
+	// no filter: ONE implicit bitmap that every label passes — the list / mask of the rows that are not vacuumed
+	RkCall r = { { ix, d_queries, nq, k, d_allow, d_allow ? allow_bits : 0, d_allow ? nfilters : 1, d_allow ? d_allow_of : nullptr, d_labels, d_dists, d_idx,
+				   d_counts, (hipStream_t) stream }, d_radius, d_totals };
+	FkCall &c = r.c;
+	c.who = "radius search";
+	// the matrix-core form where hnsw_gpu_filtered_knn_mfma_dev has one (its rules), else the listed form
+	const bool standin = knob(K_FK_MFMA_STANDIN, 0) != 0;
+	const int func = (int) ix->meta.dist_func;
+	const uint32_t kiters = (ix->stride / 4 + 15) / 16;
+	const size_t wave_bytes = round_up(round_up(kiters, 4) * 64 * 4 + (k + 1) * 8 + 128 * 4, 16);
+#ifdef PGEMB_SIMT_EMULATOR
+	const bool have_filter = false;
+#else
+	const bool have_filter = ix->n >= 4096 && ix->gfx950 && ix->max_lds >= BF_MIN_LDS;
+#endif
+	bool mfma = form == HNSW_GPU_RANGE_MFMA && func != F_MANHATTAN && wave_bytes * 4 <= 64 * 1024 && (standin || have_filter);
+	if (standin) format = ROWS_F32;
+
+	FkWs *fw = &ix->fk;
+	FkTrim trim_{fw};
+	int rc = rk_begin(c);
+	if (!rc) rc = fk_lists(c);
+	if (rc) return rc;
+	const uint32_t smin = (uint32_t) std::min<long long>(0xFFFFFFFFll, std::max<long long>(1, knob(K_FK_SAMPLE_MIN, FKM_SAMPLE_MIN)));
+	if (c.longest <= smin) mfma = false;                          // every query is answered by the scan of its whole list
+	uint32_t mwords = 0;
+	if (mfma)
+	{
+		// the row masks (counted with the list build), and a row of zeros behind them
+		const size_t nf = c.nfilters;
+		mwords = fkm_mask_words((uint32_t) ix->n);
+		if ((rc = buf_reserve(&fw->mask, (nf + 1) * (size_t) mwords * 4, "radius search", "the row masks"))) return rc;
+		if (c.allow) hipLaunchKernelGGL(fkm_mask_kernel, dim3((uint32_t) (c.nsb * nf)), dim3(256), 0, c.s, c.fl, mwords, (uint32_t *) fw->mask.p);
+		else hipLaunchKernelGGL(rk_live_kernel<RK_LIVE_MASK>, dim3((uint32_t) c.nsb), dim3(256), 0, c.s, c.fl, (const uint64_t *) nullptr, (uint32_t *) fw->mask.p);
+		HIPCHK(hipMemsetAsync((uint32_t *) fw->mask.p + nf * (size_t) mwords, 0, (size_t) mwords * 4, c.s));
+		HIPCHK(hipEventRecord(fw->ev[1], c.s));
+	}
+	// a candidate list that overflows sends a 16-bit call to the f32 operands and an f32 call to the listed form, call-wide
+	int pass = mfma ? format : -1;
+	for (;;)
+	{
+		uint64_t ovf = 0;
+		if ((rc = rk_pass(r, pass, standin, smin, mwords, &ovf))) return rc;
+		if (!ovf) break;
+		pass = pass == ROWS_F32 ? -1 : ROWS_F32;
+	}
+	fw->r.form = pass < 0 ? HNSW_GPU_RK_FORM_LISTED : pass == ROWS_F32 ? HNSW_GPU_RK_FORM_F32 : pass == ROWS_BF16 ? HNSW_GPU_RK_FORM_BF16 : HNSW_GPU_RK_FORM_F16;
+	return HNSW_GPU_OK;
+}
+
+// the host-pointer form: copy in, run on the default stream, copy out
+extern "C" int hnsw_gpu_range_knn(hnsw_gpu_index *ix, int form, int format, const coord_t *queries, size_t nq, const dist_t *radius, size_t k,
+								  const uint32_t *allow, size_t allow_bits, size_t nfilters, const uint32_t *allow_of, label_t *labels, dist_t *dists,
+								  idx_t *idx, uint32_t *counts, uint32_t *totals)
+{
+	std::unique_lock<std::recursive_mutex> lock_;
+	if (ix) lock_ = std::unique_lock<std::recursive_mutex>(ix->mu);
+	if (int rc0 = rk_check(ix, form, queries, nq, radius, k, allow, allow_bits, nfilters, labels, counts)) return rc0;
+	if (nq == 0) return HNSW_GPU_OK;
+	if (form == HNSW_GPU_RANGE_MFMA)
+		if (int rc0 = fk_check_format(ix, format)) return rc0;
+	HIPCHK(hipSetDevice(ix->device));
+	const size_t dim = ix->meta.dim, words = (allow_bits + 31) / 32;
+	const size_t qb = round_up(nq * dim * 4, 256), rb = round_up(nq * 4, 256), fb = round_up(allow ? nfilters * words * 4 : 0, 256),
+				 ob = round_up(allow && allow_of ? nq * 4 : 0, 256), lb = round_up(nq * k * 8, 256), db = round_up(nq * k * 4, 256), cb = round_up(nq * 4, 256);
+	int rc = ensure_scratch(ix, qb + rb + fb + ob + lb + 2 * db + 2 * cb);
+	if (rc) return rc;
+	char *p = (char *) ix->scratch;
+	float *dq = (float *) p, *dr = (float *) (p + qb); uint32_t *df = (uint32_t *) (p + qb + rb), *dof = (uint32_t *) (p + qb + rb + fb);
+	char *o = p + qb + rb + fb + ob;
+	uint64_t *dl = (uint64_t *) o; float *dd = (float *) (o + lb);
+	uint32_t *di = (uint32_t *) (o + lb + db), *dc = (uint32_t *) (o + lb + 2 * db), *dt = (uint32_t *) (o + lb + 2 * db + cb);
+	HIPCHK(hipMemcpy(dq, queries, nq * dim * 4, hipMemcpyHostToDevice));
+	HIPCHK(hipMemcpy(dr, radius, nq * 4, hipMemcpyHostToDevice));
+	if (allow) HIPCHK(hipMemcpy(df, allow, nfilters * words * 4, hipMemcpyHostToDevice));
+	if (allow && allow_of) HIPCHK(hipMemcpy(dof, allow_of, nq * 4, hipMemcpyHostToDevice));
+	rc = hnsw_gpu_range_knn_dev(ix, form, format, dq, nq, dr, k, allow ? df : nullptr, allow_bits, nfilters, allow && allow_of ? dof : nullptr, dl, dd, di, dc,
+								totals ? dt : nullptr, nullptr);
+	if (rc) return rc;
+	HIPCHK(hipMemcpy(labels, dl, nq * k * 8, hipMemcpyDeviceToHost));
+	if (dists) HIPCHK(hipMemcpy(dists, dd, nq * k * 4, hipMemcpyDeviceToHost));
+	if (idx) HIPCHK(hipMemcpy(idx, di, nq * k * 4, hipMemcpyDeviceToHost));
+	HIPCHK(hipMemcpy(counts, dc, nq * 4, hipMemcpyDeviceToHost));
+	if (totals) HIPCHK(hipMemcpy(totals, dt, nq * 4, hipMemcpyDeviceToHost));
+	return HNSW_GPU_OK;
+}
+
+extern "C" int hnsw_gpu_last_range_knn_form(hnsw_gpu_index *ix)
+{
+	if (!ix) return -1;
+	std::lock_guard<std::recursive_mutex> lock_(ix->mu);
+	return ix->fk.r.form;
+}
+
+extern "C" int hnsw_gpu_last_range_knn(hnsw_gpu_index *ix, uint64_t out[8])
+{
+	if (!ix || !out) return fail(HNSW_GPU_ERR_ARG, "NULL argument");
+	std::lock_guard<std::recursive_mutex> lock_(ix->mu);
+	const FkWs::Range &m = ix->fk.r;
+	out[0] = m.listed; out[1] = m.scored; out[2] = m.dist_pass; out[3] = m.appended; out[4] = m.totals;
+	out[5] = (uint64_t) std::llround((double) m.build_ms * 1000.0);
+	out[6] = (uint64_t) std::llround((double) m.filter_ms * 1000.0);
+	out[7] = (uint64_t) std::llround((double) m.call_ms * 1000.0);
 	return HNSW_GPU_OK;
 }
 

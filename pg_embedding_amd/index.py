@@ -496,6 +496,79 @@ class GpuIndex:
         return {"listed": int(v[0]), "rows_scored": int(v[1]), "dist_pass": int(v[2]), "appended": int(v[3]), "build_ms": v[4] / 1000.0,
                 "filter_ms": v[5] / 1000.0, "call_ms": v[6] / 1000.0}
 
+    # ---------------------------------------------------------------- exact radius search
+    def range_knn(self, queries: np.ndarray, radius, k: int, allow=None, allow_of=None, return_idx: bool = False, totals: bool = False,
+                  form=None, rows=None):
+        """Exact k nearest elements WITHIN a distance per query, host buffers (hnsw_gpu_range_knn): the elements that are not vacuumed,
+        pass the query's filter (allow / allow_of as in scan(); allow=None: every label passes) and have a canonical distance <= radius
+        (a scalar, or one value per query; inclusive; NaN selects nothing).  Returns a dict like filtered_knn(): labels [nq, k] u64 in
+        ascending (distance, label) order (tail ~0), dists [nq, k] f32 (tail +inf), counts [nq] u32 = min(k, elements in range), idx with
+        return_idx=True, and with totals=True totals [nq] u32 = the exact number of elements in range, whatever k is.  form=None |
+        "listed": a scan over each query's allowed rows; form="mfma": the same answer with the Q x N part on the matrix cores and the
+        radius as the filter's bound; rows=None | "f16" | "bf16" names its operands."""
+        code = self._fk_form(form, rows)
+        queries = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, self.meta.dim)
+        nq, k = queries.shape[0], int(k)
+        rad = np.ascontiguousarray(np.broadcast_to(np.asarray(radius, dtype=np.float32).reshape(-1), (nq,)))
+        words, bits, nf = _pack_allow_numpy(allow)
+        of = None if allow_of is None or words is None else np.ascontiguousarray(allow_of, dtype=np.uint32).reshape(nq)
+        out = {"labels": np.empty((nq, k), np.uint64), "dists": np.empty((nq, k), np.float32), "counts": np.empty(nq, np.uint32)}
+        if return_idx:
+            out["idx"] = np.empty((nq, k), np.uint32)
+        if totals:
+            out["totals"] = np.empty(nq, np.uint32)
+        check(self.L.hnsw_gpu_range_knn(self._h, 0 if code is None else 1, code or 0, queries.ctypes.data, nq, rad.ctypes.data, k,
+                                        None if words is None else words.ctypes.data, bits, nf, None if of is None else of.ctypes.data,
+                                        out["labels"].ctypes.data, out["dists"].ctypes.data, out["idx"].ctypes.data if return_idx else None,
+                                        out["counts"].ctypes.data, out["totals"].ctypes.data if totals else None), "hnsw_gpu_range_knn")
+        return out
+
+    def range_knn_torch(self, queries, radius, k: int, allow=None, allow_of=None, return_idx: bool = False, totals: bool = False, form=None,
+                        rows=None):
+        """range_knn() with everything resident in HBM (hnsw_gpu_range_knn_dev on torch's current stream, which the call synchronises).
+        radius: a number or a float tensor [nq]; allow / allow_of as in filtered_knn_torch(), allow=None: every label passes.  Returns a
+        dict: labels [nq, k] int64 (tail -1), dists [nq, k] (tail +inf), counts [nq] int32, idx [nq, k] int32 (tail -1) with
+        return_idx=True, totals [nq] int32 (the bits of a uint32) with totals=True."""
+        code = self._fk_form(form, rows)
+        torch = _torch()
+        assert queries.is_cuda and queries.dtype == torch.float32 and queries.is_contiguous()
+        nq, k, dev = queries.shape[0], int(k), queries.device
+        if torch.is_tensor(radius):
+            rad = radius.to(device=dev, dtype=torch.float32).reshape(-1).expand(nq).contiguous()
+        else:
+            rad = torch.full((nq,), float(radius), dtype=torch.float32, device=dev)
+        words, bits, nf = _pack_allow_torch(allow, dev)
+        of = None if allow_of is None or words is None else allow_of.to(device=dev, dtype=torch.int32).contiguous()
+        if of is not None and of.numel() != nq:
+            raise ValueError("allow_of names one filter per query")
+        out = {"labels": torch.empty((nq, k), dtype=torch.int64, device=dev),
+               "dists": torch.empty((nq, k), dtype=torch.float32, device=dev),
+               "counts": torch.empty(nq, dtype=torch.int32, device=dev)}
+        if return_idx:
+            out["idx"] = torch.empty((nq, k), dtype=torch.int32, device=dev)
+        if totals:
+            out["totals"] = torch.empty(nq, dtype=torch.int32, device=dev)
+        s = torch.cuda.current_stream(dev).cuda_stream
+        check(self.L.hnsw_gpu_range_knn_dev(self._h, 0 if code is None else 1, code or 0, queries.data_ptr(), nq, rad.data_ptr(), k, _dptr(words), bits, nf,
+                                            _dptr(of), out["labels"].data_ptr(), out["dists"].data_ptr(), _dptr(out.get("idx")), out["counts"].data_ptr(),
+                                            _dptr(out.get("totals")), s), "hnsw_gpu_range_knn_dev")
+        return out
+
+    def last_range_knn_form(self) -> Optional[str]:
+        """The form that answered the last range_knn call on this mirror: "listed", "f32", "f16" or "bf16" (the MFMA filters), or None
+        before the first one (hnsw_gpu_last_range_knn_form)."""
+        return {0: "listed", 1: "f32", 2: "f16", 3: "bf16"}.get(int(self.L.hnsw_gpu_last_range_knn_form(self._h)))
+
+    def last_range_knn(self) -> dict:
+        """The pass that answered the last range_knn call on this mirror (hnsw_gpu_last_range_knn): entries of all lists, rows the
+        threshold scan scored canonically, (query, row) pairs that passed the filter's comparison, pairs appended to a candidate list, the
+        sum of the in-range rows counted (the sum of the totals in the listed form and with totals=True); list-build, filter and
+        whole-call ms."""
+        v = (C.c_uint64 * 8)()
+        check(self.L.hnsw_gpu_last_range_knn(self._h, v), "hnsw_gpu_last_range_knn")
+        return {"listed": int(v[0]), "rows_scored": int(v[1]), "dist_pass": int(v[2]), "appended": int(v[3]), "totals": int(v[4]),
+                "build_ms": v[5] / 1000.0, "filter_ms": v[6] / 1000.0, "call_ms": v[7] / 1000.0}
+
     def last_search_ms(self, back: int = 0) -> float:
         """Device time of the search kernel launched `back` launches ago (HIP events recorded on
         the launch stream around the kernel; the last 64 launches are kept)."""
