@@ -256,8 +256,8 @@ int hnsw_gpu_filtered_knn(hnsw_gpu_index *ix, const coord_t *queries, size_t nq,
  * by the canonical code.  Same filter convention, selection, order, counts, tails and argument rules as hnsw_gpu_filtered_knn_dev.
  * Manhattan, fewer than 4096 rows, a device other than gfx950, a (dim, k) whose re-score does not fit, a call whose lists are all short
  * enough to be scanned whole, and a candidate list that overflows (16-bit -> f32 -> listed) are answered by the listed form: the same
- * bytes.  hnsw_gpu_last_filtered_knn_form (hnsw_gpu_diag.h) names the form that answered.  There is no automatic choice between the two
- * calls.  Memory: one bit per row and bitmap, and 64 KiB of candidates per query, kept in the mirror up to 64 MiB each. */
+ * bytes.  hnsw_gpu_last_filtered_knn_form (hnsw_gpu_diag.h) names the form that answered.  This call does not choose: hnsw_gpu_filtered_knn_auto_dev
+ * does, per query.  Memory: one bit per row and bitmap, and 64 KiB of candidates per query, kept in the mirror up to 64 MiB each. */
 int hnsw_gpu_filtered_knn_mfma_dev(hnsw_gpu_index *ix, int format, const coord_t *d_queries, size_t nq, size_t k,
 								   const uint32_t *d_allow, size_t allow_bits, size_t nfilters, const uint32_t *d_allow_of,
 								   label_t *d_labels, dist_t *d_dists, idx_t *d_idx, uint32_t *d_counts, void *stream);
@@ -284,7 +284,7 @@ int hnsw_gpu_filtered_knn_mfma(hnsw_gpu_index *ix, int format, const coord_t *qu
  * = every row against every query on the matrix cores, operands `format` (HNSW_GPU_ROWS_F32, or _F16 / _BF16: the reduced copy the index
  * holds, else HNSW_GPU_ERR_ARG; ignored by the listed form), with the radius as the filter's bound — min(r_q, the k-th distance over a
  * sample of the query's list) when d_totals is NULL, r_q itself when totals are asked for (every element in range must be re-scored to be
- * counted) — and a canonical re-score of what passes.  The same bytes either way; there is no automatic choice.  The matrix-core form
+ * counted) — and a canonical re-score of what passes.  The same bytes either way; this call does not choose (hnsw_gpu_range_knn_auto_dev does, per query).  The matrix-core form
  * hands the call to the listed form where hnsw_gpu_filtered_knn_mfma_dev does (Manhattan, fewer than 4096 rows, a device other than gfx950,
  * a (dim, k) whose re-score does not fit, a call whose lists are all short enough to be scanned whole) and when a query's candidate list
  * passes its 16 384 entries (16-bit -> f32 -> listed, call-wide).  With totals every element in range is a candidate, so a radius that
@@ -302,6 +302,35 @@ int hnsw_gpu_range_knn_dev(hnsw_gpu_index *ix, int form, int format, const coord
 int hnsw_gpu_range_knn(hnsw_gpu_index *ix, int form, int format, const coord_t *queries, size_t nq, const dist_t *radius, size_t k,
 					   const uint32_t *allow, size_t allow_bits, size_t nfilters, const uint32_t *allow_of,
 					   label_t *labels, dist_t *dists, idx_t *idx, uint32_t *counts, uint32_t *totals);
+
+/* The automatic calls: hnsw_gpu_filtered_knn_dev's / hnsw_gpu_range_knn_dev's answer, bit for bit, with the form chosen PER QUERY
+ * (csrc/device_fk_plan.h).  The list build gives every query's list length L_q exactly; a query is loose when its own listed
+ * cost exceeds the marginal cost of one more query in a matrix-core pass, and the loose class runs only if its summed listed cost exceeds
+ * that pass's fixed cost plus the marginal cost times its size — else every query is listed.  The tight queries then run through their
+ * lists and the loose ones through one matrix-core pass whose Q is their number, over one list build and one mask build; a call whose
+ * queries all fall in one class is that fixed form's call, on the caller's buffers.  Arguments, filter convention, selection, order,
+ * counts, tails, totals, radius rules, argument errors (outputs untouched) and nq == 0 are those of hnsw_gpu_filtered_knn_mfma_dev and
+ * hnsw_gpu_range_knn_dev; the range call has no form argument.  format names the operands the loose class MAY use (HNSW_GPU_ROWS_F32, or
+ * _F16 / _BF16: the reduced copy the index holds, else HNSW_GPU_ERR_ARG); no copy is made on the caller's behalf.  Where the matrix-core
+ * form has no pass (Manhattan, fewer than 4096 rows, a device other than gfx950, a (dim, k) whose re-score does not fit, loose lists that
+ * are all short enough to be scanned whole) every query is listed; a candidate list that overflows sends the loose class down the chain
+ * 16-bit -> f32 -> listed and leaves the listed class as it is.  Without a filter, or with d_allow_of NULL, all queries share one list: one
+ * class, so the class-level test is the whole decision.
+ *   d_plan  nq bytes or NULL: the class of each query, 0 = listed, 1 = loose (matrix cores, or what its chain ended in)
+ * hnsw_gpu_last_filtered_knn_plan / hnsw_gpu_last_range_knn_plan (hnsw_gpu_diag.h) report the plan.  The call synchronises `stream`. */
+int hnsw_gpu_filtered_knn_auto_dev(hnsw_gpu_index *ix, int format, const coord_t *d_queries, size_t nq, size_t k,
+								   const uint32_t *d_allow, size_t allow_bits, size_t nfilters, const uint32_t *d_allow_of,
+								   label_t *d_labels, dist_t *d_dists, idx_t *d_idx, uint32_t *d_counts, uint8_t *d_plan, void *stream);
+int hnsw_gpu_range_knn_auto_dev(hnsw_gpu_index *ix, int format, const coord_t *d_queries, size_t nq, const dist_t *d_radius, size_t k,
+								const uint32_t *d_allow, size_t allow_bits, size_t nfilters, const uint32_t *d_allow_of,
+								label_t *d_labels, dist_t *d_dists, idx_t *d_idx, uint32_t *d_counts, uint32_t *d_totals, uint8_t *d_plan, void *stream);
+/* Host-pointer forms: copy in, run on the default stream, copy out. */
+int hnsw_gpu_filtered_knn_auto(hnsw_gpu_index *ix, int format, const coord_t *queries, size_t nq, size_t k,
+							   const uint32_t *allow, size_t allow_bits, size_t nfilters, const uint32_t *allow_of,
+							   label_t *labels, dist_t *dists, idx_t *idx, uint32_t *counts, uint8_t *plan);
+int hnsw_gpu_range_knn_auto(hnsw_gpu_index *ix, int format, const coord_t *queries, size_t nq, const dist_t *radius, size_t k,
+							const uint32_t *allow, size_t allow_bits, size_t nfilters, const uint32_t *allow_of,
+							label_t *labels, dist_t *dists, idx_t *idx, uint32_t *counts, uint32_t *totals, uint8_t *plan);
 
 /* Milliseconds the most recent search kernel of this index spent on the device,
  * from HIP events recorded on its stream around the launch (waits for it). */

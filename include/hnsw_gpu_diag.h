@@ -140,6 +140,17 @@ int hnsw_gpu_last_range_knn_form(hnsw_gpu_index *ix);
  * call's stream.  out[2], out[3] and out[6] are zero after a listed answer. */
 int hnsw_gpu_last_range_knn(hnsw_gpu_index *ix, uint64_t out[8]);
 
+/* The plan of the mirror's last hnsw_gpu_filtered_knn_auto[_dev] / hnsw_gpu_range_knn_auto[_dev] call: out[0] = queries of the listed class,
+ * out[1] = of the loose class (0: every query was listed), out[2], out[3] = the sum of the list lengths L_q of each, out[4] = the threshold
+ * in rows (loose: L_q > out[4]; ~0 where the matrix-core form has no pass for the call; HNSW_GPU_FK_AUTO_SPLIT when that knob is set),
+ * out[5] = the model's listed cost and out[6] = its matrix-core cost of the queries above the threshold, in MICROSECONDS (the loose class
+ * runs when out[5] > out[6], and its longest list is longer than S_min), out[7] = the form that answered the loose class after any
+ * fallback (HNSW_GPU_FK_FORM_*; listed when there was none).  After such a call hnsw_gpu_last_filtered_knn_form / hnsw_gpu_last_range_knn_form
+ * name the loose class's form when there was one, else listed, and the counters of hnsw_gpu_last_filtered_knn / hnsw_gpu_last_range_knn
+ * are the sums over both classes (filter figures: the loose class's).  Zeros before the first such call. */
+int hnsw_gpu_last_filtered_knn_plan(hnsw_gpu_index *ix, uint64_t out[8]);
+int hnsw_gpu_last_range_knn_plan(hnsw_gpu_index *ix, uint64_t out[8]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -147,6 +147,13 @@ def gpu_lib():
         L.hnsw_gpu_range_knn.argtypes = [vp, i32, i32, vp, sz, vp, sz, vp, sz, sz, vp, vp, vp, vp, vp, vp]
         L.hnsw_gpu_last_range_knn_form.argtypes = [vp]
         L.hnsw_gpu_last_range_knn.argtypes = [vp, _u64p]
+    if hasattr(L, "hnsw_gpu_filtered_knn_auto_dev"):
+        L.hnsw_gpu_filtered_knn_auto_dev.argtypes = [vp, i32, vp, sz, sz, vp, sz, sz, vp, vp, vp, vp, vp, vp, vp]
+        L.hnsw_gpu_filtered_knn_auto.argtypes = [vp, i32, vp, sz, sz, vp, sz, sz, vp, vp, vp, vp, vp, vp]
+        L.hnsw_gpu_range_knn_auto_dev.argtypes = [vp, i32, vp, sz, vp, sz, vp, sz, sz, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.hnsw_gpu_range_knn_auto.argtypes = [vp, i32, vp, sz, vp, sz, vp, sz, sz, vp, vp, vp, vp, vp, vp, vp]
+        L.hnsw_gpu_last_filtered_knn_plan.argtypes = [vp, _u64p]
+        L.hnsw_gpu_last_range_knn_plan.argtypes = [vp, _u64p]
     L.hnsw_gpu_last_search_ms.argtypes = [vp, _f32p]
     L.hnsw_gpu_search_ms.argtypes = [vp, C.c_uint, _f32p]
     L.hnsw_gpu_last_search_slots.argtypes = [vp, _u32p]

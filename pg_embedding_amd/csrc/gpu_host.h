@@ -57,7 +57,7 @@ enum Knob : int
 	K_BLOCKS_PER_CU, K_STREAM_LIGHT, K_LOCALITY, K_XCD_TICKETS,
 	// test knobs (hnsw_gpu_config_set only)
 	K_BEAM16, K_NARROW5, K_LEAN, K_HASH_ENTRIES, K_LDS_SET_MIN_WAVES, K_TEAM_SPEC, K_TEAM_WPB, K_NARROW_WPB, K_ABORT_POLL_LOG2, K_MAX_BLOCKS, K_SHARDED_NO_PEER, K_BF_BIG_MIN_BLOCKS, K_LOCALITY_MIN_NQ,
-	K_FK_SAMPLE_MIN, K_FK_MFMA_STANDIN,
+	K_FK_SAMPLE_MIN, K_FK_MFMA_STANDIN, K_FK_AUTO_SPLIT,
 	K_COUNT
 };
 struct KnobVal { std::atomic<long long> v{0}; std::atomic<bool> set{false}; };
@@ -135,7 +135,8 @@ struct FkWs
 {
 	ScanBuf cells, list, part;                           // per-(bitmap, segment) counts | offsets | rows-scored word; the lists; the partial top-k lists
 	ScanBuf mask, bfs, cand;                             // matrix-core form (device_filtered_knn_mfma.h): row masks; per-query scratch; candidate lists
-	uint64_t *host = nullptr;                            // pinned: [0] entries of all lists, [1] the longest list, [2] rows scored, [3] pairs that passed the filter's comparison, [4] pairs appended, [5] candidate lists that overflowed
+	ScanBuf perm, tmp;                                   // the automatic calls (device_fk_plan.h): the partition of the query numbers; a class's compacted inputs and outputs
+	uint64_t *host = nullptr;                            // pinned, 16 words: [0] entries of all lists, [1] the longest list, [2] rows scored, [3] pairs that passed the filter's comparison, [4] pairs appended, [5] candidate lists that overflowed; [8 .. 12] the plan's words (FkPlan::host)
 	hipEvent_t ev[6] = {};                               // before the list build | after it | after the emit kernel | before the filter | after it | before a listed scan that follows a filter
 	uint64_t listed = 0, scored = 0;                     // the last call (hnsw_gpu_last_filtered_knn)
 	float build_ms = 0.f, scan_ms = 0.f;
@@ -144,6 +145,9 @@ struct FkWs
 	// the last radius search (device_range_knn.h, hnsw_gpu_last_range_knn): it uses the buffers above (bfs: its per-query scratch in both forms;
 	// host[6]: the sum of its totals) and keeps figures of its own, so the filtered k-NN diagnostics stay those of the last filtered k-NN call
 	struct Range { uint64_t listed = 0, scored = 0, dist_pass = 0, appended = 0, totals = 0; float build_ms = 0.f, filter_ms = 0.f, call_ms = 0.f; int form = -1; } r;
+	// the plan of the last automatic call of either kind (hnsw_gpu_last_filtered_knn_plan, hnsw_gpu_last_range_knn_plan): queries and ΣL_q per
+	// class, the threshold in rows, the model's two estimates for the queries above it (µs), the form that answered the loose class
+	struct Plan { uint64_t nq[2] = {0, 0}, rows[2] = {0, 0}, thresh = 0, est_listed_us = 0, est_mfma_us = 0; int loose_form = 0; } plan, rplan;
 };
 void fk_ws_free(FkWs *s);
 

@@ -10,6 +10,7 @@
 #include "device_filtered_knn.h"
 #include "device_filtered_knn_mfma.h"
 #include "device_range_knn.h"
+#include "device_fk_plan.h"
 
 #include <type_traits>
 
@@ -442,7 +443,7 @@ static const size_t FK_PART_BYTES = (size_t) 1 << 30;         // the partial lis
 
 void fk_ws_free(FkWs *s)
 {
-	buf_trim({&s->cells, &s->list, &s->part, &s->mask, &s->bfs, &s->cand}, 0);
+	buf_trim({&s->cells, &s->list, &s->part, &s->mask, &s->bfs, &s->cand, &s->perm, &s->tmp}, 0);
 	if (s->host) (void) hipHostFree(s->host);
 	s->host = nullptr;
 	for (hipEvent_t &e : s->ev) { if (e) (void) hipEventDestroy(e); e = nullptr; }
@@ -482,13 +483,13 @@ struct FkCall
 	const char *who;                                              // the call's name in a message; NULL: filtered k-NN
 };
 static const char *fk_who(const FkCall &c) { return c.who ? c.who : "filtered k-NN"; }
-struct FkTrim { FkWs *w; ~FkTrim() { buf_trim({&w->cells, &w->list, &w->part, &w->mask, &w->bfs, &w->cand}); } };   // on EVERY way out, errors included: no buffer above 64 MiB outlives its call
+struct FkTrim { FkWs *w; ~FkTrim() { buf_trim({&w->cells, &w->list, &w->part, &w->mask, &w->bfs, &w->cand, &w->perm, &w->tmp}); } };   // on EVERY way out, errors included: no buffer above 64 MiB outlives its call
 
 static int fk_begin(FkCall &c)
 {
 	HIPCHK(hipSetDevice(c.ix->device));
 	FkWs *fw = &c.ix->fk;
-	if (!fw->host) HIPCHK(hipHostMalloc((void **) &fw->host, 64, hipHostMallocDefault));
+	if (!fw->host) HIPCHK(hipHostMalloc((void **) &fw->host, 128, hipHostMallocDefault));
 	for (hipEvent_t &e : fw->ev)
 		if (!e) HIPCHK(hipEventCreate(&e));
 	fw->listed = fw->scored = 0; fw->build_ms = fw->scan_ms = 0.f;
@@ -497,8 +498,10 @@ static int fk_begin(FkCall &c)
 }
 
 // 1. the allowed lists: count per (bitmap, segment), offsets, fill.  c.allow == NULL (radius search without a filter: nfilters == 1): the one
-// list of the rows that are not vacuumed (rk_live_kernel)
-static int fk_lists(FkCall &c)
+// list of the rows that are not vacuumed (rk_live_kernel).  hook (the automatic calls; else NULL: not one launch more): the plan's kernel
+// behind the offsets, before the wait — its words arrive in the same pinned block (fw->host[8 ..])
+struct FkPlanHook { uint64_t thresh; uint8_t *plan; };
+static int fk_lists(FkCall &c, const FkPlanHook *hook = nullptr)
 {
 	hnsw_gpu_index *ix = c.ix;
 	FkWs *fw = &ix->fk;
@@ -522,6 +525,11 @@ static int fk_lists(FkCall &c)
 	if (c.allow) hipLaunchKernelGGL(fk_count_kernel, dim3((uint32_t) (nsb * nfilters)), dim3(256), 0, s, fl, cells);
 	else hipLaunchKernelGGL(rk_live_kernel<RK_LIVE_COUNT>, dim3((uint32_t) nsb), dim3(256), 0, s, fl, (const uint64_t *) nullptr, cells);
 	hipLaunchKernelGGL(fk_offsets_kernel, dim3(1), dim3(FK_SCAN_THREADS), FK_SCAN_THREADS * 8, s, (const uint32_t *) cells, nseg, (uint32_t) nfilters, off, fw->host);
+	if (hook)
+	{
+		FkPlan fp = { off, nseg, (uint32_t) nfilters, c.allow_of, (uint32_t) c.nq, hook->thresh, (uint32_t *) fw->perm.p, hook->plan, fw->host + 8 };
+		hipLaunchKernelGGL(fkp_classify_kernel, dim3(1), dim3(FKP_THREADS), FKP_LDS_BYTES, s, fp);
+	}
 	HIPCHK(hipGetLastError());
 	HIPCHK(hipStreamSynchronize(s));                              // the one wait before the scan: the lists are sized exactly
 	const size_t total = fw->host[0], longest = fw->host[1];
@@ -732,21 +740,13 @@ static int fk_mfma_pass(FkCall &c, int format, bool standin, uint32_t smin, uint
 	return HNSW_GPU_OK;
 }
 
-extern "C" int hnsw_gpu_filtered_knn_mfma_dev(hnsw_gpu_index *ix, int format, const coord_t *d_queries, size_t nq, size_t k, const uint32_t *d_allow,
-											  size_t allow_bits, size_t nfilters, const uint32_t *d_allow_of, label_t *d_labels, dist_t *d_dists,
-											  idx_t *d_idx, uint32_t *d_counts, void *stream)
+// Does the matrix-core form have a pass for this call?  The listed form answers, before any launch: not a contraction; a re-score step — a
+// query image and a k-list per wave in LDS — that does not fit; and, unless the stand-in takes the filter's place (test knob: then the
+// operands are f32 whatever `format` says), a table too small to matter or a device the filter kernel is not written for
+// (bruteforce_filter's rules; the tests' emulator has no such kernel)
+static bool fk_have_mfma(hnsw_gpu_index *ix, size_t k, bool *standin)
 {
-	std::unique_lock<std::recursive_mutex> lock_;
-	if (ix) lock_ = std::unique_lock<std::recursive_mutex>(ix->mu);
-	if (int rc0 = fk_check(ix, d_queries, nq, k, d_allow, allow_bits, nfilters, d_labels, d_counts)) return rc0;
-	if (int rc0 = fk_check_format(ix, format)) return rc0;
-	if (nq == 0) return HNSW_GPU_OK;
-	FkCall c = { ix, d_queries, nq, k, d_allow, allow_bits, nfilters, d_allow_of, d_labels, d_dists, d_idx, d_counts, (hipStream_t) stream };
-	// The listed form's answer, before any launch: not a contraction; a re-score step — a query image and a k-list per wave in LDS — that does
-	// not fit; and, unless the stand-in takes the filter's place (test knob: then the operands are f32 whatever `format` says), a table too
-	// small to matter or a device the filter kernel is not written for (bruteforce_filter's rules; the tests' emulator has no such kernel)
-	const bool standin = knob(K_FK_MFMA_STANDIN, 0) != 0;
-	const int func = (int) ix->meta.dist_func;
+	*standin = knob(K_FK_MFMA_STANDIN, 0) != 0;
 	const uint32_t kiters = (ix->stride / 4 + 15) / 16;
 	const size_t wave_bytes = round_up(round_up(kiters, 4) * 64 * 4 + (k + 1) * 8 + 128 * 4, 16);
 #ifdef PGEMB_SIMT_EMULATOR
@@ -754,29 +754,35 @@ extern "C" int hnsw_gpu_filtered_knn_mfma_dev(hnsw_gpu_index *ix, int format, co
 #else
 	const bool have_filter = ix->n >= 4096 && ix->gfx950 && ix->max_lds >= BF_MIN_LDS;
 #endif
-	if (func == F_MANHATTAN || wave_bytes * 4 > 64 * 1024 || !(standin || have_filter)) return fk_listed_call(c);
-	if (standin) format = ROWS_F32;
+	return (int) ix->meta.dist_func != F_MANHATTAN && wave_bytes * 4 <= 64 * 1024 && (*standin || have_filter);
+}
+static uint32_t fk_sample_min() { return (uint32_t) std::min<long long>(0xFFFFFFFFll, std::max<long long>(1, knob(K_FK_SAMPLE_MIN, FKM_SAMPLE_MIN))); }
 
-	FkWs *fw = &ix->fk;
-	FkTrim trim_{fw};
-	int rc = fk_begin(c);
-	if (!rc) rc = fk_lists(c);
+// 2. the row masks (counted with the list build), and a row of zeros behind them
+static int fk_masks(FkCall &c, uint32_t *mwords_out)
+{
+	FkWs *fw = &c.ix->fk;
+	const size_t nfilters = c.nfilters;
+	const uint32_t mwords = fkm_mask_words((uint32_t) c.ix->n);
+	int rc = buf_reserve(&fw->mask, (nfilters + 1) * (size_t) mwords * 4, fk_who(c), "the row masks");
 	if (rc) return rc;
-	// a list no longer than S_min is its own sample: with no longer list in the call, every query is answered by the listed scan
-	const uint32_t smin = (uint32_t) std::min<long long>(0xFFFFFFFFll, std::max<long long>(1, knob(K_FK_SAMPLE_MIN, FKM_SAMPLE_MIN)));
-	if (c.longest <= smin) return fk_listed_scan(c, fw->ev[1]);
-	// 2. the row masks (counted with the list build), and a row of zeros behind them
-	const uint32_t mwords = fkm_mask_words((uint32_t) ix->n);
-	if ((rc = buf_reserve(&fw->mask, (nfilters + 1) * (size_t) mwords * 4, "filtered k-NN", "the row masks"))) return rc;
-	hipLaunchKernelGGL(fkm_mask_kernel, dim3((uint32_t) (c.nsb * nfilters)), dim3(256), 0, c.s, c.fl, mwords, (uint32_t *) fw->mask.p);
+	if (c.allow) hipLaunchKernelGGL(fkm_mask_kernel, dim3((uint32_t) (c.nsb * nfilters)), dim3(256), 0, c.s, c.fl, mwords, (uint32_t *) fw->mask.p);
+	else hipLaunchKernelGGL(rk_live_kernel<RK_LIVE_MASK>, dim3((uint32_t) c.nsb), dim3(256), 0, c.s, c.fl, (const uint64_t *) nullptr, (uint32_t *) fw->mask.p);
 	HIPCHK(hipMemsetAsync((uint32_t *) fw->mask.p + nfilters * (size_t) mwords, 0, (size_t) mwords * 4, c.s));
 	HIPCHK(hipEventRecord(fw->ev[1], c.s));
-	// a candidate list that overflows sends a 16-bit call to the f32 operands (its bound is looser: a list that overflowed there may not
-	// in f32), and an f32 call to the listed scan
+	*mwords_out = mwords;
+	return HNSW_GPU_OK;
+}
+
+// The passes of one call (or of one class of an automatic call) over the built lists and masks: a candidate list that overflows sends a
+// 16-bit call to the f32 operands (its bound is looser: a list that overflowed there may not in f32), and an f32 call to the listed scan
+static int fk_mfma_chain(FkCall &c, int format, bool standin, uint32_t smin, uint32_t mwords)
+{
+	FkWs *fw = &c.ix->fk;
 	for (;;)
 	{
 		uint64_t ovf = 0;
-		if ((rc = fk_mfma_pass(c, format, standin, smin, mwords, &ovf))) return rc;
+		if (int rc = fk_mfma_pass(c, format, standin, smin, mwords, &ovf)) return rc;
 		if (!ovf) break;
 		if (format == ROWS_F32)
 		{
@@ -791,9 +797,217 @@ extern "C" int hnsw_gpu_filtered_knn_mfma_dev(hnsw_gpu_index *ix, int format, co
 	return HNSW_GPU_OK;
 }
 
-// the host-pointer forms: copy in, run on the default stream, copy out.  format < 0: the listed form
+extern "C" int hnsw_gpu_filtered_knn_mfma_dev(hnsw_gpu_index *ix, int format, const coord_t *d_queries, size_t nq, size_t k, const uint32_t *d_allow,
+											  size_t allow_bits, size_t nfilters, const uint32_t *d_allow_of, label_t *d_labels, dist_t *d_dists,
+											  idx_t *d_idx, uint32_t *d_counts, void *stream)
+{
+	std::unique_lock<std::recursive_mutex> lock_;
+	if (ix) lock_ = std::unique_lock<std::recursive_mutex>(ix->mu);
+	if (int rc0 = fk_check(ix, d_queries, nq, k, d_allow, allow_bits, nfilters, d_labels, d_counts)) return rc0;
+	if (int rc0 = fk_check_format(ix, format)) return rc0;
+	if (nq == 0) return HNSW_GPU_OK;
+	FkCall c = { ix, d_queries, nq, k, d_allow, allow_bits, nfilters, d_allow_of, d_labels, d_dists, d_idx, d_counts, (hipStream_t) stream };
+	bool standin = false;
+	if (!fk_have_mfma(ix, k, &standin)) return fk_listed_call(c);
+	if (standin) format = ROWS_F32;
+
+	FkWs *fw = &ix->fk;
+	FkTrim trim_{fw};
+	int rc = fk_begin(c);
+	if (!rc) rc = fk_lists(c);
+	if (rc) return rc;
+	// a list no longer than S_min is its own sample: with no longer list in the call, every query is answered by the listed scan
+	const uint32_t smin = fk_sample_min();
+	if (c.longest <= smin) return fk_listed_scan(c, fw->ev[1]);
+	uint32_t mwords = 0;
+	if ((rc = fk_masks(c, &mwords))) return rc;
+	return fk_mfma_chain(c, format, standin, smin, mwords);
+}
+
+// ------------------------------------------------------------------------------------
+// the automatic calls: each query through the form that suits its own list (device_fk_plan.h)
+// ------------------------------------------------------------------------------------
+// The cost model, in ONE place.  In µs, for a call (or class) of nq queries with ΣL_q = rows and the longest list L_max:
+//     t_listed   = max(a * rows * row_bytes, c * L_max * row_bytes / w) + m * (w k)^2
+//                  a * row_bytes = row_fix_us + row_byte_us * row_bytes            per listed row at full occupancy (the throughput term)
+//                  c * row_bytes = wave_row_fix_us + wave_row_byte_us * row_bytes  per row of ONE wave; w = the waves that share the longest
+//                                                                                  list (fk_splits, fk_waves): few long lists in a large
+//                                                                                  batch are bound by their own chains, not by bandwidth
+//                  m = merge_key2_us                                               the emit kernel's one-wave merge of w lists of k keys
+//     t_mfma(p)  = b0 + b1 * p     b0 = fixed_us + n * operand_row_bytes / bytes_per_us + m * (w_s k)^2   (w_s: the waves of a sample scan)
+//                                  b1 = a * S_min * row_bytes + n * (pair_fix_us + pair_dim_us * dim)     (sample scan + filter)
+// The constants are fits of measurements on MI355X over 1M rows of 128 and 768 dimensions, f32 and f16 operands, 1 to 1 024 queries
+// (profiles/README.md); widths between and beyond those, other n and bf16 are the model's scaling, not measurements.
+struct FkCostFormat { double fixed_us, bytes_per_us, pair_fix_us, pair_dim_us; };
+static const struct { double row_fix_us, row_byte_us, wave_row_fix_us, wave_row_byte_us, merge_key2_us; FkCostFormat f32, r16; } FK_COST = {
+	2.84e-5, 3.63e-8, 0.134, 5.1e-5, 3.4e-4,
+	{ 230.0, 1.90e6, 5.70e-7, 1.27e-8 },
+	{ 390.0, 4.27e6, 9.08e-7, 1.23e-9 },
+};
+static double fk_cost_row_us(const hnsw_gpu_index *ix) { return FK_COST.row_fix_us + FK_COST.row_byte_us * (double) ix->stride * 4.0; }
+// the waves that scan a list of `len` rows in a call of nq queries: fk_splits' and fk_waves' rule
+static double fk_cost_waves(const hnsw_gpu_index *ix, size_t nq, size_t len)
+{
+	size_t splits = std::max<size_t>(1, std::min<size_t>(64, (size_t) (4 * ix->num_cu) / std::max<size_t>(nq, 1)));
+	splits = std::min<size_t>(splits, std::max<size_t>(1, len / (4 * FK_WAVE_ROWS)));
+	return (double) std::max<size_t>(1, std::min<size_t>(4 * splits, (len + FK_WAVE_ROWS - 1) / FK_WAVE_ROWS));
+}
+static double fk_cost_listed_us(const hnsw_gpu_index *ix, size_t nq, size_t k, uint64_t rows, size_t longest)
+{
+	if (!nq || !rows) return 0.0;
+	const double w = fk_cost_waves(ix, nq, longest), row_bytes = (double) ix->stride * 4.0;
+	const double chain = (FK_COST.wave_row_fix_us + FK_COST.wave_row_byte_us * row_bytes) * (double) longest / w;
+	return std::max(fk_cost_row_us(ix) * (double) rows, chain) + FK_COST.merge_key2_us * (w * (double) k) * (w * (double) k);
+}
+static void fk_cost_mfma_us(const hnsw_gpu_index *ix, int format, uint32_t smin, double *b0, double *b1)
+{
+	const FkCostFormat &f = format == ROWS_F32 ? FK_COST.f32 : FK_COST.r16;
+	const double n = (double) ix->n, op_bytes = format == ROWS_F32 ? (double) ix->stride * 4.0 : (double) ix->rows16_bytes;
+	*b0 = f.fixed_us + n * op_bytes / f.bytes_per_us;             // (+ the sample scan's merge, which depends on p: fk_auto_settle)
+	*b1 = fk_cost_row_us(ix) * (double) std::min<size_t>(smin, ix->n) + n * (f.pair_fix_us + f.pair_dim_us * (double) ix->meta.dim);
+}
+
+// what the plan of one call settled, from the words its kernel left in the pinned block
+struct FkAuto
+{
+	bool avail, standin, forced; int format; uint32_t smin; uint64_t thresh; double b0, b1;
+	size_t loose, rows[2], longest[2];                            // queries above the threshold; ΣL_q and the longest list of [0] the others, [1] those
+	bool split;                                                   // a loose class runs
+};
+// before the list build: the threshold in rows.  No pass of the matrix-core form for this call: no query is loose
+static void fk_auto_begin(hnsw_gpu_index *ix, int format, size_t k, FkAuto *a)
+{
+	memset(a, 0, sizeof(*a));
+	a->avail = fk_have_mfma(ix, k, &a->standin);
+	a->format = a->standin ? ROWS_F32 : format;
+	a->smin = fk_sample_min();
+	fk_cost_mfma_us(ix, a->format, a->smin, &a->b0, &a->b1);
+	const long long forced = knob(K_FK_AUTO_SPLIT, -1);
+	a->forced = forced >= 0;
+	a->thresh = !a->avail ? ~0ull : a->forced ? (uint64_t) forced : (uint64_t) (a->b1 / fk_cost_row_us(ix));
+}
+// after the list build's wait: the class-level test, the plan's record, and plan[] where the loose class was not accepted
+static int fk_auto_settle(FkCall &c, FkAuto *a, uint8_t *d_plan, FkWs::Plan *pl)
+{
+	FkWs *fw = &c.ix->fk;
+	a->loose = fw->host[8]; a->rows[0] = fw->host[9]; a->rows[1] = fw->host[10]; a->longest[0] = fw->host[11]; a->longest[1] = fw->host[12];
+	if (a->loose > c.nq || a->longest[0] > c.longest || a->longest[1] > c.longest)
+		return fail(HNSW_GPU_ERR_INTERNAL, "%s: a plan of %zu loose queries of %zu, longest lists %zu and %zu of %zu", fk_who(c), a->loose, c.nq, a->longest[0], a->longest[1], c.longest);
+	*pl = FkWs::Plan();
+	pl->thresh = a->thresh;
+	// what the listed form would cost MORE with the queries above the threshold in it, against one pass over the table for those
+	const double ws = fk_cost_waves(c.ix, a->loose, fk_sample_len((uint32_t) a->longest[1], a->smin, (uint32_t) c.k));
+	pl->est_listed_us = (uint64_t) std::llround(std::max(0.0, fk_cost_listed_us(c.ix, c.nq, c.k, a->rows[0] + a->rows[1], c.longest) -
+															  fk_cost_listed_us(c.ix, c.nq - a->loose, c.k, a->rows[0], a->longest[0])));
+	pl->est_mfma_us = (uint64_t) std::llround(a->b0 + FK_COST.merge_key2_us * (ws * (double) c.k) * (ws * (double) c.k) + a->b1 * (double) a->loose);
+	// a loose class whose every list is its own sample would be answered by the sample scan: the listed form's work, with a filter on top
+	a->split = a->avail && a->loose && a->longest[1] > a->smin && (a->forced || pl->est_listed_us > pl->est_mfma_us);
+	if (!a->split && a->loose && d_plan) HIPCHK(hipMemsetAsync(d_plan, 0, c.nq, c.s));
+	const size_t p = a->split ? a->loose : 0;
+	pl->nq[0] = c.nq - p; pl->nq[1] = p;
+	pl->rows[0] = a->split ? a->rows[0] : a->rows[0] + a->rows[1]; pl->rows[1] = a->split ? a->rows[1] : 0;
+	pl->loose_form = HNSW_GPU_FK_FORM_LISTED;
+	return HNSW_GPU_OK;
+}
+
+// The compacted inputs and outputs of a call with two classes, all in perm[] order: position i of each array is query perm[i], so a class is
+// a contiguous run — the listed class positions [0, nq - p), the loose class the rest
+struct FkTmp { float *q; uint32_t *aof; float *radius; uint64_t *labels; float *dists; uint32_t *idx, *counts, *totals; };
+static int fk_auto_gather(FkCall &c, const dist_t *radius, bool totals, FkTmp *t)
+{
+	FkWs *fw = &c.ix->fk;
+	const size_t nq = c.nq, k = c.k, dim = c.ix->meta.dim;
+	const size_t o_aof = round_up(nq * dim * 4, 256), o_rad = o_aof + round_up(nq * 4, 256), o_lab = o_rad + round_up(nq * 4, 256),
+				 o_dst = o_lab + round_up(nq * k * 8, 256), o_idx = o_dst + round_up(nq * k * 4, 256), o_cnt = o_idx + round_up(nq * k * 4, 256),
+				 o_tot = o_cnt + round_up(nq * 4, 256), bytes = o_tot + round_up(nq * 4, 256);
+	if (int rc = buf_reserve(&fw->tmp, bytes, fk_who(c), "the classes' compacted queries and results")) return rc;
+	char *B = (char *) fw->tmp.p;
+	t->q = (float *) B; t->aof = c.allow_of ? (uint32_t *) (B + o_aof) : nullptr; t->radius = radius ? (float *) (B + o_rad) : nullptr;
+	t->labels = (uint64_t *) (B + o_lab); t->dists = c.dists ? (float *) (B + o_dst) : nullptr; t->idx = c.idx ? (uint32_t *) (B + o_idx) : nullptr;
+	t->counts = (uint32_t *) (B + o_cnt); t->totals = totals ? (uint32_t *) (B + o_tot) : nullptr;
+	FkGather g = { (const uint32_t *) fw->perm.p, 0u, (uint32_t) nq, c.queries, (uint32_t) dim, t->q, c.allow_of, t->aof, radius, t->radius,
+				   (dim % 4 == 0 && (uintptr_t) c.queries % 16 == 0) ? 1u : 0u };
+	const size_t chunks = nq * (g.vec4 ? dim / 4 : dim);            // (both classes in one launch: each is a run of positions)
+	hipLaunchKernelGGL(fkp_gather_kernel, dim3((uint32_t) ((chunks + 255) / 256)), dim3(256), 0, c.s, g);
+	HIPCHK(hipGetLastError());
+	return HNSW_GPU_OK;
+}
+// the call of the class at positions [first, first + count): the caller's call with the compacted buffers in place of its own
+static FkCall fk_auto_class(const FkCall &c, const FkTmp &t, size_t first, size_t count, size_t longest)
+{
+	FkCall s = c;
+	const size_t dim = c.ix->meta.dim;
+	s.queries = t.q + first * dim; s.nq = count; s.allow_of = t.aof ? t.aof + first : nullptr;
+	s.labels = t.labels + first * c.k; s.dists = t.dists ? t.dists + first * c.k : nullptr; s.idx = t.idx ? t.idx + first * c.k : nullptr;
+	s.counts = t.counts + first; s.longest = longest;
+	return s;
+}
+static int fk_auto_scatter(const FkCall &c, const FkTmp &t, size_t first, size_t count, uint32_t *totals)
+{
+	FkScatter sc = { (const uint32_t *) c.ix->fk.perm.p, (uint32_t) first, (uint32_t) count, (uint32_t) c.k, t.labels, t.dists, t.idx, t.counts, t.totals,
+					 c.labels, c.dists, c.idx, c.counts, totals };
+	hipLaunchKernelGGL(fkp_scatter_kernel, dim3((uint32_t) ((count * c.k + 255) / 256)), dim3(256), 0, c.s, sc);
+	HIPCHK(hipGetLastError());
+	return HNSW_GPU_OK;
+}
+
+extern "C" int hnsw_gpu_filtered_knn_auto_dev(hnsw_gpu_index *ix, int format, const coord_t *d_queries, size_t nq, size_t k, const uint32_t *d_allow,
+											  size_t allow_bits, size_t nfilters, const uint32_t *d_allow_of, label_t *d_labels, dist_t *d_dists,
+											  idx_t *d_idx, uint32_t *d_counts, uint8_t *d_plan, void *stream)
+{
+	std::unique_lock<std::recursive_mutex> lock_;
+	if (ix) lock_ = std::unique_lock<std::recursive_mutex>(ix->mu);
+	if (int rc0 = fk_check(ix, d_queries, nq, k, d_allow, allow_bits, nfilters, d_labels, d_counts)) return rc0;
+	if (int rc0 = fk_check_format(ix, format)) return rc0;
+	if (nq == 0) return HNSW_GPU_OK;
+	FkCall c = { ix, d_queries, nq, k, d_allow, allow_bits, nfilters, d_allow_of, d_labels, d_dists, d_idx, d_counts, (hipStream_t) stream };
+	FkWs *fw = &ix->fk;
+	FkTrim trim_{fw};
+	FkAuto a;
+	fk_auto_begin(ix, format, k, &a);
+	int rc = fk_begin(c);
+	if (!rc) rc = buf_reserve(&fw->perm, nq * 4, fk_who(c), "the plan's order of the queries");
+	const FkPlanHook hook = { a.thresh, d_plan };
+	if (!rc) rc = fk_lists(c, &hook);
+	if (!rc) rc = fk_auto_settle(c, &a, d_plan, &fw->plan);
+	if (rc) return rc;
+	// one class: the fixed form's call on the caller's own buffers
+	if (!a.split) return fk_listed_scan(c, fw->ev[1]);
+	uint32_t mwords = 0;
+	if ((rc = fk_masks(c, &mwords))) return rc;
+	if (a.loose == nq)
+	{
+		rc = fk_mfma_chain(c, a.format, a.standin, a.smin, mwords);
+		fw->plan.loose_form = fw->form;
+		return rc;
+	}
+	// two classes over the one list build and the one mask build: the loose queries first (the filter's time counts from the call's start),
+	// then the listed ones; each class's rows go back to the caller's buffers behind its pass
+	const size_t nl = nq - a.loose;
+	FkTmp t;
+	if ((rc = fk_auto_gather(c, nullptr, false, &t))) return rc;
+	FkCall cl = fk_auto_class(c, t, nl, a.loose, a.longest[1]);
+	if ((rc = fk_mfma_chain(cl, a.format, a.standin, a.smin, mwords))) return rc;
+	if ((rc = fk_auto_scatter(c, t, nl, a.loose, nullptr))) return rc;
+	const uint64_t scored = fw->scored;
+	const float scan_ms = fw->scan_ms;
+	const int form = fw->form;
+	FkCall cs = fk_auto_class(c, t, 0, nl, a.longest[0]);
+	HIPCHK(hipEventRecord(fw->ev[5], c.s));
+	HIPCHK(hipMemsetAsync(c.scored, 0, 8, c.s));
+	if ((rc = fk_listed_scan(cs, fw->ev[5]))) return rc;
+	if ((rc = fk_auto_scatter(c, t, 0, nl, nullptr))) return rc;
+	HIPCHK(hipStreamSynchronize(c.s));
+	fw->scored += scored; fw->scan_ms += scan_ms; fw->form = form;  // the counters of hnsw_gpu_last_filtered_knn: both classes
+	fw->plan.loose_form = form;
+	return HNSW_GPU_OK;
+}
+
+// the host-pointer forms: copy in, run on the default stream, copy out.  format < 0: the listed form; aut: the automatic call (plan: its
+// extra output, or NULL)
 static int fk_host(hnsw_gpu_index *ix, int format, const coord_t *queries, size_t nq, size_t k, const uint32_t *allow, size_t allow_bits,
-				   size_t nfilters, const uint32_t *allow_of, label_t *labels, dist_t *dists, idx_t *idx, uint32_t *counts)
+				   size_t nfilters, const uint32_t *allow_of, label_t *labels, dist_t *dists, idx_t *idx, uint32_t *counts, bool aut = false,
+				   uint8_t *plan = nullptr)
 {
 	std::unique_lock<std::recursive_mutex> lock_;
 	if (ix) lock_ = std::unique_lock<std::recursive_mutex>(ix->mu);
@@ -805,22 +1019,25 @@ static int fk_host(hnsw_gpu_index *ix, int format, const coord_t *queries, size_
 	const size_t dim = ix->meta.dim, words = (allow_bits + 31) / 32;
 	const size_t qb = round_up(nq * dim * 4, 256), fb = round_up(nfilters * words * 4, 256), ob = round_up(allow_of ? nq * 4 : 0, 256),
 				 lb = round_up(nq * k * 8, 256), db = round_up(nq * k * 4, 256), ib = round_up(nq * k * 4, 256), cb = round_up(nq * 4, 256);
-	int rc = ensure_scratch(ix, qb + fb + ob + lb + db + ib + cb);
+	int rc = ensure_scratch(ix, qb + fb + ob + lb + db + ib + cb + (plan ? nq : 0));
 	if (rc) return rc;
 	char *p = (char *) ix->scratch;
+	uint8_t *dp = plan ? (uint8_t *) (p + qb + fb + ob + lb + db + ib + cb) : nullptr;
 	float *dq = (float *) p; uint32_t *df = (uint32_t *) (p + qb), *dof = (uint32_t *) (p + qb + fb);
 	uint64_t *dl = (uint64_t *) (p + qb + fb + ob); float *dd = (float *) (p + qb + fb + ob + lb);
 	uint32_t *di = (uint32_t *) (p + qb + fb + ob + lb + db), *dc = (uint32_t *) (p + qb + fb + ob + lb + db + ib);
 	HIPCHK(hipMemcpy(dq, queries, nq * dim * 4, hipMemcpyHostToDevice));
 	HIPCHK(hipMemcpy(df, allow, nfilters * words * 4, hipMemcpyHostToDevice));
 	if (allow_of) HIPCHK(hipMemcpy(dof, allow_of, nq * 4, hipMemcpyHostToDevice));
-	rc = format < 0 ? hnsw_gpu_filtered_knn_dev(ix, dq, nq, k, df, allow_bits, nfilters, allow_of ? dof : nullptr, dl, dd, di, dc, nullptr)
+	rc = aut ? hnsw_gpu_filtered_knn_auto_dev(ix, format, dq, nq, k, df, allow_bits, nfilters, allow_of ? dof : nullptr, dl, dd, di, dc, dp, nullptr)
+		 : format < 0 ? hnsw_gpu_filtered_knn_dev(ix, dq, nq, k, df, allow_bits, nfilters, allow_of ? dof : nullptr, dl, dd, di, dc, nullptr)
 					: hnsw_gpu_filtered_knn_mfma_dev(ix, format, dq, nq, k, df, allow_bits, nfilters, allow_of ? dof : nullptr, dl, dd, di, dc, nullptr);
 	if (rc) return rc;
 	HIPCHK(hipMemcpy(labels, dl, nq * k * 8, hipMemcpyDeviceToHost));
 	if (dists) HIPCHK(hipMemcpy(dists, dd, nq * k * 4, hipMemcpyDeviceToHost));
 	if (idx) HIPCHK(hipMemcpy(idx, di, nq * k * 4, hipMemcpyDeviceToHost));
 	HIPCHK(hipMemcpy(counts, dc, nq * 4, hipMemcpyDeviceToHost));
+	if (plan) HIPCHK(hipMemcpy(plan, dp, nq, hipMemcpyDeviceToHost));
 	return HNSW_GPU_OK;
 }
 
@@ -837,6 +1054,26 @@ extern "C" int hnsw_gpu_filtered_knn_mfma(hnsw_gpu_index *ix, int format, const 
 	if (format < 0) return fail(HNSW_GPU_ERR_ARG, "filtered k-NN: bad format %d", format);
 	return fk_host(ix, format, queries, nq, k, allow, allow_bits, nfilters, allow_of, labels, dists, idx, counts);
 }
+
+extern "C" int hnsw_gpu_filtered_knn_auto(hnsw_gpu_index *ix, int format, const coord_t *queries, size_t nq, size_t k, const uint32_t *allow,
+											  size_t allow_bits, size_t nfilters, const uint32_t *allow_of, label_t *labels, dist_t *dists, idx_t *idx,
+											  uint32_t *counts, uint8_t *plan)
+{
+	if (format < 0) return fail(HNSW_GPU_ERR_ARG, "filtered k-NN: bad format %d", format);
+	return fk_host(ix, format, queries, nq, k, allow, allow_bits, nfilters, allow_of, labels, dists, idx, counts, true, plan);
+}
+
+static int fk_plan_out(hnsw_gpu_index *ix, FkWs::Plan FkWs::*which, uint64_t out[8])
+{
+	if (!ix || !out) return fail(HNSW_GPU_ERR_ARG, "NULL argument");
+	std::lock_guard<std::recursive_mutex> lock_(ix->mu);
+	const FkWs::Plan &p = ix->fk.*which;
+	out[0] = p.nq[0]; out[1] = p.nq[1]; out[2] = p.rows[0]; out[3] = p.rows[1]; out[4] = p.thresh; out[5] = p.est_listed_us; out[6] = p.est_mfma_us;
+	out[7] = (uint64_t) p.loose_form;
+	return HNSW_GPU_OK;
+}
+extern "C" int hnsw_gpu_last_filtered_knn_plan(hnsw_gpu_index *ix, uint64_t out[8]) { return fk_plan_out(ix, &FkWs::plan, out); }
+extern "C" int hnsw_gpu_last_range_knn_plan(hnsw_gpu_index *ix, uint64_t out[8]) { return fk_plan_out(ix, &FkWs::rplan, out); }
 
 extern "C" int hnsw_gpu_last_filtered_knn(hnsw_gpu_index *ix, uint64_t out[4])
 {
@@ -894,7 +1131,7 @@ static int rk_begin(FkCall &c)
 {
 	HIPCHK(hipSetDevice(c.ix->device));
 	FkWs *fw = &c.ix->fk;
-	if (!fw->host) HIPCHK(hipHostMalloc((void **) &fw->host, 64, hipHostMallocDefault));
+	if (!fw->host) HIPCHK(hipHostMalloc((void **) &fw->host, 128, hipHostMallocDefault));
 	for (hipEvent_t &e : fw->ev)
 		if (!e) HIPCHK(hipEventCreate(&e));
 	const int form = fw->r.form;
@@ -1032,6 +1269,22 @@ static int rk_pass(RkCall &r, int format, bool standin, uint32_t smin, uint32_t 
 	return HNSW_GPU_OK;
 }
 
+// The passes of one call (or of one class of an automatic call) over the built lists (and masks): a candidate list that overflows sends a
+// 16-bit pass to the f32 operands and an f32 pass to the listed form, for all its queries.  pass: the first one (< 0: the listed form)
+static int rk_chain(RkCall &r, int pass, bool standin, uint32_t smin, uint32_t mwords)
+{
+	FkWs *fw = &r.c.ix->fk;
+	for (;;)
+	{
+		uint64_t ovf = 0;
+		if (int rc = rk_pass(r, pass, standin, smin, mwords, &ovf)) return rc;
+		if (!ovf) break;
+		pass = pass == ROWS_F32 ? -1 : ROWS_F32;
+	}
+	fw->r.form = pass < 0 ? HNSW_GPU_RK_FORM_LISTED : pass == ROWS_F32 ? HNSW_GPU_RK_FORM_F32 : pass == ROWS_BF16 ? HNSW_GPU_RK_FORM_BF16 : HNSW_GPU_RK_FORM_F16;
+	return HNSW_GPU_OK;
+}
+
 extern "C" int hnsw_gpu_range_knn_dev(hnsw_gpu_index *ix, int form, int format, const coord_t *d_queries, size_t nq, const dist_t *d_radius, size_t k,
 									  const uint32_t *d_allow, size_t allow_bits, size_t nfilters, const uint32_t *d_allow_of, label_t *d_labels,
 									  dist_t *d_dists, idx_t *d_idx, uint32_t *d_counts, uint32_t *d_totals, void *stream)
@@ -1048,16 +1301,8 @@ extern "C" int hnsw_gpu_range_knn_dev(hnsw_gpu_index *ix, int form, int format, 
 	FkCall &c = r.c;
 	c.who = "radius search";
 	// the matrix-core form where hnsw_gpu_filtered_knn_mfma_dev has one (its rules), else the listed form
-	const bool standin = knob(K_FK_MFMA_STANDIN, 0) != 0;
-	const int func = (int) ix->meta.dist_func;
-	const uint32_t kiters = (ix->stride / 4 + 15) / 16;
-	const size_t wave_bytes = round_up(round_up(kiters, 4) * 64 * 4 + (k + 1) * 8 + 128 * 4, 16);
-#ifdef PGEMB_SIMT_EMULATOR
-	const bool have_filter = false;
-#else
-	const bool have_filter = ix->n >= 4096 && ix->gfx950 && ix->max_lds >= BF_MIN_LDS;
-#endif
-	bool mfma = form == HNSW_GPU_RANGE_MFMA && func != F_MANHATTAN && wave_bytes * 4 <= 64 * 1024 && (standin || have_filter);
+	bool standin = false;
+	bool mfma = fk_have_mfma(ix, k, &standin) && form == HNSW_GPU_RANGE_MFMA;
 	if (standin) format = ROWS_F32;
 
 	FkWs *fw = &ix->fk;
@@ -1065,37 +1310,72 @@ extern "C" int hnsw_gpu_range_knn_dev(hnsw_gpu_index *ix, int form, int format, 
 	int rc = rk_begin(c);
 	if (!rc) rc = fk_lists(c);
 	if (rc) return rc;
-	const uint32_t smin = (uint32_t) std::min<long long>(0xFFFFFFFFll, std::max<long long>(1, knob(K_FK_SAMPLE_MIN, FKM_SAMPLE_MIN)));
+	const uint32_t smin = fk_sample_min();
 	if (c.longest <= smin) mfma = false;                          // every query is answered by the scan of its whole list
 	uint32_t mwords = 0;
-	if (mfma)
+	if (mfma && (rc = fk_masks(c, &mwords))) return rc;
+	return rk_chain(r, mfma ? format : -1, standin, smin, mwords);
+}
+
+// the automatic call: hnsw_gpu_filtered_knn_auto_dev's plan from the same list lengths.  Without a filter (or without d_allow_of) there is
+// one list, so one class: the class-level test is the whole decision
+extern "C" int hnsw_gpu_range_knn_auto_dev(hnsw_gpu_index *ix, int format, const coord_t *d_queries, size_t nq, const dist_t *d_radius, size_t k,
+										   const uint32_t *d_allow, size_t allow_bits, size_t nfilters, const uint32_t *d_allow_of, label_t *d_labels,
+										   dist_t *d_dists, idx_t *d_idx, uint32_t *d_counts, uint32_t *d_totals, uint8_t *d_plan, void *stream)
+{
+	std::unique_lock<std::recursive_mutex> lock_;
+	if (ix) lock_ = std::unique_lock<std::recursive_mutex>(ix->mu);
+	if (int rc0 = rk_check(ix, HNSW_GPU_RANGE_MFMA, d_queries, nq, d_radius, k, d_allow, allow_bits, nfilters, d_labels, d_counts)) return rc0;
+	if (nq == 0) return HNSW_GPU_OK;
+	if (int rc0 = fk_check_format(ix, format)) return rc0;
+	RkCall r = { { ix, d_queries, nq, k, d_allow, d_allow ? allow_bits : 0, d_allow ? nfilters : 1, d_allow ? d_allow_of : nullptr, d_labels, d_dists, d_idx,
+				   d_counts, (hipStream_t) stream }, d_radius, d_totals };
+	FkCall &c = r.c;
+	c.who = "radius search";
+	FkWs *fw = &ix->fk;
+	FkTrim trim_{fw};
+	FkAuto a;
+	fk_auto_begin(ix, format, k, &a);
+	int rc = rk_begin(c);
+	if (!rc) rc = buf_reserve(&fw->perm, nq * 4, fk_who(c), "the plan's order of the queries");
+	const FkPlanHook hook = { a.thresh, d_plan };
+	if (!rc) rc = fk_lists(c, &hook);
+	if (!rc) rc = fk_auto_settle(c, &a, d_plan, &fw->rplan);
+	if (rc) return rc;
+	// one class: the fixed form's call on the caller's own buffers
+	if (!a.split) return rk_chain(r, -1, a.standin, a.smin, 0);
+	uint32_t mwords = 0;
+	if ((rc = fk_masks(c, &mwords))) return rc;
+	if (a.loose == nq)
 	{
-		// the row masks (counted with the list build), and a row of zeros behind them
-		const size_t nf = c.nfilters;
-		mwords = fkm_mask_words((uint32_t) ix->n);
-		if ((rc = buf_reserve(&fw->mask, (nf + 1) * (size_t) mwords * 4, "radius search", "the row masks"))) return rc;
-		if (c.allow) hipLaunchKernelGGL(fkm_mask_kernel, dim3((uint32_t) (c.nsb * nf)), dim3(256), 0, c.s, c.fl, mwords, (uint32_t *) fw->mask.p);
-		else hipLaunchKernelGGL(rk_live_kernel<RK_LIVE_MASK>, dim3((uint32_t) c.nsb), dim3(256), 0, c.s, c.fl, (const uint64_t *) nullptr, (uint32_t *) fw->mask.p);
-		HIPCHK(hipMemsetAsync((uint32_t *) fw->mask.p + nf * (size_t) mwords, 0, (size_t) mwords * 4, c.s));
-		HIPCHK(hipEventRecord(fw->ev[1], c.s));
+		rc = rk_chain(r, a.format, a.standin, a.smin, mwords);
+		fw->rplan.loose_form = fw->r.form;
+		return rc;
 	}
-	// a candidate list that overflows sends a 16-bit call to the f32 operands and an f32 call to the listed form, call-wide
-	int pass = mfma ? format : -1;
-	for (;;)
-	{
-		uint64_t ovf = 0;
-		if ((rc = rk_pass(r, pass, standin, smin, mwords, &ovf))) return rc;
-		if (!ovf) break;
-		pass = pass == ROWS_F32 ? -1 : ROWS_F32;
-	}
-	fw->r.form = pass < 0 ? HNSW_GPU_RK_FORM_LISTED : pass == ROWS_F32 ? HNSW_GPU_RK_FORM_F32 : pass == ROWS_BF16 ? HNSW_GPU_RK_FORM_BF16 : HNSW_GPU_RK_FORM_F16;
+	// two classes (hnsw_gpu_filtered_knn_auto_dev): the loose queries, then the listed ones
+	const size_t nl = nq - a.loose;
+	FkTmp t;
+	if ((rc = fk_auto_gather(c, d_radius, d_totals != nullptr, &t))) return rc;
+	RkCall rl = { fk_auto_class(c, t, nl, a.loose, a.longest[1]), t.radius + nl, t.totals ? t.totals + nl : nullptr };
+	if ((rc = rk_chain(rl, a.format, a.standin, a.smin, mwords))) return rc;
+	if ((rc = fk_auto_scatter(c, t, nl, a.loose, d_totals))) return rc;
+	const FkWs::Range loose = fw->r;
+	RkCall rs = { fk_auto_class(c, t, 0, nl, a.longest[0]), t.radius, t.totals };
+	if ((rc = rk_chain(rs, -1, a.standin, a.smin, mwords))) return rc;
+	if ((rc = fk_auto_scatter(c, t, 0, nl, d_totals))) return rc;
+	HIPCHK(hipStreamSynchronize(c.s));
+	// the counters of hnsw_gpu_last_range_knn: both classes (the listed pass's call time counts from the call's start: the whole call's)
+	FkWs::Range &m = fw->r;
+	m.scored += loose.scored; m.totals += loose.totals; m.dist_pass = loose.dist_pass; m.appended = loose.appended; m.filter_ms = loose.filter_ms;
+	m.form = loose.form;
+	fw->rplan.loose_form = loose.form;
 	return HNSW_GPU_OK;
 }
 
-// the host-pointer form: copy in, run on the default stream, copy out
-extern "C" int hnsw_gpu_range_knn(hnsw_gpu_index *ix, int form, int format, const coord_t *queries, size_t nq, const dist_t *radius, size_t k,
-								  const uint32_t *allow, size_t allow_bits, size_t nfilters, const uint32_t *allow_of, label_t *labels, dist_t *dists,
-								  idx_t *idx, uint32_t *counts, uint32_t *totals)
+// the host-pointer forms: copy in, run on the default stream, copy out.  aut: the automatic call (plan: its extra output, or NULL)
+static int rk_host(hnsw_gpu_index *ix, bool aut, int form, int format, const coord_t *queries, size_t nq, const dist_t *radius, size_t k,
+				   const uint32_t *allow, size_t allow_bits, size_t nfilters, const uint32_t *allow_of, label_t *labels, dist_t *dists,
+				   idx_t *idx, uint32_t *counts, uint32_t *totals, uint8_t *plan)
 {
 	std::unique_lock<std::recursive_mutex> lock_;
 	if (ix) lock_ = std::unique_lock<std::recursive_mutex>(ix->mu);
@@ -1107,26 +1387,44 @@ extern "C" int hnsw_gpu_range_knn(hnsw_gpu_index *ix, int form, int format, cons
 	const size_t dim = ix->meta.dim, words = (allow_bits + 31) / 32;
 	const size_t qb = round_up(nq * dim * 4, 256), rb = round_up(nq * 4, 256), fb = round_up(allow ? nfilters * words * 4 : 0, 256),
 				 ob = round_up(allow && allow_of ? nq * 4 : 0, 256), lb = round_up(nq * k * 8, 256), db = round_up(nq * k * 4, 256), cb = round_up(nq * 4, 256);
-	int rc = ensure_scratch(ix, qb + rb + fb + ob + lb + 2 * db + 2 * cb);
+	int rc = ensure_scratch(ix, qb + rb + fb + ob + lb + 2 * db + 2 * cb + (plan ? nq : 0));
 	if (rc) return rc;
 	char *p = (char *) ix->scratch;
 	float *dq = (float *) p, *dr = (float *) (p + qb); uint32_t *df = (uint32_t *) (p + qb + rb), *dof = (uint32_t *) (p + qb + rb + fb);
 	char *o = p + qb + rb + fb + ob;
 	uint64_t *dl = (uint64_t *) o; float *dd = (float *) (o + lb);
 	uint32_t *di = (uint32_t *) (o + lb + db), *dc = (uint32_t *) (o + lb + 2 * db), *dt = (uint32_t *) (o + lb + 2 * db + cb);
+	uint8_t *dp = plan ? (uint8_t *) (o + lb + 2 * db + 2 * cb) : nullptr;
 	HIPCHK(hipMemcpy(dq, queries, nq * dim * 4, hipMemcpyHostToDevice));
 	HIPCHK(hipMemcpy(dr, radius, nq * 4, hipMemcpyHostToDevice));
 	if (allow) HIPCHK(hipMemcpy(df, allow, nfilters * words * 4, hipMemcpyHostToDevice));
 	if (allow && allow_of) HIPCHK(hipMemcpy(dof, allow_of, nq * 4, hipMemcpyHostToDevice));
-	rc = hnsw_gpu_range_knn_dev(ix, form, format, dq, nq, dr, k, allow ? df : nullptr, allow_bits, nfilters, allow && allow_of ? dof : nullptr, dl, dd, di, dc,
-								totals ? dt : nullptr, nullptr);
+	rc = aut ? hnsw_gpu_range_knn_auto_dev(ix, format, dq, nq, dr, k, allow ? df : nullptr, allow_bits, nfilters, allow && allow_of ? dof : nullptr, dl, dd, di, dc,
+										   totals ? dt : nullptr, dp, nullptr)
+			 : hnsw_gpu_range_knn_dev(ix, form, format, dq, nq, dr, k, allow ? df : nullptr, allow_bits, nfilters, allow && allow_of ? dof : nullptr, dl, dd, di, dc,
+									  totals ? dt : nullptr, nullptr);
 	if (rc) return rc;
 	HIPCHK(hipMemcpy(labels, dl, nq * k * 8, hipMemcpyDeviceToHost));
 	if (dists) HIPCHK(hipMemcpy(dists, dd, nq * k * 4, hipMemcpyDeviceToHost));
 	if (idx) HIPCHK(hipMemcpy(idx, di, nq * k * 4, hipMemcpyDeviceToHost));
 	HIPCHK(hipMemcpy(counts, dc, nq * 4, hipMemcpyDeviceToHost));
 	if (totals) HIPCHK(hipMemcpy(totals, dt, nq * 4, hipMemcpyDeviceToHost));
+	if (plan) HIPCHK(hipMemcpy(plan, dp, nq, hipMemcpyDeviceToHost));
 	return HNSW_GPU_OK;
+}
+
+extern "C" int hnsw_gpu_range_knn(hnsw_gpu_index *ix, int form, int format, const coord_t *queries, size_t nq, const dist_t *radius, size_t k,
+								  const uint32_t *allow, size_t allow_bits, size_t nfilters, const uint32_t *allow_of, label_t *labels, dist_t *dists,
+								  idx_t *idx, uint32_t *counts, uint32_t *totals)
+{
+	return rk_host(ix, false, form, format, queries, nq, radius, k, allow, allow_bits, nfilters, allow_of, labels, dists, idx, counts, totals, nullptr);
+}
+
+extern "C" int hnsw_gpu_range_knn_auto(hnsw_gpu_index *ix, int format, const coord_t *queries, size_t nq, const dist_t *radius, size_t k,
+									   const uint32_t *allow, size_t allow_bits, size_t nfilters, const uint32_t *allow_of, label_t *labels, dist_t *dists,
+									   idx_t *idx, uint32_t *counts, uint32_t *totals, uint8_t *plan)
+{
+	return rk_host(ix, true, HNSW_GPU_RANGE_MFMA, format, queries, nq, radius, k, allow, allow_bits, nfilters, allow_of, labels, dists, idx, counts, totals, plan);
 }
 
 extern "C" int hnsw_gpu_last_range_knn_form(hnsw_gpu_index *ix)

@@ -412,13 +412,13 @@ class GpuIndex:
     # ---------------------------------------------------------------- exact filtered k-NN
     @staticmethod
     def _fk_form(form, rows) -> Optional[int]:
-        """None for the listed form, else the matrix-core form's operand code"""
+        """None for the listed form, else the operand code of the matrix-core form (form="mfma") or of the loose class (form="auto")"""
         if form in (None, "listed"):
             if rows is not None:
-                raise ValueError("rows= names the operands of form=\"mfma\"")
+                raise ValueError("rows= names the operands of form=\"mfma\" and form=\"auto\"")
             return None
-        if form != "mfma":
-            raise ValueError('form is None, "listed" or "mfma"')
+        if form not in ("mfma", "auto"):
+            raise ValueError('form is None, "listed", "mfma" or "auto"')
         return _rows_code(rows)
 
     def filtered_knn(self, queries: np.ndarray, k: int, allow, allow_of=None, return_idx: bool = False, form=None, rows=None):
@@ -427,7 +427,10 @@ class GpuIndex:
         allow_of as in scan().  Returns a dict: labels [nq, k] u64 in ascending (distance, label) order (tail ~0), dists [nq, k] f32
         (tail +inf), counts [nq] u32 = min(k, allowed rows), and with return_idx=True idx [nq, k] u32 element numbers (tail 0xFFFFFFFF).
         form="mfma": the same answer with the Q x N part on the matrix cores, for loose filters (hnsw_gpu_filtered_knn_mfma); rows=None |
-        "f16" | "bf16" names its operands (the f32 rows, or the reduced copy of set_reduced_rows)."""
+        "f16" | "bf16" names its operands (the f32 rows, or the reduced copy of set_reduced_rows).  form="auto": the same answer with the form
+        chosen per query from the exact list lengths (hnsw_gpu_filtered_knn_auto): the tight queries through their lists, the loose ones
+        through one matrix-core pass over the operands rows= names (no copy is made for the call); the dict then also holds plan [nq] u8,
+        0 = listed, 1 = loose, and last_filtered_knn_plan() reports the plan."""
         if allow is None:
             raise ValueError("filtered_knn needs an allow filter (bruteforce_torch takes none)")
         code = self._fk_form(form, rows)
@@ -440,7 +443,10 @@ class GpuIndex:
             out["idx"] = np.empty((nq, k), np.uint32)
         tail = (queries.ctypes.data, nq, k, words.ctypes.data, bits, nf, None if of is None else of.ctypes.data, out["labels"].ctypes.data,
                 out["dists"].ctypes.data, out["idx"].ctypes.data if return_idx else None, out["counts"].ctypes.data)
-        if code is None:
+        if form == "auto":
+            out["plan"] = np.empty(nq, np.uint8)
+            check(self.L.hnsw_gpu_filtered_knn_auto(self._h, code, *tail, out["plan"].ctypes.data), "hnsw_gpu_filtered_knn_auto")
+        elif code is None:
             check(self.L.hnsw_gpu_filtered_knn(self._h, *tail), "hnsw_gpu_filtered_knn")
         else:
             check(self.L.hnsw_gpu_filtered_knn_mfma(self._h, code, *tail), "hnsw_gpu_filtered_knn_mfma")
@@ -450,7 +456,8 @@ class GpuIndex:
         """filtered_knn() with everything resident in HBM (hnsw_gpu_filtered_knn_dev on torch's current stream, which the call
         synchronises).  allow: a bool tensor [allow_bits] / [nfilters, allow_bits] or an already packed int32 tensor; allow_of: an integer
         tensor [nq].  Returns a dict: labels [nq, k] int64 (tail -1), dists [nq, k] (tail +inf), counts [nq] int32, idx [nq, k] int32
-        (tail -1) with return_idx=True.  form / rows as in filtered_knn() (hnsw_gpu_filtered_knn_mfma_dev)."""
+        (tail -1) with return_idx=True.  form / rows as in filtered_knn() (hnsw_gpu_filtered_knn_mfma_dev, hnsw_gpu_filtered_knn_auto_dev: plan
+        [nq] uint8)."""
         if allow is None:
             raise ValueError("filtered_knn_torch needs an allow filter (bruteforce_torch takes none)")
         code = self._fk_form(form, rows)
@@ -469,7 +476,10 @@ class GpuIndex:
         s = torch.cuda.current_stream(dev).cuda_stream
         tail = (queries.data_ptr(), nq, k, words.data_ptr(), bits, nf, _dptr(of), out["labels"].data_ptr(), out["dists"].data_ptr(), _dptr(out.get("idx")),
                 out["counts"].data_ptr(), s)
-        if code is None:
+        if form == "auto":
+            out["plan"] = torch.empty(nq, dtype=torch.uint8, device=dev)
+            check(self.L.hnsw_gpu_filtered_knn_auto_dev(self._h, code, *tail[:-1], out["plan"].data_ptr(), s), "hnsw_gpu_filtered_knn_auto_dev")
+        elif code is None:
             check(self.L.hnsw_gpu_filtered_knn_dev(self._h, *tail), "hnsw_gpu_filtered_knn_dev")
         else:
             check(self.L.hnsw_gpu_filtered_knn_mfma_dev(self._h, code, *tail), "hnsw_gpu_filtered_knn_mfma_dev")
@@ -486,6 +496,25 @@ class GpuIndex:
         """The form that answered the last filtered_knn call of either form on this mirror: "listed", "f32", "f16" or "bf16" (the MFMA
         filters), or None before the first one (hnsw_gpu_last_filtered_knn_form)."""
         return {0: "listed", 1: "f32", 2: "f16", 3: "bf16"}.get(int(self.L.hnsw_gpu_last_filtered_knn_form(self._h)))
+
+    @staticmethod
+    def _plan_dict(v) -> dict:
+        return {"listed_queries": int(v[0]), "loose_queries": int(v[1]), "listed_rows": int(v[2]), "loose_rows": int(v[3]), "threshold": int(v[4]),
+                "est_listed_us": int(v[5]), "est_mfma_us": int(v[6]), "loose_form": {0: "listed", 1: "f32", 2: "f16", 3: "bf16"}.get(int(v[7]))}
+
+    def last_filtered_knn_plan(self) -> dict:
+        """The plan of the last form="auto" filtered_knn call on this mirror (hnsw_gpu_last_filtered_knn_plan): queries and summed list
+        lengths of the listed and of the loose class, the threshold in rows (loose: a list longer than it), the model's listed and
+        matrix-core cost in µs of the queries above it, and the form that answered the loose class after any fallback."""
+        v = (C.c_uint64 * 8)()
+        check(self.L.hnsw_gpu_last_filtered_knn_plan(self._h, v), "hnsw_gpu_last_filtered_knn_plan")
+        return self._plan_dict(v)
+
+    def last_range_knn_plan(self) -> dict:
+        """last_filtered_knn_plan() for the last form="auto" range_knn call (hnsw_gpu_last_range_knn_plan)."""
+        v = (C.c_uint64 * 8)()
+        check(self.L.hnsw_gpu_last_range_knn_plan(self._h, v), "hnsw_gpu_last_range_knn_plan")
+        return self._plan_dict(v)
 
     def last_filtered_knn_mfma(self) -> dict:
         """The last filter launch of a form="mfma" call on this mirror (hnsw_gpu_last_filtered_knn_mfma): entries of all allowed lists, rows
@@ -505,7 +534,8 @@ class GpuIndex:
         ascending (distance, label) order (tail ~0), dists [nq, k] f32 (tail +inf), counts [nq] u32 = min(k, elements in range), idx with
         return_idx=True, and with totals=True totals [nq] u32 = the exact number of elements in range, whatever k is.  form=None |
         "listed": a scan over each query's allowed rows; form="mfma": the same answer with the Q x N part on the matrix cores and the
-        radius as the filter's bound; rows=None | "f16" | "bf16" names its operands."""
+        radius as the filter's bound; rows=None | "f16" | "bf16" names its operands.  form="auto": the form chosen per query as in
+        filtered_knn() (hnsw_gpu_range_knn_auto; plan [nq] u8 in the dict, last_range_knn_plan())."""
         code = self._fk_form(form, rows)
         queries = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, self.meta.dim)
         nq, k = queries.shape[0], int(k)
@@ -517,10 +547,14 @@ class GpuIndex:
             out["idx"] = np.empty((nq, k), np.uint32)
         if totals:
             out["totals"] = np.empty(nq, np.uint32)
-        check(self.L.hnsw_gpu_range_knn(self._h, 0 if code is None else 1, code or 0, queries.ctypes.data, nq, rad.ctypes.data, k,
-                                        None if words is None else words.ctypes.data, bits, nf, None if of is None else of.ctypes.data,
-                                        out["labels"].ctypes.data, out["dists"].ctypes.data, out["idx"].ctypes.data if return_idx else None,
-                                        out["counts"].ctypes.data, out["totals"].ctypes.data if totals else None), "hnsw_gpu_range_knn")
+        tail = (queries.ctypes.data, nq, rad.ctypes.data, k, None if words is None else words.ctypes.data, bits, nf, None if of is None else of.ctypes.data,
+                out["labels"].ctypes.data, out["dists"].ctypes.data, out["idx"].ctypes.data if return_idx else None, out["counts"].ctypes.data,
+                out["totals"].ctypes.data if totals else None)
+        if form == "auto":
+            out["plan"] = np.empty(nq, np.uint8)
+            check(self.L.hnsw_gpu_range_knn_auto(self._h, code, *tail, out["plan"].ctypes.data), "hnsw_gpu_range_knn_auto")
+        else:
+            check(self.L.hnsw_gpu_range_knn(self._h, 0 if code is None else 1, code or 0, *tail), "hnsw_gpu_range_knn")
         return out
 
     def range_knn_torch(self, queries, radius, k: int, allow=None, allow_of=None, return_idx: bool = False, totals: bool = False, form=None,
@@ -528,7 +562,7 @@ class GpuIndex:
         """range_knn() with everything resident in HBM (hnsw_gpu_range_knn_dev on torch's current stream, which the call synchronises).
         radius: a number or a float tensor [nq]; allow / allow_of as in filtered_knn_torch(), allow=None: every label passes.  Returns a
         dict: labels [nq, k] int64 (tail -1), dists [nq, k] (tail +inf), counts [nq] int32, idx [nq, k] int32 (tail -1) with
-        return_idx=True, totals [nq] int32 (the bits of a uint32) with totals=True."""
+        return_idx=True, totals [nq] int32 (the bits of a uint32) with totals=True, plan [nq] uint8 with form="auto"."""
         code = self._fk_form(form, rows)
         torch = _torch()
         assert queries.is_cuda and queries.dtype == torch.float32 and queries.is_contiguous()
@@ -549,9 +583,13 @@ class GpuIndex:
         if totals:
             out["totals"] = torch.empty(nq, dtype=torch.int32, device=dev)
         s = torch.cuda.current_stream(dev).cuda_stream
-        check(self.L.hnsw_gpu_range_knn_dev(self._h, 0 if code is None else 1, code or 0, queries.data_ptr(), nq, rad.data_ptr(), k, _dptr(words), bits, nf,
-                                            _dptr(of), out["labels"].data_ptr(), out["dists"].data_ptr(), _dptr(out.get("idx")), out["counts"].data_ptr(),
-                                            _dptr(out.get("totals")), s), "hnsw_gpu_range_knn_dev")
+        tail = (queries.data_ptr(), nq, rad.data_ptr(), k, _dptr(words), bits, nf, _dptr(of), out["labels"].data_ptr(), out["dists"].data_ptr(),
+                _dptr(out.get("idx")), out["counts"].data_ptr(), _dptr(out.get("totals")))
+        if form == "auto":
+            out["plan"] = torch.empty(nq, dtype=torch.uint8, device=dev)
+            check(self.L.hnsw_gpu_range_knn_auto_dev(self._h, code, *tail, out["plan"].data_ptr(), s), "hnsw_gpu_range_knn_auto_dev")
+        else:
+            check(self.L.hnsw_gpu_range_knn_dev(self._h, 0 if code is None else 1, code or 0, *tail, s), "hnsw_gpu_range_knn_dev")
         return out
 
     def last_range_knn_form(self) -> Optional[str]:
