@@ -266,7 +266,7 @@ int hnsw_gpu_filtered_knn_mfma(hnsw_gpu_index *ix, int format, const coord_t *qu
 							   const uint32_t *allow, size_t allow_bits, size_t nfilters, const uint32_t *allow_of,
 							   label_t *labels, dist_t *dists, idx_t *idx, uint32_t *counts);
 
-/* Exact radius search: the k nearest elements WITHIN a distance, and how many elements are that close (csrc/device_range_knn.h) — the exact
+/* Exact radius search: the k nearest elements WITHIN a distance, and how many elements are that close (csrc/device_filtered_knn.h) — the exact
  * plan of  WHERE emb <-> q <= r [AND pred] ORDER BY emb <-> q LIMIT k.  Per query q with radius r_q = d_radius[q] and, with a filter, bitmap b:
  * R(q) = the elements that are not vacuumed (bit 48 of the label word), whose label passes b (two elements holding one label both belong),
  * and whose canonical fp32 distance d — the one the search and hnsw_dist_func compute, bit for bit — has d <= r_q.  The comparison is IEEE

@@ -1,21 +1,31 @@
-// device_filtered_knn.h — exact filtered k-NN: a canonical scan over the allowed rows only (hnsw_gpu_filtered_knn_dev, gpu_scan.hip;
-// DESIGN §4.11).
+// device_filtered_knn.h — exact filtered k-NN and exact radius search: ONE pipeline over lists of allowed rows (hnsw_gpu_filtered_knn*_dev,
+// hnsw_gpu_range_knn*_dev, gpu_scan.hip).  Filtered k-NN is the radius call with no radius and no totals.
 //
 // A(b) = the elements that are not vacuumed (bit 48 of the label word) and whose label passes bitmap b (the allow filter of
-// device_indexscan.h: bit l of a bitmap says whether label l passes, labels >= allow_bits do not).  Four steps, all deterministic:
+// device_indexscan.h: bit l of a bitmap says whether label l passes, labels >= allow_bits do not); a radius call without a filter has ONE
+// implicit bitmap that every label passes.  R(q) = the rows of A(b(q)) that QUALIFY: all of them in a call without a radius — a row whose
+// distance is NaN included: it sorts behind every number — and those with a canonical distance d <= r_q in a call with one (IEEE <= on the
+// fp32 values: a NaN radius or distance is never in range).  So "no radius" is NOT r = +inf: the comparison is switched off, wave-uniformly.
+// The answer is the min(k, |R|) elements of R by (distance, element), in hnsw_search's order, and (radius calls) |R| itself.  All deterministic:
 //
 //   1. fk_count_kernel   one wave per (bitmap, segment of FK_SEG rows): how many of its rows are in A(b) (ballot + popcount)
 //      fk_offsets_kernel one block: exclusive scan of those counts, bitmap-major -> where every (bitmap, segment) starts in the lists;
 //                        the total and the longest list go to a pinned host pair (the call's one wait before the scan)
 //      fk_fill_kernel    the count kernel's pass again, writing element numbers: list b = A(b) ascending, lists back to back, 4 bytes
 //                        per entry (CSR: offsets off[b * nseg] .. off[(b + 1) * nseg])
+//      rk_live_kernel    both passes (and the mask row of the matrix-core form) for the call without a filter: the rows that are not vacuumed
 //   2. fk_scan_kernel    bruteforce_kernel (device_topk_scan.h) with the rows read from the list: a wave takes a contiguous slice of its
 //                        query's list, 64 entries per step (loaded coalesced, once, into the wave's LDS: StagedRows), scores them with the
-//                        canonical scan (scan_topk) and keeps a sorted top-k of (ord(dist) << 32 | ELEMENT) keys.  A query
-//                        uses as many waves as its own list is long (FK_WAVE_ROWS rows each at least, at most the launch's splits * 4).
-//   3. fk_emit_kernel    one wave per query: merges the query's partial lists (merge_ranks: keys are unique), gathers the
-//                        labels of the <= k winners, ranks them by (dist, label, element) — hnsw_search's order — and writes labels,
-//                        distances, element numbers, the count and the padded tails.
+//                        canonical distance code and keeps a sorted top-k of the (ord(dist) << 32 | ELEMENT) keys of the entries that
+//                        qualify, and their number (scan_topk_within: one ballot + popcount per step) -> a partial key list and a partial
+//                        count per wave.  A query uses as many waves as its own list is long (FK_WAVE_ROWS rows each at least, at most
+//                        the launch's splits * 4).  The listed form scans every query's whole list; the matrix-core form
+//                        (device_filtered_knn_mfma.h) the lists it scans whole and, unless totals are asked for, the samples of the longer ones
+//   3. fk_merge_kernel   one wave per query: merges the partial lists (merge_ranks: keys are unique) into ONE ascending key list, sums the
+//                        partial counts; matrix-core form: the bound tau_q and the query's mask row
+//   4. fk_emit_kernel    one wave per query, from its key list and its count: gathers the labels of the min(k, count) winners, ranks them
+//                        by (dist, label, element) — hnsw_search's order — and writes labels, distances, element numbers, the count, the
+//                        padded tails and (radius calls) the total
 //
 // Selection by (dist, element), emission by (dist, label): the reference's two steps (topResults, then the sort of searchKnn's output).
 #pragma once
@@ -136,6 +146,35 @@ __global__ __launch_bounds__(256) void fk_fill_kernel(const FkLists a, const uin
 	}
 }
 
+// ---- the rows that are not vacuumed as ONE list / mask row (a call without a filter) ------------------------------------------------------
+enum { RK_LIVE_COUNT = 0, RK_LIVE_FILL = 1, RK_LIVE_MASK = 2 };
+
+// fk_count_kernel's grid and pass with nfilters = 1.  COUNT: out = counts [nseg];  FILL: out = the list, off = the segments' offsets;
+// MASK: out = the mask row, a ballot per 64 rows
+template <int MODE>
+__global__ __launch_bounds__(256) void rk_live_kernel(const FkLists a, const uint64_t *__restrict__ off, uint32_t *__restrict__ out)
+{
+	const uint32_t lane = threadIdx.x & 63u;
+	uint32_t b, seg;
+	if (!fk_cell(a, b, seg) || b != 0) return;
+	const uint64_t below = (1ull << lane) - 1ull;
+	const uint32_t r0 = seg * FK_SEG, r1 = min(a.n, r0 + FK_SEG);
+	uint32_t *dst = out;
+	if (MODE == RK_LIVE_FILL) dst = out + off[seg];
+	uint32_t c = 0;
+	for (uint32_t base = r0; base < r1; base += 64)
+	{
+		const uint32_t i = base + lane;
+		const uint64_t lab = a.labels[i < r1 ? i : r1 - 1];
+		const bool in = i < r1 && !((lab >> 48) & 1ull);
+		const uint64_t m = __ballot(in);
+		if (MODE == RK_LIVE_FILL && in) dst[c + (uint32_t) __builtin_popcountll(m & below)] = i;
+		if (MODE == RK_LIVE_MASK && lane < 2) dst[(base >> 5) + lane] = (uint32_t) (m >> (32u * lane));
+		c += (uint32_t) __builtin_popcountll(m);
+	}
+	if (MODE == RK_LIVE_COUNT && lane == 0) out[seg] = c;
+}
+
 // The sample of a list of `len` entries (the matrix-core form's bound, device_filtered_knn_mfma.h): its first min(len, max(smin, k len / 2048))
 // entries — the exhaustive filter's sample rule (bruteforce_filter, gpu_scan.hip) applied to the list
 __host__ __device__ inline uint32_t fk_sample_len(uint32_t len, uint32_t smin, uint32_t k)
@@ -150,23 +189,62 @@ struct FkScan
 	const float *queries; uint32_t nq, k, splits;
 	const uint32_t *list; const uint64_t *off; uint32_t nseg; const uint32_t *allow_of;
 	uint64_t *part;                  // [nq][splits * 4][k] ascending keys, ~0 = none
+	uint32_t *pcount;                // [nq][splits * 4] qualifying entries of every wave's slice
 	unsigned long long *scored;      // rows scored by the call (one atomic per wave)
-	uint32_t smin;                   // 0: a query's whole list; else only its sample (fk_sample_len)
+	uint32_t smin;                   // 0: a query's whole list; else the matrix-core form's scan: its sample (fk_sample_len)
+	uint32_t skip_samples;           // matrix-core form with totals: only the lists that are scanned whole
+	const float *radius;             // NULL: no threshold, every scanned row qualifies; else [nq]
+	int func;
 };
 
-// the waves query qi scans with, out of the launch's splits * 4, from the length of its own list
+// a radius that no distance satisfies: NaN, or negative under L2 (a rounded square root: never below +0)
+__device__ __forceinline__ bool rk_selects_nothing(float r, int func) { return r != r || (func == F_L2 && r < 0.f); }
+
+// ---- the wave loop: scan_topk (device_topk_scan.h) with a threshold and a count -------------------------------------------------------------
+// One wave: entries [lo, hi) of `src`; the k smallest keys among those that qualify, ascending, in top[0 .. return value); nqual = how many
+// entries qualified (one ballot + popcount per step, no atomic).  within (wave-uniform): an entry qualifies if d <= radius, else always.
+template <int FUNC, class Source>
+__device__ __forceinline__ uint32_t scan_topk_within(const float *__restrict__ vec, uint32_t stride, const float4 *q4, uint32_t nchunks,
+													 uint32_t kiters, const Source &src, uint32_t lo, uint32_t hi, uint64_t *top, float *sums,
+													 uint32_t k, bool within, float radius, uint32_t &nqual, int lane)
+{
+	float qnorm = 0.f;
+	if (FUNC == F_COSINE) qnorm = query_norm(q4, nchunks, kiters, lane);
+	uint32_t tsize = 0, nin = 0;
+	uint64_t worst = ~0ull;
+	for (uint32_t base = lo; base < hi; base += 64)
+	{
+		const uint32_t cnt = min(64u, hi - base);
+		const uint32_t id = src.id(base, cnt, lane);
+		score_rows<FUNC, 4, 2>(vec, stride, q4, nchunks, kiters, src.rows(base), cnt, sums, lane);
+		wave_sync();
+		const float dl = finish_dist<FUNC>(sums[lane], sums[OUT2 + lane], qnorm);
+		const bool in = (uint32_t) lane < cnt && (!within || dl <= radius);   // (IEEE: false for a NaN on either side)
+		nin += (uint32_t) __builtin_popcountll(__ballot(in));
+		topk_offer(top, tsize, worst, ((uint64_t) ord_f32(dl) << 32) | id, in, k, lane);
+		wave_sync();
+	}
+	nqual = nin;
+	return tsize;
+}
+
+// the waves query qi scans with, out of the launch's splits * 4, from the length of what it scans
 __device__ __forceinline__ uint32_t fk_waves(uint32_t len, uint32_t splits)
 {
 	return min(splits * 4u, (len + FK_WAVE_ROWS - 1) / FK_WAVE_ROWS);
 }
 
-__device__ __forceinline__ void fk_list_of(const FkScan &a, uint32_t qi, const uint32_t *&list, uint32_t &len)
+// What query qi scans: `len` leading entries of the list of its bitmap b; whole = that is the whole list.  A sample that is not wanted
+// (skip_samples) and any list under a radius that selects nothing (no row can be in range) is not scanned at all.
+__device__ __forceinline__ void fk_list_of(const FkScan &a, uint32_t qi, const uint32_t *&list, uint32_t &len, bool &whole, uint32_t &b)
 {
-	const uint32_t b = a.allow_of ? a.allow_of[qi] : 0u;
+	b = a.allow_of ? a.allow_of[qi] : 0u;
 	const uint64_t o = a.off[(size_t) b * a.nseg];
 	list = a.list + o;
-	len = (uint32_t) (a.off[(size_t) (b + 1) * a.nseg] - o);          // (a list is a subset of the < 2^32 elements)
-	if (a.smin) len = fk_sample_len(len, a.smin, a.k);
+	const uint32_t full = (uint32_t) (a.off[(size_t) (b + 1) * a.nseg] - o);      // (a list is a subset of the < 2^32 elements)
+	len = a.smin ? fk_sample_len(full, a.smin, a.k) : full;
+	whole = len == full;
+	if ((!whole && a.skip_samples) || (a.radius && rk_selects_nothing(a.radius[qi], a.func))) len = 0;
 }
 
 // grid = splits * nq blocks (rounded up to 8), 4 waves each.  Block order: query number fastest within a split, so the blocks resident at
@@ -186,8 +264,8 @@ __global__ __launch_bounds__(256) void fk_scan_kernel(const FkScan a)
 #endif
 	if (L >= nblk) return;
 	const uint32_t sp = L / a.nq, qi = L - sp * a.nq;
-	const uint32_t *list; uint32_t len;
-	fk_list_of(a, qi, list, len);
+	const uint32_t *list; uint32_t len, b; bool whole;
+	fk_list_of(a, qi, list, len, whole, b);
 	const uint32_t nw = fk_waves(len, a.splits);
 	if (sp * 4u >= nw) return;                                        // (block-uniform) a short list leaves the later splits idle
 	stage_query_block(reinterpret_cast<float *>(smem), a.queries + (size_t) qi * a.dim, a.dim, a.qpad_floats);
@@ -200,37 +278,88 @@ __global__ __launch_bounds__(256) void fk_scan_kernel(const FkScan a)
 	float *sums = reinterpret_cast<float *>(wbase + (size_t) 4 * (k + 1) * 8) + wib * 128;
 	uint32_t *ids = reinterpret_cast<uint32_t *>(wbase + (size_t) 4 * (k + 1) * 8 + 4 * 128 * 4) + wib * 64;
 	const uint32_t lo = (uint32_t) ((uint64_t) len * w / nw), hi = (uint32_t) ((uint64_t) len * (w + 1) / nw);
-	const uint32_t tsize = scan_topk<FUNC>(a.vec, a.stride, q4, a.nchunks, a.kiters, StagedRows{list, ids}, lo, hi, top, sums, k, lane);
+	const bool within = a.radius != nullptr;
+	uint32_t nqual = 0;
+	const uint32_t tsize = scan_topk_within<FUNC>(a.vec, a.stride, q4, a.nchunks, a.kiters, StagedRows{list, ids}, lo, hi, top, sums, k, within,
+												  within ? a.radius[qi] : 0.f, nqual, lane);
 	store_partial(a.part + ((size_t) qi * a.splits * 4u + w) * k, top, tsize, k, lane);
-	if (lane == 0) atomicAdd(a.scored, (unsigned long long) (hi - lo));
+	if (lane == 0)
+	{
+		a.pcount[(size_t) qi * a.splits * 4u + w] = nqual;
+		atomicAdd(a.scored, (unsigned long long) (hi - lo));
+	}
+}
+
+struct FkMerge
+{
+	FkScan s;
+	uint32_t nfilters;
+	uint64_t *keys;                  // [nq][k] the scan's keys, ascending, ~0 = none
+	uint32_t *count;                 // [nq] qualifying rows of the scan where it is the query's answer, else 0 (the re-score's to write)
+	float *tau;                      // NULL (listed form), or [nq] the bound for make_bounds_kernel
+	uint32_t *mask_of;               // [nq] the query's mask row: its bitmap, or nfilters (zeros) when the scan answered it
+};
+
+// One wave per query (block = 64 threads).  LDS: k keys.  The bound (matrix-core form): with k qualifying rows in the sample its k-th
+// distance — the sample is a subset of R, and under a radius its keys are in range, so the k-th is the smaller of the two — else the
+// radius (none: +inf).  A query whose scan is its complete answer — a list no longer than its sample, a radius that selects nothing —
+// needs no candidate: a bound of 0 keeps its pairs out of the block's pass list, the zero mask row out of its candidates.
+__global__ __launch_bounds__(64) void fk_merge_kernel(const FkMerge a)
+{
+	extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+	const uint32_t qi = blockIdx.x, lane = threadIdx.x, k = a.s.k;
+	uint64_t *win = reinterpret_cast<uint64_t *>(smem);
+	const uint32_t *list; uint32_t len, b; bool whole;
+	fk_list_of(a.s, qi, list, len, whole, b);
+	const uint32_t nw = fk_waves(len, a.s.splits);
+	for (uint32_t i = lane; i < k; i += 64) win[i] = ~0ull;
+	wave_sync();
+	merge_ranks(a.s.part + (size_t) qi * a.s.splits * 4u * k, nw, k, (int) lane, [win](uint32_t rank, uint64_t key) { win[rank] = key; });
+	uint32_t nin = 0;
+	for (uint32_t w = lane; w < nw; w += 64) nin += a.s.pcount[(size_t) qi * a.s.splits * 4u + w];
+	for (int o = 32; o > 0; o >>= 1) nin += (uint32_t) __shfl_xor((int) nin, o);
+	wave_sync();
+	for (uint32_t i = lane; i < k; i += 64) a.keys[(size_t) qi * k + i] = win[i];
+	if (lane == 0)
+	{
+		const float r = a.s.radius ? a.s.radius[qi] : __builtin_inff();
+		const bool answered = whole || rk_selects_nothing(r, a.s.func);
+		a.count[qi] = answered ? nin : 0u;
+		if (a.tau)
+		{
+			a.tau[qi] = answered ? 0.f : nin >= k ? unord_f32((uint32_t) (win[k - 1] >> 32)) : r;
+			a.mask_of[qi] = answered ? a.nfilters : b;
+		}
+	}
 }
 
 struct FkEmit
 {
-	FkScan s;
-	const uint64_t *single;          // NULL, or [nq][k]: every query's keys as ONE ascending list (~0 = none) in place of its partial lists
+	const uint64_t *keys;            // [nq][k] every query's keys as ONE ascending list (~0 = none)
+	const uint32_t *count;           // [nq] the rows that qualified: the answer holds min(k, count) of them, the first keys of the list
+	uint32_t k;
 	const uint64_t *labels; uint32_t n;
 	uint64_t *out_labels; float *out_dists; uint32_t *out_idx; uint32_t *out_counts;
+	uint32_t *out_totals;            // NULL, or [nq] <- count
+	unsigned long long *sum;         // NULL, or the call's sum of the counts
 };
 
 // One wave per query (block = 64 threads).  LDS: k winner keys | k labels.
 __global__ __launch_bounds__(64) void fk_emit_kernel(const FkEmit a)
 {
 	extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-	const uint32_t qi = blockIdx.x, lane = threadIdx.x, k = a.s.k;
+	const uint32_t qi = blockIdx.x, lane = threadIdx.x, k = a.k;
 	uint64_t *win = reinterpret_cast<uint64_t *>(smem), *lab = win + k;
-	const uint32_t *list; uint32_t len;
-	fk_list_of(a.s, qi, list, len);
-	const uint32_t nlists = a.single ? 1u : fk_waves(len, a.s.splits);
-	const uint64_t *src = a.single ? a.single + (size_t) qi * k : a.s.part + (size_t) qi * a.s.splits * 4u * k;
-	const uint32_t cnt = min(k, len);                                 // every listed row was scored: the merge finds min(k, |A|) keys
-	// 1. the key merge over the lists this query's waves wrote (one element, one key: merge_ranks)
-	merge_ranks(src, nlists, k, (int) lane, [win](uint32_t rank, uint64_t key) { win[rank] = key; });
+	const uint32_t total = a.count[qi], cnt = min(k, total);
+	// 1. the winners' keys and labels
+	for (uint32_t i = lane; i < cnt; i += 64)
+	{
+		const uint64_t key = a.keys[(size_t) qi * k + i];
+		win[i] = key;
+		lab[i] = a.labels[min((uint32_t) key, a.n - 1u)];
+	}
 	wave_sync();
-	// 2. the winners' labels
-	for (uint32_t i = lane; i < cnt; i += 64) lab[i] = a.labels[min((uint32_t) win[i], a.n - 1u)];
-	wave_sync();
-	// 3. hnsw_search's order: ascending (distance, label); equal pairs by element number (win is ascending by (distance, element))
+	// 2. hnsw_search's order: ascending (distance, label); equal pairs by element number (win is ascending by (distance, element))
 	const size_t obase = (size_t) qi * k;
 	for (uint32_t b = 0; b < cnt; b += 64)
 	{
@@ -258,7 +387,12 @@ __global__ __launch_bounds__(64) void fk_emit_kernel(const FkEmit a)
 		if (a.out_dists) a.out_dists[obase + i] = __builtin_inff();
 		if (a.out_idx) a.out_idx[obase + i] = LINK_NONE;
 	}
-	if (lane == 0) a.out_counts[qi] = cnt;
+	if (lane == 0)
+	{
+		a.out_counts[qi] = cnt;
+		if (a.out_totals) a.out_totals[qi] = total;
+		if (a.sum && total) atomicAdd(a.sum, (unsigned long long) total);
+	}
 }
 
 }  // namespace pgemb

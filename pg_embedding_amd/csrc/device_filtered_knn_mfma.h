@@ -1,23 +1,30 @@
-// device_filtered_knn_mfma.h — exact filtered k-NN for LOOSE filters: the Q x N part on the matrix cores (hnsw_gpu_filtered_knn_mfma_dev,
-// gpu_scan.hip).
+// device_filtered_knn_mfma.h — exact filtered k-NN and exact radius search for LOOSE filters: the Q x N part on the matrix cores (the
+// matrix-core form of hnsw_gpu_filtered_knn_mfma_dev / hnsw_gpu_range_knn_dev, the loose class of the automatic calls, gpu_scan.hip;
+// DESIGN §4.11b, §4.12).
 //
 // The listed scan (device_filtered_knn.h) costs |A(b)| canonical rows per query: at a pass rate of 1/10 that is more than scoring EVERY
-// row on the matrix cores (device_bf_mfma.h).  This form keeps the listed call's answer, bit for bit, and moves the bulk of the work:
+// row on the matrix cores (device_bf_mfma.h).  This form keeps the listed form's answer, bit for bit, and moves the bulk of the work:
 //
-//   1. the lists A(b), as the listed form builds them (fk_count / fk_offsets / fk_fill)
+//   1. the lists A(b), as the listed form builds them (fk_count / fk_offsets / fk_fill, or rk_live_kernel without a filter)
 //   2. fkm_mask_kernel    one bit per element number and bitmap: bit r of mask row b = (r in A(b)); one more row of zeros
-//   3. fk_scan_kernel     over the SAMPLE of every query's list, its first S(b) = fk_sample_len(|A(b)|) entries: the query's k best keys
-//      fkm_bounds_kernel  merges them: tau_q = the k-th distance (inf with fewer than k).  A query whose list is no longer than its sample
-//                         is ANSWERED BY ITS SAMPLE — that scan is its complete answer — and gets the row of zeros as its mask row
+//      (rk_live_kernel<RK_LIVE_MASK> without a filter: the one row of the rows that are not vacuumed)
+//   3. fk_scan_kernel     over the SAMPLE of every query's list, its first S(b) = fk_sample_len(|A(b)|) entries: the query's k best
+//                         qualifying keys and their number.  With totals only the lists no longer than their sample are scanned
+//      fk_merge_kernel    merges them and sets the bound: tau_q = the k-th qualifying distance of the sample, with fewer than k the radius
+//                         (none: +inf), with totals the radius (every in-range row must reach the re-score to be counted).  A query
+//                         whose list is no longer than its sample is ANSWERED BY ITS SAMPLE — that scan is its complete answer — and
+//                         so is one whose radius selects nothing: both get a bound of 0 and the row of zeros as their mask row
 //   4. bf_mfma_filter_kernel<BfAllow<P>, ...>  all Q x N dot products against make_bounds_kernel's margin of tau_q, as the exhaustive
 //                         call runs it; a passing pair is appended to the query's candidate list only if the row's mask bit is set
 //                         (bf_append<true>).  Counters: pairs that passed the comparison | pairs that were appended (bf_count)
-//   5. bf_rescore_kernel  canonical distances of the candidates, top-k by (dist, element)
-//   6. fkm_keys_kernel    the re-score's result as a key list, over the sample's keys except where the sample answered
-//      fk_emit_kernel     labels, (dist, label, element) order, counts and tails — from that one key list per query
+//   5. fkm_rescore_kernel canonical distances of the candidates: the top-k qualifying keys by (dist, element) and their number, over the
+//                         sample's keys and count except where the sample answered
+//      fk_emit_kernel     labels, (dist, label, element) order, counts, tails and totals — from that one key list and count per query
 //
-// Exactness: the sample is a subset of A(b), so tau_q is an upper bound of the k-th distance over A(b); the filter keeps every row within
-// tau_q (device_bf_mfma.h, device_bf_mfma16.h), the mask keeps exactly the rows of A(b), and the survivors are ranked by the canonical code.
+// Exactness: the sample is a subset of A(b) and its kept keys qualify, so tau_q is an upper bound of the k-th qualifying distance (no
+// totals) or the radius itself (totals); the filter keeps every row within tau_q (device_bf_mfma.h, device_bf_mfma16.h), the mask keeps
+// exactly the rows of A(b), and the survivors are ranked — and compared with the radius — by the canonical code.  The qualifying count of
+// the re-score is then |R| (totals) or at least min(k, |R|).
 //
 // fkm_standin_kernel replaces step 4 where the filter kernel cannot run (the tests' SIMT emulator models neither MFMA nor direct-to-LDS
 // loads; knob HNSW_GPU_FK_MFMA_STANDIN): every pair whose canonical distance is <= tau_q goes through the same bf_append<true> / bf_count.
@@ -58,47 +65,36 @@ __global__ __launch_bounds__(256) void fkm_mask_kernel(const FkLists a, uint32_t
 	}
 }
 
-struct FkmBounds
-{
-	FkScan s;                        // the sample scan (s.smin != 0)
-	uint32_t nfilters;
-	uint64_t *keys;                  // [nq][k] the sample's keys, ascending, ~0 = none
-	float *tau;                      // [nq]
-	uint32_t *mask_of;               // [nq] the query's mask row: its bitmap, or nfilters (zeros) when its sample answered it
-};
-
-// One wave per query (block = 64 threads).  LDS: k keys.
-__global__ __launch_bounds__(64) void fkm_bounds_kernel(const FkmBounds a)
+// One wave per query, bf_rescore_kernel's shape and LDS (device_topk_scan.h): canonical distances of the filter's candidates; the top-k
+// among those that qualify (d <= r; radius == NULL: all of them) as keys, and their number.  A query the scan answered (mask row nfilters)
+// keeps what fk_merge_kernel wrote.
+template <int FUNC>
+__global__ __launch_bounds__(256) void fkm_rescore_kernel(const float *__restrict__ vec, uint32_t dim, uint32_t stride, uint32_t nchunks,
+														  uint32_t kiters, uint32_t qpad_floats, const float *__restrict__ queries, uint32_t nq,
+														  const float *__restrict__ radius, const uint32_t *__restrict__ mask_of, uint32_t nfilters,
+														  const uint32_t *__restrict__ cand, const uint32_t *__restrict__ cand_cnt, uint32_t cap,
+														  uint32_t k, uint64_t *__restrict__ keys, uint32_t *__restrict__ count,
+														  uint32_t *__restrict__ overflow)
 {
 	extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-	const uint32_t qi = blockIdx.x, lane = threadIdx.x, k = a.s.k;
-	uint64_t *win = reinterpret_cast<uint64_t *>(smem);
-	const uint32_t b = a.s.allow_of ? a.s.allow_of[qi] : 0u;
-	const uint32_t len = (uint32_t) (a.s.off[(size_t) (b + 1) * a.s.nseg] - a.s.off[(size_t) b * a.s.nseg]);
-	const uint32_t slen = fk_sample_len(len, a.s.smin, k);
-	for (uint32_t i = lane; i < k; i += 64) win[i] = ~0ull;
-	wave_sync();
-	merge_ranks(a.s.part + (size_t) qi * a.s.splits * 4u * k, fk_waves(slen, a.s.splits), k, (int) lane, [win](uint32_t rank, uint64_t key) { win[rank] = key; });
-	wave_sync();
-	for (uint32_t i = lane; i < k; i += 64) a.keys[(size_t) qi * k + i] = win[i];
-	if (lane == 0)
-	{
-		const bool answered = len <= slen;
-		// (an answered query needs no candidate: a bound of 0 keeps its pairs out of the block's pass list, the zero mask row out of its candidates)
-		a.tau[qi] = answered ? 0.f : slen >= k ? unord_f32((uint32_t) (win[k - 1] >> 32)) : __builtin_inff();
-		a.mask_of[qi] = answered ? a.nfilters : b;
-	}
-}
-
-// the re-score's (element, distance) lists as keys, in place of the sample's keys of every query the sample did not answer
-__global__ __launch_bounds__(256) void fkm_keys_kernel(const uint32_t *__restrict__ ridx, const float *__restrict__ rdist, const uint32_t *__restrict__ mask_of,
-													   uint32_t nfilters, uint32_t nq, uint32_t k, uint64_t *__restrict__ keys)
-{
-	const size_t i = (size_t) blockIdx.x * blockDim.x + threadIdx.x;
-	if (i >= (size_t) nq * k) return;
-	if (mask_of[i / k] == nfilters) return;
-	const uint32_t e = ridx[i];
-	keys[i] = e == LINK_NONE ? ~0ull : ((uint64_t) ord_f32(rdist[i]) << 32) | e;
+	const int lane = threadIdx.x & 63;
+	const uint32_t wib = threadIdx.x >> 6;
+	const uint32_t qi = blockIdx.x * 4 + wib;
+	if (qi >= nq || mask_of[qi] == nfilters) return;
+	const size_t wave_bytes = (size_t) qpad_floats * 4 + (size_t) (k + 1) * 8 + 128 * 4;
+	unsigned char *my = smem + wib * ((wave_bytes + 15) & ~(size_t) 15);
+	const float4 *q4 = reinterpret_cast<const float4 *>(my);
+	uint64_t *top = reinterpret_cast<uint64_t *>(my + (size_t) qpad_floats * 4);
+	float *sums = reinterpret_cast<float *>(top + (k + 1));
+	stage_query_wave(reinterpret_cast<float *>(my), queries + (size_t) qi * dim, dim, qpad_floats, lane);
+	uint32_t cnt = cand_cnt[qi];
+	if (cnt > cap) { if (lane == 0) atomicAdd(overflow, 1u); cnt = cap; }
+	const bool within = radius != nullptr;
+	uint32_t nqual = 0;
+	const uint32_t tsize = scan_topk_within<FUNC>(vec, stride, q4, nchunks, kiters, CandidateRows{cand + (size_t) qi * cap}, 0u, cnt, top, sums, k,
+												  within, within ? radius[qi] : 0.f, nqual, lane);
+	store_partial(keys + (size_t) qi * k, top, tsize, k, lane);
+	if (lane == 0) count[qi] = nqual;
 }
 
 // The filter's stand-in: one block per query, its 4 waves stride over all rows 64 at a time with the canonical distance code; a pair passes

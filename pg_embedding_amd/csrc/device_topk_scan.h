@@ -5,7 +5,8 @@
 // the row numbers of a step come from (a Source below):
 //   bruteforce_kernel   the rows themselves, a contiguous slice per wave            -> a partial list per wave, merged by key_merge_kernel
 //   bf_rescore_kernel   a query's candidate list (the survivors of the MFMA filter)  -> the query's result
-//   fk_scan_kernel      a slice of a query's list of allowed rows (device_filtered_knn.h) -> a partial list per wave, merged by fk_emit_kernel
+//   fk_scan_kernel      a slice of a query's list of allowed rows (device_filtered_knn.h: the loop with a threshold and a count,
+//                       scan_topk_within)                                            -> a partial list per wave, merged by fk_merge_kernel
 // Keys are unique (one row, one key), so lists merge by rank: a key's place is the number of keys below it (merge_ranks).
 #pragma once
 #include "device_dist.h"

@@ -1,7 +1,7 @@
 // gpu_scan.hip — batched distances (hnsw_dist_func over many rows), exhaustive k-NN: canonical scan (csrc/device_topk_scan.h), MFMA filter over
-// the f32 rows or the reduced copy (csrc/device_bf_mfma.h, csrc/device_bf_mfma16.h), and exact filtered k-NN: the canonical scan over lists of
-// allowed rows (csrc/device_filtered_knn.h) or, for loose filters, the MFMA filter with the allow test at its append (csrc/device_filtered_knn_mfma.h),
-// and exact radius search over the same lists, masks and filter (csrc/device_range_knn.h)
+// the f32 rows or the reduced copy (csrc/device_bf_mfma.h, csrc/device_bf_mfma16.h), and exact filtered k-NN and exact radius search, one
+// pipeline: the canonical scan over lists of allowed rows (csrc/device_filtered_knn.h) or, for loose filters, the MFMA filter with the allow
+// test at its append (csrc/device_filtered_knn_mfma.h), chosen per query in the automatic calls (csrc/device_fk_plan.h)
 // One translation unit of libhnsw_gpu.so (csrc/gpu_host.h lists them); gfx950 only, plain HIP runtime, no framework types in any signature.
 #include "gpu_host.h"
 #include "device_topk_scan.h"
@@ -9,7 +9,6 @@
 #include "device_bf_mfma16.h"
 #include "device_filtered_knn.h"
 #include "device_filtered_knn_mfma.h"
-#include "device_range_knn.h"
 #include "device_fk_plan.h"
 
 #include <type_traits>
@@ -25,6 +24,18 @@ static void with_func(int func, F &&f)
 		default: f(std::integral_constant<int, F_MANHATTAN>{}); break;
 	}
 }
+
+// The query image of the canonical distance code in LDS — the row's 16-byte chunks padded with zeros to whole steps of 16 chunks x 4 — and
+// the dynamic LDS of every kernel that stages one, in ONE place: the contract checks and the launch sites take their sizes from here
+struct QueryGeom
+{
+	uint32_t nchunks, kiters, qpad;                               // 16-byte chunks of a row | steps of 16 chunks | floats of the image
+	explicit QueryGeom(size_t stride) : nchunks((uint32_t) (stride / 4)), kiters((nchunks + 15) / 16), qpad((uint32_t) round_up(kiters, 4) * 64) {}
+	size_t lds_dist() const { return (size_t) qpad * 4 + 4 * 128 * 4; }                        // image | 4 x 128 sums: dist_batch_kernel, fkm_standin_kernel
+	size_t lds_scan(size_t k) const { return lds_dist() + 4 * (k + 1) * 8; }                   // image | 4 x (k + 1) keys | 4 x 128 sums: bruteforce_kernel
+	size_t lds_listed(size_t k) const { return lds_scan(k) + 4 * 64 * 4; }                     // ... | 4 x 64 staged element numbers: fk_scan_kernel
+	size_t lds_rescore(size_t k) const { return 4 * round_up((size_t) qpad * 4 + (k + 1) * 8 + 128 * 4, 16); }   // per wave: image | k + 1 keys | 128 sums: bf_rescore_kernel, fkm_rescore_kernel
+};
 
 // ------------------------------------------------------------------------------------
 // batched distances (hnsw_dist_func over many rows)
@@ -64,15 +75,13 @@ extern "C" int hnsw_gpu_dist_batch_dev(dist_func_t func, const coord_t *d_q, con
 	if (dim == 0 || row_stride < dim || (row_stride & 3) || (((uintptr_t) d_rows) & 15))
 		return fail(HNSW_GPU_ERR_ARG, "rows must be 16-byte aligned with stride %% 4 == 0 and stride >= dim");
 	if (nrows >= 0xFFFFFFF0ull) return fail(HNSW_GPU_ERR_ARG, "too many rows");
-	const uint32_t nchunks = (uint32_t) (row_stride / 4), kiters = (nchunks + 15) / 16;
-	const uint32_t qpad = (uint32_t) round_up(kiters, 4) * 64;
-	const size_t lds = (size_t) qpad * 4 + 4 * 128 * 4;
-	if (lds > 64 * 1024) return fail(HNSW_GPU_ERR_ARG, "dim %zu too large", dim);
+	const QueryGeom g(row_stride);
+	if (g.lds_dist() > 64 * 1024) return fail(HNSW_GPU_ERR_ARG, "dim %zu too large", dim);
 	const uint32_t blocks = (uint32_t) std::min<size_t>((nrows + 255) / 256, 256 * 8);
 	hipStream_t s = (hipStream_t) stream;
 	with_func((int) func, [&](auto F) {
-		hipLaunchKernelGGL(dist_batch_kernel<decltype(F)::value>, dim3(blocks), dim3(256), lds, s, d_q, d_rows, (uint32_t) nrows, (uint32_t) dim,
-						   (uint32_t) row_stride, nchunks, kiters, qpad, d_out);
+		hipLaunchKernelGGL(dist_batch_kernel<decltype(F)::value>, dim3(blocks), dim3(256), g.lds_dist(), s, d_q, d_rows, (uint32_t) nrows, (uint32_t) dim,
+						   (uint32_t) row_stride, g.nchunks, g.kiters, g.qpad, d_out);
 	});
 	HIPCHK(hipGetLastError());
 	return HNSW_GPU_OK;
@@ -161,13 +170,11 @@ static int bruteforce_prefix(hnsw_gpu_index *ix, size_t nrows, const coord_t *d_
 	if (nq > 65535) return fail(HNSW_GPU_ERR_ARG, "at most 65535 queries per call");
 	HIPCHK(hipSetDevice(ix->device));
 	hipStream_t s = (hipStream_t) stream;
-	const uint32_t nchunks = ix->stride / 4, kiters = (nchunks + 15) / 16;
-	const uint32_t qpad = (uint32_t) round_up(kiters, 4) * 64;
+	const QueryGeom g(ix->stride);
 	uint32_t splits = (uint32_t) std::max<size_t>(1, std::min<size_t>(64, (size_t) (4 * ix->num_cu) / nq));
 	splits = (uint32_t) std::min<size_t>(splits, std::max<size_t>(1, nrows / 64));
 	const uint32_t nlists = splits * 4;
-	const size_t lds = (size_t) qpad * 4 + (size_t) 4 * (k + 1) * 8 + 4 * 128 * 4;
-	if (lds > 64 * 1024) return fail(HNSW_GPU_ERR_ARG, "k/dim too large for brute force");
+	if (g.lds_scan(k) > 64 * 1024) return fail(HNSW_GPU_ERR_ARG, "k/dim too large for brute force");
 	int rc = ensure_scratch(ix, nq * nlists * k * 8);
 	if (rc) return rc;
 	uint64_t *part = (uint64_t *) ix->scratch;
@@ -178,8 +185,8 @@ static int bruteforce_prefix(hnsw_gpu_index *ix, size_t nrows, const coord_t *d_
 						   0x7F800000u);
 	dim3 grid(splits, (uint32_t) nq);
 	with_func((int) ix->meta.dist_func, [&](auto F) {
-		hipLaunchKernelGGL(bruteforce_kernel<decltype(F)::value>, grid, dim3(256), lds, s, ix->vec, (uint32_t) nrows, (uint32_t) ix->meta.dim, ix->stride,
-						   nchunks, kiters, qpad, d_queries, (uint32_t) k, part);
+		hipLaunchKernelGGL(bruteforce_kernel<decltype(F)::value>, grid, dim3(256), g.lds_scan(k), s, ix->vec, (uint32_t) nrows, (uint32_t) ix->meta.dim, ix->stride,
+						   g.nchunks, g.kiters, g.qpad, d_queries, (uint32_t) k, part);
 	});
 	hipLaunchKernelGGL(key_merge_kernel, dim3((uint32_t) nq), dim3(64), 0, s, part, nlists, (uint32_t) k, d_idx, d_dists);
 	HIPCHK(hipGetLastError());
@@ -312,6 +319,26 @@ static void bf_queries_side(bool reduced, int format, const coord_t *d_queries, 
 		hipLaunchKernelGGL(r16_query_kernel<ROWS_F16>, qgrid, dim3(256), 0, s, d_queries, (uint32_t) nq, dim, qchunks, qcopy, qn, qterms);
 }
 
+// 16-byte chunks of the filter's copy of a query: f32 zero padded to whole K steps, 16-bit the copy's row
+static uint32_t bf_qchunks(const hnsw_gpu_index *ix, bool reduced) { return reduced ? ix->rows16_bytes / 16 : (uint32_t) round_up(ix->stride, BF_TK) / 4; }
+
+// the filter's arguments for nq queries against all rows of the index, in ONE place (a form with the allow test adds its mask and counters)
+static BfArgs bf_args(const hnsw_gpu_index *ix, bool reduced, size_t nq, const uint4 *qcopy, const float *qn, const float *bound, const float2 *qterms,
+					  uint32_t *cand, uint32_t *cnt, uint32_t cap)
+{
+	const uint32_t dim = (uint32_t) ix->meta.dim;
+	BfArgs a;
+	memset(&a, 0, sizeof(a));
+	a.queries = qcopy; a.qnorm = qn; a.qbound = bound; a.qterms = qterms;
+	a.rows = reduced ? (const uint4 *) ix->rows16 : (const uint4 *) ix->vec; a.xnorm = ix->xnorm; a.xterms = ix->r16x;
+	a.nq = (uint32_t) nq; a.n = (uint32_t) ix->n; a.qchunks = bf_qchunks(ix, reduced); a.rchunks = reduced ? ix->rows16_bytes / 16 : ix->stride / 4;
+	a.ksteps = a.qchunks / BF_CH; a.func = (int) ix->meta.dist_func;
+	a.xscale = 0.5f * (1.f - 2.f * ((float) dim + 32.f) * 0x1p-24f);          // (1 - eD) / 2: make_bounds_kernel
+	a.eabs = r16_abs_term(dim);
+	a.cand = cand; a.cand_cnt = cnt; a.cap = cap;
+	return a;
+}
+
 // Both forms of the call: a bound per query from a canonical scan of a sample, the filter over the f32 rows (reduced == false) or over the
 // reduced copy of `format`, the canonical re-score of the survivors.  A form that cannot answer hands the call down: the 16-bit filter to
 // the f32 filter, that one to the canonical scan — the same answer, bit for bit (the filter's survivors are re-scored by that code anyway).
@@ -335,20 +362,14 @@ static int bruteforce_filter(hnsw_gpu_index *ix, bool reduced, int format, const
 	HIPCHK(hipSetDevice(ix->device));
 	if (!ix->gfx950 || ix->max_lds < BF_MIN_LDS) return scan();
 	hipStream_t s = (hipStream_t) stream_;
-	const uint32_t n = (uint32_t) ix->n, stride = ix->stride, dim = (uint32_t) ix->meta.dim;
-	const uint32_t nchunks = stride / 4, kiters = (nchunks + 15) / 16;
-	const uint32_t qpadf = (uint32_t) round_up(kiters, 4) * 64;
-	const size_t wave_bytes = round_up((size_t) qpadf * 4 + (k + 1) * 8 + 128 * 4, 16);
-	const size_t lds = wave_bytes * 4;
-	if (lds > 64 * 1024) return scan();
+	const uint32_t dim = (uint32_t) ix->meta.dim;
+	const QueryGeom g(ix->stride);
+	if (g.lds_rescore(k) > 64 * 1024) return scan();
 
 	// the rows' side, current on this stream: the reduced copy and the bound's per-row terms, or the |row|^2 cache
 	int rc = bf_rows_side(ix, reduced, s);
 	if (rc) return rc;
-	// 16-byte chunks of the filter's query copy (f32: zero padded to whole K steps; 16-bit: the copy's row) and of a row
-	const uint32_t qchunks = reduced ? ix->rows16_bytes / 16 : (uint32_t) round_up(stride, BF_TK) / 4;
-	const uint32_t rchunks = reduced ? ix->rows16_bytes / 16 : nchunks;
-
+	const uint32_t qchunks = bf_qchunks(ix, reduced);
 	const uint32_t cap = 16384;
 	const size_t sample = std::min<size_t>(ix->n, std::max<size_t>(8192, (size_t) k * ix->n / 2048));
 	// scratch carve
@@ -389,14 +410,8 @@ static int bruteforce_filter(hnsw_gpu_index *ix, bool reduced, int format, const
 	ix->bf_cnt_off = o_cnt; ix->bf_cnt_nq = nq;
 
 	// 2. the dense contraction + filter
-	BfArgs a;
-	memset(&a, 0, sizeof(a));
-	a.queries = qcopy; a.qnorm = qn; a.qbound = bound; a.qterms = qterms;
-	a.rows = reduced ? (const uint4 *) ix->rows16 : (const uint4 *) ix->vec; a.xnorm = ix->xnorm; a.xterms = ix->r16x;
-	a.nq = (uint32_t) nq; a.n = n; a.qchunks = qchunks; a.rchunks = rchunks; a.ksteps = qchunks / BF_CH; a.func = func;
-	a.xscale = 0.5f * (1.f - 2.f * ((float) dim + 32.f) * 0x1p-24f);          // (1 - eD) / 2: make_bounds_kernel
-	a.eabs = r16_abs_term(dim);
-	a.cand = cand; a.cand_cnt = cnt; a.cap = cap; a.clocks = (unsigned long long *) (B + o_clk);
+	BfArgs a = bf_args(ix, reduced, nq, qcopy, qn, bound, qterms, cand, cnt, cap);
+	a.clocks = (unsigned long long *) (B + o_clk);
 	HIPCHK(hipMemsetAsync(a.clocks, 0, 16, s));                  // (written only by a block from the middle of the launch that does not exit early: a small table must not leave stale ticks behind)
 	if (!ix->bf_e0) { HIPCHK(hipEventCreate(&ix->bf_e0)); HIPCHK(hipEventCreate(&ix->bf_e1)); }
 	hipEvent_t e0 = ix->bf_e0, e1 = ix->bf_e1;
@@ -408,8 +423,8 @@ static int bruteforce_filter(hnsw_gpu_index *ix, bool reduced, int format, const
 	// 3. canonical re-score of the survivors against the fp32 rows
 	with_func(func, [&](auto F) {
 		if constexpr (decltype(F)::value != F_MANHATTAN)           // (answered by the scan above: no re-score kernel is compiled for it)
-			hipLaunchKernelGGL(bf_rescore_kernel<decltype(F)::value>, dim3((uint32_t) ((nq + 3) / 4)), dim3(256), lds, s, ix->vec, dim, stride, nchunks, kiters,
-							   qpadf, d_queries, (uint32_t) nq, cand, cnt, cap, (uint32_t) k, d_idx, d_dists, overflow);
+			hipLaunchKernelGGL(bf_rescore_kernel<decltype(F)::value>, dim3((uint32_t) ((nq + 3) / 4)), dim3(256), g.lds_rescore(k), s, ix->vec, dim, ix->stride, g.nchunks,
+							   g.kiters, g.qpad, d_queries, (uint32_t) nq, cand, cnt, cap, (uint32_t) k, d_idx, d_dists, overflow);
 	});
 	HIPCHK(hipGetLastError());
 	uint32_t ovf = 0;
@@ -437,9 +452,14 @@ extern "C" int hnsw_gpu_bruteforce_reduced_dev(hnsw_gpu_index *ix, int format, c
 }
 
 // ------------------------------------------------------------------------------------
-// exact filtered k-NN: the canonical scan over the allowed rows only (device_filtered_knn.h)
+// exact filtered k-NN and exact radius search: ONE host path over the lists of allowed rows (device_filtered_knn.h),
+// with the Q x N part on the matrix cores for loose filters (device_filtered_knn_mfma.h; §4.11b) and each query through the form that
+// suits its own list in the automatic calls (device_fk_plan.h; §4.11c).  Filtered k-NN is the radius call with no radius and no totals.
 // ------------------------------------------------------------------------------------
 static const size_t FK_PART_BYTES = (size_t) 1 << 30;         // the partial lists of a call: more splits are not worth more memory than this
+enum { FK_LISTED = HNSW_GPU_RANGE_LISTED, FK_MFMA = HNSW_GPU_RANGE_MFMA };   // the form a caller asks for (the automatic calls: per query)
+static_assert(HNSW_GPU_RK_FORM_LISTED == HNSW_GPU_FK_FORM_LISTED && HNSW_GPU_RK_FORM_F32 == HNSW_GPU_FK_FORM_F32 && HNSW_GPU_RK_FORM_F16 == HNSW_GPU_FK_FORM_F16 &&
+			  HNSW_GPU_RK_FORM_BF16 == HNSW_GPU_FK_FORM_BF16, "one set of names for the form that answered");
 
 void fk_ws_free(FkWs *s)
 {
@@ -449,22 +469,29 @@ void fk_ws_free(FkWs *s)
 	for (hipEvent_t &e : s->ev) { if (e) (void) hipEventDestroy(e); e = nullptr; }
 }
 
-// the caller's contract, checked before anything is launched or copied (the outputs stay untouched)
-static int fk_check(hnsw_gpu_index *ix, const void *queries, size_t nq, size_t k, const void *allow, size_t allow_bits, size_t nfilters,
-					const void *labels, const void *counts)
+// what the two families of entry points differ in: their name in a message, what they require, and where their diagnostics go — the
+// figures of one are not touched by a call of the other
+struct FkFamily
 {
-	if (!ix) return fail(HNSW_GPU_ERR_ARG, "index is NULL");
-	if (nq == 0) return HNSW_GPU_OK;
-	if (!queries || !allow || !labels || !counts) return fail(HNSW_GPU_ERR_ARG, "filtered k-NN: NULL buffer (the filter is required: hnsw_gpu_bruteforce_dev takes none)");
-	if (k == 0 || k > 1024) return fail(HNSW_GPU_ERR_ARG, "k %zu out of range [1, 1024]", k);
-	if (nq > 65535) return fail(HNSW_GPU_ERR_ARG, "at most 65535 queries per call");
-	if (allow_bits == 0 || nfilters == 0) return fail(HNSW_GPU_ERR_ARG, "filtered k-NN: an allow filter of no bits");
-	if ((allow_bits + 31) / 32 >= 0xFFFFFFFFull || nfilters >= 0xFFFFFFFFull) return fail(HNSW_GPU_ERR_ARG, "filtered k-NN: allow filter too large");
-	const uint32_t kiters = (ix->stride / 4 + 15) / 16;
-	const size_t lds = round_up(kiters, 4) * 64 * 4 + (size_t) 4 * (k + 1) * 8 + 4 * 128 * 4 + 4 * 64 * 4;
-	if (lds > 64 * 1024) return fail(HNSW_GPU_ERR_ARG, "k/dim too large for filtered k-NN");
-	return HNSW_GPU_OK;
-}
+	const char *who; bool range;
+	FkWs::Diag FkWs::*diag;                                       // the pass that answered the last call (both classes of an automatic call)
+	FkWs::Diag FkWs::*filter;                                     // NULL, or: the last filter launch of the last call, whatever form answered in the end
+	FkWs::Plan FkWs::*plan;
+};
+static const FkFamily FK_KNN = { "filtered k-NN", false, &FkWs::k, &FkWs::kf, &FkWs::plan };
+static const FkFamily FK_RANGE = { "radius search", true, &FkWs::r, nullptr, &FkWs::rplan };
+
+// one call: its arguments (radius, totals: NULL in filtered k-NN), and what its list build found
+struct FkCall
+{
+	const FkFamily *fam;
+	hnsw_gpu_index *ix; const coord_t *queries; size_t nq; const dist_t *radius; size_t k; const uint32_t *allow; size_t allow_bits, nfilters;
+	const uint32_t *allow_of; label_t *labels; dist_t *dists; idx_t *idx; uint32_t *counts, *totals; hipStream_t s;
+	FkLists fl; uint64_t *off; unsigned long long *scored; size_t nsb, total, longest;
+	bool later;                                                   // a pass that follows another of the call: its scan time counts from ev[5], not from the list build
+};
+struct FkTrim { FkWs *w; ~FkTrim() { buf_trim({&w->cells, &w->list, &w->part, &w->mask, &w->bfs, &w->cand, &w->perm, &w->tmp}); } };   // on EVERY way out, errors included: no buffer above 64 MiB outlives its call
+
 // the matrix-core form's operands: the f32 rows, or the reduced copy the index holds (hnsw_gpu_bruteforce_reduced_dev's rule)
 static int fk_check_format(hnsw_gpu_index *ix, int format)
 {
@@ -473,17 +500,24 @@ static int fk_check_format(hnsw_gpu_index *ix, int format)
 		return fail(HNSW_GPU_ERR_ARG, "filtered k-NN: format %d is neither f32 nor the reduced copy this index holds (%d; hnsw_gpu_index_set_reduced_rows)", format, ix->rows_fmt);
 	return HNSW_GPU_OK;
 }
-
-// one call: its arguments, and what its list build found
-struct FkCall
+// the caller's contract, checked before anything is launched or copied (the outputs stay untouched).  Filtered k-NN requires the filter,
+// radius search the radii (its filter is optional: without one, allow_bits and nfilters are not looked at); the listed form ignores `format`
+static int fk_check(const FkCall &c, int form, int format)
 {
-	hnsw_gpu_index *ix; const coord_t *queries; size_t nq, k; const uint32_t *allow; size_t allow_bits, nfilters; const uint32_t *allow_of;
-	label_t *labels; dist_t *dists; idx_t *idx; uint32_t *counts; hipStream_t s;
-	FkLists fl; uint64_t *off; unsigned long long *scored; size_t nsb, total, longest;
-	const char *who;                                              // the call's name in a message; NULL: filtered k-NN
-};
-static const char *fk_who(const FkCall &c) { return c.who ? c.who : "filtered k-NN"; }
-struct FkTrim { FkWs *w; ~FkTrim() { buf_trim({&w->cells, &w->list, &w->part, &w->mask, &w->bfs, &w->cand, &w->perm, &w->tmp}); } };   // on EVERY way out, errors included: no buffer above 64 MiB outlives its call
+	const char *who = c.fam->who;
+	const bool range = c.fam->range, filter = c.allow || !range;
+	if (!c.ix) return fail(HNSW_GPU_ERR_ARG, "index is NULL");
+	if (c.nq == 0) return range || form == FK_LISTED ? HNSW_GPU_OK : fk_check_format(c.ix, format);
+	if (form != FK_LISTED && form != FK_MFMA) return fail(HNSW_GPU_ERR_ARG, "%s: form %d is neither listed (0) nor matrix cores (1)", who, form);
+	if (!c.queries || (range ? !c.radius : !c.allow) || !c.labels || !c.counts)
+		return fail(HNSW_GPU_ERR_ARG, "%s: NULL buffer%s", who, range ? "" : " (the filter is required: hnsw_gpu_bruteforce_dev takes none)");
+	if (c.k == 0 || c.k > 1024) return fail(HNSW_GPU_ERR_ARG, "k %zu out of range [1, 1024]", c.k);
+	if (c.nq > 65535) return fail(HNSW_GPU_ERR_ARG, "at most 65535 queries per call");
+	if (filter && (c.allow_bits == 0 || c.nfilters == 0)) return fail(HNSW_GPU_ERR_ARG, "%s: an allow filter of no bits", who);
+	if (filter && ((c.allow_bits + 31) / 32 >= 0xFFFFFFFFull || c.nfilters >= 0xFFFFFFFFull)) return fail(HNSW_GPU_ERR_ARG, "%s: allow filter too large", who);
+	if (QueryGeom(c.ix->stride).lds_listed(c.k) > 64 * 1024) return fail(HNSW_GPU_ERR_ARG, "k/dim too large for %s", who);
+	return form == FK_LISTED ? HNSW_GPU_OK : fk_check_format(c.ix, format);
+}
 
 static int fk_begin(FkCall &c)
 {
@@ -492,8 +526,11 @@ static int fk_begin(FkCall &c)
 	if (!fw->host) HIPCHK(hipHostMalloc((void **) &fw->host, 128, hipHostMallocDefault));
 	for (hipEvent_t &e : fw->ev)
 		if (!e) HIPCHK(hipEventCreate(&e));
-	fw->listed = fw->scored = 0; fw->build_ms = fw->scan_ms = 0.f;
-	fw->m = FkWs::Mfma();
+	FkWs::Diag &d = fw->*c.fam->diag;
+	const int form = d.form;
+	d = FkWs::Diag();
+	d.form = form;                                                // (the form that answered the last call that ended well)
+	if (c.fam->filter) fw->*c.fam->filter = FkWs::Diag();
 	return HNSW_GPU_OK;
 }
 
@@ -509,9 +546,9 @@ static int fk_lists(FkCall &c, const FkPlanHook *hook = nullptr)
 	const size_t n = ix->n, nfilters = c.nfilters;
 	const uint32_t nseg = (uint32_t) std::max<size_t>(1, (n + FK_SEG - 1) / FK_SEG);
 	const size_t ncells = (size_t) nseg * nfilters, nsb = (nseg + 3) / 4;
-	if (nsb * nfilters >= 0x7FFFFFFFull) return fail(HNSW_GPU_ERR_ARG, "%s: %zu filters over %zu rows are too many for one call", fk_who(c), nfilters, n);
+	if (nsb * nfilters >= 0x7FFFFFFFull) return fail(HNSW_GPU_ERR_ARG, "%s: %zu filters over %zu rows are too many for one call", c.fam->who, nfilters, n);
 	const size_t o_off = round_up(ncells * 4, 256), o_scored = o_off + round_up((ncells + 1) * 8, 256);
-	int rc = buf_reserve(&fw->cells, o_scored + 256, fk_who(c), "the list offsets");
+	int rc = buf_reserve(&fw->cells, o_scored + 256, c.fam->who, "the list offsets");
 	if (rc) return rc;
 	uint32_t *cells = (uint32_t *) fw->cells.p;
 	uint64_t *off = (uint64_t *) ((char *) fw->cells.p + o_off);
@@ -533,8 +570,8 @@ static int fk_lists(FkCall &c, const FkPlanHook *hook = nullptr)
 	HIPCHK(hipGetLastError());
 	HIPCHK(hipStreamSynchronize(s));                              // the one wait before the scan: the lists are sized exactly
 	const size_t total = fw->host[0], longest = fw->host[1];
-	if (longest > n || total > n * nfilters) return fail(HNSW_GPU_ERR_INTERNAL, "%s: %zu listed rows, longest list %zu, of %zu rows", fk_who(c), total, longest, n);
-	if ((rc = buf_reserve(&fw->list, total * 4, fk_who(c), "the lists of allowed rows"))) return rc;
+	if (longest > n || total > n * nfilters) return fail(HNSW_GPU_ERR_INTERNAL, "%s: %zu listed rows, longest list %zu, of %zu rows", c.fam->who, total, longest, n);
+	if ((rc = buf_reserve(&fw->list, total * 4, c.fam->who, "the lists of allowed rows"))) return rc;
 	if (total && c.allow) hipLaunchKernelGGL(fk_fill_kernel, dim3((uint32_t) (nsb * nfilters)), dim3(256), 0, s, fl, (const uint64_t *) off, (uint32_t *) fw->list.p);
 	else if (total) hipLaunchKernelGGL(rk_live_kernel<RK_LIVE_FILL>, dim3((uint32_t) nsb), dim3(256), 0, s, fl, (const uint64_t *) off, (uint32_t *) fw->list.p);
 	HIPCHK(hipMemsetAsync(scored, 0, 8, s));
@@ -543,25 +580,9 @@ static int fk_lists(FkCall &c, const FkPlanHook *hook = nullptr)
 	return HNSW_GPU_OK;
 }
 
-// what the scan and emit kernels of a call share (splits, the partial lists and the sample are the caller's)
-static FkEmit fk_kernel_args(const FkCall &c)
-{
-	hnsw_gpu_index *ix = c.ix;
-	const uint32_t nchunks = ix->stride / 4, kiters = (nchunks + 15) / 16;
-	FkEmit fe;
-	memset(&fe, 0, sizeof(fe));
-	FkScan &fs = fe.s;
-	fs.vec = ix->vec; fs.dim = (uint32_t) ix->meta.dim; fs.stride = ix->stride; fs.nchunks = nchunks; fs.kiters = kiters;
-	fs.qpad_floats = (uint32_t) round_up(kiters, 4) * 64;
-	fs.queries = c.queries; fs.nq = (uint32_t) c.nq; fs.k = (uint32_t) c.k;
-	fs.list = (const uint32_t *) ix->fk.list.p; fs.off = c.off; fs.nseg = c.fl.nseg; fs.allow_of = c.allow_of;
-	fs.scored = c.scored;
-	fe.labels = ix->labels; fe.n = (uint32_t) ix->n;
-	fe.out_labels = c.labels; fe.out_dists = c.dists; fe.out_idx = c.idx; fe.out_counts = c.counts;
-	return fe;
-}
-// Splits as the exhaustive scan chooses them, from the longest list a query scans (a query with a shorter one uses fewer waves: fk_waves),
-// and room for the partial lists.  (FK_XCD_REMAP variant builds: a list long enough for it gets at least one slice per XCD to keep apart.)
+// Splits as the exhaustive scan chooses them, from the longest run of list entries a query scans (a query with a shorter one uses fewer
+// waves: fk_waves), and room for the partial lists.  (FK_XCD_REMAP variant builds: a list long enough for it gets at least one slice per
+// XCD to keep apart.)
 static int fk_splits(const FkCall &c, size_t longest, uint32_t *out)
 {
 	hnsw_gpu_index *ix = c.ix;
@@ -571,87 +592,38 @@ static int fk_splits(const FkCall &c, size_t longest, uint32_t *out)
 	splits = (uint32_t) std::min<size_t>(splits, std::max<size_t>(1, longest / (4 * FK_WAVE_ROWS)));
 	while (splits > 1 && nq * splits * 4 * k * 8 > FK_PART_BYTES) splits /= 2;
 	*out = splits;
-	if (!longest) return HNSW_GPU_OK;                             // (no list, no scan: the emit kernel reads no partial list)
-	return buf_reserve(&ix->fk.part, nq * splits * 4 * k * 8, fk_who(c), "the partial result lists");
-}
-static void fk_scan_launch(const FkCall &c, const FkScan &fs)
-{
-	const size_t lds = (size_t) fs.qpad_floats * 4 + (size_t) 4 * (c.k + 1) * 8 + 4 * 128 * 4 + 4 * 64 * 4;
-	const dim3 grid((uint32_t) round_up((size_t) fs.splits * c.nq, 8));
-	with_func((int) c.ix->meta.dist_func, [&](auto F) { hipLaunchKernelGGL(fk_scan_kernel<decltype(F)::value>, grid, dim3(256), lds, c.s, fs); });
+	if (!longest) return HNSW_GPU_OK;                             // (no list, no scan: the merge kernel reads no partial list)
+	return buf_reserve(&ix->fk.part, nq * splits * 4 * k * 8, c.fam->who, "the partial result lists");
 }
 
-// 2. the listed scan over the whole lists, 3. merge + emit; `start`: the event the scan's time counts from
-static int fk_listed_scan(FkCall &c, hipEvent_t start)
-{
-	FkWs *fw = &c.ix->fk;
-	hipStream_t s = c.s;
-	uint32_t splits = 1;
-	int rc = fk_splits(c, c.longest, &splits);
-	if (rc) return rc;
-	FkEmit fe = fk_kernel_args(c);
-	fe.s.splits = splits; fe.s.part = (uint64_t *) fw->part.p;
-	if (c.longest) fk_scan_launch(c, fe.s);
-	hipLaunchKernelGGL(fk_emit_kernel, dim3((uint32_t) c.nq), dim3(64), c.k * 16, s, fe);
-	hipError_t e = hipGetLastError();
-	if (e == hipSuccess) e = hipEventRecord(fw->ev[2], s);
-	if (e == hipSuccess) e = hipMemcpyAsync(&fw->host[2], c.scored, 8, hipMemcpyDeviceToHost, s);
-	const hipError_t e2 = hipStreamSynchronize(s);
-	if (e == hipSuccess) e = e2;
-	if (e != hipSuccess) return fail(HNSW_GPU_ERR_HIP, "filtered k-NN: %s", hipGetErrorString(e));
-	fw->listed = c.total; fw->scored = fw->host[2];
-	(void) hipEventElapsedTime(&fw->build_ms, fw->ev[0], fw->ev[1]);
-	(void) hipEventElapsedTime(&fw->scan_ms, start, fw->ev[2]);
-	fw->form = HNSW_GPU_FK_FORM_LISTED;
-	return HNSW_GPU_OK;
-}
-
-static int fk_listed_call(FkCall &c)
-{
-	FkTrim trim_{&c.ix->fk};
-	int rc = fk_begin(c);
-	if (!rc) rc = fk_lists(c);
-	if (!rc) rc = fk_listed_scan(c, c.ix->fk.ev[1]);
-	return rc;
-}
-
-extern "C" int hnsw_gpu_filtered_knn_dev(hnsw_gpu_index *ix, const coord_t *d_queries, size_t nq, size_t k, const uint32_t *d_allow,
-										 size_t allow_bits, size_t nfilters, const uint32_t *d_allow_of, label_t *d_labels, dist_t *d_dists,
-										 idx_t *d_idx, uint32_t *d_counts, void *stream)
-{
-	std::unique_lock<std::recursive_mutex> lock_;
-	if (ix) lock_ = std::unique_lock<std::recursive_mutex>(ix->mu);
-	if (int rc0 = fk_check(ix, d_queries, nq, k, d_allow, allow_bits, nfilters, d_labels, d_counts)) return rc0;
-	if (nq == 0) return HNSW_GPU_OK;
-	FkCall c = { ix, d_queries, nq, k, d_allow, allow_bits, nfilters, d_allow_of, d_labels, d_dists, d_idx, d_counts, (hipStream_t) stream };
-	return fk_listed_call(c);
-}
-
-// ------------------------------------------------------------------------------------
-// exact filtered k-NN for loose filters: the Q x N part on the matrix cores, the allow test where a pair is appended
-// (device_filtered_knn_mfma.h)
-// ------------------------------------------------------------------------------------
-// One pass over the built lists and masks with the operands of `format`: sample scan -> bounds -> filter (or its stand-in) -> re-score ->
-// emit.  *ovf = candidate lists that overflowed (then the outputs are not the answer: the caller hands the call down).
-static int fk_mfma_pass(FkCall &c, int format, bool standin, uint32_t smin, uint32_t mwords, uint64_t *ovf)
+// One pass over the built lists (and masks).  format < 0: the listed form — the scan over every query's whole list, merge, emit.  Else
+// the matrix-core form with the operands of `format`: the scan over the lists no longer than their sample and (without totals) over the
+// samples of the others -> merge + bounds -> filter (or its stand-in) -> re-score -> emit.  *ovf = candidate lists that overflowed (then
+// the outputs are not the answer: the caller hands the call down).
+static int fk_pass(FkCall &c, int format, bool standin, uint32_t smin, uint32_t mwords, uint64_t *ovf)
 {
 	hnsw_gpu_index *ix = c.ix;
 	FkWs *fw = &ix->fk;
 	hipStream_t s = c.s;
-	const bool reduced = format != ROWS_F32;
+	const bool listed = format < 0, reduced = !listed && format != ROWS_F32, skip = !listed && c.totals;
 	const size_t nq = c.nq, k = c.k;
 	const int func = (int) ix->meta.dist_func;
-	const uint32_t n = (uint32_t) ix->n, stride = ix->stride, dim = (uint32_t) ix->meta.dim;
-	const uint32_t nchunks = stride / 4, kiters = (nchunks + 15) / 16;
-	const uint32_t qpadf = (uint32_t) round_up(kiters, 4) * 64;
-	const size_t wave_bytes = round_up((size_t) qpadf * 4 + (k + 1) * 8 + 128 * 4, 16);
-	int rc = bf_rows_side(ix, reduced, s);
+	const uint32_t dim = (uint32_t) ix->meta.dim;
+	const QueryGeom g(ix->stride);
+	int rc = listed ? HNSW_GPU_OK : bf_rows_side(ix, reduced, s);
 	if (rc) return rc;
-	const uint32_t qchunks = reduced ? ix->rows16_bytes / 16 : (uint32_t) round_up(stride, BF_TK) / 4;
-	const uint32_t rchunks = reduced ? ix->rows16_bytes / 16 : nchunks;
+	const uint32_t qchunks = listed ? 0 : bf_qchunks(ix, reduced);
 	const uint32_t cap = 16384;
+	// the longest run of list entries a query scans: its whole list, its sample, or (totals) a list no longer than its sample
+	const size_t slongest = listed ? c.longest : skip ? std::min<size_t>(c.longest, smin) : fk_sample_len((uint32_t) c.longest, smin, (uint32_t) k);
+	uint32_t splits = 1;
+	if ((rc = fk_splits(c, slongest, &splits))) return rc;
 	// scratch carve
-	const size_t o_q = 0;
+	const size_t o_keys = 0;
+	const size_t o_rcnt = o_keys + round_up(nq * k * 8, 256);
+	const size_t o_pcnt = o_rcnt + round_up(nq * 4, 256);
+	const size_t o_sum = o_pcnt + round_up(nq * (size_t) splits * 16, 256);
+	const size_t o_q = o_sum + 256;
 	const size_t o_qn = o_q + round_up(nq * (size_t) qchunks * 16, 256);
 	const size_t o_qt = o_qn + round_up(nq * 4, 256);
 	const size_t o_tau = o_qt + round_up(nq * 8, 256);
@@ -659,84 +631,83 @@ static int fk_mfma_pass(FkCall &c, int format, bool standin, uint32_t smin, uint
 	const size_t o_mof = o_bound + round_up(nq * 4, 256);
 	const size_t o_cnt = o_mof + round_up(nq * 4, 256);
 	const size_t o_fcnt = o_cnt + round_up(nq * 4 + 64, 256);
-	const size_t o_ridx = o_fcnt + 256;
-	const size_t o_rdist = o_ridx + round_up(nq * k * 4, 256);
-	const size_t o_keys = o_rdist + round_up(nq * k * 4, 256);
-	const size_t total = o_keys + round_up(nq * k * 8, 256);
-	if ((rc = buf_reserve(&fw->bfs, total, "filtered k-NN", "the filter's scratch"))) return rc;
-	if ((rc = buf_reserve(&fw->cand, nq * (size_t) cap * 4, "filtered k-NN", "the candidate lists"))) return rc;
+	const size_t total = o_fcnt + 256;
+	if ((rc = buf_reserve(&fw->bfs, total, c.fam->who, "the per-query scratch"))) return rc;
+	if (!listed && (rc = buf_reserve(&fw->cand, nq * (size_t) cap * 4, c.fam->who, "the candidate lists"))) return rc;
 	char *B = (char *) fw->bfs.p;
-	uint4 *qcopy = (uint4 *) (B + o_q);
-	float *qn = (float *) (B + o_qn), *tau = (float *) (B + o_tau), *bound = (float *) (B + o_bound), *rdist = (float *) (B + o_rdist);
-	float2 *qterms = (float2 *) (B + o_qt);
-	uint32_t *mask_of = (uint32_t *) (B + o_mof), *cnt = (uint32_t *) (B + o_cnt), *ridx = (uint32_t *) (B + o_ridx), *cand = (uint32_t *) fw->cand.p;
-	uint32_t *overflow = cnt + nq;
-	unsigned long long *fcnt = (unsigned long long *) (B + o_fcnt);
 	uint64_t *keys = (uint64_t *) (B + o_keys);
+	uint32_t *rcount = (uint32_t *) (B + o_rcnt), *pcount = (uint32_t *) (B + o_pcnt);
+	unsigned long long *sum = c.radius ? (unsigned long long *) (B + o_sum) : nullptr, *fcnt = (unsigned long long *) (B + o_fcnt);
+	uint4 *qcopy = (uint4 *) (B + o_q);
+	float *qn = (float *) (B + o_qn), *tau = (float *) (B + o_tau), *bound = (float *) (B + o_bound);
+	float2 *qterms = (float2 *) (B + o_qt);
+	uint32_t *mask_of = (uint32_t *) (B + o_mof), *cnt = (uint32_t *) (B + o_cnt), *cand = (uint32_t *) fw->cand.p;
+	uint32_t *overflow = cnt + nq;
 
-	// 3. the sample scan: the listed scan core over the first S(b) entries of every query's list, then tau_q, the sample's keys and the mask rows
-	const uint32_t slongest = fk_sample_len((uint32_t) c.longest, smin, (uint32_t) k);
-	uint32_t splits = 1;
-	if ((rc = fk_splits(c, slongest, &splits))) return rc;
-	FkEmit fe = fk_kernel_args(c);
-	FkmBounds fb;
-	memset(&fb, 0, sizeof(fb));
-	fb.s = fe.s;
-	fb.s.splits = splits; fb.s.part = (uint64_t *) fw->part.p; fb.s.smin = smin;
-	fb.nfilters = (uint32_t) c.nfilters; fb.keys = keys; fb.tau = tau; fb.mask_of = mask_of;
-	HIPCHK(hipMemsetAsync(c.scored, 0, 8, s));
-	fk_scan_launch(c, fb.s);
-	hipLaunchKernelGGL(fkm_bounds_kernel, dim3((uint32_t) nq), dim3(64), k * 8, s, fb);
-	bf_queries_side(reduced, format, c.queries, nq, dim, qchunks, qcopy, qn, qterms, s);
-	hipLaunchKernelGGL(make_bounds_kernel, dim3((uint32_t) ((nq + 255) / 256)), dim3(256), 0, s, (const float *) tau, qn, (uint32_t) nq, func, dim, bound);
-	HIPCHK(hipMemsetAsync(cnt, 0, nq * 4 + 64, s));               // (the candidate counts and the overflow word behind them)
-	HIPCHK(hipMemsetAsync(fcnt, 0, 16, s));
-
-	// 4. the filter over all rows, the allow test at its append
-	BfArgs a;
-	memset(&a, 0, sizeof(a));
-	a.queries = qcopy; a.qnorm = qn; a.qbound = bound; a.qterms = qterms;
-	a.rows = reduced ? (const uint4 *) ix->rows16 : (const uint4 *) ix->vec; a.xnorm = ix->xnorm; a.xterms = ix->r16x;
-	a.nq = (uint32_t) nq; a.n = n; a.qchunks = qchunks; a.rchunks = rchunks; a.ksteps = qchunks / BF_CH; a.func = func;
-	a.xscale = 0.5f * (1.f - 2.f * ((float) dim + 32.f) * 0x1p-24f);          // (1 - eD) / 2: make_bounds_kernel
-	a.eabs = r16_abs_term(dim);
-	a.cand = cand; a.cand_cnt = cnt; a.cap = cap;
-	a.mask = (const uint32_t *) fw->mask.p; a.mask_of = mask_of; a.mwords = mwords; a.fcnt = fcnt;
-	HIPCHK(hipEventRecord(fw->ev[3], s));
-	if (standin)
+	// the scan, then per query: its keys, its count of qualifying rows and (matrix-core form) its bound and mask row
+	FkMerge fm;
+	memset(&fm, 0, sizeof(fm));
+	FkScan &fs = fm.s;
+	fs.vec = ix->vec; fs.dim = dim; fs.stride = ix->stride; fs.nchunks = g.nchunks; fs.kiters = g.kiters; fs.qpad_floats = g.qpad;
+	fs.queries = c.queries; fs.nq = (uint32_t) nq; fs.k = (uint32_t) k; fs.splits = splits;
+	fs.list = (const uint32_t *) fw->list.p; fs.off = c.off; fs.nseg = c.fl.nseg; fs.allow_of = c.allow_of;
+	fs.part = (uint64_t *) fw->part.p; fs.pcount = pcount; fs.scored = c.scored; fs.smin = listed ? 0u : smin; fs.skip_samples = skip ? 1u : 0u;
+	fs.radius = c.radius; fs.func = func;
+	fm.nfilters = (uint32_t) c.nfilters; fm.keys = keys; fm.count = rcount; fm.tau = listed ? nullptr : tau; fm.mask_of = mask_of;
+	if (sum) HIPCHK(hipMemsetAsync(sum, 0, 8, s));
+	if (slongest)
+	{
+		const dim3 grid((uint32_t) round_up((size_t) splits * nq, 8));
+		with_func(func, [&](auto F) { hipLaunchKernelGGL(fk_scan_kernel<decltype(F)::value>, grid, dim3(256), g.lds_listed(k), s, fs); });
+	}
+	hipLaunchKernelGGL(fk_merge_kernel, dim3((uint32_t) nq), dim3(64), k * 8, s, fm);
+	if (!listed)
+	{
+		bf_queries_side(reduced, format, c.queries, nq, dim, qchunks, qcopy, qn, qterms, s);
+		hipLaunchKernelGGL(make_bounds_kernel, dim3((uint32_t) ((nq + 255) / 256)), dim3(256), 0, s, (const float *) tau, qn, (uint32_t) nq, func, dim, bound);
+		HIPCHK(hipMemsetAsync(cnt, 0, nq * 4 + 64, s));               // (the candidate counts and the overflow word behind them)
+		HIPCHK(hipMemsetAsync(fcnt, 0, 16, s));
+		// the filter over all rows, the allow test (the mask of allowed, or of live, rows) at its append
+		BfArgs a = bf_args(ix, reduced, nq, qcopy, qn, bound, qterms, cand, cnt, cap);
+		a.mask = (const uint32_t *) fw->mask.p; a.mask_of = mask_of; a.mwords = mwords; a.fcnt = fcnt;
+		HIPCHK(hipEventRecord(fw->ev[3], s));
+		if (standin)
+			with_func(func, [&](auto F) {
+				hipLaunchKernelGGL(fkm_standin_kernel<decltype(F)::value>, dim3((uint32_t) nq), dim3(256), g.lds_dist(), s, a, ix->vec, dim, ix->stride, g.nchunks,
+								   g.kiters, g.qpad, c.queries, (const float *) tau);
+			});
+		else if ((rc = with_form(format, [&](auto p) { return bf_filter_pick<BfAllow<decltype(p)>>(ix, a, s); })))
+			return rc;
+		HIPCHK(hipEventRecord(fw->ev[4], s));
 		with_func(func, [&](auto F) {
-			hipLaunchKernelGGL(fkm_standin_kernel<decltype(F)::value>, dim3((uint32_t) nq), dim3(256), (size_t) qpadf * 4 + 4 * 128 * 4, s, a, ix->vec, dim, stride,
-							   nchunks, kiters, qpadf, c.queries, (const float *) tau);
+			if constexpr (decltype(F)::value != F_MANHATTAN)           // (answered by the listed form: no re-score kernel is compiled for it)
+				hipLaunchKernelGGL(fkm_rescore_kernel<decltype(F)::value>, dim3((uint32_t) ((nq + 3) / 4)), dim3(256), g.lds_rescore(k), s, ix->vec, dim, ix->stride,
+								   g.nchunks, g.kiters, g.qpad, c.queries, (uint32_t) nq, c.radius, (const uint32_t *) mask_of, (uint32_t) c.nfilters,
+								   (const uint32_t *) cand, (const uint32_t *) cnt, cap, (uint32_t) k, keys, rcount, overflow);
 		});
-	else if ((rc = with_form(format, [&](auto p) { return bf_filter_pick<BfAllow<decltype(p)>>(ix, a, s); })))
-		return rc;
-	HIPCHK(hipEventRecord(fw->ev[4], s));
-
-	// 5. canonical re-score of the candidates, 6. one key list per query -> emit
-	with_func(func, [&](auto F) {
-		if constexpr (decltype(F)::value != F_MANHATTAN)           // (answered by the listed form: no re-score kernel is compiled for it)
-			hipLaunchKernelGGL(bf_rescore_kernel<decltype(F)::value>, dim3((uint32_t) ((nq + 3) / 4)), dim3(256), wave_bytes * 4, s, ix->vec, dim, stride, nchunks,
-							   kiters, qpadf, c.queries, (uint32_t) nq, cand, cnt, cap, (uint32_t) k, ridx, rdist, overflow);
-	});
-	hipLaunchKernelGGL(fkm_keys_kernel, dim3((uint32_t) ((nq * k + 255) / 256)), dim3(256), 0, s, (const uint32_t *) ridx, (const float *) rdist,
-					   (const uint32_t *) mask_of, (uint32_t) c.nfilters, (uint32_t) nq, (uint32_t) k, keys);
-	fe.single = keys;
+	}
+	// one key list and one count per query -> labels, order, counts, tails, totals
+	const FkEmit fe = { keys, rcount, (uint32_t) k, ix->labels, (uint32_t) ix->n, c.labels, c.dists, c.idx, c.counts, c.totals, sum };
 	hipLaunchKernelGGL(fk_emit_kernel, dim3((uint32_t) nq), dim3(64), k * 16, s, fe);
 	hipError_t e = hipGetLastError();
 	if (e == hipSuccess) e = hipEventRecord(fw->ev[2], s);
-	fw->host[5] = 0;
+	fw->host[3] = fw->host[4] = fw->host[5] = fw->host[6] = 0;
 	if (e == hipSuccess) e = hipMemcpyAsync(&fw->host[2], c.scored, 8, hipMemcpyDeviceToHost, s);
-	if (e == hipSuccess) e = hipMemcpyAsync(&fw->host[3], fcnt, 16, hipMemcpyDeviceToHost, s);
-	if (e == hipSuccess) e = hipMemcpyAsync(&fw->host[5], overflow, 4, hipMemcpyDeviceToHost, s);
+	if (e == hipSuccess && sum) e = hipMemcpyAsync(&fw->host[6], sum, 8, hipMemcpyDeviceToHost, s);
+	if (e == hipSuccess && !listed) e = hipMemcpyAsync(&fw->host[3], fcnt, 16, hipMemcpyDeviceToHost, s);
+	if (e == hipSuccess && !listed) e = hipMemcpyAsync(&fw->host[5], overflow, 4, hipMemcpyDeviceToHost, s);
 	const hipError_t e2 = hipStreamSynchronize(s);
 	if (e == hipSuccess) e = e2;
-	if (e != hipSuccess) return fail(HNSW_GPU_ERR_HIP, "filtered k-NN: %s", hipGetErrorString(e));
+	if (e != hipSuccess) return fail(HNSW_GPU_ERR_HIP, "%s: %s", c.fam->who, hipGetErrorString(e));
 	*ovf = fw->host[5];
-	FkWs::Mfma &m = fw->m;
-	m.listed = c.total; m.scored = fw->host[2]; m.dist_pass = fw->host[3]; m.appended = fw->host[4];
+	FkWs::Diag &m = fw->*c.fam->diag;
+	m.listed = c.total; m.scored = fw->host[2]; m.dist_pass = fw->host[3]; m.appended = fw->host[4]; m.totals = fw->host[6];
+	m.filter_ms = 0.f;
 	(void) hipEventElapsedTime(&m.build_ms, fw->ev[0], fw->ev[1]);
-	(void) hipEventElapsedTime(&m.filter_ms, fw->ev[3], fw->ev[4]);
+	if (!listed) (void) hipEventElapsedTime(&m.filter_ms, fw->ev[3], fw->ev[4]);
 	(void) hipEventElapsedTime(&m.call_ms, fw->ev[0], fw->ev[2]);
+	(void) hipEventElapsedTime(&m.scan_ms, fw->ev[c.later ? 5 : 1], fw->ev[2]);
+	if (!listed && c.fam->filter) fw->*c.fam->filter = m;
 	return HNSW_GPU_OK;
 }
 
@@ -747,16 +718,24 @@ static int fk_mfma_pass(FkCall &c, int format, bool standin, uint32_t smin, uint
 static bool fk_have_mfma(hnsw_gpu_index *ix, size_t k, bool *standin)
 {
 	*standin = knob(K_FK_MFMA_STANDIN, 0) != 0;
-	const uint32_t kiters = (ix->stride / 4 + 15) / 16;
-	const size_t wave_bytes = round_up(round_up(kiters, 4) * 64 * 4 + (k + 1) * 8 + 128 * 4, 16);
 #ifdef PGEMB_SIMT_EMULATOR
 	const bool have_filter = false;
 #else
 	const bool have_filter = ix->n >= 4096 && ix->gfx950 && ix->max_lds >= BF_MIN_LDS;
 #endif
-	return (int) ix->meta.dist_func != F_MANHATTAN && wave_bytes * 4 <= 64 * 1024 && (*standin || have_filter);
+	return (int) ix->meta.dist_func != F_MANHATTAN && QueryGeom(ix->stride).lds_rescore(k) <= 64 * 1024 && (*standin || have_filter);
 }
 static uint32_t fk_sample_min() { return (uint32_t) std::min<long long>(0xFFFFFFFFll, std::max<long long>(1, knob(K_FK_SAMPLE_MIN, FKM_SAMPLE_MIN))); }
+// the matrix-core pass a call may take: whether it has one, with the filter or its stand-in, its operands and S_min
+struct FkMfma { bool avail, standin; int format; uint32_t smin; };
+static FkMfma fk_mfma_of(hnsw_gpu_index *ix, int format, size_t k)
+{
+	FkMfma m;
+	m.avail = fk_have_mfma(ix, k, &m.standin);
+	m.format = m.standin ? ROWS_F32 : format;
+	m.smin = fk_sample_min();
+	return m;
+}
 
 // 2. the row masks (counted with the list build), and a row of zeros behind them
 static int fk_masks(FkCall &c, uint32_t *mwords_out)
@@ -764,7 +743,7 @@ static int fk_masks(FkCall &c, uint32_t *mwords_out)
 	FkWs *fw = &c.ix->fk;
 	const size_t nfilters = c.nfilters;
 	const uint32_t mwords = fkm_mask_words((uint32_t) c.ix->n);
-	int rc = buf_reserve(&fw->mask, (nfilters + 1) * (size_t) mwords * 4, fk_who(c), "the row masks");
+	int rc = buf_reserve(&fw->mask, (nfilters + 1) * (size_t) mwords * 4, c.fam->who, "the row masks");
 	if (rc) return rc;
 	if (c.allow) hipLaunchKernelGGL(fkm_mask_kernel, dim3((uint32_t) (c.nsb * nfilters)), dim3(256), 0, c.s, c.fl, mwords, (uint32_t *) fw->mask.p);
 	else hipLaunchKernelGGL(rk_live_kernel<RK_LIVE_MASK>, dim3((uint32_t) c.nsb), dim3(256), 0, c.s, c.fl, (const uint64_t *) nullptr, (uint32_t *) fw->mask.p);
@@ -774,66 +753,43 @@ static int fk_masks(FkCall &c, uint32_t *mwords_out)
 	return HNSW_GPU_OK;
 }
 
-// The passes of one call (or of one class of an automatic call) over the built lists and masks: a candidate list that overflows sends a
-// 16-bit call to the f32 operands (its bound is looser: a list that overflowed there may not in f32), and an f32 call to the listed scan
-static int fk_mfma_chain(FkCall &c, int format, bool standin, uint32_t smin, uint32_t mwords)
+// Before a pass that follows another of the call: the rows-scored word, which the list build cleared for the first one, is cleared again;
+// timed: the pass's scan time counts from here (a listed pass behind a filter; a 16-bit pass handed to f32 keeps counting from the build)
+static int fk_again(FkCall &c, bool timed)
+{
+	HIPCHK(hipMemsetAsync(c.scored, 0, 8, c.s));
+	if (!timed) return HNSW_GPU_OK;
+	HIPCHK(hipEventRecord(c.ix->fk.ev[5], c.s));
+	c.later = true;
+	return HNSW_GPU_OK;
+}
+
+// The passes of one call (or of one class of an automatic call) over the built lists (and masks): a candidate list that overflows sends a
+// 16-bit pass to the f32 operands (its bound is looser: a list that overflowed there may not in f32) and an f32 pass to the listed form,
+// for all its queries.  pass: the first one (< 0: the listed form)
+static int fk_chain(FkCall &c, int pass, bool standin, uint32_t smin, uint32_t mwords)
 {
 	FkWs *fw = &c.ix->fk;
 	for (;;)
 	{
 		uint64_t ovf = 0;
-		if (int rc = fk_mfma_pass(c, format, standin, smin, mwords, &ovf)) return rc;
+		if (int rc = fk_pass(c, pass, standin, smin, mwords, &ovf)) return rc;
 		if (!ovf) break;
-		if (format == ROWS_F32)
-		{
-			HIPCHK(hipEventRecord(fw->ev[5], c.s));
-			HIPCHK(hipMemsetAsync(c.scored, 0, 8, c.s));
-			return fk_listed_scan(c, fw->ev[5]);
-		}
-		format = ROWS_F32;
+		pass = pass == ROWS_F32 ? -1 : ROWS_F32;
+		if (int rc = fk_again(c, pass < 0)) return rc;
 	}
-	fw->listed = fw->m.listed; fw->scored = fw->m.scored; fw->build_ms = fw->m.build_ms; fw->scan_ms = fw->m.call_ms - fw->m.build_ms;
-	fw->form = format == ROWS_F32 ? HNSW_GPU_FK_FORM_F32 : format == ROWS_BF16 ? HNSW_GPU_FK_FORM_BF16 : HNSW_GPU_FK_FORM_F16;
+	(fw->*c.fam->diag).form = pass < 0 ? HNSW_GPU_FK_FORM_LISTED : pass == ROWS_F32 ? HNSW_GPU_FK_FORM_F32 : pass == ROWS_BF16 ? HNSW_GPU_FK_FORM_BF16 : HNSW_GPU_FK_FORM_F16;
 	return HNSW_GPU_OK;
 }
 
-extern "C" int hnsw_gpu_filtered_knn_mfma_dev(hnsw_gpu_index *ix, int format, const coord_t *d_queries, size_t nq, size_t k, const uint32_t *d_allow,
-											  size_t allow_bits, size_t nfilters, const uint32_t *d_allow_of, label_t *d_labels, dist_t *d_dists,
-											  idx_t *d_idx, uint32_t *d_counts, void *stream)
-{
-	std::unique_lock<std::recursive_mutex> lock_;
-	if (ix) lock_ = std::unique_lock<std::recursive_mutex>(ix->mu);
-	if (int rc0 = fk_check(ix, d_queries, nq, k, d_allow, allow_bits, nfilters, d_labels, d_counts)) return rc0;
-	if (int rc0 = fk_check_format(ix, format)) return rc0;
-	if (nq == 0) return HNSW_GPU_OK;
-	FkCall c = { ix, d_queries, nq, k, d_allow, allow_bits, nfilters, d_allow_of, d_labels, d_dists, d_idx, d_counts, (hipStream_t) stream };
-	bool standin = false;
-	if (!fk_have_mfma(ix, k, &standin)) return fk_listed_call(c);
-	if (standin) format = ROWS_F32;
-
-	FkWs *fw = &ix->fk;
-	FkTrim trim_{fw};
-	int rc = fk_begin(c);
-	if (!rc) rc = fk_lists(c);
-	if (rc) return rc;
-	// a list no longer than S_min is its own sample: with no longer list in the call, every query is answered by the listed scan
-	const uint32_t smin = fk_sample_min();
-	if (c.longest <= smin) return fk_listed_scan(c, fw->ev[1]);
-	uint32_t mwords = 0;
-	if ((rc = fk_masks(c, &mwords))) return rc;
-	return fk_mfma_chain(c, format, standin, smin, mwords);
-}
-
-// ------------------------------------------------------------------------------------
-// the automatic calls: each query through the form that suits its own list (device_fk_plan.h)
-// ------------------------------------------------------------------------------------
+// ---- the automatic calls: each query through the form that suits its own list (device_fk_plan.h) -----------------------------
 // The cost model, in ONE place.  In µs, for a call (or class) of nq queries with ΣL_q = rows and the longest list L_max:
 //     t_listed   = max(a * rows * row_bytes, c * L_max * row_bytes / w) + m * (w k)^2
 //                  a * row_bytes = row_fix_us + row_byte_us * row_bytes            per listed row at full occupancy (the throughput term)
 //                  c * row_bytes = wave_row_fix_us + wave_row_byte_us * row_bytes  per row of ONE wave; w = the waves that share the longest
 //                                                                                  list (fk_splits, fk_waves): few long lists in a large
 //                                                                                  batch are bound by their own chains, not by bandwidth
-//                  m = merge_key2_us                                               the emit kernel's one-wave merge of w lists of k keys
+//                  m = merge_key2_us                                               the merge kernel's one-wave merge of w lists of k keys
 //     t_mfma(p)  = b0 + b1 * p     b0 = fixed_us + n * operand_row_bytes / bytes_per_us + m * (w_s k)^2   (w_s: the waves of a sample scan)
 //                                  b1 = a * S_min * row_bytes + n * (pair_fix_us + pair_dim_us * dim)     (sample scan + filter)
 // The constants are fits of measurements on MI355X over 1M rows of 128 and 768 dimensions, f32 and f16 operands, 1 to 1 024 queries
@@ -867,41 +823,38 @@ static void fk_cost_mfma_us(const hnsw_gpu_index *ix, int format, uint32_t smin,
 	*b1 = fk_cost_row_us(ix) * (double) std::min<size_t>(smin, ix->n) + n * (f.pair_fix_us + f.pair_dim_us * (double) ix->meta.dim);
 }
 
-// what the plan of one call settled, from the words its kernel left in the pinned block
+// the plan of an automatic call: its threshold, and what its kernel settled, from the words it left in the pinned block
 struct FkAuto
 {
-	bool avail, standin, forced; int format; uint32_t smin; uint64_t thresh; double b0, b1;
+	bool forced; uint64_t thresh; double b0, b1;
 	size_t loose, rows[2], longest[2];                            // queries above the threshold; ΣL_q and the longest list of [0] the others, [1] those
 	bool split;                                                   // a loose class runs
 };
 // before the list build: the threshold in rows.  No pass of the matrix-core form for this call: no query is loose
-static void fk_auto_begin(hnsw_gpu_index *ix, int format, size_t k, FkAuto *a)
+static void fk_auto_begin(hnsw_gpu_index *ix, const FkMfma &m, FkAuto *a)
 {
 	memset(a, 0, sizeof(*a));
-	a->avail = fk_have_mfma(ix, k, &a->standin);
-	a->format = a->standin ? ROWS_F32 : format;
-	a->smin = fk_sample_min();
-	fk_cost_mfma_us(ix, a->format, a->smin, &a->b0, &a->b1);
+	fk_cost_mfma_us(ix, m.format, m.smin, &a->b0, &a->b1);
 	const long long forced = knob(K_FK_AUTO_SPLIT, -1);
 	a->forced = forced >= 0;
-	a->thresh = !a->avail ? ~0ull : a->forced ? (uint64_t) forced : (uint64_t) (a->b1 / fk_cost_row_us(ix));
+	a->thresh = !m.avail ? ~0ull : a->forced ? (uint64_t) forced : (uint64_t) (a->b1 / fk_cost_row_us(ix));
 }
 // after the list build's wait: the class-level test, the plan's record, and plan[] where the loose class was not accepted
-static int fk_auto_settle(FkCall &c, FkAuto *a, uint8_t *d_plan, FkWs::Plan *pl)
+static int fk_auto_settle(FkCall &c, const FkMfma &m, FkAuto *a, uint8_t *d_plan, FkWs::Plan *pl)
 {
 	FkWs *fw = &c.ix->fk;
 	a->loose = fw->host[8]; a->rows[0] = fw->host[9]; a->rows[1] = fw->host[10]; a->longest[0] = fw->host[11]; a->longest[1] = fw->host[12];
 	if (a->loose > c.nq || a->longest[0] > c.longest || a->longest[1] > c.longest)
-		return fail(HNSW_GPU_ERR_INTERNAL, "%s: a plan of %zu loose queries of %zu, longest lists %zu and %zu of %zu", fk_who(c), a->loose, c.nq, a->longest[0], a->longest[1], c.longest);
+		return fail(HNSW_GPU_ERR_INTERNAL, "%s: a plan of %zu loose queries of %zu, longest lists %zu and %zu of %zu", c.fam->who, a->loose, c.nq, a->longest[0], a->longest[1], c.longest);
 	*pl = FkWs::Plan();
 	pl->thresh = a->thresh;
 	// what the listed form would cost MORE with the queries above the threshold in it, against one pass over the table for those
-	const double ws = fk_cost_waves(c.ix, a->loose, fk_sample_len((uint32_t) a->longest[1], a->smin, (uint32_t) c.k));
+	const double ws = fk_cost_waves(c.ix, a->loose, fk_sample_len((uint32_t) a->longest[1], m.smin, (uint32_t) c.k));
 	pl->est_listed_us = (uint64_t) std::llround(std::max(0.0, fk_cost_listed_us(c.ix, c.nq, c.k, a->rows[0] + a->rows[1], c.longest) -
 															  fk_cost_listed_us(c.ix, c.nq - a->loose, c.k, a->rows[0], a->longest[0])));
 	pl->est_mfma_us = (uint64_t) std::llround(a->b0 + FK_COST.merge_key2_us * (ws * (double) c.k) * (ws * (double) c.k) + a->b1 * (double) a->loose);
 	// a loose class whose every list is its own sample would be answered by the sample scan: the listed form's work, with a filter on top
-	a->split = a->avail && a->loose && a->longest[1] > a->smin && (a->forced || pl->est_listed_us > pl->est_mfma_us);
+	a->split = m.avail && a->loose && a->longest[1] > m.smin && (a->forced || pl->est_listed_us > pl->est_mfma_us);
 	if (!a->split && a->loose && d_plan) HIPCHK(hipMemsetAsync(d_plan, 0, c.nq, c.s));
 	const size_t p = a->split ? a->loose : 0;
 	pl->nq[0] = c.nq - p; pl->nq[1] = p;
@@ -913,19 +866,19 @@ static int fk_auto_settle(FkCall &c, FkAuto *a, uint8_t *d_plan, FkWs::Plan *pl)
 // The compacted inputs and outputs of a call with two classes, all in perm[] order: position i of each array is query perm[i], so a class is
 // a contiguous run — the listed class positions [0, nq - p), the loose class the rest
 struct FkTmp { float *q; uint32_t *aof; float *radius; uint64_t *labels; float *dists; uint32_t *idx, *counts, *totals; };
-static int fk_auto_gather(FkCall &c, const dist_t *radius, bool totals, FkTmp *t)
+static int fk_auto_gather(FkCall &c, FkTmp *t)
 {
 	FkWs *fw = &c.ix->fk;
 	const size_t nq = c.nq, k = c.k, dim = c.ix->meta.dim;
 	const size_t o_aof = round_up(nq * dim * 4, 256), o_rad = o_aof + round_up(nq * 4, 256), o_lab = o_rad + round_up(nq * 4, 256),
 				 o_dst = o_lab + round_up(nq * k * 8, 256), o_idx = o_dst + round_up(nq * k * 4, 256), o_cnt = o_idx + round_up(nq * k * 4, 256),
 				 o_tot = o_cnt + round_up(nq * 4, 256), bytes = o_tot + round_up(nq * 4, 256);
-	if (int rc = buf_reserve(&fw->tmp, bytes, fk_who(c), "the classes' compacted queries and results")) return rc;
+	if (int rc = buf_reserve(&fw->tmp, bytes, c.fam->who, "the classes' compacted queries and results")) return rc;
 	char *B = (char *) fw->tmp.p;
-	t->q = (float *) B; t->aof = c.allow_of ? (uint32_t *) (B + o_aof) : nullptr; t->radius = radius ? (float *) (B + o_rad) : nullptr;
+	t->q = (float *) B; t->aof = c.allow_of ? (uint32_t *) (B + o_aof) : nullptr; t->radius = c.radius ? (float *) (B + o_rad) : nullptr;
 	t->labels = (uint64_t *) (B + o_lab); t->dists = c.dists ? (float *) (B + o_dst) : nullptr; t->idx = c.idx ? (uint32_t *) (B + o_idx) : nullptr;
-	t->counts = (uint32_t *) (B + o_cnt); t->totals = totals ? (uint32_t *) (B + o_tot) : nullptr;
-	FkGather g = { (const uint32_t *) fw->perm.p, 0u, (uint32_t) nq, c.queries, (uint32_t) dim, t->q, c.allow_of, t->aof, radius, t->radius,
+	t->counts = (uint32_t *) (B + o_cnt); t->totals = c.totals ? (uint32_t *) (B + o_tot) : nullptr;
+	FkGather g = { (const uint32_t *) fw->perm.p, 0u, (uint32_t) nq, c.queries, (uint32_t) dim, t->q, c.allow_of, t->aof, c.radius, t->radius,
 				   (dim % 4 == 0 && (uintptr_t) c.queries % 16 == 0) ? 1u : 0u };
 	const size_t chunks = nq * (g.vec4 ? dim / 4 : dim);            // (both classes in one launch: each is a run of positions)
 	hipLaunchKernelGGL(fkp_gather_kernel, dim3((uint32_t) ((chunks + 255) / 256)), dim3(256), 0, c.s, g);
@@ -937,114 +890,153 @@ static FkCall fk_auto_class(const FkCall &c, const FkTmp &t, size_t first, size_
 {
 	FkCall s = c;
 	const size_t dim = c.ix->meta.dim;
-	s.queries = t.q + first * dim; s.nq = count; s.allow_of = t.aof ? t.aof + first : nullptr;
+	s.queries = t.q + first * dim; s.nq = count; s.allow_of = t.aof ? t.aof + first : nullptr; s.radius = t.radius ? t.radius + first : nullptr;
 	s.labels = t.labels + first * c.k; s.dists = t.dists ? t.dists + first * c.k : nullptr; s.idx = t.idx ? t.idx + first * c.k : nullptr;
-	s.counts = t.counts + first; s.longest = longest;
+	s.counts = t.counts + first; s.totals = t.totals ? t.totals + first : nullptr; s.longest = longest;
 	return s;
 }
-static int fk_auto_scatter(const FkCall &c, const FkTmp &t, size_t first, size_t count, uint32_t *totals)
+static int fk_auto_scatter(const FkCall &c, const FkTmp &t, size_t first, size_t count)
 {
 	FkScatter sc = { (const uint32_t *) c.ix->fk.perm.p, (uint32_t) first, (uint32_t) count, (uint32_t) c.k, t.labels, t.dists, t.idx, t.counts, t.totals,
-					 c.labels, c.dists, c.idx, c.counts, totals };
+					 c.labels, c.dists, c.idx, c.counts, c.totals };
 	hipLaunchKernelGGL(fkp_scatter_kernel, dim3((uint32_t) ((count * c.k + 255) / 256)), dim3(256), 0, c.s, sc);
 	HIPCHK(hipGetLastError());
 	return HNSW_GPU_OK;
+}
+
+// ---- the driver of every device-pointer entry point ------------------------------------------------------------------------------------------
+// form: FK_LISTED, or FK_MFMA — the matrix-core form where it has a pass for the call (fk_have_mfma), with the operands of `format`;
+// aut: per query (form is FK_MFMA; d_plan: the plan's extra output, or NULL).  Whichever is asked for, the call splits three ways over the
+// one list build: no query takes the matrix-core pass; all do; or (an automatic call with two classes) the loose ones do
+static int fk_run(FkCall c, int form, int format, bool aut, uint8_t *d_plan)
+{
+	std::unique_lock<std::recursive_mutex> lock_;
+	if (c.ix) lock_ = std::unique_lock<std::recursive_mutex>(c.ix->mu);
+	if (int rc0 = fk_check(c, form, format)) return rc0;
+	if (c.nq == 0) return HNSW_GPU_OK;
+	// no filter: ONE implicit bitmap that every label passes — the list / mask of the rows that are not vacuumed
+	if (!c.allow) { c.allow_bits = 0; c.nfilters = 1; c.allow_of = nullptr; }
+	hnsw_gpu_index *ix = c.ix;
+	FkWs *fw = &ix->fk;
+	FkTrim trim_{fw};
+	FkWs::Diag &d = fw->*c.fam->diag;
+	FkWs::Plan &pl = fw->*c.fam->plan;
+	const size_t nq = c.nq;
+	const FkMfma m = fk_mfma_of(ix, format, c.k);
+	FkAuto a = {};
+	if (aut) fk_auto_begin(ix, m, &a);
+	int rc = fk_begin(c);
+	if (!rc && aut) rc = buf_reserve(&fw->perm, nq * 4, c.fam->who, "the plan's order of the queries");
+	const FkPlanHook hook = { a.thresh, d_plan };
+	if (!rc) rc = fk_lists(c, aut ? &hook : nullptr);
+	if (!rc && aut) rc = fk_auto_settle(c, m, &a, d_plan, &pl);
+	if (rc) return rc;
+	// the queries of the matrix-core pass.  A list no longer than S_min is its own sample: with no longer list in the call, every query
+	// is answered by the scan of its whole list
+	const size_t loose = aut ? (a.split ? a.loose : 0) : form == FK_MFMA && m.avail && c.longest > m.smin ? nq : 0;
+	if (!loose) return fk_chain(c, -1, m.standin, m.smin, 0);
+	uint32_t mwords = 0;
+	if ((rc = fk_masks(c, &mwords))) return rc;
+	if (loose == nq)
+	{
+		rc = fk_chain(c, m.format, m.standin, m.smin, mwords);
+		if (aut) pl.loose_form = d.form;
+		return rc;
+	}
+	// two classes over the one list build and the one mask build: the loose queries first (the filter's time counts from the call's start),
+	// then the listed ones; each class's rows go back to the caller's buffers behind its pass
+	const size_t nl = nq - loose;
+	FkTmp t;
+	if ((rc = fk_auto_gather(c, &t))) return rc;
+	FkCall cl = fk_auto_class(c, t, nl, loose, a.longest[1]);
+	if ((rc = fk_chain(cl, m.format, m.standin, m.smin, mwords))) return rc;
+	if ((rc = fk_auto_scatter(c, t, nl, loose))) return rc;
+	const FkWs::Diag first = d;
+	FkCall cs = fk_auto_class(c, t, 0, nl, a.longest[0]);
+	if ((rc = fk_again(cs, true))) return rc;
+	if ((rc = fk_chain(cs, -1, m.standin, m.smin, mwords))) return rc;
+	if ((rc = fk_auto_scatter(c, t, 0, nl))) return rc;
+	HIPCHK(hipStreamSynchronize(c.s));
+	// the call's figures: the sums over both classes, the loose class's filter and form (the listed pass's call time counts from the call's start: the whole call's)
+	d.scored += first.scored; d.totals += first.totals; d.scan_ms += first.scan_ms;
+	d.dist_pass = first.dist_pass; d.appended = first.appended; d.filter_ms = first.filter_ms; d.form = first.form;
+	pl.loose_form = first.form;
+	return HNSW_GPU_OK;
+}
+
+// the driver of every host-pointer entry point: copy in, run on the default stream, copy out
+static int fk_host(const FkCall &h, int form, int format, bool aut, uint8_t *plan)
+{
+	hnsw_gpu_index *ix = h.ix;
+	std::unique_lock<std::recursive_mutex> lock_;
+	if (ix) lock_ = std::unique_lock<std::recursive_mutex>(ix->mu);
+	if (int rc0 = fk_check(h, form, format)) return rc0;
+	if (h.nq == 0) return HNSW_GPU_OK;
+	HIPCHK(hipSetDevice(ix->device));
+	const size_t nq = h.nq, k = h.k, dim = ix->meta.dim, words = (h.allow_bits + 31) / 32;
+	const bool of = h.allow && h.allow_of;
+	const size_t qb = round_up(nq * dim * 4, 256), rb = round_up(h.radius ? nq * 4 : 0, 256), fb = round_up(h.allow ? h.nfilters * words * 4 : 0, 256),
+				 ob = round_up(of ? nq * 4 : 0, 256), lb = round_up(nq * k * 8, 256), db = round_up(nq * k * 4, 256), cb = round_up(nq * 4, 256);
+	int rc = ensure_scratch(ix, qb + rb + fb + ob + lb + 2 * db + 2 * cb + (plan ? nq : 0));
+	if (rc) return rc;
+	char *p = (char *) ix->scratch, *o = p + qb + rb + fb + ob;
+	FkCall d = h;
+	d.queries = (float *) p; d.radius = h.radius ? (float *) (p + qb) : nullptr; d.allow = h.allow ? (uint32_t *) (p + qb + rb) : nullptr;
+	d.allow_of = of ? (uint32_t *) (p + qb + rb + fb) : nullptr;
+	d.labels = (uint64_t *) o; d.dists = (float *) (o + lb); d.idx = (uint32_t *) (o + lb + db); d.counts = (uint32_t *) (o + lb + 2 * db);
+	d.totals = h.totals ? (uint32_t *) (o + lb + 2 * db + cb) : nullptr; d.s = nullptr;
+	uint8_t *dp = plan ? (uint8_t *) (o + lb + 2 * db + 2 * cb) : nullptr;
+	HIPCHK(hipMemcpy((void *) d.queries, h.queries, nq * dim * 4, hipMemcpyHostToDevice));
+	if (h.radius) HIPCHK(hipMemcpy((void *) d.radius, h.radius, nq * 4, hipMemcpyHostToDevice));
+	if (h.allow) HIPCHK(hipMemcpy((void *) d.allow, h.allow, h.nfilters * words * 4, hipMemcpyHostToDevice));
+	if (of) HIPCHK(hipMemcpy((void *) d.allow_of, h.allow_of, nq * 4, hipMemcpyHostToDevice));
+	if ((rc = fk_run(d, form, format, aut, dp))) return rc;
+	HIPCHK(hipMemcpy(h.labels, d.labels, nq * k * 8, hipMemcpyDeviceToHost));
+	if (h.dists) HIPCHK(hipMemcpy(h.dists, d.dists, nq * k * 4, hipMemcpyDeviceToHost));
+	if (h.idx) HIPCHK(hipMemcpy(h.idx, d.idx, nq * k * 4, hipMemcpyDeviceToHost));
+	HIPCHK(hipMemcpy(h.counts, d.counts, nq * 4, hipMemcpyDeviceToHost));
+	if (h.totals) HIPCHK(hipMemcpy(h.totals, d.totals, nq * 4, hipMemcpyDeviceToHost));
+	if (plan) HIPCHK(hipMemcpy(plan, dp, nq, hipMemcpyDeviceToHost));
+	return HNSW_GPU_OK;
+}
+
+// ---- the entry points: the call record, the driver ---------------------------------------------------------------------------------------------
+static FkCall fk_knn_call(hnsw_gpu_index *ix, const coord_t *queries, size_t nq, size_t k, const uint32_t *allow, size_t allow_bits, size_t nfilters,
+						  const uint32_t *allow_of, label_t *labels, dist_t *dists, idx_t *idx, uint32_t *counts, void *stream)
+{
+	return { &FK_KNN, ix, queries, nq, nullptr, k, allow, allow_bits, nfilters, allow_of, labels, dists, idx, counts, nullptr, (hipStream_t) stream };
+}
+static FkCall fk_range_call(hnsw_gpu_index *ix, const coord_t *queries, size_t nq, const dist_t *radius, size_t k, const uint32_t *allow, size_t allow_bits,
+							size_t nfilters, const uint32_t *allow_of, label_t *labels, dist_t *dists, idx_t *idx, uint32_t *counts, uint32_t *totals, void *stream)
+{
+	return { &FK_RANGE, ix, queries, nq, radius, k, allow, allow_bits, nfilters, allow_of, labels, dists, idx, counts, totals, (hipStream_t) stream };
+}
+
+extern "C" int hnsw_gpu_filtered_knn_dev(hnsw_gpu_index *ix, const coord_t *d_queries, size_t nq, size_t k, const uint32_t *d_allow,
+										 size_t allow_bits, size_t nfilters, const uint32_t *d_allow_of, label_t *d_labels, dist_t *d_dists,
+										 idx_t *d_idx, uint32_t *d_counts, void *stream)
+{
+	return fk_run(fk_knn_call(ix, d_queries, nq, k, d_allow, allow_bits, nfilters, d_allow_of, d_labels, d_dists, d_idx, d_counts, stream), FK_LISTED, ROWS_F32, false, nullptr);
+}
+
+extern "C" int hnsw_gpu_filtered_knn_mfma_dev(hnsw_gpu_index *ix, int format, const coord_t *d_queries, size_t nq, size_t k, const uint32_t *d_allow,
+											  size_t allow_bits, size_t nfilters, const uint32_t *d_allow_of, label_t *d_labels, dist_t *d_dists,
+											  idx_t *d_idx, uint32_t *d_counts, void *stream)
+{
+	return fk_run(fk_knn_call(ix, d_queries, nq, k, d_allow, allow_bits, nfilters, d_allow_of, d_labels, d_dists, d_idx, d_counts, stream), FK_MFMA, format, false, nullptr);
 }
 
 extern "C" int hnsw_gpu_filtered_knn_auto_dev(hnsw_gpu_index *ix, int format, const coord_t *d_queries, size_t nq, size_t k, const uint32_t *d_allow,
 											  size_t allow_bits, size_t nfilters, const uint32_t *d_allow_of, label_t *d_labels, dist_t *d_dists,
 											  idx_t *d_idx, uint32_t *d_counts, uint8_t *d_plan, void *stream)
 {
-	std::unique_lock<std::recursive_mutex> lock_;
-	if (ix) lock_ = std::unique_lock<std::recursive_mutex>(ix->mu);
-	if (int rc0 = fk_check(ix, d_queries, nq, k, d_allow, allow_bits, nfilters, d_labels, d_counts)) return rc0;
-	if (int rc0 = fk_check_format(ix, format)) return rc0;
-	if (nq == 0) return HNSW_GPU_OK;
-	FkCall c = { ix, d_queries, nq, k, d_allow, allow_bits, nfilters, d_allow_of, d_labels, d_dists, d_idx, d_counts, (hipStream_t) stream };
-	FkWs *fw = &ix->fk;
-	FkTrim trim_{fw};
-	FkAuto a;
-	fk_auto_begin(ix, format, k, &a);
-	int rc = fk_begin(c);
-	if (!rc) rc = buf_reserve(&fw->perm, nq * 4, fk_who(c), "the plan's order of the queries");
-	const FkPlanHook hook = { a.thresh, d_plan };
-	if (!rc) rc = fk_lists(c, &hook);
-	if (!rc) rc = fk_auto_settle(c, &a, d_plan, &fw->plan);
-	if (rc) return rc;
-	// one class: the fixed form's call on the caller's own buffers
-	if (!a.split) return fk_listed_scan(c, fw->ev[1]);
-	uint32_t mwords = 0;
-	if ((rc = fk_masks(c, &mwords))) return rc;
-	if (a.loose == nq)
-	{
-		rc = fk_mfma_chain(c, a.format, a.standin, a.smin, mwords);
-		fw->plan.loose_form = fw->form;
-		return rc;
-	}
-	// two classes over the one list build and the one mask build: the loose queries first (the filter's time counts from the call's start),
-	// then the listed ones; each class's rows go back to the caller's buffers behind its pass
-	const size_t nl = nq - a.loose;
-	FkTmp t;
-	if ((rc = fk_auto_gather(c, nullptr, false, &t))) return rc;
-	FkCall cl = fk_auto_class(c, t, nl, a.loose, a.longest[1]);
-	if ((rc = fk_mfma_chain(cl, a.format, a.standin, a.smin, mwords))) return rc;
-	if ((rc = fk_auto_scatter(c, t, nl, a.loose, nullptr))) return rc;
-	const uint64_t scored = fw->scored;
-	const float scan_ms = fw->scan_ms;
-	const int form = fw->form;
-	FkCall cs = fk_auto_class(c, t, 0, nl, a.longest[0]);
-	HIPCHK(hipEventRecord(fw->ev[5], c.s));
-	HIPCHK(hipMemsetAsync(c.scored, 0, 8, c.s));
-	if ((rc = fk_listed_scan(cs, fw->ev[5]))) return rc;
-	if ((rc = fk_auto_scatter(c, t, 0, nl, nullptr))) return rc;
-	HIPCHK(hipStreamSynchronize(c.s));
-	fw->scored += scored; fw->scan_ms += scan_ms; fw->form = form;  // the counters of hnsw_gpu_last_filtered_knn: both classes
-	fw->plan.loose_form = form;
-	return HNSW_GPU_OK;
-}
-
-// the host-pointer forms: copy in, run on the default stream, copy out.  format < 0: the listed form; aut: the automatic call (plan: its
-// extra output, or NULL)
-static int fk_host(hnsw_gpu_index *ix, int format, const coord_t *queries, size_t nq, size_t k, const uint32_t *allow, size_t allow_bits,
-				   size_t nfilters, const uint32_t *allow_of, label_t *labels, dist_t *dists, idx_t *idx, uint32_t *counts, bool aut = false,
-				   uint8_t *plan = nullptr)
-{
-	std::unique_lock<std::recursive_mutex> lock_;
-	if (ix) lock_ = std::unique_lock<std::recursive_mutex>(ix->mu);
-	if (int rc0 = fk_check(ix, queries, nq, k, allow, allow_bits, nfilters, labels, counts)) return rc0;
-	if (format >= 0)
-		if (int rc0 = fk_check_format(ix, format)) return rc0;
-	if (nq == 0) return HNSW_GPU_OK;
-	HIPCHK(hipSetDevice(ix->device));
-	const size_t dim = ix->meta.dim, words = (allow_bits + 31) / 32;
-	const size_t qb = round_up(nq * dim * 4, 256), fb = round_up(nfilters * words * 4, 256), ob = round_up(allow_of ? nq * 4 : 0, 256),
-				 lb = round_up(nq * k * 8, 256), db = round_up(nq * k * 4, 256), ib = round_up(nq * k * 4, 256), cb = round_up(nq * 4, 256);
-	int rc = ensure_scratch(ix, qb + fb + ob + lb + db + ib + cb + (plan ? nq : 0));
-	if (rc) return rc;
-	char *p = (char *) ix->scratch;
-	uint8_t *dp = plan ? (uint8_t *) (p + qb + fb + ob + lb + db + ib + cb) : nullptr;
-	float *dq = (float *) p; uint32_t *df = (uint32_t *) (p + qb), *dof = (uint32_t *) (p + qb + fb);
-	uint64_t *dl = (uint64_t *) (p + qb + fb + ob); float *dd = (float *) (p + qb + fb + ob + lb);
-	uint32_t *di = (uint32_t *) (p + qb + fb + ob + lb + db), *dc = (uint32_t *) (p + qb + fb + ob + lb + db + ib);
-	HIPCHK(hipMemcpy(dq, queries, nq * dim * 4, hipMemcpyHostToDevice));
-	HIPCHK(hipMemcpy(df, allow, nfilters * words * 4, hipMemcpyHostToDevice));
-	if (allow_of) HIPCHK(hipMemcpy(dof, allow_of, nq * 4, hipMemcpyHostToDevice));
-	rc = aut ? hnsw_gpu_filtered_knn_auto_dev(ix, format, dq, nq, k, df, allow_bits, nfilters, allow_of ? dof : nullptr, dl, dd, di, dc, dp, nullptr)
-		 : format < 0 ? hnsw_gpu_filtered_knn_dev(ix, dq, nq, k, df, allow_bits, nfilters, allow_of ? dof : nullptr, dl, dd, di, dc, nullptr)
-					: hnsw_gpu_filtered_knn_mfma_dev(ix, format, dq, nq, k, df, allow_bits, nfilters, allow_of ? dof : nullptr, dl, dd, di, dc, nullptr);
-	if (rc) return rc;
-	HIPCHK(hipMemcpy(labels, dl, nq * k * 8, hipMemcpyDeviceToHost));
-	if (dists) HIPCHK(hipMemcpy(dists, dd, nq * k * 4, hipMemcpyDeviceToHost));
-	if (idx) HIPCHK(hipMemcpy(idx, di, nq * k * 4, hipMemcpyDeviceToHost));
-	HIPCHK(hipMemcpy(counts, dc, nq * 4, hipMemcpyDeviceToHost));
-	if (plan) HIPCHK(hipMemcpy(plan, dp, nq, hipMemcpyDeviceToHost));
-	return HNSW_GPU_OK;
+	return fk_run(fk_knn_call(ix, d_queries, nq, k, d_allow, allow_bits, nfilters, d_allow_of, d_labels, d_dists, d_idx, d_counts, stream), FK_MFMA, format, true, d_plan);
 }
 
 extern "C" int hnsw_gpu_filtered_knn(hnsw_gpu_index *ix, const coord_t *queries, size_t nq, size_t k, const uint32_t *allow, size_t allow_bits,
 									 size_t nfilters, const uint32_t *allow_of, label_t *labels, dist_t *dists, idx_t *idx, uint32_t *counts)
 {
-	return fk_host(ix, -1, queries, nq, k, allow, allow_bits, nfilters, allow_of, labels, dists, idx, counts);
+	return fk_host(fk_knn_call(ix, queries, nq, k, allow, allow_bits, nfilters, allow_of, labels, dists, idx, counts, nullptr), FK_LISTED, ROWS_F32, false, nullptr);
 }
 
 extern "C" int hnsw_gpu_filtered_knn_mfma(hnsw_gpu_index *ix, int format, const coord_t *queries, size_t nq, size_t k, const uint32_t *allow,
@@ -1052,17 +1044,50 @@ extern "C" int hnsw_gpu_filtered_knn_mfma(hnsw_gpu_index *ix, int format, const 
 										  uint32_t *counts)
 {
 	if (format < 0) return fail(HNSW_GPU_ERR_ARG, "filtered k-NN: bad format %d", format);
-	return fk_host(ix, format, queries, nq, k, allow, allow_bits, nfilters, allow_of, labels, dists, idx, counts);
+	return fk_host(fk_knn_call(ix, queries, nq, k, allow, allow_bits, nfilters, allow_of, labels, dists, idx, counts, nullptr), FK_MFMA, format, false, nullptr);
 }
 
 extern "C" int hnsw_gpu_filtered_knn_auto(hnsw_gpu_index *ix, int format, const coord_t *queries, size_t nq, size_t k, const uint32_t *allow,
-											  size_t allow_bits, size_t nfilters, const uint32_t *allow_of, label_t *labels, dist_t *dists, idx_t *idx,
-											  uint32_t *counts, uint8_t *plan)
+										  size_t allow_bits, size_t nfilters, const uint32_t *allow_of, label_t *labels, dist_t *dists, idx_t *idx,
+										  uint32_t *counts, uint8_t *plan)
 {
 	if (format < 0) return fail(HNSW_GPU_ERR_ARG, "filtered k-NN: bad format %d", format);
-	return fk_host(ix, format, queries, nq, k, allow, allow_bits, nfilters, allow_of, labels, dists, idx, counts, true, plan);
+	return fk_host(fk_knn_call(ix, queries, nq, k, allow, allow_bits, nfilters, allow_of, labels, dists, idx, counts, nullptr), FK_MFMA, format, true, plan);
 }
 
+extern "C" int hnsw_gpu_range_knn_dev(hnsw_gpu_index *ix, int form, int format, const coord_t *d_queries, size_t nq, const dist_t *d_radius, size_t k,
+									  const uint32_t *d_allow, size_t allow_bits, size_t nfilters, const uint32_t *d_allow_of, label_t *d_labels,
+									  dist_t *d_dists, idx_t *d_idx, uint32_t *d_counts, uint32_t *d_totals, void *stream)
+{
+	return fk_run(fk_range_call(ix, d_queries, nq, d_radius, k, d_allow, allow_bits, nfilters, d_allow_of, d_labels, d_dists, d_idx, d_counts, d_totals, stream),
+				  form, format, false, nullptr);
+}
+
+// the automatic call: hnsw_gpu_filtered_knn_auto_dev's plan from the same list lengths.  Without a filter (or without d_allow_of) there is
+// one list, so one class: the class-level test is the whole decision
+extern "C" int hnsw_gpu_range_knn_auto_dev(hnsw_gpu_index *ix, int format, const coord_t *d_queries, size_t nq, const dist_t *d_radius, size_t k,
+										   const uint32_t *d_allow, size_t allow_bits, size_t nfilters, const uint32_t *d_allow_of, label_t *d_labels,
+										   dist_t *d_dists, idx_t *d_idx, uint32_t *d_counts, uint32_t *d_totals, uint8_t *d_plan, void *stream)
+{
+	return fk_run(fk_range_call(ix, d_queries, nq, d_radius, k, d_allow, allow_bits, nfilters, d_allow_of, d_labels, d_dists, d_idx, d_counts, d_totals, stream),
+				  FK_MFMA, format, true, d_plan);
+}
+
+extern "C" int hnsw_gpu_range_knn(hnsw_gpu_index *ix, int form, int format, const coord_t *queries, size_t nq, const dist_t *radius, size_t k,
+								  const uint32_t *allow, size_t allow_bits, size_t nfilters, const uint32_t *allow_of, label_t *labels, dist_t *dists,
+								  idx_t *idx, uint32_t *counts, uint32_t *totals)
+{
+	return fk_host(fk_range_call(ix, queries, nq, radius, k, allow, allow_bits, nfilters, allow_of, labels, dists, idx, counts, totals, nullptr), form, format, false, nullptr);
+}
+
+extern "C" int hnsw_gpu_range_knn_auto(hnsw_gpu_index *ix, int format, const coord_t *queries, size_t nq, const dist_t *radius, size_t k,
+									   const uint32_t *allow, size_t allow_bits, size_t nfilters, const uint32_t *allow_of, label_t *labels, dist_t *dists,
+									   idx_t *idx, uint32_t *counts, uint32_t *totals, uint8_t *plan)
+{
+	return fk_host(fk_range_call(ix, queries, nq, radius, k, allow, allow_bits, nfilters, allow_of, labels, dists, idx, counts, totals, nullptr), FK_MFMA, format, true, plan);
+}
+
+// ---- what the last call of either family left (include/hnsw_gpu_diag.h) -------------------------------------------------------------------
 static int fk_plan_out(hnsw_gpu_index *ix, FkWs::Plan FkWs::*which, uint64_t out[8])
 {
 	if (!ix || !out) return fail(HNSW_GPU_ERR_ARG, "NULL argument");
@@ -1075,376 +1100,45 @@ static int fk_plan_out(hnsw_gpu_index *ix, FkWs::Plan FkWs::*which, uint64_t out
 extern "C" int hnsw_gpu_last_filtered_knn_plan(hnsw_gpu_index *ix, uint64_t out[8]) { return fk_plan_out(ix, &FkWs::plan, out); }
 extern "C" int hnsw_gpu_last_range_knn_plan(hnsw_gpu_index *ix, uint64_t out[8]) { return fk_plan_out(ix, &FkWs::rplan, out); }
 
+static uint64_t fk_us(float ms) { return (uint64_t) std::llround((double) ms * 1000.0); }
+
 extern "C" int hnsw_gpu_last_filtered_knn(hnsw_gpu_index *ix, uint64_t out[4])
 {
 	if (!ix || !out) return fail(HNSW_GPU_ERR_ARG, "NULL argument");
 	std::lock_guard<std::recursive_mutex> lock_(ix->mu);
-	out[0] = ix->fk.listed;
-	out[1] = ix->fk.scored;
-	out[2] = (uint64_t) std::llround((double) ix->fk.build_ms * 1000.0);
-	out[3] = (uint64_t) std::llround((double) ix->fk.scan_ms * 1000.0);
+	const FkWs::Diag &m = ix->fk.k;
+	out[0] = m.listed; out[1] = m.scored; out[2] = fk_us(m.build_ms); out[3] = fk_us(m.scan_ms);
 	return HNSW_GPU_OK;
-}
-
-extern "C" int hnsw_gpu_last_filtered_knn_form(hnsw_gpu_index *ix)
-{
-	if (!ix) return -1;
-	std::lock_guard<std::recursive_mutex> lock_(ix->mu);
-	return ix->fk.form;
 }
 
 extern "C" int hnsw_gpu_last_filtered_knn_mfma(hnsw_gpu_index *ix, uint64_t out[7])
 {
 	if (!ix || !out) return fail(HNSW_GPU_ERR_ARG, "NULL argument");
 	std::lock_guard<std::recursive_mutex> lock_(ix->mu);
-	const FkWs::Mfma &m = ix->fk.m;
+	const FkWs::Diag &m = ix->fk.kf;
 	out[0] = m.listed; out[1] = m.scored; out[2] = m.dist_pass; out[3] = m.appended;
-	out[4] = (uint64_t) std::llround((double) m.build_ms * 1000.0);
-	out[5] = (uint64_t) std::llround((double) m.filter_ms * 1000.0);
-	out[6] = (uint64_t) std::llround((double) m.call_ms * 1000.0);
+	out[4] = fk_us(m.build_ms); out[5] = fk_us(m.filter_ms); out[6] = fk_us(m.call_ms);
 	return HNSW_GPU_OK;
-}
-
-// ------------------------------------------------------------------------------------
-// exact radius search: the k nearest within a distance, with totals (device_range_knn.h)
-// ------------------------------------------------------------------------------------
-struct RkCall { FkCall c; const dist_t *radius; uint32_t *totals; };
-
-static int rk_check(hnsw_gpu_index *ix, int form, const void *queries, size_t nq, const void *radius, size_t k, const void *allow, size_t allow_bits,
-					size_t nfilters, const void *labels, const void *counts)
-{
-	if (!ix) return fail(HNSW_GPU_ERR_ARG, "index is NULL");
-	if (nq == 0) return HNSW_GPU_OK;
-	if (form != HNSW_GPU_RANGE_LISTED && form != HNSW_GPU_RANGE_MFMA) return fail(HNSW_GPU_ERR_ARG, "radius search: form %d is neither listed (0) nor matrix cores (1)", form);
-	if (!queries || !radius || !labels || !counts) return fail(HNSW_GPU_ERR_ARG, "radius search: NULL buffer");
-	if (k == 0 || k > 1024) return fail(HNSW_GPU_ERR_ARG, "k %zu out of range [1, 1024]", k);
-	if (nq > 65535) return fail(HNSW_GPU_ERR_ARG, "at most 65535 queries per call");
-	if (allow && (allow_bits == 0 || nfilters == 0)) return fail(HNSW_GPU_ERR_ARG, "radius search: an allow filter of no bits");
-	if (allow && ((allow_bits + 31) / 32 >= 0xFFFFFFFFull || nfilters >= 0xFFFFFFFFull)) return fail(HNSW_GPU_ERR_ARG, "radius search: allow filter too large");
-	const uint32_t kiters = (ix->stride / 4 + 15) / 16;
-	const size_t lds = round_up(kiters, 4) * 64 * 4 + (size_t) 4 * (k + 1) * 8 + 4 * 128 * 4 + 4 * 64 * 4;
-	if (lds > 64 * 1024) return fail(HNSW_GPU_ERR_ARG, "k/dim too large for radius search");
-	return HNSW_GPU_OK;
-}
-
-static int rk_begin(FkCall &c)
-{
-	HIPCHK(hipSetDevice(c.ix->device));
-	FkWs *fw = &c.ix->fk;
-	if (!fw->host) HIPCHK(hipHostMalloc((void **) &fw->host, 128, hipHostMallocDefault));
-	for (hipEvent_t &e : fw->ev)
-		if (!e) HIPCHK(hipEventCreate(&e));
-	const int form = fw->r.form;
-	fw->r = FkWs::Range();
-	fw->r.form = form;                                            // (the form that answered the last call that ended well)
-	return HNSW_GPU_OK;
-}
-
-// One pass over the built lists (and masks).  format < 0: the listed form — the threshold scan over every query's whole list, merge,
-// emit.  Else the matrix-core form with the operands of `format`: the scan over the lists no longer than their sample and (without totals)
-// over the samples of the others -> merge + bounds -> filter (or its stand-in) -> threshold re-score -> emit.  *ovf = candidate lists
-// that overflowed (then the outputs are not the answer: the caller hands the call down).
-static int rk_pass(RkCall &r, int format, bool standin, uint32_t smin, uint32_t mwords, uint64_t *ovf)
-{
-	FkCall &c = r.c;
-	hnsw_gpu_index *ix = c.ix;
-	FkWs *fw = &ix->fk;
-	hipStream_t s = c.s;
-	const bool listed = format < 0, reduced = !listed && format != ROWS_F32, skip = !listed && r.totals;
-	const size_t nq = c.nq, k = c.k;
-	const int func = (int) ix->meta.dist_func;
-	const uint32_t n = (uint32_t) ix->n, stride = ix->stride, dim = (uint32_t) ix->meta.dim;
-	const uint32_t nchunks = stride / 4, kiters = (nchunks + 15) / 16;
-	const uint32_t qpadf = (uint32_t) round_up(kiters, 4) * 64;
-	const size_t wave_bytes = round_up((size_t) qpadf * 4 + (k + 1) * 8 + 128 * 4, 16);
-	int rc = listed ? HNSW_GPU_OK : bf_rows_side(ix, reduced, s);
-	if (rc) return rc;
-	const uint32_t qchunks = listed ? 0 : reduced ? ix->rows16_bytes / 16 : (uint32_t) round_up(stride, BF_TK) / 4;
-	const uint32_t rchunks = reduced ? ix->rows16_bytes / 16 : nchunks;
-	const uint32_t cap = 16384;
-	// the longest run of list entries a query scans: its whole list, its sample, or (totals) a list no longer than its sample
-	const size_t slongest = listed ? c.longest : skip ? std::min<size_t>(c.longest, smin) : fk_sample_len((uint32_t) c.longest, smin, (uint32_t) k);
-	uint32_t splits = 1;
-	if ((rc = fk_splits(c, slongest, &splits))) return rc;
-	// scratch carve
-	const size_t o_keys = 0;
-	const size_t o_rcnt = o_keys + round_up(nq * k * 8, 256);
-	const size_t o_off = o_rcnt + round_up(nq * 4, 256);
-	const size_t o_aof = o_off + round_up(nq * 16, 256);
-	const size_t o_pcnt = o_aof + round_up(nq * 4, 256);
-	const size_t o_sum = o_pcnt + round_up(nq * (size_t) splits * 16, 256);
-	const size_t o_q = o_sum + 256;
-	const size_t o_qn = o_q + round_up(nq * (size_t) qchunks * 16, 256);
-	const size_t o_qt = o_qn + round_up(nq * 4, 256);
-	const size_t o_tau = o_qt + round_up(nq * 8, 256);
-	const size_t o_bound = o_tau + round_up(nq * 4, 256);
-	const size_t o_mof = o_bound + round_up(nq * 4, 256);
-	const size_t o_cnt = o_mof + round_up(nq * 4, 256);
-	const size_t o_fcnt = o_cnt + round_up(nq * 4 + 64, 256);
-	const size_t total = o_fcnt + 256;
-	if ((rc = buf_reserve(&fw->bfs, total, "radius search", "the per-query scratch"))) return rc;
-	if (!listed && (rc = buf_reserve(&fw->cand, nq * (size_t) cap * 4, "radius search", "the candidate lists"))) return rc;
-	char *B = (char *) fw->bfs.p;
-	uint64_t *keys = (uint64_t *) (B + o_keys), *off2 = (uint64_t *) (B + o_off);
-	uint32_t *rcount = (uint32_t *) (B + o_rcnt), *aof2 = (uint32_t *) (B + o_aof), *pcount = (uint32_t *) (B + o_pcnt);
-	unsigned long long *sum = (unsigned long long *) (B + o_sum), *fcnt = (unsigned long long *) (B + o_fcnt);
-	uint4 *qcopy = (uint4 *) (B + o_q);
-	float *qn = (float *) (B + o_qn), *tau = (float *) (B + o_tau), *bound = (float *) (B + o_bound);
-	float2 *qterms = (float2 *) (B + o_qt);
-	uint32_t *mask_of = (uint32_t *) (B + o_mof), *cnt = (uint32_t *) (B + o_cnt), *cand = (uint32_t *) fw->cand.p;
-	uint32_t *overflow = cnt + nq;
-
-	// the threshold scan, then per query: its keys, its in-range count and (matrix-core form) its bound and mask row
-	FkEmit fe = fk_kernel_args(c);
-	RkMerge rm;
-	memset(&rm, 0, sizeof(rm));
-	rm.r.s = fe.s;
-	rm.r.s.splits = splits; rm.r.s.part = (uint64_t *) fw->part.p; rm.r.s.smin = listed ? 0u : smin;
-	rm.r.radius = r.radius; rm.r.pcount = pcount; rm.r.skip_samples = skip ? 1u : 0u; rm.r.func = func;
-	rm.nfilters = (uint32_t) c.nfilters; rm.keys = keys; rm.rcount = rcount; rm.tau = listed ? nullptr : tau; rm.mask_of = mask_of;
-	HIPCHK(hipMemsetAsync(c.scored, 0, 8, s));
-	HIPCHK(hipMemsetAsync(sum, 0, 8, s));
-	if (slongest)
-	{
-		const size_t lds = (size_t) qpadf * 4 + (size_t) 4 * (k + 1) * 8 + 4 * 128 * 4 + 4 * 64 * 4;
-		const dim3 grid((uint32_t) round_up((size_t) splits * nq, 8));
-		with_func(func, [&](auto F) { hipLaunchKernelGGL(rk_scan_kernel<decltype(F)::value>, grid, dim3(256), lds, s, rm.r); });
-	}
-	hipLaunchKernelGGL(rk_merge_kernel, dim3((uint32_t) nq), dim3(64), k * 8, s, rm);
-	if (!listed)
-	{
-		bf_queries_side(reduced, format, c.queries, nq, dim, qchunks, qcopy, qn, qterms, s);
-		hipLaunchKernelGGL(make_bounds_kernel, dim3((uint32_t) ((nq + 255) / 256)), dim3(256), 0, s, (const float *) tau, qn, (uint32_t) nq, func, dim, bound);
-		HIPCHK(hipMemsetAsync(cnt, 0, nq * 4 + 64, s));               // (the candidate counts and the overflow word behind them)
-		HIPCHK(hipMemsetAsync(fcnt, 0, 16, s));
-		// the filter over all rows, the allow test (the mask of allowed, or of live, rows) at its append
-		BfArgs a;
-		memset(&a, 0, sizeof(a));
-		a.queries = qcopy; a.qnorm = qn; a.qbound = bound; a.qterms = qterms;
-		a.rows = reduced ? (const uint4 *) ix->rows16 : (const uint4 *) ix->vec; a.xnorm = ix->xnorm; a.xterms = ix->r16x;
-		a.nq = (uint32_t) nq; a.n = n; a.qchunks = qchunks; a.rchunks = rchunks; a.ksteps = qchunks / BF_CH; a.func = func;
-		a.xscale = 0.5f * (1.f - 2.f * ((float) dim + 32.f) * 0x1p-24f);          // (1 - eD) / 2: make_bounds_kernel
-		a.eabs = r16_abs_term(dim);
-		a.cand = cand; a.cand_cnt = cnt; a.cap = cap;
-		a.mask = (const uint32_t *) fw->mask.p; a.mask_of = mask_of; a.mwords = mwords; a.fcnt = fcnt;
-		HIPCHK(hipEventRecord(fw->ev[3], s));
-		if (standin)
-			with_func(func, [&](auto F) {
-				hipLaunchKernelGGL(fkm_standin_kernel<decltype(F)::value>, dim3((uint32_t) nq), dim3(256), (size_t) qpadf * 4 + 4 * 128 * 4, s, a, ix->vec, dim, stride,
-								   nchunks, kiters, qpadf, c.queries, (const float *) tau);
-			});
-		else if ((rc = with_form(format, [&](auto p) { return bf_filter_pick<BfAllow<decltype(p)>>(ix, a, s); })))
-			return rc;
-		HIPCHK(hipEventRecord(fw->ev[4], s));
-		with_func(func, [&](auto F) {
-			if constexpr (decltype(F)::value != F_MANHATTAN)           // (answered by the listed form: no re-score kernel is compiled for it)
-				hipLaunchKernelGGL(rk_rescore_kernel<decltype(F)::value>, dim3((uint32_t) ((nq + 3) / 4)), dim3(256), wave_bytes * 4, s, ix->vec, dim, stride, nchunks,
-								   kiters, qpadf, c.queries, (uint32_t) nq, r.radius, (const uint32_t *) mask_of, (uint32_t) c.nfilters, (const uint32_t *) cand,
-								   (const uint32_t *) cnt, cap, (uint32_t) k, keys, rcount, overflow);
-		});
-	}
-	// counts as list lengths, totals -> the emit kernel over one key list per query
-	hipLaunchKernelGGL(rk_finish_kernel, dim3((uint32_t) ((nq + 255) / 256)), dim3(256), 0, s, (const uint32_t *) rcount, (uint32_t) nq, (uint32_t) k, off2, aof2,
-					   r.totals, sum);
-	fe.s.off = off2; fe.s.allow_of = aof2; fe.s.nseg = 1; fe.s.smin = 0;
-	fe.single = keys;
-	hipLaunchKernelGGL(fk_emit_kernel, dim3((uint32_t) nq), dim3(64), k * 16, s, fe);
-	hipError_t e = hipGetLastError();
-	if (e == hipSuccess) e = hipEventRecord(fw->ev[2], s);
-	fw->host[3] = fw->host[4] = fw->host[5] = 0;
-	if (e == hipSuccess) e = hipMemcpyAsync(&fw->host[2], c.scored, 8, hipMemcpyDeviceToHost, s);
-	if (e == hipSuccess) e = hipMemcpyAsync(&fw->host[6], sum, 8, hipMemcpyDeviceToHost, s);
-	if (e == hipSuccess && !listed) e = hipMemcpyAsync(&fw->host[3], fcnt, 16, hipMemcpyDeviceToHost, s);
-	if (e == hipSuccess && !listed) e = hipMemcpyAsync(&fw->host[5], overflow, 4, hipMemcpyDeviceToHost, s);
-	const hipError_t e2 = hipStreamSynchronize(s);
-	if (e == hipSuccess) e = e2;
-	if (e != hipSuccess) return fail(HNSW_GPU_ERR_HIP, "radius search: %s", hipGetErrorString(e));
-	*ovf = fw->host[5];
-	FkWs::Range &m = fw->r;
-	m.listed = c.total; m.scored = fw->host[2]; m.dist_pass = fw->host[3]; m.appended = fw->host[4]; m.totals = fw->host[6];
-	m.filter_ms = 0.f;
-	(void) hipEventElapsedTime(&m.build_ms, fw->ev[0], fw->ev[1]);
-	if (!listed) (void) hipEventElapsedTime(&m.filter_ms, fw->ev[3], fw->ev[4]);
-	(void) hipEventElapsedTime(&m.call_ms, fw->ev[0], fw->ev[2]);
-	return HNSW_GPU_OK;
-}
-
-// The passes of one call (or of one class of an automatic call) over the built lists (and masks): a candidate list that overflows sends a
-// 16-bit pass to the f32 operands and an f32 pass to the listed form, for all its queries.  pass: the first one (< 0: the listed form)
-static int rk_chain(RkCall &r, int pass, bool standin, uint32_t smin, uint32_t mwords)
-{
-	FkWs *fw = &r.c.ix->fk;
-	for (;;)
-	{
-		uint64_t ovf = 0;
-		if (int rc = rk_pass(r, pass, standin, smin, mwords, &ovf)) return rc;
-		if (!ovf) break;
-		pass = pass == ROWS_F32 ? -1 : ROWS_F32;
-	}
-	fw->r.form = pass < 0 ? HNSW_GPU_RK_FORM_LISTED : pass == ROWS_F32 ? HNSW_GPU_RK_FORM_F32 : pass == ROWS_BF16 ? HNSW_GPU_RK_FORM_BF16 : HNSW_GPU_RK_FORM_F16;
-	return HNSW_GPU_OK;
-}
-
-extern "C" int hnsw_gpu_range_knn_dev(hnsw_gpu_index *ix, int form, int format, const coord_t *d_queries, size_t nq, const dist_t *d_radius, size_t k,
-									  const uint32_t *d_allow, size_t allow_bits, size_t nfilters, const uint32_t *d_allow_of, label_t *d_labels,
-									  dist_t *d_dists, idx_t *d_idx, uint32_t *d_counts, uint32_t *d_totals, void *stream)
-{
-	std::unique_lock<std::recursive_mutex> lock_;
-	if (ix) lock_ = std::unique_lock<std::recursive_mutex>(ix->mu);
-	if (int rc0 = rk_check(ix, form, d_queries, nq, d_radius, k, d_allow, allow_bits, nfilters, d_labels, d_counts)) return rc0;
-	if (nq == 0) return HNSW_GPU_OK;
-	if (form == HNSW_GPU_RANGE_MFMA)
-		if (int rc0 = fk_check_format(ix, format)) return rc0;
-	// no filter: ONE implicit bitmap that every label passes — the list / mask of the rows that are not vacuumed
-	RkCall r = { { ix, d_queries, nq, k, d_allow, d_allow ? allow_bits : 0, d_allow ? nfilters : 1, d_allow ? d_allow_of : nullptr, d_labels, d_dists, d_idx,
-				   d_counts, (hipStream_t) stream }, d_radius, d_totals };
-	FkCall &c = r.c;
-	c.who = "radius search";
-	// the matrix-core form where hnsw_gpu_filtered_knn_mfma_dev has one (its rules), else the listed form
-	bool standin = false;
-	bool mfma = fk_have_mfma(ix, k, &standin) && form == HNSW_GPU_RANGE_MFMA;
-	if (standin) format = ROWS_F32;
-
-	FkWs *fw = &ix->fk;
-	FkTrim trim_{fw};
-	int rc = rk_begin(c);
-	if (!rc) rc = fk_lists(c);
-	if (rc) return rc;
-	const uint32_t smin = fk_sample_min();
-	if (c.longest <= smin) mfma = false;                          // every query is answered by the scan of its whole list
-	uint32_t mwords = 0;
-	if (mfma && (rc = fk_masks(c, &mwords))) return rc;
-	return rk_chain(r, mfma ? format : -1, standin, smin, mwords);
-}
-
-// the automatic call: hnsw_gpu_filtered_knn_auto_dev's plan from the same list lengths.  Without a filter (or without d_allow_of) there is
-// one list, so one class: the class-level test is the whole decision
-extern "C" int hnsw_gpu_range_knn_auto_dev(hnsw_gpu_index *ix, int format, const coord_t *d_queries, size_t nq, const dist_t *d_radius, size_t k,
-										   const uint32_t *d_allow, size_t allow_bits, size_t nfilters, const uint32_t *d_allow_of, label_t *d_labels,
-										   dist_t *d_dists, idx_t *d_idx, uint32_t *d_counts, uint32_t *d_totals, uint8_t *d_plan, void *stream)
-{
-	std::unique_lock<std::recursive_mutex> lock_;
-	if (ix) lock_ = std::unique_lock<std::recursive_mutex>(ix->mu);
-	if (int rc0 = rk_check(ix, HNSW_GPU_RANGE_MFMA, d_queries, nq, d_radius, k, d_allow, allow_bits, nfilters, d_labels, d_counts)) return rc0;
-	if (nq == 0) return HNSW_GPU_OK;
-	if (int rc0 = fk_check_format(ix, format)) return rc0;
-	RkCall r = { { ix, d_queries, nq, k, d_allow, d_allow ? allow_bits : 0, d_allow ? nfilters : 1, d_allow ? d_allow_of : nullptr, d_labels, d_dists, d_idx,
-				   d_counts, (hipStream_t) stream }, d_radius, d_totals };
-	FkCall &c = r.c;
-	c.who = "radius search";
-	FkWs *fw = &ix->fk;
-	FkTrim trim_{fw};
-	FkAuto a;
-	fk_auto_begin(ix, format, k, &a);
-	int rc = rk_begin(c);
-	if (!rc) rc = buf_reserve(&fw->perm, nq * 4, fk_who(c), "the plan's order of the queries");
-	const FkPlanHook hook = { a.thresh, d_plan };
-	if (!rc) rc = fk_lists(c, &hook);
-	if (!rc) rc = fk_auto_settle(c, &a, d_plan, &fw->rplan);
-	if (rc) return rc;
-	// one class: the fixed form's call on the caller's own buffers
-	if (!a.split) return rk_chain(r, -1, a.standin, a.smin, 0);
-	uint32_t mwords = 0;
-	if ((rc = fk_masks(c, &mwords))) return rc;
-	if (a.loose == nq)
-	{
-		rc = rk_chain(r, a.format, a.standin, a.smin, mwords);
-		fw->rplan.loose_form = fw->r.form;
-		return rc;
-	}
-	// two classes (hnsw_gpu_filtered_knn_auto_dev): the loose queries, then the listed ones
-	const size_t nl = nq - a.loose;
-	FkTmp t;
-	if ((rc = fk_auto_gather(c, d_radius, d_totals != nullptr, &t))) return rc;
-	RkCall rl = { fk_auto_class(c, t, nl, a.loose, a.longest[1]), t.radius + nl, t.totals ? t.totals + nl : nullptr };
-	if ((rc = rk_chain(rl, a.format, a.standin, a.smin, mwords))) return rc;
-	if ((rc = fk_auto_scatter(c, t, nl, a.loose, d_totals))) return rc;
-	const FkWs::Range loose = fw->r;
-	RkCall rs = { fk_auto_class(c, t, 0, nl, a.longest[0]), t.radius, t.totals };
-	if ((rc = rk_chain(rs, -1, a.standin, a.smin, mwords))) return rc;
-	if ((rc = fk_auto_scatter(c, t, 0, nl, d_totals))) return rc;
-	HIPCHK(hipStreamSynchronize(c.s));
-	// the counters of hnsw_gpu_last_range_knn: both classes (the listed pass's call time counts from the call's start: the whole call's)
-	FkWs::Range &m = fw->r;
-	m.scored += loose.scored; m.totals += loose.totals; m.dist_pass = loose.dist_pass; m.appended = loose.appended; m.filter_ms = loose.filter_ms;
-	m.form = loose.form;
-	fw->rplan.loose_form = loose.form;
-	return HNSW_GPU_OK;
-}
-
-// the host-pointer forms: copy in, run on the default stream, copy out.  aut: the automatic call (plan: its extra output, or NULL)
-static int rk_host(hnsw_gpu_index *ix, bool aut, int form, int format, const coord_t *queries, size_t nq, const dist_t *radius, size_t k,
-				   const uint32_t *allow, size_t allow_bits, size_t nfilters, const uint32_t *allow_of, label_t *labels, dist_t *dists,
-				   idx_t *idx, uint32_t *counts, uint32_t *totals, uint8_t *plan)
-{
-	std::unique_lock<std::recursive_mutex> lock_;
-	if (ix) lock_ = std::unique_lock<std::recursive_mutex>(ix->mu);
-	if (int rc0 = rk_check(ix, form, queries, nq, radius, k, allow, allow_bits, nfilters, labels, counts)) return rc0;
-	if (nq == 0) return HNSW_GPU_OK;
-	if (form == HNSW_GPU_RANGE_MFMA)
-		if (int rc0 = fk_check_format(ix, format)) return rc0;
-	HIPCHK(hipSetDevice(ix->device));
-	const size_t dim = ix->meta.dim, words = (allow_bits + 31) / 32;
-	const size_t qb = round_up(nq * dim * 4, 256), rb = round_up(nq * 4, 256), fb = round_up(allow ? nfilters * words * 4 : 0, 256),
-				 ob = round_up(allow && allow_of ? nq * 4 : 0, 256), lb = round_up(nq * k * 8, 256), db = round_up(nq * k * 4, 256), cb = round_up(nq * 4, 256);
-	int rc = ensure_scratch(ix, qb + rb + fb + ob + lb + 2 * db + 2 * cb + (plan ? nq : 0));
-	if (rc) return rc;
-	char *p = (char *) ix->scratch;
-	float *dq = (float *) p, *dr = (float *) (p + qb); uint32_t *df = (uint32_t *) (p + qb + rb), *dof = (uint32_t *) (p + qb + rb + fb);
-	char *o = p + qb + rb + fb + ob;
-	uint64_t *dl = (uint64_t *) o; float *dd = (float *) (o + lb);
-	uint32_t *di = (uint32_t *) (o + lb + db), *dc = (uint32_t *) (o + lb + 2 * db), *dt = (uint32_t *) (o + lb + 2 * db + cb);
-	uint8_t *dp = plan ? (uint8_t *) (o + lb + 2 * db + 2 * cb) : nullptr;
-	HIPCHK(hipMemcpy(dq, queries, nq * dim * 4, hipMemcpyHostToDevice));
-	HIPCHK(hipMemcpy(dr, radius, nq * 4, hipMemcpyHostToDevice));
-	if (allow) HIPCHK(hipMemcpy(df, allow, nfilters * words * 4, hipMemcpyHostToDevice));
-	if (allow && allow_of) HIPCHK(hipMemcpy(dof, allow_of, nq * 4, hipMemcpyHostToDevice));
-	rc = aut ? hnsw_gpu_range_knn_auto_dev(ix, format, dq, nq, dr, k, allow ? df : nullptr, allow_bits, nfilters, allow && allow_of ? dof : nullptr, dl, dd, di, dc,
-										   totals ? dt : nullptr, dp, nullptr)
-			 : hnsw_gpu_range_knn_dev(ix, form, format, dq, nq, dr, k, allow ? df : nullptr, allow_bits, nfilters, allow && allow_of ? dof : nullptr, dl, dd, di, dc,
-									  totals ? dt : nullptr, nullptr);
-	if (rc) return rc;
-	HIPCHK(hipMemcpy(labels, dl, nq * k * 8, hipMemcpyDeviceToHost));
-	if (dists) HIPCHK(hipMemcpy(dists, dd, nq * k * 4, hipMemcpyDeviceToHost));
-	if (idx) HIPCHK(hipMemcpy(idx, di, nq * k * 4, hipMemcpyDeviceToHost));
-	HIPCHK(hipMemcpy(counts, dc, nq * 4, hipMemcpyDeviceToHost));
-	if (totals) HIPCHK(hipMemcpy(totals, dt, nq * 4, hipMemcpyDeviceToHost));
-	if (plan) HIPCHK(hipMemcpy(plan, dp, nq, hipMemcpyDeviceToHost));
-	return HNSW_GPU_OK;
-}
-
-extern "C" int hnsw_gpu_range_knn(hnsw_gpu_index *ix, int form, int format, const coord_t *queries, size_t nq, const dist_t *radius, size_t k,
-								  const uint32_t *allow, size_t allow_bits, size_t nfilters, const uint32_t *allow_of, label_t *labels, dist_t *dists,
-								  idx_t *idx, uint32_t *counts, uint32_t *totals)
-{
-	return rk_host(ix, false, form, format, queries, nq, radius, k, allow, allow_bits, nfilters, allow_of, labels, dists, idx, counts, totals, nullptr);
-}
-
-extern "C" int hnsw_gpu_range_knn_auto(hnsw_gpu_index *ix, int format, const coord_t *queries, size_t nq, const dist_t *radius, size_t k,
-									   const uint32_t *allow, size_t allow_bits, size_t nfilters, const uint32_t *allow_of, label_t *labels, dist_t *dists,
-									   idx_t *idx, uint32_t *counts, uint32_t *totals, uint8_t *plan)
-{
-	return rk_host(ix, true, HNSW_GPU_RANGE_MFMA, format, queries, nq, radius, k, allow, allow_bits, nfilters, allow_of, labels, dists, idx, counts, totals, plan);
-}
-
-extern "C" int hnsw_gpu_last_range_knn_form(hnsw_gpu_index *ix)
-{
-	if (!ix) return -1;
-	std::lock_guard<std::recursive_mutex> lock_(ix->mu);
-	return ix->fk.r.form;
 }
 
 extern "C" int hnsw_gpu_last_range_knn(hnsw_gpu_index *ix, uint64_t out[8])
 {
 	if (!ix || !out) return fail(HNSW_GPU_ERR_ARG, "NULL argument");
 	std::lock_guard<std::recursive_mutex> lock_(ix->mu);
-	const FkWs::Range &m = ix->fk.r;
+	const FkWs::Diag &m = ix->fk.r;
 	out[0] = m.listed; out[1] = m.scored; out[2] = m.dist_pass; out[3] = m.appended; out[4] = m.totals;
-	out[5] = (uint64_t) std::llround((double) m.build_ms * 1000.0);
-	out[6] = (uint64_t) std::llround((double) m.filter_ms * 1000.0);
-	out[7] = (uint64_t) std::llround((double) m.call_ms * 1000.0);
+	out[5] = fk_us(m.build_ms); out[6] = fk_us(m.filter_ms); out[7] = fk_us(m.call_ms);
 	return HNSW_GPU_OK;
 }
+
+static int fk_form_out(hnsw_gpu_index *ix, FkWs::Diag FkWs::*which)
+{
+	if (!ix) return -1;
+	std::lock_guard<std::recursive_mutex> lock_(ix->mu);
+	return (ix->fk.*which).form;
+}
+extern "C" int hnsw_gpu_last_filtered_knn_form(hnsw_gpu_index *ix) { return fk_form_out(ix, &FkWs::k); }
+extern "C" int hnsw_gpu_last_range_knn_form(hnsw_gpu_index *ix) { return fk_form_out(ix, &FkWs::r); }
 
 extern "C" int hnsw_gpu_last_bruteforce_form(hnsw_gpu_index *ix)
 {

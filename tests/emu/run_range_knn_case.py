@@ -1,4 +1,4 @@
-"""Exact radius search (csrc/device_range_knn.h, hnsw_gpu_range_knn[_dev]) on the SIMT-emulated library, compared bit for bit with the numpy
+"""Exact radius search (csrc/device_filtered_knn.h, hnsw_gpu_range_knn[_dev]) on the SIMT-emulated library, compared bit for bit with the numpy
 yardstick of tests/range_knn_util.py.  Every case of tests/filtered_knn_util.py runs with every radius kind in one call
 (range_knn_util.spread with a limit of 40 queries: a case of up to three queries runs every kind for every query; a larger one runs every
 kind at least once per call, each query with one to three kinds — the emulator's time does not allow more; the device tier,

@@ -226,3 +226,82 @@ def group_metrics():
 
 GROUPS = {"lengths": group_lengths, "k": group_k, "per_query": group_per_query, "bits": group_bits, "vacuum_and_twins": group_vacuum_and_twins,
           "ties": group_ties, "dims": group_dims, "metrics": group_metrics}
+
+
+# ---- rows whose distance is NaN (tests/test_filtered_knn_nan_emu.py, tests/test_gpu_filtered_knn_nan.py) ----------------------------------
+
+NAN_ALLOW_OF = (0, 1, 2, 1, 0)
+NAN_SHORT = (3, 7, 8, 9, 100, 101)
+
+
+def nan_rows(n):
+    """the elements that carry a NaN coordinate"""
+    return (3, 100, 101, n // 2, n - 1)
+
+
+def nan_case(n, func, k):
+    """n x 16 rows of which five hold a NaN coordinate, so that their distance to any query is NaN; three bitmaps — every row, the six rows
+    NAN_SHORT (three of them NaN rows), every other row — and five queries over them.  Filtered k-NN has no threshold: a NaN distance sorts
+    behind every number and is returned where the list has room for it; radius search compares d <= r, which no NaN passes."""
+    X = gmm(n, 16, k=12, seed=3) if func == L2 else np.random.default_rng(21).standard_normal((n, 16)).astype(np.float32)
+    X = np.array(X, np.float32)
+    X[list(nan_rows(n)), 5] = np.nan
+    clean = np.delete(X, nan_rows(n), axis=0)
+    allow = np.zeros((3, n), bool)
+    allow[0] = True
+    allow[1, list(NAN_SHORT)] = True
+    allow[2, ::2] = True
+    return make(f"nan_{n}x16_func{func}_k{k}", X, func, queries(clean, len(NAN_ALLOW_OF), seed=31), k, allow, NAN_ALLOW_OF)
+
+
+def nan_expect(case):
+    """per query: (the allowed elements with a finite distance in the answer's order — by (ord(d), label, element) —, their distance bits,
+    the allowed NaN rows by element, |A|)"""
+    labels = case["labels"]
+    out = []
+    for i, q in enumerate(case["Q"]):
+        A = members(labels, case["dead"], case["allow"][int(case["allow_of"][i])])
+        d = oracle.port_dist_many(case["func"], q, np.ascontiguousarray(case["X"][A]))
+        nan = np.isnan(d)
+        fin = np.nonzero(~nan)[0]
+        fin = fin[np.lexsort((A[fin], labels[A[fin]], ord32(d[fin])))]
+        out.append((A[fin].tolist(), d[fin].view(np.uint32).tolist(), A[nan].tolist(), len(A)))
+    return out
+
+
+def nan_sign(got, query=1):
+    """the sign bit of the NaN distances a filtered k-NN answer holds for `query` (None: it holds none, or both signs).  The keys are
+    ord_f32(distance) << 32 | element: a NaN with the sign bit clear sorts behind every number, one with the sign bit set before every
+    number — which of the two the canonical distance code produces from a NaN coordinate is the arithmetic's, not the contract's."""
+    d = np.asarray(got["dists"]).view(np.float32)[query]
+    signs = set(np.signbit(d[np.isnan(d)]).tolist())
+    return signs.pop() if len(signs) == 1 else None
+
+
+def nan_check(case, got, want, nan_first=False, within=False):
+    """got against nan_expect: counts = min(k, |A|); the NaN rows as ONE block in element order with a NaN distance (isnan: no bit pattern) —
+    behind the finite rows, or before them with nan_first —; the finite rows in the yardstick's order with its distance bits; padded tails.
+    within: radius search at +inf — the finite rows only, totals = their number."""
+    k, bad = case["k"], []
+    labels, dists, idx, counts = (np.asarray(got[n]) for n in ("labels", "dists", "idx", "counts"))
+    labels, dbits, dists, idx, counts = labels.view(np.uint64), dists.view(np.uint32), dists.view(np.float32), idx.view(np.uint32), counts.view(np.uint32)
+    for i, (fin, fbits, nan, size) in enumerate(want):
+        nan = [] if within else nan
+        c = min(k, len(fin) + len(nan))
+        if int(counts[i]) != c:
+            bad.append((i, "count", int(counts[i]), c))
+            continue
+        order = (nan + fin if nan_first else fin + nan)[:c]
+        f0 = min(c, len(nan)) if nan_first else 0                     # the finite rows are positions [f0, f1)
+        f1 = c if nan_first else min(c, len(fin))
+        if idx[i, :c].tolist() != order or labels[i, :c].tolist() != case["labels"][order].tolist():
+            bad.append((i, "rows", idx[i, :c].tolist(), order))
+        elif dbits[i, f0:f1].tolist() != fbits[:f1 - f0]:
+            bad.append((i, "finite distance bits"))
+        elif not (np.isnan(dists[i, :f0]).all() and np.isnan(dists[i, f1:c]).all()):
+            bad.append((i, "NaN distances", dists[i, :c].tolist()))
+        if (labels[i, c:] != np.uint64(NO_LABEL)).any() or (dbits[i, c:] != 0x7F800000).any() or (idx[i, c:] != NO_IDX).any():
+            bad.append((i, "tail"))
+        if within and got.get("totals") is not None and int(np.asarray(got["totals"]).view(np.uint32)[i]) != len(fin):
+            bad.append((i, "total", int(np.asarray(got["totals"]).view(np.uint32)[i]), len(fin)))
+    return bad

@@ -1,4 +1,4 @@
-"""Shared by the tests of exact radius search (csrc/device_range_knn.h, hnsw_gpu_range_knn[_dev]; tests/emu/run_range_knn_case.py,
+"""Shared by the tests of exact radius search (csrc/device_filtered_knn.h, hnsw_gpu_range_knn[_dev]; tests/emu/run_range_knn_case.py,
 tests/test_gpu_range_knn.py): the yardstick in numpy, radii with teeth, and the bitwise comparison.
 
 Yardstick, per query q with radius r and bitmap b (none: every label passes): d = oracle.port_dist_many over the allowed rows that are not

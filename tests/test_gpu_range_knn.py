@@ -1,4 +1,4 @@
-"""Exact radius search on the device (csrc/device_range_knn.h, hnsw_gpu_range_knn[_dev]; GpuIndex.range_knn_torch / range_knn): every query
+"""Exact radius search on the device (csrc/device_filtered_knn.h, hnsw_gpu_range_knn[_dev]; GpuIndex.range_knn_torch / range_knn): every query
 of every case compared bit for bit — labels, distance bits, element numbers, counts, totals, tail padding — with the numpy yardstick of
 tests/range_knn_util.py (oracle.port_dist_many over the allowed live rows, cut at the radius with IEEE <=), the form that answered, and the
 counters.  Radii with teeth: the exact distance of a query's j-th nearest allowed row, the float just below it, below the nearest row, +inf

@@ -1,4 +1,4 @@
-"""Exact radius search (csrc/device_range_knn.h, hnsw_gpu_range_knn[_dev]) on the SIMT-emulated library: the list build (with a filter and
+"""Exact radius search (csrc/device_filtered_knn.h, hnsw_gpu_range_knn[_dev]) on the SIMT-emulated library: the list build (with a filter and
 without), the threshold scan with its in-range counts, the merge and its bounds, the append with its allow test, the threshold re-score, the
 emit kernel and the host code are the product's own, executed on the CPU; only the MFMA filter launch is replaced by its stand-in
 (HNSW_GPU_FK_MFMA_STANDIN, as in tests/test_filtered_knn_mfma_emu.py; HNSW_GPU_FK_SAMPLE_MIN = 64).
