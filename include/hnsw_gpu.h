@@ -332,6 +332,37 @@ int hnsw_gpu_range_knn_auto(hnsw_gpu_index *ix, int format, const coord_t *queri
 							const uint32_t *allow, size_t allow_bits, size_t nfilters, const uint32_t *allow_of,
 							label_t *labels, dist_t *dists, idx_t *idx, uint32_t *counts, uint32_t *totals, uint8_t *plan);
 
+/* Exact grouped k-NN: the k nearest DISTINCT GROUPS, each shown through its nearest member (csrc/device_grouped_knn.h) — the exact plan of
+ *   SELECT DISTINCT ON (doc_id) ... [WHERE pred] [AND emb <-> q <= r] ORDER BY emb <-> q LIMIT k   over a table with several rows per document.
+ * d_group_of (required) is a table over label VALUES — the allow bitmap's convention, so one label space serves both: the group of an
+ * element with label l is d_group_of[l]; an element whose label is >= group_entries takes no part, and neither does one whose group word
+ * is 0xFFFFFFFF (a caller's way to exclude rows); two elements that hold one label share its group.
+ * R(q) is hnsw_gpu_range_knn_dev's set — not vacuumed, label passes the query's bitmap where there is a filter (d_allow NULL = every label
+ * passes: allow_bits, nfilters and d_allow_of are ignored), canonical fp32 distance d <= r_q by IEEE <= where there is a radius (d_radius NULL
+ * = no radius: the comparison is switched off; a NaN radius, or a negative one under L2, selects nothing; a NaN distance is outside the
+ * contract) — further restricted to the elements that take part.  For each group g with a member in R(q), rep(g) is its member with the
+ * smallest (distance, element number).  The answer is the min(k, number of such groups) representatives with the smallest (distance,
+ * element number), written in ascending (distance, label, element number) order — hnsw_search's order.  Every distance is the search's, bit
+ * for bit.
+ *   d_labels  nq*k, unused tail = ~0          d_dists   nq*k or NULL, tail = +inf        d_idx  nq*k element numbers or NULL, tail = 0xFFFFFFFF
+ *   d_groups  nq*k or NULL: the group of each returned row, tail = 0xFFFFFFFF           d_counts  nq rows per query
+ * The de-duplication happens in the scan's top-k list, so the call is exact where over-fetching c * k rows and de-duplicating on the host
+ * is not (one document with many near chunks fills any fixed c * k).  The work per query is its list of allowed rows, as in
+ * hnsw_gpu_filtered_knn_dev, with 4 more bytes per listed row (its group word), under the same 64 MiB keep-between-calls rule.
+ * Argument rules as filtered k-NN: k outside [1, 1024], nq > 65535, a NULL d_queries / d_group_of / d_labels / d_counts, group_entries == 0,
+ * with a filter allow_bits == 0 or nfilters == 0, k and dim too large for one block's LDS (the listed form's need plus 4 (k + 1) bytes per
+ * wave): HNSW_GPU_ERR_ARG before anything is launched (outputs untouched); nq == 0: OK, nothing touched.  The call synchronises `stream`.
+ * hnsw_gpu_last_grouped_knn (hnsw_gpu_diag.h) reports its counters. */
+int hnsw_gpu_grouped_knn_dev(hnsw_gpu_index *ix, const coord_t *d_queries, size_t nq, size_t k,
+							 const uint32_t *d_group_of, size_t group_entries, const dist_t *d_radius,
+							 const uint32_t *d_allow, size_t allow_bits, size_t nfilters, const uint32_t *d_allow_of,
+							 label_t *d_labels, dist_t *d_dists, idx_t *d_idx, uint32_t *d_groups, uint32_t *d_counts, void *stream);
+/* Host-pointer form: copies in, runs on the default stream, copies out. */
+int hnsw_gpu_grouped_knn(hnsw_gpu_index *ix, const coord_t *queries, size_t nq, size_t k,
+						 const uint32_t *group_of, size_t group_entries, const dist_t *radius,
+						 const uint32_t *allow, size_t allow_bits, size_t nfilters, const uint32_t *allow_of,
+						 label_t *labels, dist_t *dists, idx_t *idx, uint32_t *groups, uint32_t *counts);
+
 /* Milliseconds the most recent search kernel of this index spent on the device,
  * from HIP events recorded on its stream around the launch (waits for it). */
 int hnsw_gpu_last_search_ms(hnsw_gpu_index *ix, float *ms);

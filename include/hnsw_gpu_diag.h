@@ -140,6 +140,13 @@ int hnsw_gpu_last_range_knn_form(hnsw_gpu_index *ix);
  * call's stream.  out[2], out[3] and out[6] are zero after a listed answer. */
 int hnsw_gpu_last_range_knn(hnsw_gpu_index *ix, uint64_t out[8]);
 
+/* The mirror's last hnsw_gpu_grouped_knn[_dev] call, hnsw_gpu_last_filtered_knn's four figures (the figures of the other families are not
+ * touched): out[0] = entries of all lists together (the list build is filtered k-NN's: elements that take no part in the grouping are
+ * listed too), out[1] = rows the scan kernel scored (the sum of the queries' own list lengths; a radius that selects nothing scans
+ * nothing), out[2] = the list build including the group words of the lists and out[3] = scan + merge + emit, both in MICROSECONDS from
+ * HIP events on the call's stream.  Zeros before the first call. */
+int hnsw_gpu_last_grouped_knn(hnsw_gpu_index *ix, uint64_t out[4]);
+
 /* The plan of the mirror's last hnsw_gpu_filtered_knn_auto[_dev] / hnsw_gpu_range_knn_auto[_dev] call: out[0] = queries of the listed class,
  * out[1] = of the loose class (0: every query was listed), out[2], out[3] = the sum of the list lengths L_q of each, out[4] = the threshold
  * in rows (loose: L_q > out[4]; ~0 where the matrix-core form has no pass for the call; HNSW_GPU_FK_AUTO_SPLIT when that knob is set),

@@ -6,7 +6,7 @@ searchBaseLayer / searchKnn loop of hnswalg.cpp as hand-written gfx950 kernels i
 implementation: every entry point fails loudly without the built HIP library and a device.
 """
 from .index import (  # noqa: F401
-    DIST_L2, DIST_COSINE, DIST_MANHATTAN, OPCLASS, LABEL_DELETED, NO_LABEL, ROWS_F16, ROWS_BF16,
+    DIST_L2, DIST_COSINE, DIST_MANHATTAN, OPCLASS, LABEL_DELETED, NO_LABEL, NO_GROUP, ROWS_F16, ROWS_BF16,
     DEFAULT_M, DEFAULT_EF_CONSTRUCTION, DEFAULT_EF_SEARCH,
     GpuIndex, SearchContext, SearchStream, make_meta, dist_batch, l2_distance, cosine_distance, manhattan_distance,
     merge_topk_torch, merge_packed_torch, LocalShardedIndex,

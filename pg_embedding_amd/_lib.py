@@ -154,6 +154,10 @@ def gpu_lib():
         L.hnsw_gpu_range_knn_auto.argtypes = [vp, i32, vp, sz, vp, sz, vp, sz, sz, vp, vp, vp, vp, vp, vp, vp]
         L.hnsw_gpu_last_filtered_knn_plan.argtypes = [vp, _u64p]
         L.hnsw_gpu_last_range_knn_plan.argtypes = [vp, _u64p]
+    if hasattr(L, "hnsw_gpu_grouped_knn_dev"):
+        L.hnsw_gpu_grouped_knn_dev.argtypes = [vp, vp, sz, sz, vp, sz, vp, vp, sz, sz, vp, vp, vp, vp, vp, vp, vp]
+        L.hnsw_gpu_grouped_knn.argtypes = [vp, vp, sz, sz, vp, sz, vp, vp, sz, sz, vp, vp, vp, vp, vp, vp]
+        L.hnsw_gpu_last_grouped_knn.argtypes = [vp, _u64p]
     L.hnsw_gpu_last_search_ms.argtypes = [vp, _f32p]
     L.hnsw_gpu_search_ms.argtypes = [vp, C.c_uint, _f32p]
     L.hnsw_gpu_last_search_slots.argtypes = [vp, _u32p]

@@ -25,7 +25,7 @@
 //                        partial counts; matrix-core form: the bound tau_q and the query's mask row
 //   4. fk_emit_kernel    one wave per query, from its key list and its count: gathers the labels of the min(k, count) winners, ranks them
 //                        by (dist, label, element) — hnsw_search's order — and writes labels, distances, element numbers, the count, the
-//                        padded tails and (radius calls) the total
+//                        padded tails and (radius calls) the total; (grouped k-NN, device_grouped_knn.h) the group of every returned row
 //
 // Selection by (dist, element), emission by (dist, label): the reference's two steps (topResults, then the sort of searchKnn's output).
 #pragma once
@@ -342,6 +342,8 @@ struct FkEmit
 	uint64_t *out_labels; float *out_dists; uint32_t *out_idx; uint32_t *out_counts;
 	uint32_t *out_totals;            // NULL, or [nq] <- count
 	unsigned long long *sum;         // NULL, or the call's sum of the counts
+	const uint32_t *groups;          // NULL, or [nq][k] the group of every key (grouped k-NN, device_grouped_knn.h) ...
+	uint32_t *out_groups;            // ... and NULL, or [nq][k] <- the group of every returned row, tail 0xFFFFFFFF
 };
 
 // One wave per query (block = 64 threads).  LDS: k winner keys | k labels.
@@ -379,6 +381,7 @@ __global__ __launch_bounds__(64) void fk_emit_kernel(const FkEmit a)
 			a.out_labels[obase + rank] = li;
 			if (a.out_dists) a.out_dists[obase + rank] = unord_f32(di);
 			if (a.out_idx) a.out_idx[obase + rank] = (uint32_t) ki;
+			if (a.out_groups) a.out_groups[obase + rank] = a.groups[obase + i];
 		}
 	}
 	for (uint32_t i = cnt + lane; i < k; i += 64)
@@ -386,6 +389,7 @@ __global__ __launch_bounds__(64) void fk_emit_kernel(const FkEmit a)
 		a.out_labels[obase + i] = ~0ull;
 		if (a.out_dists) a.out_dists[obase + i] = __builtin_inff();
 		if (a.out_idx) a.out_idx[obase + i] = LINK_NONE;
+		if (a.out_groups) a.out_groups[obase + i] = LINK_NONE;
 	}
 	if (lane == 0)
 	{

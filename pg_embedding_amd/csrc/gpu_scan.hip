@@ -1,7 +1,8 @@
 // gpu_scan.hip — batched distances (hnsw_dist_func over many rows), exhaustive k-NN: canonical scan (csrc/device_topk_scan.h), MFMA filter over
 // the f32 rows or the reduced copy (csrc/device_bf_mfma.h, csrc/device_bf_mfma16.h), and exact filtered k-NN and exact radius search, one
 // pipeline: the canonical scan over lists of allowed rows (csrc/device_filtered_knn.h) or, for loose filters, the MFMA filter with the allow
-// test at its append (csrc/device_filtered_knn_mfma.h), chosen per query in the automatic calls (csrc/device_fk_plan.h)
+// test at its append (csrc/device_filtered_knn_mfma.h), chosen per query in the automatic calls (csrc/device_fk_plan.h); and exact grouped
+// k-NN over the same lists (csrc/device_grouped_knn.h)
 // One translation unit of libhnsw_gpu.so (csrc/gpu_host.h lists them); gfx950 only, plain HIP runtime, no framework types in any signature.
 #include "gpu_host.h"
 #include "device_topk_scan.h"
@@ -10,6 +11,7 @@
 #include "device_filtered_knn.h"
 #include "device_filtered_knn_mfma.h"
 #include "device_fk_plan.h"
+#include "device_grouped_knn.h"
 
 #include <type_traits>
 
@@ -34,6 +36,7 @@ struct QueryGeom
 	size_t lds_dist() const { return (size_t) qpad * 4 + 4 * 128 * 4; }                        // image | 4 x 128 sums: dist_batch_kernel, fkm_standin_kernel
 	size_t lds_scan(size_t k) const { return lds_dist() + 4 * (k + 1) * 8; }                   // image | 4 x (k + 1) keys | 4 x 128 sums: bruteforce_kernel
 	size_t lds_listed(size_t k) const { return lds_scan(k) + 4 * 64 * 4; }                     // ... | 4 x 64 staged element numbers: fk_scan_kernel
+	size_t lds_grouped(size_t k) const { return lds_listed(k) + 4 * (k + 1) * 4; }             // ... | 4 x (k + 1) group words: gk_scan_kernel
 	size_t lds_rescore(size_t k) const { return 4 * round_up((size_t) qpad * 4 + (k + 1) * 8 + 128 * 4, 16); }   // per wave: image | k + 1 keys | 128 sums: bf_rescore_kernel, fkm_rescore_kernel
 };
 
@@ -463,7 +466,7 @@ static_assert(HNSW_GPU_RK_FORM_LISTED == HNSW_GPU_FK_FORM_LISTED && HNSW_GPU_RK_
 
 void fk_ws_free(FkWs *s)
 {
-	buf_trim({&s->cells, &s->list, &s->part, &s->mask, &s->bfs, &s->cand, &s->perm, &s->tmp}, 0);
+	buf_trim({&s->cells, &s->list, &s->part, &s->mask, &s->bfs, &s->cand, &s->perm, &s->tmp, &s->grp}, 0);
 	if (s->host) (void) hipHostFree(s->host);
 	s->host = nullptr;
 	for (hipEvent_t &e : s->ev) { if (e) (void) hipEventDestroy(e); e = nullptr; }
@@ -474,12 +477,14 @@ void fk_ws_free(FkWs *s)
 struct FkFamily
 {
 	const char *who; bool range;
+	bool grouped;                                                 // grouped k-NN: radius and filter both optional, the group table required; listed form only
 	FkWs::Diag FkWs::*diag;                                       // the pass that answered the last call (both classes of an automatic call)
 	FkWs::Diag FkWs::*filter;                                     // NULL, or: the last filter launch of the last call, whatever form answered in the end
 	FkWs::Plan FkWs::*plan;
 };
-static const FkFamily FK_KNN = { "filtered k-NN", false, &FkWs::k, &FkWs::kf, &FkWs::plan };
-static const FkFamily FK_RANGE = { "radius search", true, &FkWs::r, nullptr, &FkWs::rplan };
+static const FkFamily FK_KNN = { "filtered k-NN", false, false, &FkWs::k, &FkWs::kf, &FkWs::plan };
+static const FkFamily FK_RANGE = { "radius search", true, false, &FkWs::r, nullptr, &FkWs::rplan };
+static const FkFamily FK_GROUPED = { "grouped k-NN", false, true, &FkWs::g, nullptr, nullptr };
 
 // one call: its arguments (radius, totals: NULL in filtered k-NN), and what its list build found
 struct FkCall
@@ -489,8 +494,9 @@ struct FkCall
 	const uint32_t *allow_of; label_t *labels; dist_t *dists; idx_t *idx; uint32_t *counts, *totals; hipStream_t s;
 	FkLists fl; uint64_t *off; unsigned long long *scored; size_t nsb, total, longest;
 	bool later;                                                   // a pass that follows another of the call: its scan time counts from ev[5], not from the list build
+	const uint32_t *group_of; size_t group_entries; uint32_t *groups;   // grouped k-NN: the table over label values, and NULL or the output
 };
-struct FkTrim { FkWs *w; ~FkTrim() { buf_trim({&w->cells, &w->list, &w->part, &w->mask, &w->bfs, &w->cand, &w->perm, &w->tmp}); } };   // on EVERY way out, errors included: no buffer above 64 MiB outlives its call
+struct FkTrim { FkWs *w; ~FkTrim() { buf_trim({&w->cells, &w->list, &w->part, &w->mask, &w->bfs, &w->cand, &w->perm, &w->tmp, &w->grp}); } };   // on EVERY way out, errors included: no buffer above 64 MiB outlives its call
 
 // the matrix-core form's operands: the f32 rows, or the reduced copy the index holds (hnsw_gpu_bruteforce_reduced_dev's rule)
 static int fk_check_format(hnsw_gpu_index *ix, int format)
@@ -505,17 +511,19 @@ static int fk_check_format(hnsw_gpu_index *ix, int format)
 static int fk_check(const FkCall &c, int form, int format)
 {
 	const char *who = c.fam->who;
-	const bool range = c.fam->range, filter = c.allow || !range;
+	const bool range = c.fam->range, grouped = c.fam->grouped, filter = c.allow || !(range || grouped);
 	if (!c.ix) return fail(HNSW_GPU_ERR_ARG, "index is NULL");
 	if (c.nq == 0) return range || form == FK_LISTED ? HNSW_GPU_OK : fk_check_format(c.ix, format);
 	if (form != FK_LISTED && form != FK_MFMA) return fail(HNSW_GPU_ERR_ARG, "%s: form %d is neither listed (0) nor matrix cores (1)", who, form);
-	if (!c.queries || (range ? !c.radius : !c.allow) || !c.labels || !c.counts)
-		return fail(HNSW_GPU_ERR_ARG, "%s: NULL buffer%s", who, range ? "" : " (the filter is required: hnsw_gpu_bruteforce_dev takes none)");
+	if (!c.queries || (grouped ? !c.group_of : range ? !c.radius : !c.allow) || !c.labels || !c.counts)
+		return fail(HNSW_GPU_ERR_ARG, "%s: NULL buffer%s", who, range || grouped ? "" : " (the filter is required: hnsw_gpu_bruteforce_dev takes none)");
+	if (grouped && c.group_entries == 0) return fail(HNSW_GPU_ERR_ARG, "%s: a group table of no entries", who);
 	if (c.k == 0 || c.k > 1024) return fail(HNSW_GPU_ERR_ARG, "k %zu out of range [1, 1024]", c.k);
 	if (c.nq > 65535) return fail(HNSW_GPU_ERR_ARG, "at most 65535 queries per call");
 	if (filter && (c.allow_bits == 0 || c.nfilters == 0)) return fail(HNSW_GPU_ERR_ARG, "%s: an allow filter of no bits", who);
 	if (filter && ((c.allow_bits + 31) / 32 >= 0xFFFFFFFFull || c.nfilters >= 0xFFFFFFFFull)) return fail(HNSW_GPU_ERR_ARG, "%s: allow filter too large", who);
-	if (QueryGeom(c.ix->stride).lds_listed(c.k) > 64 * 1024) return fail(HNSW_GPU_ERR_ARG, "k/dim too large for %s", who);
+	const QueryGeom g(c.ix->stride);
+	if ((grouped ? g.lds_grouped(c.k) : g.lds_listed(c.k)) > 64 * 1024) return fail(HNSW_GPU_ERR_ARG, "k/dim too large for %s", who);
 	return form == FK_LISTED ? HNSW_GPU_OK : fk_check_format(c.ix, format);
 }
 
@@ -581,19 +589,19 @@ static int fk_lists(FkCall &c, const FkPlanHook *hook = nullptr)
 }
 
 // Splits as the exhaustive scan chooses them, from the longest run of list entries a query scans (a query with a shorter one uses fewer
-// waves: fk_waves), and room for the partial lists.  (FK_XCD_REMAP variant builds: a list long enough for it gets at least one slice per
-// XCD to keep apart.)
-static int fk_splits(const FkCall &c, size_t longest, uint32_t *out)
+// waves: fk_waves), and room for the partial lists (entry_bytes: a key, and in grouped k-NN its group word).  (FK_XCD_REMAP variant builds:
+// a list long enough for it gets at least one slice per XCD to keep apart.)
+static int fk_splits(const FkCall &c, size_t longest, uint32_t *out, size_t entry_bytes = 8)
 {
 	hnsw_gpu_index *ix = c.ix;
 	const size_t nq = c.nq, k = c.k;
 	uint32_t splits = (uint32_t) std::max<size_t>(1, std::min<size_t>(64, (size_t) (4 * ix->num_cu) / nq));
 	if (FK_XCD_REMAP && longest >= 8192) splits = std::max(splits, 8u);
 	splits = (uint32_t) std::min<size_t>(splits, std::max<size_t>(1, longest / (4 * FK_WAVE_ROWS)));
-	while (splits > 1 && nq * splits * 4 * k * 8 > FK_PART_BYTES) splits /= 2;
+	while (splits > 1 && nq * splits * 4 * k * entry_bytes > FK_PART_BYTES) splits /= 2;
 	*out = splits;
 	if (!longest) return HNSW_GPU_OK;                             // (no list, no scan: the merge kernel reads no partial list)
-	return buf_reserve(&ix->fk.part, nq * splits * 4 * k * 8, c.fam->who, "the partial result lists");
+	return buf_reserve(&ix->fk.part, nq * splits * 4 * k * entry_bytes, c.fam->who, "the partial result lists");
 }
 
 // One pass over the built lists (and masks).  format < 0: the listed form — the scan over every query's whole list, merge, emit.  Else
@@ -964,6 +972,88 @@ static int fk_run(FkCall c, int form, int format, bool aut, uint8_t *d_plan)
 	return HNSW_GPU_OK;
 }
 
+// ---- exact grouped k-NN: the listed form's host path with the grouped list in the scan and the merge (device_grouped_knn.h) ----
+// behind the list build: the group word of every list entry (counted with the build's time, like the masks of the matrix-core form)
+static int gk_groups(FkCall &c)
+{
+	FkWs *fw = &c.ix->fk;
+	if (int rc = buf_reserve(&fw->grp, c.total * 4, c.fam->who, "the group words of the lists")) return rc;
+	if (c.total)
+	{
+		const GkGroups gg = { (const uint32_t *) fw->list.p, c.total, c.ix->labels, c.group_of, c.group_entries, (uint32_t *) fw->grp.p };
+		const uint32_t blocks = (uint32_t) std::min<size_t>((c.total + 255) / 256, (size_t) c.ix->num_cu * 8);
+		hipLaunchKernelGGL(gk_groups_kernel, dim3(blocks), dim3(256), 0, c.s, gg);
+		HIPCHK(hipGetLastError());
+	}
+	HIPCHK(hipEventRecord(fw->ev[1], c.s));
+	return HNSW_GPU_OK;
+}
+
+// the scan over every query's whole list -> merge -> emit: fk_pass's listed form, pairs of (key, group) in place of keys
+static int gk_pass(FkCall &c)
+{
+	hnsw_gpu_index *ix = c.ix;
+	FkWs *fw = &ix->fk;
+	hipStream_t s = c.s;
+	const size_t nq = c.nq, k = c.k;
+	const int func = (int) ix->meta.dist_func;
+	const QueryGeom g(ix->stride);
+	uint32_t splits = 1;
+	int rc = fk_splits(c, c.longest, &splits, 12);
+	if (rc) return rc;
+	const size_t o_grp = round_up(nq * k * 8, 256), o_cnt = o_grp + round_up(nq * k * 4, 256), total = o_cnt + round_up(nq * 4, 256);
+	if ((rc = buf_reserve(&fw->bfs, total, c.fam->who, "the per-query scratch"))) return rc;
+	char *B = (char *) fw->bfs.p;
+	uint64_t *keys = (uint64_t *) B;
+	uint32_t *groups = (uint32_t *) (B + o_grp), *rcount = (uint32_t *) (B + o_cnt);
+	GkMerge gm;
+	memset(&gm, 0, sizeof(gm));
+	FkScan &fs = gm.g.s;
+	fs.vec = ix->vec; fs.dim = (uint32_t) ix->meta.dim; fs.stride = ix->stride; fs.nchunks = g.nchunks; fs.kiters = g.kiters; fs.qpad_floats = g.qpad;
+	fs.queries = c.queries; fs.nq = (uint32_t) nq; fs.k = (uint32_t) k; fs.splits = splits;
+	fs.list = (const uint32_t *) fw->list.p; fs.off = c.off; fs.nseg = c.fl.nseg; fs.allow_of = c.allow_of;
+	fs.part = (uint64_t *) fw->part.p; fs.scored = c.scored; fs.radius = c.radius; fs.func = func;
+	gm.g.glist = (const uint32_t *) fw->grp.p;
+	gm.g.gpart = (uint32_t *) ((char *) fw->part.p + nq * splits * 4 * k * 8);     // the partial groups behind the partial keys
+	gm.keys = keys; gm.groups = groups; gm.count = rcount;
+	if (c.longest)
+	{
+		const dim3 grid((uint32_t) round_up((size_t) splits * nq, 8));
+		with_func(func, [&](auto F) { hipLaunchKernelGGL(gk_scan_kernel<decltype(F)::value>, grid, dim3(256), g.lds_grouped(k), s, gm.g); });
+	}
+	hipLaunchKernelGGL(gk_merge_kernel, dim3((uint32_t) nq), dim3(64), (k + 1) * 12, s, gm);
+	const FkEmit fe = { keys, rcount, (uint32_t) k, ix->labels, (uint32_t) ix->n, c.labels, c.dists, c.idx, c.counts, nullptr, nullptr, groups, c.groups };
+	hipLaunchKernelGGL(fk_emit_kernel, dim3((uint32_t) nq), dim3(64), k * 16, s, fe);
+	hipError_t e = hipGetLastError();
+	if (e == hipSuccess) e = hipEventRecord(fw->ev[2], s);
+	if (e == hipSuccess) e = hipMemcpyAsync(&fw->host[2], c.scored, 8, hipMemcpyDeviceToHost, s);
+	const hipError_t e2 = hipStreamSynchronize(s);
+	if (e == hipSuccess) e = e2;
+	if (e != hipSuccess) return fail(HNSW_GPU_ERR_HIP, "%s: %s", c.fam->who, hipGetErrorString(e));
+	FkWs::Diag &m = fw->*c.fam->diag;
+	m.listed = c.total; m.scored = fw->host[2];
+	(void) hipEventElapsedTime(&m.build_ms, fw->ev[0], fw->ev[1]);
+	(void) hipEventElapsedTime(&m.call_ms, fw->ev[0], fw->ev[2]);
+	(void) hipEventElapsedTime(&m.scan_ms, fw->ev[1], fw->ev[2]);
+	m.form = HNSW_GPU_FK_FORM_LISTED;
+	return HNSW_GPU_OK;
+}
+
+static int gk_run(FkCall c)
+{
+	std::unique_lock<std::recursive_mutex> lock_;
+	if (c.ix) lock_ = std::unique_lock<std::recursive_mutex>(c.ix->mu);
+	if (int rc0 = fk_check(c, FK_LISTED, ROWS_F32)) return rc0;
+	if (c.nq == 0) return HNSW_GPU_OK;
+	if (!c.allow) { c.allow_bits = 0; c.nfilters = 1; c.allow_of = nullptr; }   // (fk_run: ONE implicit bitmap that every label passes)
+	FkTrim trim_{&c.ix->fk};
+	int rc = fk_begin(c);
+	if (!rc) rc = fk_lists(c);
+	if (!rc) rc = gk_groups(c);
+	if (!rc) rc = gk_pass(c);
+	return rc;
+}
+
 // the driver of every host-pointer entry point: copy in, run on the default stream, copy out
 static int fk_host(const FkCall &h, int form, int format, bool aut, uint8_t *plan)
 {
@@ -977,7 +1067,8 @@ static int fk_host(const FkCall &h, int form, int format, bool aut, uint8_t *pla
 	const bool of = h.allow && h.allow_of;
 	const size_t qb = round_up(nq * dim * 4, 256), rb = round_up(h.radius ? nq * 4 : 0, 256), fb = round_up(h.allow ? h.nfilters * words * 4 : 0, 256),
 				 ob = round_up(of ? nq * 4 : 0, 256), lb = round_up(nq * k * 8, 256), db = round_up(nq * k * 4, 256), cb = round_up(nq * 4, 256);
-	int rc = ensure_scratch(ix, qb + rb + fb + ob + lb + 2 * db + 2 * cb + (plan ? nq : 0));
+	const size_t tb = round_up(h.group_of ? h.group_entries * 4 : 0, 256), o_tab = qb + rb + fb + ob + lb + 2 * db + 2 * cb + round_up(plan ? nq : 0, 256);
+	int rc = ensure_scratch(ix, o_tab + tb + (h.groups ? db : 0));   // (grouped k-NN: the group table and the groups behind everything else)
 	if (rc) return rc;
 	char *p = (char *) ix->scratch, *o = p + qb + rb + fb + ob;
 	FkCall d = h;
@@ -986,16 +1077,19 @@ static int fk_host(const FkCall &h, int form, int format, bool aut, uint8_t *pla
 	d.labels = (uint64_t *) o; d.dists = (float *) (o + lb); d.idx = (uint32_t *) (o + lb + db); d.counts = (uint32_t *) (o + lb + 2 * db);
 	d.totals = h.totals ? (uint32_t *) (o + lb + 2 * db + cb) : nullptr; d.s = nullptr;
 	uint8_t *dp = plan ? (uint8_t *) (o + lb + 2 * db + 2 * cb) : nullptr;
+	d.group_of = h.group_of ? (uint32_t *) (p + o_tab) : nullptr; d.groups = h.groups ? (uint32_t *) (p + o_tab + tb) : nullptr;
+	if (h.group_of) HIPCHK(hipMemcpy((void *) d.group_of, h.group_of, h.group_entries * 4, hipMemcpyHostToDevice));
 	HIPCHK(hipMemcpy((void *) d.queries, h.queries, nq * dim * 4, hipMemcpyHostToDevice));
 	if (h.radius) HIPCHK(hipMemcpy((void *) d.radius, h.radius, nq * 4, hipMemcpyHostToDevice));
 	if (h.allow) HIPCHK(hipMemcpy((void *) d.allow, h.allow, h.nfilters * words * 4, hipMemcpyHostToDevice));
 	if (of) HIPCHK(hipMemcpy((void *) d.allow_of, h.allow_of, nq * 4, hipMemcpyHostToDevice));
-	if ((rc = fk_run(d, form, format, aut, dp))) return rc;
+	if ((rc = h.fam->grouped ? gk_run(d) : fk_run(d, form, format, aut, dp))) return rc;
 	HIPCHK(hipMemcpy(h.labels, d.labels, nq * k * 8, hipMemcpyDeviceToHost));
 	if (h.dists) HIPCHK(hipMemcpy(h.dists, d.dists, nq * k * 4, hipMemcpyDeviceToHost));
 	if (h.idx) HIPCHK(hipMemcpy(h.idx, d.idx, nq * k * 4, hipMemcpyDeviceToHost));
 	HIPCHK(hipMemcpy(h.counts, d.counts, nq * 4, hipMemcpyDeviceToHost));
 	if (h.totals) HIPCHK(hipMemcpy(h.totals, d.totals, nq * 4, hipMemcpyDeviceToHost));
+	if (h.groups) HIPCHK(hipMemcpy(h.groups, d.groups, nq * k * 4, hipMemcpyDeviceToHost));
 	if (plan) HIPCHK(hipMemcpy(plan, dp, nq, hipMemcpyDeviceToHost));
 	return HNSW_GPU_OK;
 }
@@ -1087,6 +1181,31 @@ extern "C" int hnsw_gpu_range_knn_auto(hnsw_gpu_index *ix, int format, const coo
 	return fk_host(fk_range_call(ix, queries, nq, radius, k, allow, allow_bits, nfilters, allow_of, labels, dists, idx, counts, totals, nullptr), FK_MFMA, format, true, plan);
 }
 
+static FkCall gk_call(hnsw_gpu_index *ix, const coord_t *queries, size_t nq, size_t k, const uint32_t *group_of, size_t group_entries, const dist_t *radius,
+					  const uint32_t *allow, size_t allow_bits, size_t nfilters, const uint32_t *allow_of, label_t *labels, dist_t *dists, idx_t *idx,
+					  uint32_t *groups, uint32_t *counts, void *stream)
+{
+	FkCall c = { &FK_GROUPED, ix, queries, nq, radius, k, allow, allow_bits, nfilters, allow_of, labels, dists, idx, counts, nullptr, (hipStream_t) stream };
+	c.group_of = group_of; c.group_entries = group_entries; c.groups = groups;
+	return c;
+}
+
+extern "C" int hnsw_gpu_grouped_knn_dev(hnsw_gpu_index *ix, const coord_t *d_queries, size_t nq, size_t k, const uint32_t *d_group_of, size_t group_entries,
+										const dist_t *d_radius, const uint32_t *d_allow, size_t allow_bits, size_t nfilters, const uint32_t *d_allow_of,
+										label_t *d_labels, dist_t *d_dists, idx_t *d_idx, uint32_t *d_groups, uint32_t *d_counts, void *stream)
+{
+	return gk_run(gk_call(ix, d_queries, nq, k, d_group_of, group_entries, d_radius, d_allow, allow_bits, nfilters, d_allow_of, d_labels, d_dists, d_idx, d_groups,
+						  d_counts, stream));
+}
+
+extern "C" int hnsw_gpu_grouped_knn(hnsw_gpu_index *ix, const coord_t *queries, size_t nq, size_t k, const uint32_t *group_of, size_t group_entries,
+									const dist_t *radius, const uint32_t *allow, size_t allow_bits, size_t nfilters, const uint32_t *allow_of, label_t *labels,
+									dist_t *dists, idx_t *idx, uint32_t *groups, uint32_t *counts)
+{
+	return fk_host(gk_call(ix, queries, nq, k, group_of, group_entries, radius, allow, allow_bits, nfilters, allow_of, labels, dists, idx, groups, counts, nullptr),
+				   FK_LISTED, ROWS_F32, false, nullptr);
+}
+
 // ---- what the last call of either family left (include/hnsw_gpu_diag.h) -------------------------------------------------------------------
 static int fk_plan_out(hnsw_gpu_index *ix, FkWs::Plan FkWs::*which, uint64_t out[8])
 {
@@ -1107,6 +1226,15 @@ extern "C" int hnsw_gpu_last_filtered_knn(hnsw_gpu_index *ix, uint64_t out[4])
 	if (!ix || !out) return fail(HNSW_GPU_ERR_ARG, "NULL argument");
 	std::lock_guard<std::recursive_mutex> lock_(ix->mu);
 	const FkWs::Diag &m = ix->fk.k;
+	out[0] = m.listed; out[1] = m.scored; out[2] = fk_us(m.build_ms); out[3] = fk_us(m.scan_ms);
+	return HNSW_GPU_OK;
+}
+
+extern "C" int hnsw_gpu_last_grouped_knn(hnsw_gpu_index *ix, uint64_t out[4])
+{
+	if (!ix || !out) return fail(HNSW_GPU_ERR_ARG, "NULL argument");
+	std::lock_guard<std::recursive_mutex> lock_(ix->mu);
+	const FkWs::Diag &m = ix->fk.g;
 	out[0] = m.listed; out[1] = m.scored; out[2] = fk_us(m.build_ms); out[3] = fk_us(m.scan_ms);
 	return HNSW_GPU_OK;
 }

@@ -19,6 +19,7 @@ OPCLASS = {"ann_l2_ops": DIST_L2, "ann_cos_ops": DIST_COSINE, "ann_manhattan_ops
 DEFAULT_M, DEFAULT_EF_CONSTRUCTION, DEFAULT_EF_SEARCH = 100, 16, 64   # embedding.c:111-113
 LABEL_DELETED = np.uint64(1) << np.uint64(48)          # embedding.c:44,948-953
 NO_LABEL = np.uint64(0xFFFFFFFFFFFFFFFF)
+NO_GROUP = 0xFFFFFFFF                                   # a group_of word: the label takes no part; a groups output word: no row (grouped_knn)
 # reduced rows (include/hnsw_gpu.h HNSW_GPU_ROWS_*): the 16-bit copy a search may walk over before its exact fp32 re-rank
 ROWS_F32, ROWS_F16, ROWS_BF16 = 0, 1, 2
 _ROWS = {None: ROWS_F32, "f32": ROWS_F32, "f16": ROWS_F16, "bf16": ROWS_BF16}
@@ -606,6 +607,75 @@ class GpuIndex:
         check(self.L.hnsw_gpu_last_range_knn(self._h, v), "hnsw_gpu_last_range_knn")
         return {"listed": int(v[0]), "rows_scored": int(v[1]), "dist_pass": int(v[2]), "appended": int(v[3]), "totals": int(v[4]),
                 "build_ms": v[5] / 1000.0, "filter_ms": v[6] / 1000.0, "call_ms": v[7] / 1000.0}
+
+    # ---------------------------------------------------------------- exact grouped k-NN
+    def grouped_knn(self, queries: np.ndarray, k: int, group_of, allow=None, allow_of=None, radius=None, return_idx: bool = False):
+        """Exact k nearest distinct GROUPS per query, each through its nearest member, host buffers (hnsw_gpu_grouped_knn): the plan of
+        SELECT DISTINCT ON (doc_id) ... ORDER BY emb <-> q LIMIT k over a table with several rows per document.  group_of: a uint32 / int32
+        array over label VALUES — the group of an element with label l is group_of[l]; a label >= len(group_of) or a group word NO_GROUP
+        (0xFFFFFFFF, -1) takes no part.  allow / allow_of as in range_knn() (allow=None: every label passes); radius: None (no radius), a
+        scalar or one value per query (inclusive; NaN selects nothing).  Returns a dict: labels [nq, k] u64 in ascending (distance, label)
+        order (tail ~0), dists [nq, k] f32 (tail +inf), groups [nq, k] u32 = the group of each row (tail 0xFFFFFFFF), counts [nq] u32 =
+        min(k, groups with a member in range), and with return_idx=True idx [nq, k] u32 element numbers (tail 0xFFFFFFFF)."""
+        queries = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, self.meta.dim)
+        nq, k = queries.shape[0], int(k)
+        tab = np.asarray(group_of)
+        if tab.dtype not in (np.uint32, np.int32) or tab.ndim != 1:
+            raise ValueError("group_of is a uint32 or int32 array over label values")
+        tab = np.ascontiguousarray(tab).view(np.uint32)
+        rad = None if radius is None else np.ascontiguousarray(np.broadcast_to(np.asarray(radius, dtype=np.float32).reshape(-1), (nq,)))
+        words, bits, nf = _pack_allow_numpy(allow)
+        of = None if allow_of is None or words is None else np.ascontiguousarray(allow_of, dtype=np.uint32).reshape(nq)
+        out = {"labels": np.empty((nq, k), np.uint64), "dists": np.empty((nq, k), np.float32), "groups": np.empty((nq, k), np.uint32),
+               "counts": np.empty(nq, np.uint32)}
+        if return_idx:
+            out["idx"] = np.empty((nq, k), np.uint32)
+        check(self.L.hnsw_gpu_grouped_knn(self._h, queries.ctypes.data, nq, k, tab.ctypes.data, tab.shape[0], None if rad is None else rad.ctypes.data,
+                                          None if words is None else words.ctypes.data, bits, nf, None if of is None else of.ctypes.data,
+                                          out["labels"].ctypes.data, out["dists"].ctypes.data, out["idx"].ctypes.data if return_idx else None,
+                                          out["groups"].ctypes.data, out["counts"].ctypes.data), "hnsw_gpu_grouped_knn")
+        return out
+
+    def grouped_knn_torch(self, queries, k: int, group_of, allow=None, allow_of=None, radius=None, return_idx: bool = False):
+        """grouped_knn() with everything resident in HBM (hnsw_gpu_grouped_knn_dev on torch's current stream, which the call synchronises).
+        group_of: an int32 (the bits of a uint32) or uint32 tensor over label values; allow / allow_of as in filtered_knn_torch(), allow=None:
+        every label passes; radius: None, a number or a float tensor [nq].  Returns a dict: labels [nq, k] int64 (tail -1), dists [nq, k]
+        (tail +inf), groups [nq, k] int32 (tail -1), counts [nq] int32, idx [nq, k] int32 (tail -1) with return_idx=True."""
+        torch = _torch()
+        assert queries.is_cuda and queries.dtype == torch.float32 and queries.is_contiguous()
+        nq, k, dev = queries.shape[0], int(k), queries.device
+        if group_of.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) or group_of.dim() != 1:
+            raise ValueError("group_of is an int32 or uint32 tensor over label values")
+        tab = group_of.to(dev).contiguous()
+        if radius is None:
+            rad = None
+        elif torch.is_tensor(radius):
+            rad = radius.to(device=dev, dtype=torch.float32).reshape(-1).expand(nq).contiguous()
+        else:
+            rad = torch.full((nq,), float(radius), dtype=torch.float32, device=dev)
+        words, bits, nf = _pack_allow_torch(allow, dev)
+        of = None if allow_of is None or words is None else allow_of.to(device=dev, dtype=torch.int32).contiguous()
+        if of is not None and of.numel() != nq:
+            raise ValueError("allow_of names one filter per query")
+        out = {"labels": torch.empty((nq, k), dtype=torch.int64, device=dev),
+               "dists": torch.empty((nq, k), dtype=torch.float32, device=dev),
+               "groups": torch.empty((nq, k), dtype=torch.int32, device=dev),
+               "counts": torch.empty(nq, dtype=torch.int32, device=dev)}
+        if return_idx:
+            out["idx"] = torch.empty((nq, k), dtype=torch.int32, device=dev)
+        s = torch.cuda.current_stream(dev).cuda_stream
+        check(self.L.hnsw_gpu_grouped_knn_dev(self._h, queries.data_ptr(), nq, k, tab.data_ptr(), tab.numel(), _dptr(rad), _dptr(words), bits, nf, _dptr(of),
+                                              out["labels"].data_ptr(), out["dists"].data_ptr(), _dptr(out.get("idx")), out["groups"].data_ptr(),
+                                              out["counts"].data_ptr(), s), "hnsw_gpu_grouped_knn_dev")
+        return out
+
+    def last_grouped_knn(self) -> dict:
+        """The last grouped_knn call on this mirror (hnsw_gpu_last_grouped_knn), last_filtered_knn()'s four figures: entries of all lists,
+        rows the scan scored (= the sum of the queries' own list lengths), list-build ms (with the lists' group words) and scan + merge +
+        emit ms."""
+        v = (C.c_uint64 * 4)()
+        check(self.L.hnsw_gpu_last_grouped_knn(self._h, v), "hnsw_gpu_last_grouped_knn")
+        return {"listed": int(v[0]), "rows_scored": int(v[1]), "build_ms": v[2] / 1000.0, "scan_ms": v[3] / 1000.0}
 
     def last_search_ms(self, back: int = 0) -> float:
         """Device time of the search kernel launched `back` launches ago (HIP events recorded on
