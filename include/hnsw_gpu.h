@@ -352,7 +352,7 @@ int hnsw_gpu_range_knn_auto(hnsw_gpu_index *ix, int format, const coord_t *queri
  * Argument rules as filtered k-NN: k outside [1, 1024], nq > 65535, a NULL d_queries / d_group_of / d_labels / d_counts, group_entries == 0,
  * with a filter allow_bits == 0 or nfilters == 0, k and dim too large for one block's LDS (the listed form's need plus 4 (k + 1) bytes per
  * wave): HNSW_GPU_ERR_ARG before anything is launched (outputs untouched); nq == 0: OK, nothing touched.  The call synchronises `stream`.
- * hnsw_gpu_last_grouped_knn (hnsw_gpu_diag.h) reports its counters. */
+ * hnsw_gpu_last_grouped_knn (hnsw_gpu_diag.h) reports its counters.  This is the LISTED form: every allowed row of every query is scored. */
 int hnsw_gpu_grouped_knn_dev(hnsw_gpu_index *ix, const coord_t *d_queries, size_t nq, size_t k,
 							 const uint32_t *d_group_of, size_t group_entries, const dist_t *d_radius,
 							 const uint32_t *d_allow, size_t allow_bits, size_t nfilters, const uint32_t *d_allow_of,
@@ -362,6 +362,36 @@ int hnsw_gpu_grouped_knn(hnsw_gpu_index *ix, const coord_t *queries, size_t nq, 
 						 const uint32_t *group_of, size_t group_entries, const dist_t *radius,
 						 const uint32_t *allow, size_t allow_bits, size_t nfilters, const uint32_t *allow_of,
 						 label_t *labels, dist_t *dists, idx_t *idx, uint32_t *groups, uint32_t *counts);
+
+/* The matrix-core form of grouped k-NN, for loose filters and for no filter (csrc/device_grouped_knn_mfma.h):
+ * hnsw_gpu_grouped_knn_dev's answer, bit for bit, with the Q x N part on the matrix cores as in hnsw_gpu_filtered_knn_mfma_dev.  The bound of
+ * a query is the key of the k-th DISTINCT GROUP of a sample of its list (with a radius: at most the radius), the row masks hold the allowed
+ * rows that take part, and the filter's survivors are scored canonically into the same de-duplicating list.  format: HNSW_GPU_ROWS_F32, or
+ * _F16 / _BF16 = the reduced copy the index holds (else HNSW_GPU_ERR_ARG, outputs untouched).  The listed form answers, with the same bytes:
+ * Manhattan, fewer than 4096 rows, a device other than gfx950, a (dim, k) whose re-score does not fit one block's LDS, a call with no list
+ * longer than its sample; a candidate list that overflows sends a 16-bit pass to f32 and an f32 pass to the listed form.  Arguments and
+ * argument rules are hnsw_gpu_grouped_knn_dev's.  hnsw_gpu_last_grouped_knn_form names the form that answered, hnsw_gpu_last_grouped_knn_mfma
+ * reports the filter's counters (hnsw_gpu_diag.h).  The sample is fk_sample_len's with k * HNSW_GPU_GK_SAMPLE_FACTOR in place of k. */
+int hnsw_gpu_grouped_knn_mfma_dev(hnsw_gpu_index *ix, int format, const coord_t *d_queries, size_t nq, size_t k,
+								  const uint32_t *d_group_of, size_t group_entries, const dist_t *d_radius,
+								  const uint32_t *d_allow, size_t allow_bits, size_t nfilters, const uint32_t *d_allow_of,
+								  label_t *d_labels, dist_t *d_dists, idx_t *d_idx, uint32_t *d_groups, uint32_t *d_counts, void *stream);
+int hnsw_gpu_grouped_knn_mfma(hnsw_gpu_index *ix, int format, const coord_t *queries, size_t nq, size_t k,
+							  const uint32_t *group_of, size_t group_entries, const dist_t *radius,
+							  const uint32_t *allow, size_t allow_bits, size_t nfilters, const uint32_t *allow_of,
+							  label_t *labels, dist_t *dists, idx_t *idx, uint32_t *groups, uint32_t *counts);
+/* The automatic call: the form chosen per query from its list length, as hnsw_gpu_filtered_knn_auto_dev chooses it (same plan kernel, cost
+ * model and knob); tight queries through the listed form, loose ones through one matrix-core pass, over one build of the lists, group words
+ * and masks.  Without a filter, or with d_allow_of NULL, the whole call goes one way.  d_plan: nq bytes or NULL, 0 = listed, 1 = loose.
+ * hnsw_gpu_last_grouped_knn_plan (hnsw_gpu_diag.h) reports the plan. */
+int hnsw_gpu_grouped_knn_auto_dev(hnsw_gpu_index *ix, int format, const coord_t *d_queries, size_t nq, size_t k,
+								  const uint32_t *d_group_of, size_t group_entries, const dist_t *d_radius,
+								  const uint32_t *d_allow, size_t allow_bits, size_t nfilters, const uint32_t *d_allow_of,
+								  label_t *d_labels, dist_t *d_dists, idx_t *d_idx, uint32_t *d_groups, uint32_t *d_counts, uint8_t *d_plan, void *stream);
+int hnsw_gpu_grouped_knn_auto(hnsw_gpu_index *ix, int format, const coord_t *queries, size_t nq, size_t k,
+							  const uint32_t *group_of, size_t group_entries, const dist_t *radius,
+							  const uint32_t *allow, size_t allow_bits, size_t nfilters, const uint32_t *allow_of,
+							  label_t *labels, dist_t *dists, idx_t *idx, uint32_t *groups, uint32_t *counts, uint8_t *plan);
 
 /* Milliseconds the most recent search kernel of this index spent on the device,
  * from HIP events recorded on its stream around the launch (waits for it). */

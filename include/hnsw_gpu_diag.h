@@ -140,18 +140,29 @@ int hnsw_gpu_last_range_knn_form(hnsw_gpu_index *ix);
  * call's stream.  out[2], out[3] and out[6] are zero after a listed answer. */
 int hnsw_gpu_last_range_knn(hnsw_gpu_index *ix, uint64_t out[8]);
 
-/* The mirror's last hnsw_gpu_grouped_knn[_dev] call, hnsw_gpu_last_filtered_knn's four figures (the figures of the other families are not
- * touched): out[0] = entries of all lists together (the list build is filtered k-NN's: elements that take no part in the grouping are
+/* The pass that answered the mirror's last grouped k-NN call, through whichever entry point (hnsw_gpu_grouped_knn[_dev], _mfma[_dev],
+ * _auto[_dev]), in hnsw_gpu_last_filtered_knn's four figures.  The figures of filtered k-NN and of radius search are not touched.
+ * out[0] = entries of all lists together (the list build is filtered k-NN's: elements that take no part in the grouping are
  * listed too), out[1] = rows the scan kernel scored (the sum of the queries' own list lengths; a radius that selects nothing scans
  * nothing), out[2] = the list build including the group words of the lists and out[3] = scan + merge + emit, both in MICROSECONDS from
- * HIP events on the call's stream.  Zeros before the first call. */
+ * HIP events on the call's stream.  Zeros before the first call.  After a call that the matrix-core form answered: out[1] = the rows of the
+ * sample scans, out[2] includes the elements' group words and the row masks. */
 int hnsw_gpu_last_grouped_knn(hnsw_gpu_index *ix, uint64_t out[4]);
+/* The form that answered the last grouped k-NN call that ended well (HNSW_GPU_FK_FORM_*), -1 before the first; the last filter launch of
+ * that call, hnsw_gpu_last_filtered_knn_mfma's seven figures (zeros when it ran none); the plan of the last hnsw_gpu_grouped_knn_auto[_dev]
+ * call, hnsw_gpu_last_filtered_knn_plan's eight figures. */
+int hnsw_gpu_last_grouped_knn_form(hnsw_gpu_index *ix);
+int hnsw_gpu_last_grouped_knn_mfma(hnsw_gpu_index *ix, uint64_t out[7]);
+int hnsw_gpu_last_grouped_knn_plan(hnsw_gpu_index *ix, uint64_t out[8]);
+/* The queries whose candidate list overflowed in that last filter launch (then the call was handed down: 16-bit operands to f32, f32 to
+ * the listed form); 0 when the call ran no filter, -1 for a NULL index. */
+long long hnsw_gpu_last_grouped_knn_overflowed(hnsw_gpu_index *ix);
 
 /* The plan of the mirror's last hnsw_gpu_filtered_knn_auto[_dev] / hnsw_gpu_range_knn_auto[_dev] call: out[0] = queries of the listed class,
  * out[1] = of the loose class (0: every query was listed), out[2], out[3] = the sum of the list lengths L_q of each, out[4] = the threshold
  * in rows (loose: L_q > out[4]; ~0 where the matrix-core form has no pass for the call; HNSW_GPU_FK_AUTO_SPLIT when that knob is set),
  * out[5] = the model's listed cost and out[6] = its matrix-core cost of the queries above the threshold, in MICROSECONDS (the loose class
- * runs when out[5] > out[6], and its longest list is longer than S_min), out[7] = the form that answered the loose class after any
+ * runs when out[5] > out[6], and its longest list is longer than its sample), out[7] = the form that answered the loose class after any
  * fallback (HNSW_GPU_FK_FORM_*; listed when there was none).  After such a call hnsw_gpu_last_filtered_knn_form / hnsw_gpu_last_range_knn_form
  * name the loose class's form when there was one, else listed, and the counters of hnsw_gpu_last_filtered_knn / hnsw_gpu_last_range_knn
  * are the sums over both classes (filter figures: the loose class's).  Zeros before the first such call. */

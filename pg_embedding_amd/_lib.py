@@ -158,6 +158,16 @@ def gpu_lib():
         L.hnsw_gpu_grouped_knn_dev.argtypes = [vp, vp, sz, sz, vp, sz, vp, vp, sz, sz, vp, vp, vp, vp, vp, vp, vp]
         L.hnsw_gpu_grouped_knn.argtypes = [vp, vp, sz, sz, vp, sz, vp, vp, sz, sz, vp, vp, vp, vp, vp, vp]
         L.hnsw_gpu_last_grouped_knn.argtypes = [vp, _u64p]
+    if hasattr(L, "hnsw_gpu_grouped_knn_mfma_dev"):
+        L.hnsw_gpu_grouped_knn_mfma_dev.argtypes = [vp, i32, vp, sz, sz, vp, sz, vp, vp, sz, sz, vp, vp, vp, vp, vp, vp, vp]
+        L.hnsw_gpu_grouped_knn_mfma.argtypes = [vp, i32, vp, sz, sz, vp, sz, vp, vp, sz, sz, vp, vp, vp, vp, vp, vp]
+        L.hnsw_gpu_grouped_knn_auto_dev.argtypes = [vp, i32, vp, sz, sz, vp, sz, vp, vp, sz, sz, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.hnsw_gpu_grouped_knn_auto.argtypes = [vp, i32, vp, sz, sz, vp, sz, vp, vp, sz, sz, vp, vp, vp, vp, vp, vp, vp]
+        L.hnsw_gpu_last_grouped_knn_form.argtypes = [vp]
+        L.hnsw_gpu_last_grouped_knn_mfma.argtypes = [vp, _u64p]
+        L.hnsw_gpu_last_grouped_knn_plan.argtypes = [vp, _u64p]
+        L.hnsw_gpu_last_grouped_knn_overflowed.argtypes = [vp]
+        L.hnsw_gpu_last_grouped_knn_overflowed.restype = C.c_longlong
     L.hnsw_gpu_last_search_ms.argtypes = [vp, _f32p]
     L.hnsw_gpu_search_ms.argtypes = [vp, C.c_uint, _f32p]
     L.hnsw_gpu_last_search_slots.argtypes = [vp, _u32p]

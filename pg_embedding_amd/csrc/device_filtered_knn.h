@@ -192,6 +192,7 @@ struct FkScan
 	uint32_t *pcount;                // [nq][splits * 4] qualifying entries of every wave's slice
 	unsigned long long *scored;      // rows scored by the call (one atomic per wave)
 	uint32_t smin;                   // 0: a query's whole list; else the matrix-core form's scan: its sample (fk_sample_len)
+	uint32_t sample_k;               // the k of the sample rule: k (grouped k-NN: k * its sample factor, device_grouped_knn_mfma.h)
 	uint32_t skip_samples;           // matrix-core form with totals: only the lists that are scanned whole
 	const float *radius;             // NULL: no threshold, every scanned row qualifies; else [nq]
 	int func;
@@ -242,7 +243,7 @@ __device__ __forceinline__ void fk_list_of(const FkScan &a, uint32_t qi, const u
 	const uint64_t o = a.off[(size_t) b * a.nseg];
 	list = a.list + o;
 	const uint32_t full = (uint32_t) (a.off[(size_t) (b + 1) * a.nseg] - o);      // (a list is a subset of the < 2^32 elements)
-	len = a.smin ? fk_sample_len(full, a.smin, a.k) : full;
+	len = a.smin ? fk_sample_len(full, a.smin, a.sample_k) : full;
 	whole = len == full;
 	if ((!whole && a.skip_samples) || (a.radius && rk_selects_nothing(a.radius[qi], a.func))) len = 0;
 }

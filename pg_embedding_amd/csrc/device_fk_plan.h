@@ -147,6 +147,7 @@ struct FkScatter
 	const uint32_t *perm; uint32_t first, count, k;
 	const uint64_t *labels; const float *dists; const uint32_t *idx; const uint32_t *counts; const uint32_t *totals;   // [nq][k] / [nq] in perm[] order
 	uint64_t *out_labels; float *out_dists; uint32_t *out_idx; uint32_t *out_counts; uint32_t *out_totals;             // the caller's; dists / idx / totals may be NULL
+	const uint32_t *groups; uint32_t *out_groups;                    // grouped k-NN: [nq][k] in perm[] order, and the caller's; NULL: none
 };
 
 // grid = ceil(count * k / 256) blocks of 256: thread t moves entry t % k of position first + t / k
@@ -160,6 +161,7 @@ __global__ __launch_bounds__(256) void fkp_scatter_kernel(const FkScatter a)
 	a.out_labels[dst] = a.labels[src];
 	if (a.out_dists) a.out_dists[dst] = a.dists[src];
 	if (a.out_idx) a.out_idx[dst] = a.idx[src];
+	if (a.out_groups) a.out_groups[dst] = a.groups[src];
 	if (j == 0)
 	{
 		a.out_counts[q] = a.counts[pos];

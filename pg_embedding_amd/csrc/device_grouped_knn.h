@@ -140,15 +140,23 @@ __device__ __forceinline__ void store_grouped(uint64_t *__restrict__ kdst, uint3
 
 struct GkScan
 {
-	FkScan s;                        // fk_scan_kernel's arguments (smin = 0, skip_samples = 0: every query's whole list; pcount unused)
+	FkScan s;                        // fk_scan_kernel's arguments (skip_samples = 0; smin = 0: every query's whole list, else the matrix-core form's samples; pcount unused)
 	const uint32_t *glist;           // the group words of s.list, entry for entry
 	uint32_t *gpart;                 // [nq][splits * 4][k] the groups of s.part's keys, GK_NONE = none
 };
 
-// scan_topk_within with the grouped list: entries [lo, hi) of the wave's slice; an entry is offered if it takes part and (within) d <= radius
-template <int FUNC>
+// the group of a list entry: the word next to it, loaded coalesced, once per step, like the list itself
+struct ListGroups
+{
+	const uint32_t *glist;
+	__device__ __forceinline__ uint32_t operator()(uint32_t base, uint32_t cnt, int lane, uint32_t) const { return glist[base + min((uint32_t) lane, cnt - 1u)]; }
+};
+
+// scan_topk_within with the grouped list: entries [lo, hi) of `src`; an entry is offered if it takes part and (within) d <= radius.
+// group_of(base, cnt, lane, id): the group word of entry base + lane, element id (any word for lane >= cnt: it is not offered)
+template <int FUNC, class Source, class Groups>
 __device__ __forceinline__ uint32_t scan_grouped_within(const float *__restrict__ vec, uint32_t stride, const float4 *q4, uint32_t nchunks,
-														uint32_t kiters, const StagedRows &src, const uint32_t *__restrict__ glist, uint32_t lo,
+														uint32_t kiters, const Source &src, const Groups &group_of, uint32_t lo,
 														uint32_t hi, uint64_t *top, uint32_t *grp, float *sums, uint32_t k, bool within, float radius,
 														int lane)
 {
@@ -160,7 +168,7 @@ __device__ __forceinline__ uint32_t scan_grouped_within(const float *__restrict_
 	{
 		const uint32_t cnt = min(64u, hi - base);
 		const uint32_t id = src.id(base, cnt, lane);
-		const uint32_t g = glist[base + min((uint32_t) lane, cnt - 1u)];    // coalesced, once per step, like the list itself
+		const uint32_t g = group_of(base, cnt, lane, id);
 		score_rows<FUNC, 4, 2>(vec, stride, q4, nchunks, kiters, src.rows(base), cnt, sums, lane);
 		wave_sync();
 		const float dl = finish_dist<FUNC>(sums[lane], sums[OUT2 + lane], qnorm);
@@ -199,7 +207,7 @@ __global__ __launch_bounds__(256) void gk_scan_kernel(const GkScan g)
 	uint32_t *grp = reinterpret_cast<uint32_t *>(wbase + o_grp) + (size_t) wib * (k + 1);
 	const uint32_t lo = (uint32_t) ((uint64_t) len * w / nw), hi = (uint32_t) ((uint64_t) len * (w + 1) / nw);
 	const bool within = a.radius != nullptr;
-	const uint32_t tsize = scan_grouped_within<FUNC>(a.vec, a.stride, q4, a.nchunks, a.kiters, StagedRows{list, ids}, g.glist + (list - a.list), lo, hi,
+	const uint32_t tsize = scan_grouped_within<FUNC>(a.vec, a.stride, q4, a.nchunks, a.kiters, StagedRows{list, ids}, ListGroups{g.glist + (list - a.list)}, lo, hi,
 													 top, grp, sums, k, within, within ? a.radius[qi] : 0.f, lane);
 	const size_t po = ((size_t) qi * a.splits * 4u + w) * k;
 	store_grouped(a.part + po, g.gpart + po, top, grp, tsize, k, lane);
@@ -212,10 +220,16 @@ struct GkMerge
 	uint64_t *keys;                  // [nq][k] the answer's keys, ascending, ~0 = none
 	uint32_t *groups;                // [nq][k] their groups
 	uint32_t *count;                 // [nq] the groups with a member in R(q), up to k: the rows of the answer
+	float *tau;                      // NULL (listed form), or [nq] the bound for make_bounds_kernel (device_grouped_knn_mfma.h)
+	uint32_t *mask_of;               // [nq] the query's mask row: its bitmap, or nfilters (zeros) when the scan answered it
+	uint32_t nfilters;
 };
 
 // One wave per query (block = 64 threads).  LDS: k + 1 keys | k + 1 group words.  The partial lists in wave order, 64 pairs per offer; a
 // partial list is ascending, so it is left at its first step that holds no key or, with a full list, starts at or above the worst key.
+// The bound (matrix-core form), fk_merge_kernel's with groups for rows: with k distinct groups in the sample the key of the k-th — each of
+// them has a member within it, so the k best representatives over the whole list are — else the radius (none: +inf); a query whose scan is
+// its complete answer (a list no longer than its sample, a radius that selects nothing) gets a bound of 0 and the zero mask row.
 __global__ __launch_bounds__(64) void gk_merge_kernel(const GkMerge a)
 {
 	extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -243,7 +257,17 @@ __global__ __launch_bounds__(64) void gk_merge_kernel(const GkMerge a)
 		}
 	}
 	store_grouped(a.keys + (size_t) qi * k, a.groups + (size_t) qi * k, top, grp, tsize, k, lane);
-	if (lane == 0) a.count[qi] = tsize;
+	if (lane == 0)
+	{
+		a.count[qi] = tsize;                                              // (a query that is not answered here: the re-score's to write again)
+		if (a.tau)
+		{
+			const float r = s.radius ? s.radius[qi] : __builtin_inff();
+			const bool answered = whole || rk_selects_nothing(r, s.func);
+			a.tau[qi] = answered ? 0.f : tsize >= k ? unord_f32((uint32_t) (worst >> 32)) : r;
+			a.mask_of[qi] = answered ? a.nfilters : b;
+		}
+	}
 }
 
 }  // namespace pgemb

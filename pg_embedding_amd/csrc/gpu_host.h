@@ -57,7 +57,7 @@ enum Knob : int
 	K_BLOCKS_PER_CU, K_STREAM_LIGHT, K_LOCALITY, K_XCD_TICKETS,
 	// test knobs (hnsw_gpu_config_set only)
 	K_BEAM16, K_NARROW5, K_LEAN, K_HASH_ENTRIES, K_LDS_SET_MIN_WAVES, K_TEAM_SPEC, K_TEAM_WPB, K_NARROW_WPB, K_ABORT_POLL_LOG2, K_MAX_BLOCKS, K_SHARDED_NO_PEER, K_BF_BIG_MIN_BLOCKS, K_LOCALITY_MIN_NQ,
-	K_FK_SAMPLE_MIN, K_FK_MFMA_STANDIN, K_FK_AUTO_SPLIT,
+	K_FK_SAMPLE_MIN, K_FK_MFMA_STANDIN, K_FK_AUTO_SPLIT, K_GK_SAMPLE_FACTOR,
 	K_COUNT
 };
 struct KnobVal { std::atomic<long long> v{0}; std::atomic<bool> set{false}; };
@@ -136,7 +136,7 @@ struct FkWs
 	ScanBuf cells, list, part;                           // per-(bitmap, segment) counts | offsets | rows-scored word; the lists; the partial top-k lists
 	ScanBuf mask, bfs, cand;                             // row masks (matrix-core form, device_filtered_knn_mfma.h); per-query scratch (both forms); candidate lists
 	ScanBuf perm, tmp;                                   // the automatic calls (device_fk_plan.h): the partition of the query numbers; a class's compacted inputs and outputs
-	ScanBuf grp;                                         // grouped k-NN (device_grouped_knn.h): the group word of every list entry
+	ScanBuf grp, egrp;                                   // grouped k-NN (device_grouped_knn.h): the group word of every list entry; (matrix-core form, device_grouped_knn_mfma.h) of every element
 	uint64_t *host = nullptr;                            // pinned, 16 words: [0] entries of all lists, [1] the longest list, [2] rows scored, [3] pairs that passed the filter's comparison, [4] pairs appended, [5] candidate lists that overflowed; [8 .. 12] the plan's words (FkPlan::host)
 	hipEvent_t ev[6] = {};                               // before the list build | after it | after the emit kernel | before the filter | after it | before a listed scan that follows a filter
 	// What the last call of each family left (include/hnsw_gpu_diag.h), one record type: k = the pass that answered the last filtered k-NN
@@ -145,11 +145,11 @@ struct FkWs
 	// (hnsw_gpu_last_range_knn[_form]; host[6]: the sum of its totals).  A call of one family leaves the other's records alone.  form: the form
 	// that answered the last call that ended well (HNSW_GPU_FK_FORM_* = HNSW_GPU_RK_FORM_*); scan_ms: from the end of the list (and mask)
 	// build, or of the pass before, to the end of the emit kernel
-	struct Diag { uint64_t listed = 0, scored = 0, dist_pass = 0, appended = 0, totals = 0; float build_ms = 0.f, filter_ms = 0.f, call_ms = 0.f, scan_ms = 0.f; int form = -1; } k, kf, r;
-	Diag g;                                              // the last grouped k-NN call (hnsw_gpu_last_grouped_knn: listed, scored, build_ms, scan_ms)
-	// the plan of the last automatic call of either kind (hnsw_gpu_last_filtered_knn_plan, hnsw_gpu_last_range_knn_plan): queries and ΣL_q per
+	struct Diag { uint64_t listed = 0, scored = 0, dist_pass = 0, appended = 0, totals = 0, overflowed = 0; float build_ms = 0.f, filter_ms = 0.f, call_ms = 0.f, scan_ms = 0.f; int form = -1; } k, kf, r;
+	Diag g, gf;                                          // the last grouped k-NN call: g = the pass that answered (hnsw_gpu_last_grouped_knn[_form]), gf = its last filter launch, as kf (hnsw_gpu_last_grouped_knn_mfma)
+	// the plan of the last automatic call of each kind (hnsw_gpu_last_filtered_knn_plan, hnsw_gpu_last_range_knn_plan, hnsw_gpu_last_grouped_knn_plan): queries and ΣL_q per
 	// class, the threshold in rows, the model's two estimates for the queries above it (µs), the form that answered the loose class
-	struct Plan { uint64_t nq[2] = {0, 0}, rows[2] = {0, 0}, thresh = 0, est_listed_us = 0, est_mfma_us = 0; int loose_form = 0; } plan, rplan;
+	struct Plan { uint64_t nq[2] = {0, 0}, rows[2] = {0, 0}, thresh = 0, est_listed_us = 0, est_mfma_us = 0; int loose_form = 0; } plan, rplan, gplan;
 };
 void fk_ws_free(FkWs *s);
 

@@ -2,7 +2,7 @@
 // the f32 rows or the reduced copy (csrc/device_bf_mfma.h, csrc/device_bf_mfma16.h), and exact filtered k-NN and exact radius search, one
 // pipeline: the canonical scan over lists of allowed rows (csrc/device_filtered_knn.h) or, for loose filters, the MFMA filter with the allow
 // test at its append (csrc/device_filtered_knn_mfma.h), chosen per query in the automatic calls (csrc/device_fk_plan.h); and exact grouped
-// k-NN over the same lists (csrc/device_grouped_knn.h)
+// k-NN over the same lists, in the same forms (csrc/device_grouped_knn.h, csrc/device_grouped_knn_mfma.h)
 // One translation unit of libhnsw_gpu.so (csrc/gpu_host.h lists them); gfx950 only, plain HIP runtime, no framework types in any signature.
 #include "gpu_host.h"
 #include "device_topk_scan.h"
@@ -12,6 +12,7 @@
 #include "device_filtered_knn_mfma.h"
 #include "device_fk_plan.h"
 #include "device_grouped_knn.h"
+#include "device_grouped_knn_mfma.h"
 
 #include <type_traits>
 
@@ -38,6 +39,7 @@ struct QueryGeom
 	size_t lds_listed(size_t k) const { return lds_scan(k) + 4 * 64 * 4; }                     // ... | 4 x 64 staged element numbers: fk_scan_kernel
 	size_t lds_grouped(size_t k) const { return lds_listed(k) + 4 * (k + 1) * 4; }             // ... | 4 x (k + 1) group words: gk_scan_kernel
 	size_t lds_rescore(size_t k) const { return 4 * round_up((size_t) qpad * 4 + (k + 1) * 8 + 128 * 4, 16); }   // per wave: image | k + 1 keys | 128 sums: bf_rescore_kernel, fkm_rescore_kernel
+	size_t lds_rescore_grouped(size_t k) const { return 4 * round_up((size_t) qpad * 4 + (k + 1) * 8 + 128 * 4 + (k + 1) * 4, 16); }   // ... | k + 1 group words: gkm_rescore_kernel
 };
 
 // ------------------------------------------------------------------------------------
@@ -466,25 +468,25 @@ static_assert(HNSW_GPU_RK_FORM_LISTED == HNSW_GPU_FK_FORM_LISTED && HNSW_GPU_RK_
 
 void fk_ws_free(FkWs *s)
 {
-	buf_trim({&s->cells, &s->list, &s->part, &s->mask, &s->bfs, &s->cand, &s->perm, &s->tmp, &s->grp}, 0);
+	buf_trim({&s->cells, &s->list, &s->part, &s->mask, &s->bfs, &s->cand, &s->perm, &s->tmp, &s->grp, &s->egrp}, 0);
 	if (s->host) (void) hipHostFree(s->host);
 	s->host = nullptr;
 	for (hipEvent_t &e : s->ev) { if (e) (void) hipEventDestroy(e); e = nullptr; }
 }
 
-// what the two families of entry points differ in: their name in a message, what they require, and where their diagnostics go — the
+// what the three families of entry points differ in: their name in a message, what they require, and where their diagnostics go — the
 // figures of one are not touched by a call of the other
 struct FkFamily
 {
 	const char *who; bool range;
-	bool grouped;                                                 // grouped k-NN: radius and filter both optional, the group table required; listed form only
+	bool grouped;                                                 // grouped k-NN: radius and filter both optional, the group table required; (key, group) pairs in place of keys
 	FkWs::Diag FkWs::*diag;                                       // the pass that answered the last call (both classes of an automatic call)
 	FkWs::Diag FkWs::*filter;                                     // NULL, or: the last filter launch of the last call, whatever form answered in the end
 	FkWs::Plan FkWs::*plan;
 };
 static const FkFamily FK_KNN = { "filtered k-NN", false, false, &FkWs::k, &FkWs::kf, &FkWs::plan };
 static const FkFamily FK_RANGE = { "radius search", true, false, &FkWs::r, nullptr, &FkWs::rplan };
-static const FkFamily FK_GROUPED = { "grouped k-NN", false, true, &FkWs::g, nullptr, nullptr };
+static const FkFamily FK_GROUPED = { "grouped k-NN", false, true, &FkWs::g, &FkWs::gf, &FkWs::gplan };
 
 // one call: its arguments (radius, totals: NULL in filtered k-NN), and what its list build found
 struct FkCall
@@ -496,14 +498,14 @@ struct FkCall
 	bool later;                                                   // a pass that follows another of the call: its scan time counts from ev[5], not from the list build
 	const uint32_t *group_of; size_t group_entries; uint32_t *groups;   // grouped k-NN: the table over label values, and NULL or the output
 };
-struct FkTrim { FkWs *w; ~FkTrim() { buf_trim({&w->cells, &w->list, &w->part, &w->mask, &w->bfs, &w->cand, &w->perm, &w->tmp, &w->grp}); } };   // on EVERY way out, errors included: no buffer above 64 MiB outlives its call
+struct FkTrim { FkWs *w; ~FkTrim() { buf_trim({&w->cells, &w->list, &w->part, &w->mask, &w->bfs, &w->cand, &w->perm, &w->tmp, &w->grp, &w->egrp}); } };   // on EVERY way out, errors included: no buffer above 64 MiB outlives its call
 
 // the matrix-core form's operands: the f32 rows, or the reduced copy the index holds (hnsw_gpu_bruteforce_reduced_dev's rule)
-static int fk_check_format(hnsw_gpu_index *ix, int format)
+static int fk_check_format(const char *who, hnsw_gpu_index *ix, int format)
 {
 	if (format == ROWS_F32) return HNSW_GPU_OK;
 	if ((format != ROWS_F16 && format != ROWS_BF16) || ix->rows_fmt != format || !ix->rows16)
-		return fail(HNSW_GPU_ERR_ARG, "filtered k-NN: format %d is neither f32 nor the reduced copy this index holds (%d; hnsw_gpu_index_set_reduced_rows)", format, ix->rows_fmt);
+		return fail(HNSW_GPU_ERR_ARG, "%s: format %d is neither f32 nor the reduced copy this index holds (%d; hnsw_gpu_index_set_reduced_rows)", who, format, ix->rows_fmt);
 	return HNSW_GPU_OK;
 }
 // the caller's contract, checked before anything is launched or copied (the outputs stay untouched).  Filtered k-NN requires the filter,
@@ -513,7 +515,7 @@ static int fk_check(const FkCall &c, int form, int format)
 	const char *who = c.fam->who;
 	const bool range = c.fam->range, grouped = c.fam->grouped, filter = c.allow || !(range || grouped);
 	if (!c.ix) return fail(HNSW_GPU_ERR_ARG, "index is NULL");
-	if (c.nq == 0) return range || form == FK_LISTED ? HNSW_GPU_OK : fk_check_format(c.ix, format);
+	if (c.nq == 0) return range || form == FK_LISTED ? HNSW_GPU_OK : fk_check_format(who, c.ix, format);
 	if (form != FK_LISTED && form != FK_MFMA) return fail(HNSW_GPU_ERR_ARG, "%s: form %d is neither listed (0) nor matrix cores (1)", who, form);
 	if (!c.queries || (grouped ? !c.group_of : range ? !c.radius : !c.allow) || !c.labels || !c.counts)
 		return fail(HNSW_GPU_ERR_ARG, "%s: NULL buffer%s", who, range || grouped ? "" : " (the filter is required: hnsw_gpu_bruteforce_dev takes none)");
@@ -524,7 +526,7 @@ static int fk_check(const FkCall &c, int form, int format)
 	if (filter && ((c.allow_bits + 31) / 32 >= 0xFFFFFFFFull || c.nfilters >= 0xFFFFFFFFull)) return fail(HNSW_GPU_ERR_ARG, "%s: allow filter too large", who);
 	const QueryGeom g(c.ix->stride);
 	if ((grouped ? g.lds_grouped(c.k) : g.lds_listed(c.k)) > 64 * 1024) return fail(HNSW_GPU_ERR_ARG, "k/dim too large for %s", who);
-	return form == FK_LISTED ? HNSW_GPU_OK : fk_check_format(c.ix, format);
+	return form == FK_LISTED ? HNSW_GPU_OK : fk_check_format(who, c.ix, format);
 }
 
 static int fk_begin(FkCall &c)
@@ -604,16 +606,29 @@ static int fk_splits(const FkCall &c, size_t longest, uint32_t *out, size_t entr
 	return buf_reserve(&ix->fk.part, nq * splits * 4 * k * entry_bytes, c.fam->who, "the partial result lists");
 }
 
+// the matrix-core pass a call may take: whether it has one, with the filter or its stand-in, its operands, and the sample rule's S_min and
+// k (fk_sample_len) — k; grouped k-NN: k * its sample factor, since its bound is the k-th GROUP of the sample, not the k-th row.  The knobs
+// are read ONCE per call: every pass and the plan size and scan the same samples
+struct FkMfma
+{
+	bool avail, standin; int format; uint32_t smin, sample_k;
+	size_t sample_len(size_t len) const { return fk_sample_len((uint32_t) len, smin, sample_k); }
+	bool samples(size_t len) const { return sample_len(len) < len; }   // a list of len rows is longer than its sample: the filter has work
+};
+
 // One pass over the built lists (and masks).  format < 0: the listed form — the scan over every query's whole list, merge, emit.  Else
 // the matrix-core form with the operands of `format`: the scan over the lists no longer than their sample and (without totals) over the
 // samples of the others -> merge + bounds -> filter (or its stand-in) -> re-score -> emit.  *ovf = candidate lists that overflowed (then
-// the outputs are not the answer: the caller hands the call down).
-static int fk_pass(FkCall &c, int format, bool standin, uint32_t smin, uint32_t mwords, uint64_t *ovf)
+// the outputs are not the answer: the caller hands the call down).  Grouped k-NN: the same pass with its own scan, merge and re-score — a
+// list of (key, group) pairs, one per group, where the others keep keys (device_grouped_knn.h, device_grouped_knn_mfma.h; no totals).
+static int fk_pass(FkCall &c, int format, const FkMfma &m, uint32_t mwords, uint64_t *ovf)
 {
 	hnsw_gpu_index *ix = c.ix;
 	FkWs *fw = &ix->fk;
 	hipStream_t s = c.s;
-	const bool listed = format < 0, reduced = !listed && format != ROWS_F32, skip = !listed && c.totals;
+	const bool standin = m.standin;
+	const uint32_t smin = m.smin;
+	const bool listed = format < 0, reduced = !listed && format != ROWS_F32, skip = !listed && c.totals, grouped = c.fam->grouped;
 	const size_t nq = c.nq, k = c.k;
 	const int func = (int) ix->meta.dist_func;
 	const uint32_t dim = (uint32_t) ix->meta.dim;
@@ -623,9 +638,9 @@ static int fk_pass(FkCall &c, int format, bool standin, uint32_t smin, uint32_t 
 	const uint32_t qchunks = listed ? 0 : bf_qchunks(ix, reduced);
 	const uint32_t cap = 16384;
 	// the longest run of list entries a query scans: its whole list, its sample, or (totals) a list no longer than its sample
-	const size_t slongest = listed ? c.longest : skip ? std::min<size_t>(c.longest, smin) : fk_sample_len((uint32_t) c.longest, smin, (uint32_t) k);
+	const size_t slongest = listed ? c.longest : skip ? std::min<size_t>(c.longest, smin) : m.sample_len(c.longest);
 	uint32_t splits = 1;
-	if ((rc = fk_splits(c, slongest, &splits))) return rc;
+	if ((rc = fk_splits(c, slongest, &splits, grouped ? 12 : 8))) return rc;
 	// scratch carve
 	const size_t o_keys = 0;
 	const size_t o_rcnt = o_keys + round_up(nq * k * 8, 256);
@@ -639,18 +654,19 @@ static int fk_pass(FkCall &c, int format, bool standin, uint32_t smin, uint32_t 
 	const size_t o_mof = o_bound + round_up(nq * 4, 256);
 	const size_t o_cnt = o_mof + round_up(nq * 4, 256);
 	const size_t o_fcnt = o_cnt + round_up(nq * 4 + 64, 256);
-	const size_t total = o_fcnt + 256;
+	const size_t o_grp = o_fcnt + 256;                            // (grouped k-NN: the group of every key)
+	const size_t total = o_grp + (grouped ? round_up(nq * k * 4, 256) : 0);
 	if ((rc = buf_reserve(&fw->bfs, total, c.fam->who, "the per-query scratch"))) return rc;
 	if (!listed && (rc = buf_reserve(&fw->cand, nq * (size_t) cap * 4, c.fam->who, "the candidate lists"))) return rc;
 	char *B = (char *) fw->bfs.p;
 	uint64_t *keys = (uint64_t *) (B + o_keys);
 	uint32_t *rcount = (uint32_t *) (B + o_rcnt), *pcount = (uint32_t *) (B + o_pcnt);
-	unsigned long long *sum = c.radius ? (unsigned long long *) (B + o_sum) : nullptr, *fcnt = (unsigned long long *) (B + o_fcnt);
+	unsigned long long *sum = c.radius && !grouped ? (unsigned long long *) (B + o_sum) : nullptr, *fcnt = (unsigned long long *) (B + o_fcnt);
 	uint4 *qcopy = (uint4 *) (B + o_q);
 	float *qn = (float *) (B + o_qn), *tau = (float *) (B + o_tau), *bound = (float *) (B + o_bound);
 	float2 *qterms = (float2 *) (B + o_qt);
 	uint32_t *mask_of = (uint32_t *) (B + o_mof), *cnt = (uint32_t *) (B + o_cnt), *cand = (uint32_t *) fw->cand.p;
-	uint32_t *overflow = cnt + nq;
+	uint32_t *overflow = cnt + nq, *kgroups = grouped ? (uint32_t *) (B + o_grp) : nullptr;
 
 	// the scan, then per query: its keys, its count of qualifying rows and (matrix-core form) its bound and mask row
 	FkMerge fm;
@@ -660,15 +676,34 @@ static int fk_pass(FkCall &c, int format, bool standin, uint32_t smin, uint32_t 
 	fs.queries = c.queries; fs.nq = (uint32_t) nq; fs.k = (uint32_t) k; fs.splits = splits;
 	fs.list = (const uint32_t *) fw->list.p; fs.off = c.off; fs.nseg = c.fl.nseg; fs.allow_of = c.allow_of;
 	fs.part = (uint64_t *) fw->part.p; fs.pcount = pcount; fs.scored = c.scored; fs.smin = listed ? 0u : smin; fs.skip_samples = skip ? 1u : 0u;
+	fs.sample_k = m.sample_k;
 	fs.radius = c.radius; fs.func = func;
 	fm.nfilters = (uint32_t) c.nfilters; fm.keys = keys; fm.count = rcount; fm.tau = listed ? nullptr : tau; fm.mask_of = mask_of;
 	if (sum) HIPCHK(hipMemsetAsync(sum, 0, 8, s));
-	if (slongest)
+	if (grouped)
 	{
-		const dim3 grid((uint32_t) round_up((size_t) splits * nq, 8));
-		with_func(func, [&](auto F) { hipLaunchKernelGGL(fk_scan_kernel<decltype(F)::value>, grid, dim3(256), g.lds_listed(k), s, fs); });
+		GkMerge gm;
+		memset(&gm, 0, sizeof(gm));
+		gm.g.s = fs;
+		gm.g.glist = (const uint32_t *) fw->grp.p;
+		gm.g.gpart = (uint32_t *) ((char *) fw->part.p + nq * splits * 4 * k * 8);     // the partial groups behind the partial keys
+		gm.keys = keys; gm.groups = kgroups; gm.count = rcount; gm.tau = fm.tau; gm.mask_of = mask_of; gm.nfilters = fm.nfilters;
+		if (slongest)
+		{
+			const dim3 grid((uint32_t) round_up((size_t) splits * nq, 8));
+			with_func(func, [&](auto F) { hipLaunchKernelGGL(gk_scan_kernel<decltype(F)::value>, grid, dim3(256), g.lds_grouped(k), s, gm.g); });
+		}
+		hipLaunchKernelGGL(gk_merge_kernel, dim3((uint32_t) nq), dim3(64), (k + 1) * 12, s, gm);
 	}
-	hipLaunchKernelGGL(fk_merge_kernel, dim3((uint32_t) nq), dim3(64), k * 8, s, fm);
+	else
+	{
+		if (slongest)
+		{
+			const dim3 grid((uint32_t) round_up((size_t) splits * nq, 8));
+			with_func(func, [&](auto F) { hipLaunchKernelGGL(fk_scan_kernel<decltype(F)::value>, grid, dim3(256), g.lds_listed(k), s, fs); });
+		}
+		hipLaunchKernelGGL(fk_merge_kernel, dim3((uint32_t) nq), dim3(64), k * 8, s, fm);
+	}
 	if (!listed)
 	{
 		bf_queries_side(reduced, format, c.queries, nq, dim, qchunks, qcopy, qn, qterms, s);
@@ -687,15 +722,23 @@ static int fk_pass(FkCall &c, int format, bool standin, uint32_t smin, uint32_t 
 		else if ((rc = with_form(format, [&](auto p) { return bf_filter_pick<BfAllow<decltype(p)>>(ix, a, s); })))
 			return rc;
 		HIPCHK(hipEventRecord(fw->ev[4], s));
-		with_func(func, [&](auto F) {
-			if constexpr (decltype(F)::value != F_MANHATTAN)           // (answered by the listed form: no re-score kernel is compiled for it)
-				hipLaunchKernelGGL(fkm_rescore_kernel<decltype(F)::value>, dim3((uint32_t) ((nq + 3) / 4)), dim3(256), g.lds_rescore(k), s, ix->vec, dim, ix->stride,
-								   g.nchunks, g.kiters, g.qpad, c.queries, (uint32_t) nq, c.radius, (const uint32_t *) mask_of, (uint32_t) c.nfilters,
-								   (const uint32_t *) cand, (const uint32_t *) cnt, cap, (uint32_t) k, keys, rcount, overflow);
-		});
+		if (grouped)
+			with_func(func, [&](auto F) {
+				if constexpr (decltype(F)::value != F_MANHATTAN)
+					hipLaunchKernelGGL(gkm_rescore_kernel<decltype(F)::value>, dim3((uint32_t) ((nq + 3) / 4)), dim3(256), g.lds_rescore_grouped(k), s, ix->vec, dim,
+									   ix->stride, g.nchunks, g.kiters, g.qpad, c.queries, (uint32_t) nq, c.radius, (const uint32_t *) mask_of, (uint32_t) c.nfilters,
+									   (const uint32_t *) cand, (const uint32_t *) cnt, cap, (const uint32_t *) fw->egrp.p, (uint32_t) k, keys, kgroups, rcount, overflow);
+			});
+		else
+			with_func(func, [&](auto F) {
+				if constexpr (decltype(F)::value != F_MANHATTAN)           // (answered by the listed form: no re-score kernel is compiled for it)
+					hipLaunchKernelGGL(fkm_rescore_kernel<decltype(F)::value>, dim3((uint32_t) ((nq + 3) / 4)), dim3(256), g.lds_rescore(k), s, ix->vec, dim, ix->stride,
+									   g.nchunks, g.kiters, g.qpad, c.queries, (uint32_t) nq, c.radius, (const uint32_t *) mask_of, (uint32_t) c.nfilters,
+									   (const uint32_t *) cand, (const uint32_t *) cnt, cap, (uint32_t) k, keys, rcount, overflow);
+			});
 	}
 	// one key list and one count per query -> labels, order, counts, tails, totals
-	const FkEmit fe = { keys, rcount, (uint32_t) k, ix->labels, (uint32_t) ix->n, c.labels, c.dists, c.idx, c.counts, c.totals, sum };
+	const FkEmit fe = { keys, rcount, (uint32_t) k, ix->labels, (uint32_t) ix->n, c.labels, c.dists, c.idx, c.counts, c.totals, sum, kgroups, c.groups };
 	hipLaunchKernelGGL(fk_emit_kernel, dim3((uint32_t) nq), dim3(64), k * 16, s, fe);
 	hipError_t e = hipGetLastError();
 	if (e == hipSuccess) e = hipEventRecord(fw->ev[2], s);
@@ -708,14 +751,14 @@ static int fk_pass(FkCall &c, int format, bool standin, uint32_t smin, uint32_t 
 	if (e == hipSuccess) e = e2;
 	if (e != hipSuccess) return fail(HNSW_GPU_ERR_HIP, "%s: %s", c.fam->who, hipGetErrorString(e));
 	*ovf = fw->host[5];
-	FkWs::Diag &m = fw->*c.fam->diag;
-	m.listed = c.total; m.scored = fw->host[2]; m.dist_pass = fw->host[3]; m.appended = fw->host[4]; m.totals = fw->host[6];
-	m.filter_ms = 0.f;
-	(void) hipEventElapsedTime(&m.build_ms, fw->ev[0], fw->ev[1]);
-	if (!listed) (void) hipEventElapsedTime(&m.filter_ms, fw->ev[3], fw->ev[4]);
-	(void) hipEventElapsedTime(&m.call_ms, fw->ev[0], fw->ev[2]);
-	(void) hipEventElapsedTime(&m.scan_ms, fw->ev[c.later ? 5 : 1], fw->ev[2]);
-	if (!listed && c.fam->filter) fw->*c.fam->filter = m;
+	FkWs::Diag &d = fw->*c.fam->diag;
+	d.listed = c.total; d.scored = fw->host[2]; d.dist_pass = fw->host[3]; d.appended = fw->host[4]; d.totals = fw->host[6]; d.overflowed = fw->host[5];
+	d.filter_ms = 0.f;
+	(void) hipEventElapsedTime(&d.build_ms, fw->ev[0], fw->ev[1]);
+	if (!listed) (void) hipEventElapsedTime(&d.filter_ms, fw->ev[3], fw->ev[4]);
+	(void) hipEventElapsedTime(&d.call_ms, fw->ev[0], fw->ev[2]);
+	(void) hipEventElapsedTime(&d.scan_ms, fw->ev[c.later ? 5 : 1], fw->ev[2]);
+	if (!listed && c.fam->filter) fw->*c.fam->filter = d;
 	return HNSW_GPU_OK;
 }
 
@@ -723,7 +766,7 @@ static int fk_pass(FkCall &c, int format, bool standin, uint32_t smin, uint32_t 
 // query image and a k-list per wave in LDS — that does not fit; and, unless the stand-in takes the filter's place (test knob: then the
 // operands are f32 whatever `format` says), a table too small to matter or a device the filter kernel is not written for
 // (bruteforce_filter's rules; the tests' emulator has no such kernel)
-static bool fk_have_mfma(hnsw_gpu_index *ix, size_t k, bool *standin)
+static bool fk_have_mfma(hnsw_gpu_index *ix, size_t k, bool grouped, bool *standin)
 {
 	*standin = knob(K_FK_MFMA_STANDIN, 0) != 0;
 #ifdef PGEMB_SIMT_EMULATOR
@@ -731,21 +774,39 @@ static bool fk_have_mfma(hnsw_gpu_index *ix, size_t k, bool *standin)
 #else
 	const bool have_filter = ix->n >= 4096 && ix->gfx950 && ix->max_lds >= BF_MIN_LDS;
 #endif
-	return (int) ix->meta.dist_func != F_MANHATTAN && QueryGeom(ix->stride).lds_rescore(k) <= 64 * 1024 && (*standin || have_filter);
+	const QueryGeom g(ix->stride);
+	return (int) ix->meta.dist_func != F_MANHATTAN && (grouped ? g.lds_rescore_grouped(k) : g.lds_rescore(k)) <= 64 * 1024 && (*standin || have_filter);
 }
 static uint32_t fk_sample_min() { return (uint32_t) std::min<long long>(0xFFFFFFFFll, std::max<long long>(1, knob(K_FK_SAMPLE_MIN, FKM_SAMPLE_MIN))); }
-// the matrix-core pass a call may take: whether it has one, with the filter or its stand-in, its operands and S_min
-struct FkMfma { bool avail, standin; int format; uint32_t smin; };
-static FkMfma fk_mfma_of(hnsw_gpu_index *ix, int format, size_t k)
+static FkMfma fk_mfma_of(hnsw_gpu_index *ix, int format, size_t k, bool grouped)
 {
 	FkMfma m;
-	m.avail = fk_have_mfma(ix, k, &m.standin);
+	m.avail = fk_have_mfma(ix, k, grouped, &m.standin);
 	m.format = m.standin ? ROWS_F32 : format;
 	m.smin = fk_sample_min();
+	m.sample_k = (uint32_t) (grouped ? k * (size_t) std::min<long long>(64, std::max<long long>(1, knob(K_GK_SAMPLE_FACTOR, GKM_SAMPLE_FACTOR))) : k);
 	return m;
 }
 
-// 2. the row masks (counted with the list build), and a row of zeros behind them
+// 1b. grouped k-NN (device_grouped_knn.h), behind the list build: the group word of every list entry (counted with the
+// build's time, like the masks of the matrix-core form)
+static int gk_groups(FkCall &c)
+{
+	FkWs *fw = &c.ix->fk;
+	if (int rc = buf_reserve(&fw->grp, c.total * 4, c.fam->who, "the group words of the lists")) return rc;
+	if (c.total)
+	{
+		const GkGroups gg = { (const uint32_t *) fw->list.p, c.total, c.ix->labels, c.group_of, c.group_entries, (uint32_t *) fw->grp.p };
+		const uint32_t blocks = (uint32_t) std::min<size_t>((c.total + 255) / 256, (size_t) c.ix->num_cu * 8);
+		hipLaunchKernelGGL(gk_groups_kernel, dim3(blocks), dim3(256), 0, c.s, gg);
+		HIPCHK(hipGetLastError());
+	}
+	HIPCHK(hipEventRecord(fw->ev[1], c.s));
+	return HNSW_GPU_OK;
+}
+
+// 2. the row masks (counted with the list build), and a row of zeros behind them.  Grouped k-NN: first the group word of every element
+// (which the re-score reads again), then the masks of the allowed rows that take part
 static int fk_masks(FkCall &c, uint32_t *mwords_out)
 {
 	FkWs *fw = &c.ix->fk;
@@ -753,7 +814,15 @@ static int fk_masks(FkCall &c, uint32_t *mwords_out)
 	const uint32_t mwords = fkm_mask_words((uint32_t) c.ix->n);
 	int rc = buf_reserve(&fw->mask, (nfilters + 1) * (size_t) mwords * 4, c.fam->who, "the row masks");
 	if (rc) return rc;
-	if (c.allow) hipLaunchKernelGGL(fkm_mask_kernel, dim3((uint32_t) (c.nsb * nfilters)), dim3(256), 0, c.s, c.fl, mwords, (uint32_t *) fw->mask.p);
+	if (c.fam->grouped)
+	{
+		if ((rc = buf_reserve(&fw->egrp, c.ix->n * 4, c.fam->who, "the group words of the elements"))) return rc;
+		const GkmGroups gg = { c.ix->labels, (uint32_t) c.ix->n, c.group_of, c.group_entries, (uint32_t *) fw->egrp.p };
+		const uint32_t blocks = (uint32_t) std::min<size_t>((c.ix->n + 255) / 256, (size_t) c.ix->num_cu * 8);
+		hipLaunchKernelGGL(gkm_groups_kernel, dim3(blocks), dim3(256), 0, c.s, gg);
+		hipLaunchKernelGGL(gkm_mask_kernel, dim3((uint32_t) (c.nsb * nfilters)), dim3(256), 0, c.s, c.fl, (const uint32_t *) fw->egrp.p, mwords, (uint32_t *) fw->mask.p);
+	}
+	else if (c.allow) hipLaunchKernelGGL(fkm_mask_kernel, dim3((uint32_t) (c.nsb * nfilters)), dim3(256), 0, c.s, c.fl, mwords, (uint32_t *) fw->mask.p);
 	else hipLaunchKernelGGL(rk_live_kernel<RK_LIVE_MASK>, dim3((uint32_t) c.nsb), dim3(256), 0, c.s, c.fl, (const uint64_t *) nullptr, (uint32_t *) fw->mask.p);
 	HIPCHK(hipMemsetAsync((uint32_t *) fw->mask.p + nfilters * (size_t) mwords, 0, (size_t) mwords * 4, c.s));
 	HIPCHK(hipEventRecord(fw->ev[1], c.s));
@@ -775,13 +844,13 @@ static int fk_again(FkCall &c, bool timed)
 // The passes of one call (or of one class of an automatic call) over the built lists (and masks): a candidate list that overflows sends a
 // 16-bit pass to the f32 operands (its bound is looser: a list that overflowed there may not in f32) and an f32 pass to the listed form,
 // for all its queries.  pass: the first one (< 0: the listed form)
-static int fk_chain(FkCall &c, int pass, bool standin, uint32_t smin, uint32_t mwords)
+static int fk_chain(FkCall &c, int pass, const FkMfma &m, uint32_t mwords)
 {
 	FkWs *fw = &c.ix->fk;
 	for (;;)
 	{
 		uint64_t ovf = 0;
-		if (int rc = fk_pass(c, pass, standin, smin, mwords, &ovf)) return rc;
+		if (int rc = fk_pass(c, pass, m, mwords, &ovf)) return rc;
 		if (!ovf) break;
 		pass = pass == ROWS_F32 ? -1 : ROWS_F32;
 		if (int rc = fk_again(c, pass < 0)) return rc;
@@ -857,12 +926,12 @@ static int fk_auto_settle(FkCall &c, const FkMfma &m, FkAuto *a, uint8_t *d_plan
 	*pl = FkWs::Plan();
 	pl->thresh = a->thresh;
 	// what the listed form would cost MORE with the queries above the threshold in it, against one pass over the table for those
-	const double ws = fk_cost_waves(c.ix, a->loose, fk_sample_len((uint32_t) a->longest[1], m.smin, (uint32_t) c.k));
+	const double ws = fk_cost_waves(c.ix, a->loose, m.sample_len(a->longest[1]));
 	pl->est_listed_us = (uint64_t) std::llround(std::max(0.0, fk_cost_listed_us(c.ix, c.nq, c.k, a->rows[0] + a->rows[1], c.longest) -
 															  fk_cost_listed_us(c.ix, c.nq - a->loose, c.k, a->rows[0], a->longest[0])));
 	pl->est_mfma_us = (uint64_t) std::llround(a->b0 + FK_COST.merge_key2_us * (ws * (double) c.k) * (ws * (double) c.k) + a->b1 * (double) a->loose);
 	// a loose class whose every list is its own sample would be answered by the sample scan: the listed form's work, with a filter on top
-	a->split = m.avail && a->loose && a->longest[1] > m.smin && (a->forced || pl->est_listed_us > pl->est_mfma_us);
+	a->split = m.avail && a->loose && m.samples(a->longest[1]) && (a->forced || pl->est_listed_us > pl->est_mfma_us);
 	if (!a->split && a->loose && d_plan) HIPCHK(hipMemsetAsync(d_plan, 0, c.nq, c.s));
 	const size_t p = a->split ? a->loose : 0;
 	pl->nq[0] = c.nq - p; pl->nq[1] = p;
@@ -873,19 +942,19 @@ static int fk_auto_settle(FkCall &c, const FkMfma &m, FkAuto *a, uint8_t *d_plan
 
 // The compacted inputs and outputs of a call with two classes, all in perm[] order: position i of each array is query perm[i], so a class is
 // a contiguous run — the listed class positions [0, nq - p), the loose class the rest
-struct FkTmp { float *q; uint32_t *aof; float *radius; uint64_t *labels; float *dists; uint32_t *idx, *counts, *totals; };
+struct FkTmp { float *q; uint32_t *aof; float *radius; uint64_t *labels; float *dists; uint32_t *idx, *counts, *totals, *groups; };
 static int fk_auto_gather(FkCall &c, FkTmp *t)
 {
 	FkWs *fw = &c.ix->fk;
 	const size_t nq = c.nq, k = c.k, dim = c.ix->meta.dim;
 	const size_t o_aof = round_up(nq * dim * 4, 256), o_rad = o_aof + round_up(nq * 4, 256), o_lab = o_rad + round_up(nq * 4, 256),
 				 o_dst = o_lab + round_up(nq * k * 8, 256), o_idx = o_dst + round_up(nq * k * 4, 256), o_cnt = o_idx + round_up(nq * k * 4, 256),
-				 o_tot = o_cnt + round_up(nq * 4, 256), bytes = o_tot + round_up(nq * 4, 256);
+				 o_tot = o_cnt + round_up(nq * 4, 256), o_grp = o_tot + round_up(nq * 4, 256), bytes = o_grp + round_up(c.groups ? nq * k * 4 : 0, 256);
 	if (int rc = buf_reserve(&fw->tmp, bytes, c.fam->who, "the classes' compacted queries and results")) return rc;
 	char *B = (char *) fw->tmp.p;
 	t->q = (float *) B; t->aof = c.allow_of ? (uint32_t *) (B + o_aof) : nullptr; t->radius = c.radius ? (float *) (B + o_rad) : nullptr;
 	t->labels = (uint64_t *) (B + o_lab); t->dists = c.dists ? (float *) (B + o_dst) : nullptr; t->idx = c.idx ? (uint32_t *) (B + o_idx) : nullptr;
-	t->counts = (uint32_t *) (B + o_cnt); t->totals = c.totals ? (uint32_t *) (B + o_tot) : nullptr;
+	t->counts = (uint32_t *) (B + o_cnt); t->totals = c.totals ? (uint32_t *) (B + o_tot) : nullptr; t->groups = c.groups ? (uint32_t *) (B + o_grp) : nullptr;
 	FkGather g = { (const uint32_t *) fw->perm.p, 0u, (uint32_t) nq, c.queries, (uint32_t) dim, t->q, c.allow_of, t->aof, c.radius, t->radius,
 				   (dim % 4 == 0 && (uintptr_t) c.queries % 16 == 0) ? 1u : 0u };
 	const size_t chunks = nq * (g.vec4 ? dim / 4 : dim);            // (both classes in one launch: each is a run of positions)
@@ -900,13 +969,13 @@ static FkCall fk_auto_class(const FkCall &c, const FkTmp &t, size_t first, size_
 	const size_t dim = c.ix->meta.dim;
 	s.queries = t.q + first * dim; s.nq = count; s.allow_of = t.aof ? t.aof + first : nullptr; s.radius = t.radius ? t.radius + first : nullptr;
 	s.labels = t.labels + first * c.k; s.dists = t.dists ? t.dists + first * c.k : nullptr; s.idx = t.idx ? t.idx + first * c.k : nullptr;
-	s.counts = t.counts + first; s.totals = t.totals ? t.totals + first : nullptr; s.longest = longest;
+	s.counts = t.counts + first; s.totals = t.totals ? t.totals + first : nullptr; s.groups = t.groups ? t.groups + first * c.k : nullptr; s.longest = longest;
 	return s;
 }
 static int fk_auto_scatter(const FkCall &c, const FkTmp &t, size_t first, size_t count)
 {
 	FkScatter sc = { (const uint32_t *) c.ix->fk.perm.p, (uint32_t) first, (uint32_t) count, (uint32_t) c.k, t.labels, t.dists, t.idx, t.counts, t.totals,
-					 c.labels, c.dists, c.idx, c.counts, c.totals };
+					 c.labels, c.dists, c.idx, c.counts, c.totals, t.groups, c.groups };
 	hipLaunchKernelGGL(fkp_scatter_kernel, dim3((uint32_t) ((count * c.k + 255) / 256)), dim3(256), 0, c.s, sc);
 	HIPCHK(hipGetLastError());
 	return HNSW_GPU_OK;
@@ -930,24 +999,26 @@ static int fk_run(FkCall c, int form, int format, bool aut, uint8_t *d_plan)
 	FkWs::Diag &d = fw->*c.fam->diag;
 	FkWs::Plan &pl = fw->*c.fam->plan;
 	const size_t nq = c.nq;
-	const FkMfma m = fk_mfma_of(ix, format, c.k);
+	const FkMfma m = fk_mfma_of(ix, format, c.k, c.fam->grouped);
 	FkAuto a = {};
 	if (aut) fk_auto_begin(ix, m, &a);
 	int rc = fk_begin(c);
 	if (!rc && aut) rc = buf_reserve(&fw->perm, nq * 4, c.fam->who, "the plan's order of the queries");
 	const FkPlanHook hook = { a.thresh, d_plan };
 	if (!rc) rc = fk_lists(c, aut ? &hook : nullptr);
+	if (!rc && c.fam->grouped) rc = gk_groups(c);
 	if (!rc && aut) rc = fk_auto_settle(c, m, &a, d_plan, &pl);
 	if (rc) return rc;
-	// the queries of the matrix-core pass.  A list no longer than S_min is its own sample: with no longer list in the call, every query
-	// is answered by the scan of its whole list
-	const size_t loose = aut ? (a.split ? a.loose : 0) : form == FK_MFMA && m.avail && c.longest > m.smin ? nq : 0;
-	if (!loose) return fk_chain(c, -1, m.standin, m.smin, 0);
+	// the queries of the matrix-core pass.  A list no longer than its sample is its own sample (one of at most S_min rows; in grouped k-NN
+	// every list where k * the sample factor reaches 2 048): with no longer list in the call, every query is answered by the scan of its
+	// whole list — the listed pass, before the masks are built or anything else is launched
+	const size_t loose = aut ? (a.split ? a.loose : 0) : form == FK_MFMA && m.avail && m.samples(c.longest) ? nq : 0;
+	if (!loose) return fk_chain(c, -1, m, 0);
 	uint32_t mwords = 0;
 	if ((rc = fk_masks(c, &mwords))) return rc;
 	if (loose == nq)
 	{
-		rc = fk_chain(c, m.format, m.standin, m.smin, mwords);
+		rc = fk_chain(c, m.format, m, mwords);
 		if (aut) pl.loose_form = d.form;
 		return rc;
 	}
@@ -957,12 +1028,12 @@ static int fk_run(FkCall c, int form, int format, bool aut, uint8_t *d_plan)
 	FkTmp t;
 	if ((rc = fk_auto_gather(c, &t))) return rc;
 	FkCall cl = fk_auto_class(c, t, nl, loose, a.longest[1]);
-	if ((rc = fk_chain(cl, m.format, m.standin, m.smin, mwords))) return rc;
+	if ((rc = fk_chain(cl, m.format, m, mwords))) return rc;
 	if ((rc = fk_auto_scatter(c, t, nl, loose))) return rc;
 	const FkWs::Diag first = d;
 	FkCall cs = fk_auto_class(c, t, 0, nl, a.longest[0]);
 	if ((rc = fk_again(cs, true))) return rc;
-	if ((rc = fk_chain(cs, -1, m.standin, m.smin, mwords))) return rc;
+	if ((rc = fk_chain(cs, -1, m, mwords))) return rc;
 	if ((rc = fk_auto_scatter(c, t, 0, nl))) return rc;
 	HIPCHK(hipStreamSynchronize(c.s));
 	// the call's figures: the sums over both classes, the loose class's filter and form (the listed pass's call time counts from the call's start: the whole call's)
@@ -970,88 +1041,6 @@ static int fk_run(FkCall c, int form, int format, bool aut, uint8_t *d_plan)
 	d.dist_pass = first.dist_pass; d.appended = first.appended; d.filter_ms = first.filter_ms; d.form = first.form;
 	pl.loose_form = first.form;
 	return HNSW_GPU_OK;
-}
-
-// ---- exact grouped k-NN: the listed form's host path with the grouped list in the scan and the merge (device_grouped_knn.h) ----
-// behind the list build: the group word of every list entry (counted with the build's time, like the masks of the matrix-core form)
-static int gk_groups(FkCall &c)
-{
-	FkWs *fw = &c.ix->fk;
-	if (int rc = buf_reserve(&fw->grp, c.total * 4, c.fam->who, "the group words of the lists")) return rc;
-	if (c.total)
-	{
-		const GkGroups gg = { (const uint32_t *) fw->list.p, c.total, c.ix->labels, c.group_of, c.group_entries, (uint32_t *) fw->grp.p };
-		const uint32_t blocks = (uint32_t) std::min<size_t>((c.total + 255) / 256, (size_t) c.ix->num_cu * 8);
-		hipLaunchKernelGGL(gk_groups_kernel, dim3(blocks), dim3(256), 0, c.s, gg);
-		HIPCHK(hipGetLastError());
-	}
-	HIPCHK(hipEventRecord(fw->ev[1], c.s));
-	return HNSW_GPU_OK;
-}
-
-// the scan over every query's whole list -> merge -> emit: fk_pass's listed form, pairs of (key, group) in place of keys
-static int gk_pass(FkCall &c)
-{
-	hnsw_gpu_index *ix = c.ix;
-	FkWs *fw = &ix->fk;
-	hipStream_t s = c.s;
-	const size_t nq = c.nq, k = c.k;
-	const int func = (int) ix->meta.dist_func;
-	const QueryGeom g(ix->stride);
-	uint32_t splits = 1;
-	int rc = fk_splits(c, c.longest, &splits, 12);
-	if (rc) return rc;
-	const size_t o_grp = round_up(nq * k * 8, 256), o_cnt = o_grp + round_up(nq * k * 4, 256), total = o_cnt + round_up(nq * 4, 256);
-	if ((rc = buf_reserve(&fw->bfs, total, c.fam->who, "the per-query scratch"))) return rc;
-	char *B = (char *) fw->bfs.p;
-	uint64_t *keys = (uint64_t *) B;
-	uint32_t *groups = (uint32_t *) (B + o_grp), *rcount = (uint32_t *) (B + o_cnt);
-	GkMerge gm;
-	memset(&gm, 0, sizeof(gm));
-	FkScan &fs = gm.g.s;
-	fs.vec = ix->vec; fs.dim = (uint32_t) ix->meta.dim; fs.stride = ix->stride; fs.nchunks = g.nchunks; fs.kiters = g.kiters; fs.qpad_floats = g.qpad;
-	fs.queries = c.queries; fs.nq = (uint32_t) nq; fs.k = (uint32_t) k; fs.splits = splits;
-	fs.list = (const uint32_t *) fw->list.p; fs.off = c.off; fs.nseg = c.fl.nseg; fs.allow_of = c.allow_of;
-	fs.part = (uint64_t *) fw->part.p; fs.scored = c.scored; fs.radius = c.radius; fs.func = func;
-	gm.g.glist = (const uint32_t *) fw->grp.p;
-	gm.g.gpart = (uint32_t *) ((char *) fw->part.p + nq * splits * 4 * k * 8);     // the partial groups behind the partial keys
-	gm.keys = keys; gm.groups = groups; gm.count = rcount;
-	if (c.longest)
-	{
-		const dim3 grid((uint32_t) round_up((size_t) splits * nq, 8));
-		with_func(func, [&](auto F) { hipLaunchKernelGGL(gk_scan_kernel<decltype(F)::value>, grid, dim3(256), g.lds_grouped(k), s, gm.g); });
-	}
-	hipLaunchKernelGGL(gk_merge_kernel, dim3((uint32_t) nq), dim3(64), (k + 1) * 12, s, gm);
-	const FkEmit fe = { keys, rcount, (uint32_t) k, ix->labels, (uint32_t) ix->n, c.labels, c.dists, c.idx, c.counts, nullptr, nullptr, groups, c.groups };
-	hipLaunchKernelGGL(fk_emit_kernel, dim3((uint32_t) nq), dim3(64), k * 16, s, fe);
-	hipError_t e = hipGetLastError();
-	if (e == hipSuccess) e = hipEventRecord(fw->ev[2], s);
-	if (e == hipSuccess) e = hipMemcpyAsync(&fw->host[2], c.scored, 8, hipMemcpyDeviceToHost, s);
-	const hipError_t e2 = hipStreamSynchronize(s);
-	if (e == hipSuccess) e = e2;
-	if (e != hipSuccess) return fail(HNSW_GPU_ERR_HIP, "%s: %s", c.fam->who, hipGetErrorString(e));
-	FkWs::Diag &m = fw->*c.fam->diag;
-	m.listed = c.total; m.scored = fw->host[2];
-	(void) hipEventElapsedTime(&m.build_ms, fw->ev[0], fw->ev[1]);
-	(void) hipEventElapsedTime(&m.call_ms, fw->ev[0], fw->ev[2]);
-	(void) hipEventElapsedTime(&m.scan_ms, fw->ev[1], fw->ev[2]);
-	m.form = HNSW_GPU_FK_FORM_LISTED;
-	return HNSW_GPU_OK;
-}
-
-static int gk_run(FkCall c)
-{
-	std::unique_lock<std::recursive_mutex> lock_;
-	if (c.ix) lock_ = std::unique_lock<std::recursive_mutex>(c.ix->mu);
-	if (int rc0 = fk_check(c, FK_LISTED, ROWS_F32)) return rc0;
-	if (c.nq == 0) return HNSW_GPU_OK;
-	if (!c.allow) { c.allow_bits = 0; c.nfilters = 1; c.allow_of = nullptr; }   // (fk_run: ONE implicit bitmap that every label passes)
-	FkTrim trim_{&c.ix->fk};
-	int rc = fk_begin(c);
-	if (!rc) rc = fk_lists(c);
-	if (!rc) rc = gk_groups(c);
-	if (!rc) rc = gk_pass(c);
-	return rc;
 }
 
 // the driver of every host-pointer entry point: copy in, run on the default stream, copy out
@@ -1083,7 +1072,7 @@ static int fk_host(const FkCall &h, int form, int format, bool aut, uint8_t *pla
 	if (h.radius) HIPCHK(hipMemcpy((void *) d.radius, h.radius, nq * 4, hipMemcpyHostToDevice));
 	if (h.allow) HIPCHK(hipMemcpy((void *) d.allow, h.allow, h.nfilters * words * 4, hipMemcpyHostToDevice));
 	if (of) HIPCHK(hipMemcpy((void *) d.allow_of, h.allow_of, nq * 4, hipMemcpyHostToDevice));
-	if ((rc = h.fam->grouped ? gk_run(d) : fk_run(d, form, format, aut, dp))) return rc;
+	if ((rc = fk_run(d, form, format, aut, dp))) return rc;
 	HIPCHK(hipMemcpy(h.labels, d.labels, nq * k * 8, hipMemcpyDeviceToHost));
 	if (h.dists) HIPCHK(hipMemcpy(h.dists, d.dists, nq * k * 4, hipMemcpyDeviceToHost));
 	if (h.idx) HIPCHK(hipMemcpy(h.idx, d.idx, nq * k * 4, hipMemcpyDeviceToHost));
@@ -1190,20 +1179,30 @@ static FkCall gk_call(hnsw_gpu_index *ix, const coord_t *queries, size_t nq, siz
 	return c;
 }
 
-extern "C" int hnsw_gpu_grouped_knn_dev(hnsw_gpu_index *ix, const coord_t *d_queries, size_t nq, size_t k, const uint32_t *d_group_of, size_t group_entries,
-										const dist_t *d_radius, const uint32_t *d_allow, size_t allow_bits, size_t nfilters, const uint32_t *d_allow_of,
-										label_t *d_labels, dist_t *d_dists, idx_t *d_idx, uint32_t *d_groups, uint32_t *d_counts, void *stream)
+#define GK_ARGS_DEV const coord_t *d_queries, size_t nq, size_t k, const uint32_t *d_group_of, size_t group_entries, const dist_t *d_radius, const uint32_t *d_allow, \
+	size_t allow_bits, size_t nfilters, const uint32_t *d_allow_of, label_t *d_labels, dist_t *d_dists, idx_t *d_idx, uint32_t *d_groups, uint32_t *d_counts
+#define GK_CALL_DEV(stream) gk_call(ix, d_queries, nq, k, d_group_of, group_entries, d_radius, d_allow, allow_bits, nfilters, d_allow_of, d_labels, d_dists, d_idx, d_groups, d_counts, stream)
+#define GK_ARGS_HOST const coord_t *queries, size_t nq, size_t k, const uint32_t *group_of, size_t group_entries, const dist_t *radius, const uint32_t *allow, \
+	size_t allow_bits, size_t nfilters, const uint32_t *allow_of, label_t *labels, dist_t *dists, idx_t *idx, uint32_t *groups, uint32_t *counts
+#define GK_CALL_HOST gk_call(ix, queries, nq, k, group_of, group_entries, radius, allow, allow_bits, nfilters, allow_of, labels, dists, idx, groups, counts, nullptr)
+
+extern "C" int hnsw_gpu_grouped_knn_dev(hnsw_gpu_index *ix, GK_ARGS_DEV, void *stream) { return fk_run(GK_CALL_DEV(stream), FK_LISTED, ROWS_F32, false, nullptr); }
+extern "C" int hnsw_gpu_grouped_knn_mfma_dev(hnsw_gpu_index *ix, int format, GK_ARGS_DEV, void *stream) { return fk_run(GK_CALL_DEV(stream), FK_MFMA, format, false, nullptr); }
+extern "C" int hnsw_gpu_grouped_knn_auto_dev(hnsw_gpu_index *ix, int format, GK_ARGS_DEV, uint8_t *d_plan, void *stream)
 {
-	return gk_run(gk_call(ix, d_queries, nq, k, d_group_of, group_entries, d_radius, d_allow, allow_bits, nfilters, d_allow_of, d_labels, d_dists, d_idx, d_groups,
-						  d_counts, stream));
+	return fk_run(GK_CALL_DEV(stream), FK_MFMA, format, true, d_plan);
 }
 
-extern "C" int hnsw_gpu_grouped_knn(hnsw_gpu_index *ix, const coord_t *queries, size_t nq, size_t k, const uint32_t *group_of, size_t group_entries,
-									const dist_t *radius, const uint32_t *allow, size_t allow_bits, size_t nfilters, const uint32_t *allow_of, label_t *labels,
-									dist_t *dists, idx_t *idx, uint32_t *groups, uint32_t *counts)
+extern "C" int hnsw_gpu_grouped_knn(hnsw_gpu_index *ix, GK_ARGS_HOST) { return fk_host(GK_CALL_HOST, FK_LISTED, ROWS_F32, false, nullptr); }
+extern "C" int hnsw_gpu_grouped_knn_mfma(hnsw_gpu_index *ix, int format, GK_ARGS_HOST)
 {
-	return fk_host(gk_call(ix, queries, nq, k, group_of, group_entries, radius, allow, allow_bits, nfilters, allow_of, labels, dists, idx, groups, counts, nullptr),
-				   FK_LISTED, ROWS_F32, false, nullptr);
+	if (format < 0) return fail(HNSW_GPU_ERR_ARG, "grouped k-NN: bad format %d", format);
+	return fk_host(GK_CALL_HOST, FK_MFMA, format, false, nullptr);
+}
+extern "C" int hnsw_gpu_grouped_knn_auto(hnsw_gpu_index *ix, int format, GK_ARGS_HOST, uint8_t *plan)
+{
+	if (format < 0) return fail(HNSW_GPU_ERR_ARG, "grouped k-NN: bad format %d", format);
+	return fk_host(GK_CALL_HOST, FK_MFMA, format, true, plan);
 }
 
 // ---- what the last call of either family left (include/hnsw_gpu_diag.h) -------------------------------------------------------------------
@@ -1218,6 +1217,7 @@ static int fk_plan_out(hnsw_gpu_index *ix, FkWs::Plan FkWs::*which, uint64_t out
 }
 extern "C" int hnsw_gpu_last_filtered_knn_plan(hnsw_gpu_index *ix, uint64_t out[8]) { return fk_plan_out(ix, &FkWs::plan, out); }
 extern "C" int hnsw_gpu_last_range_knn_plan(hnsw_gpu_index *ix, uint64_t out[8]) { return fk_plan_out(ix, &FkWs::rplan, out); }
+extern "C" int hnsw_gpu_last_grouped_knn_plan(hnsw_gpu_index *ix, uint64_t out[8]) { return fk_plan_out(ix, &FkWs::gplan, out); }
 
 static uint64_t fk_us(float ms) { return (uint64_t) std::llround((double) ms * 1000.0); }
 
@@ -1239,15 +1239,18 @@ extern "C" int hnsw_gpu_last_grouped_knn(hnsw_gpu_index *ix, uint64_t out[4])
 	return HNSW_GPU_OK;
 }
 
-extern "C" int hnsw_gpu_last_filtered_knn_mfma(hnsw_gpu_index *ix, uint64_t out[7])
+static int fk_filter_out(hnsw_gpu_index *ix, FkWs::Diag FkWs::*which, uint64_t out[7])
 {
 	if (!ix || !out) return fail(HNSW_GPU_ERR_ARG, "NULL argument");
 	std::lock_guard<std::recursive_mutex> lock_(ix->mu);
-	const FkWs::Diag &m = ix->fk.kf;
+	const FkWs::Diag &m = ix->fk.*which;
 	out[0] = m.listed; out[1] = m.scored; out[2] = m.dist_pass; out[3] = m.appended;
 	out[4] = fk_us(m.build_ms); out[5] = fk_us(m.filter_ms); out[6] = fk_us(m.call_ms);
 	return HNSW_GPU_OK;
 }
+extern "C" int hnsw_gpu_last_filtered_knn_mfma(hnsw_gpu_index *ix, uint64_t out[7]) { return fk_filter_out(ix, &FkWs::kf, out); }
+extern "C" int hnsw_gpu_last_grouped_knn_mfma(hnsw_gpu_index *ix, uint64_t out[7]) { return fk_filter_out(ix, &FkWs::gf, out); }
+extern "C" long long hnsw_gpu_last_grouped_knn_overflowed(hnsw_gpu_index *ix) { return ix ? (long long) ix->fk.gf.overflowed : -1; }
 
 extern "C" int hnsw_gpu_last_range_knn(hnsw_gpu_index *ix, uint64_t out[8])
 {
@@ -1267,6 +1270,7 @@ static int fk_form_out(hnsw_gpu_index *ix, FkWs::Diag FkWs::*which)
 }
 extern "C" int hnsw_gpu_last_filtered_knn_form(hnsw_gpu_index *ix) { return fk_form_out(ix, &FkWs::k); }
 extern "C" int hnsw_gpu_last_range_knn_form(hnsw_gpu_index *ix) { return fk_form_out(ix, &FkWs::r); }
+extern "C" int hnsw_gpu_last_grouped_knn_form(hnsw_gpu_index *ix) { return fk_form_out(ix, &FkWs::g); }
 
 extern "C" int hnsw_gpu_last_bruteforce_form(hnsw_gpu_index *ix)
 {

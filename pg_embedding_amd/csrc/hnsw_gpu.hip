@@ -45,7 +45,7 @@ static const KnobDef g_knob_def[K_COUNT] = {
 	{ "HNSW_GPU_BEAM16", false }, { "HNSW_GPU_NARROW5", false }, { "HNSW_GPU_LEAN", false }, { "HNSW_GPU_HASH_ENTRIES", false }, { "HNSW_GPU_LDS_SET_MIN_WAVES", false },
 	{ "HNSW_GPU_TEAM_SPEC", false }, { "HNSW_GPU_TEAM_WPB", false }, { "HNSW_GPU_NARROW_WPB", false }, { "HNSW_GPU_ABORT_POLL_LOG2", false }, { "HNSW_GPU_MAX_BLOCKS", false }, { "HNSW_GPU_SHARDED_NO_PEER", false },
 	{ "HNSW_GPU_BF_BIG_MIN_BLOCKS", false }, { "HNSW_GPU_LOCALITY_MIN_NQ", false },
-	{ "HNSW_GPU_FK_SAMPLE_MIN", false }, { "HNSW_GPU_FK_MFMA_STANDIN", false }, { "HNSW_GPU_FK_AUTO_SPLIT", false },
+	{ "HNSW_GPU_FK_SAMPLE_MIN", false }, { "HNSW_GPU_FK_MFMA_STANDIN", false }, { "HNSW_GPU_FK_AUTO_SPLIT", false }, { "HNSW_GPU_GK_SAMPLE_FACTOR", true },
 };
 KnobVal g_knob[K_COUNT];
 static std::once_flag g_knob_once;

@@ -609,14 +609,19 @@ class GpuIndex:
                 "build_ms": v[5] / 1000.0, "filter_ms": v[6] / 1000.0, "call_ms": v[7] / 1000.0}
 
     # ---------------------------------------------------------------- exact grouped k-NN
-    def grouped_knn(self, queries: np.ndarray, k: int, group_of, allow=None, allow_of=None, radius=None, return_idx: bool = False):
+    def grouped_knn(self, queries: np.ndarray, k: int, group_of, allow=None, allow_of=None, radius=None, return_idx: bool = False, form=None,
+                    rows=None):
         """Exact k nearest distinct GROUPS per query, each through its nearest member, host buffers (hnsw_gpu_grouped_knn): the plan of
         SELECT DISTINCT ON (doc_id) ... ORDER BY emb <-> q LIMIT k over a table with several rows per document.  group_of: a uint32 / int32
         array over label VALUES — the group of an element with label l is group_of[l]; a label >= len(group_of) or a group word NO_GROUP
         (0xFFFFFFFF, -1) takes no part.  allow / allow_of as in range_knn() (allow=None: every label passes); radius: None (no radius), a
         scalar or one value per query (inclusive; NaN selects nothing).  Returns a dict: labels [nq, k] u64 in ascending (distance, label)
         order (tail ~0), dists [nq, k] f32 (tail +inf), groups [nq, k] u32 = the group of each row (tail 0xFFFFFFFF), counts [nq] u32 =
-        min(k, groups with a member in range), and with return_idx=True idx [nq, k] u32 element numbers (tail 0xFFFFFFFF)."""
+        min(k, groups with a member in range), and with return_idx=True idx [nq, k] u32 element numbers (tail 0xFFFFFFFF).  form=None |
+        "listed": a scan over each query's allowed rows; form="mfma": the same bytes with the Q x N part on the matrix cores, for loose filters
+        and for no filter (hnsw_gpu_grouped_knn_mfma); rows=None | "f16" | "bf16" names its operands; form="auto": the form chosen per query
+        as in filtered_knn() (hnsw_gpu_grouped_knn_auto; plan [nq] u8 in the dict, last_grouped_knn_plan())."""
+        code = self._fk_form(form, rows)
         queries = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, self.meta.dim)
         nq, k = queries.shape[0], int(k)
         tab = np.asarray(group_of)
@@ -630,17 +635,26 @@ class GpuIndex:
                "counts": np.empty(nq, np.uint32)}
         if return_idx:
             out["idx"] = np.empty((nq, k), np.uint32)
-        check(self.L.hnsw_gpu_grouped_knn(self._h, queries.ctypes.data, nq, k, tab.ctypes.data, tab.shape[0], None if rad is None else rad.ctypes.data,
-                                          None if words is None else words.ctypes.data, bits, nf, None if of is None else of.ctypes.data,
-                                          out["labels"].ctypes.data, out["dists"].ctypes.data, out["idx"].ctypes.data if return_idx else None,
-                                          out["groups"].ctypes.data, out["counts"].ctypes.data), "hnsw_gpu_grouped_knn")
+        tail = (queries.ctypes.data, nq, k, tab.ctypes.data, tab.shape[0], None if rad is None else rad.ctypes.data,
+                None if words is None else words.ctypes.data, bits, nf, None if of is None else of.ctypes.data,
+                out["labels"].ctypes.data, out["dists"].ctypes.data, out["idx"].ctypes.data if return_idx else None,
+                out["groups"].ctypes.data, out["counts"].ctypes.data)
+        if form == "auto":
+            out["plan"] = np.empty(nq, np.uint8)
+            check(self.L.hnsw_gpu_grouped_knn_auto(self._h, code, *tail, out["plan"].ctypes.data), "hnsw_gpu_grouped_knn_auto")
+        elif code is None:
+            check(self.L.hnsw_gpu_grouped_knn(self._h, *tail), "hnsw_gpu_grouped_knn")
+        else:
+            check(self.L.hnsw_gpu_grouped_knn_mfma(self._h, code, *tail), "hnsw_gpu_grouped_knn_mfma")
         return out
 
-    def grouped_knn_torch(self, queries, k: int, group_of, allow=None, allow_of=None, radius=None, return_idx: bool = False):
+    def grouped_knn_torch(self, queries, k: int, group_of, allow=None, allow_of=None, radius=None, return_idx: bool = False, form=None, rows=None):
         """grouped_knn() with everything resident in HBM (hnsw_gpu_grouped_knn_dev on torch's current stream, which the call synchronises).
         group_of: an int32 (the bits of a uint32) or uint32 tensor over label values; allow / allow_of as in filtered_knn_torch(), allow=None:
         every label passes; radius: None, a number or a float tensor [nq].  Returns a dict: labels [nq, k] int64 (tail -1), dists [nq, k]
-        (tail +inf), groups [nq, k] int32 (tail -1), counts [nq] int32, idx [nq, k] int32 (tail -1) with return_idx=True."""
+        (tail +inf), groups [nq, k] int32 (tail -1), counts [nq] int32, idx [nq, k] int32 (tail -1) with return_idx=True.  form / rows as in
+        grouped_knn() (hnsw_gpu_grouped_knn_mfma_dev, hnsw_gpu_grouped_knn_auto_dev: plan [nq] uint8)."""
+        code = self._fk_form(form, rows)
         torch = _torch()
         assert queries.is_cuda and queries.dtype == torch.float32 and queries.is_contiguous()
         nq, k, dev = queries.shape[0], int(k), queries.device
@@ -664,9 +678,15 @@ class GpuIndex:
         if return_idx:
             out["idx"] = torch.empty((nq, k), dtype=torch.int32, device=dev)
         s = torch.cuda.current_stream(dev).cuda_stream
-        check(self.L.hnsw_gpu_grouped_knn_dev(self._h, queries.data_ptr(), nq, k, tab.data_ptr(), tab.numel(), _dptr(rad), _dptr(words), bits, nf, _dptr(of),
-                                              out["labels"].data_ptr(), out["dists"].data_ptr(), _dptr(out.get("idx")), out["groups"].data_ptr(),
-                                              out["counts"].data_ptr(), s), "hnsw_gpu_grouped_knn_dev")
+        tail = (queries.data_ptr(), nq, k, tab.data_ptr(), tab.numel(), _dptr(rad), _dptr(words), bits, nf, _dptr(of), out["labels"].data_ptr(),
+                out["dists"].data_ptr(), _dptr(out.get("idx")), out["groups"].data_ptr(), out["counts"].data_ptr())
+        if form == "auto":
+            out["plan"] = torch.empty(nq, dtype=torch.uint8, device=dev)
+            check(self.L.hnsw_gpu_grouped_knn_auto_dev(self._h, code, *tail, out["plan"].data_ptr(), s), "hnsw_gpu_grouped_knn_auto_dev")
+        elif code is None:
+            check(self.L.hnsw_gpu_grouped_knn_dev(self._h, *tail, s), "hnsw_gpu_grouped_knn_dev")
+        else:
+            check(self.L.hnsw_gpu_grouped_knn_mfma_dev(self._h, code, *tail, s), "hnsw_gpu_grouped_knn_mfma_dev")
         return out
 
     def last_grouped_knn(self) -> dict:
@@ -676,6 +696,25 @@ class GpuIndex:
         v = (C.c_uint64 * 4)()
         check(self.L.hnsw_gpu_last_grouped_knn(self._h, v), "hnsw_gpu_last_grouped_knn")
         return {"listed": int(v[0]), "rows_scored": int(v[1]), "build_ms": v[2] / 1000.0, "scan_ms": v[3] / 1000.0}
+
+    def last_grouped_knn_form(self) -> Optional[str]:
+        """The form that answered the last grouped_knn call of any form on this mirror: "listed", "f32", "f16" or "bf16", or None before
+        the first one (hnsw_gpu_last_grouped_knn_form)."""
+        return {0: "listed", 1: "f32", 2: "f16", 3: "bf16"}.get(int(self.L.hnsw_gpu_last_grouped_knn_form(self._h)))
+
+    def last_grouped_knn_mfma(self) -> dict:
+        """last_filtered_knn_mfma() for the last filter launch of a grouped_knn call (hnsw_gpu_last_grouped_knn_mfma); zeros when the last
+        call ran no filter.  overflowed: the queries whose candidate list overflowed in that launch (the call was handed down)."""
+        v = (C.c_uint64 * 7)()
+        check(self.L.hnsw_gpu_last_grouped_knn_mfma(self._h, v), "hnsw_gpu_last_grouped_knn_mfma")
+        return {"listed": int(v[0]), "rows_scored": int(v[1]), "dist_pass": int(v[2]), "appended": int(v[3]), "build_ms": v[4] / 1000.0,
+                "filter_ms": v[5] / 1000.0, "call_ms": v[6] / 1000.0, "overflowed": int(self.L.hnsw_gpu_last_grouped_knn_overflowed(self._h))}
+
+    def last_grouped_knn_plan(self) -> dict:
+        """last_filtered_knn_plan() for the last form="auto" grouped_knn call (hnsw_gpu_last_grouped_knn_plan)."""
+        v = (C.c_uint64 * 8)()
+        check(self.L.hnsw_gpu_last_grouped_knn_plan(self._h, v), "hnsw_gpu_last_grouped_knn_plan")
+        return self._plan_dict(v)
 
     def last_search_ms(self, back: int = 0) -> float:
         """Device time of the search kernel launched `back` launches ago (HIP events recorded on
