@@ -13,16 +13,18 @@
 //                        the total and the longest list go to a pinned host pair (the call's one wait before the scan)
 //      fk_fill_kernel    the count kernel's pass again, writing element numbers: list b = A(b) ascending, lists back to back, 4 bytes
 //                        per entry (CSR: offsets off[b * nseg] .. off[(b + 1) * nseg])
-//      rk_live_kernel    both passes (and the mask row of the matrix-core form) for the call without a filter: the rows that are not vacuumed
-//   2. fk_scan_kernel    bruteforce_kernel (device_topk_scan.h) with the rows read from the list: a wave takes a contiguous slice of its
-//                        query's list, 64 entries per step (loaded coalesced, once, into the wave's LDS: StagedRows), scores them with the
-//                        canonical distance code and keeps a sorted top-k of the (ord(dist) << 32 | ELEMENT) keys of the entries that
-//                        qualify, and their number (scan_topk_within: one ballot + popcount per step) -> a partial key list and a partial
-//                        count per wave.  A query uses as many waves as its own list is long (FK_WAVE_ROWS rows each at least, at most
-//                        the launch's splits * 4).  The listed form scans every query's whole list; the matrix-core form
+//                        (both kernels serve the call without a filter too: fk_in is then the vacuum test alone)
+//   2. fk_scan_kernel<FUNC, List>  bruteforce_kernel (device_topk_scan.h) with the rows read from the list: a wave takes a contiguous slice
+//                        of its query's list, 64 entries per step (loaded coalesced, once, into the wave's LDS: StagedRows), scores them
+//                        with the canonical distance code and offers the (ord(dist) << 32 | ELEMENT) keys of the entries that qualify to
+//                        its List (scan_list, device_topk_scan.h) -> a partial list per wave and (KeyList) a partial count of the
+//                        qualifying entries.  A query uses as many waves as its own list is long (FK_WAVE_ROWS rows each at least, at
+//                        most the launch's splits * 4).  The listed form scans every query's whole list; the matrix-core form
 //                        (device_filtered_knn_mfma.h) the lists it scans whole and, unless totals are asked for, the samples of the longer ones
+//                        List = KeyList: filtered k-NN and radius search; GroupedList: grouped k-NN (device_grouped_knn.h)
 //   3. fk_merge_kernel   one wave per query: merges the partial lists (merge_ranks: keys are unique) into ONE ascending key list, sums the
-//                        partial counts; matrix-core form: the bound tau_q and the query's mask row
+//                        partial counts (grouped k-NN: gk_merge_kernel, by offers); matrix-core form: the bound tau_q and the query's mask
+//                        row (fk_merge_tail, the end of both)
 //   4. fk_emit_kernel    one wave per query, from its key list and its count: gathers the labels of the min(k, count) winners, ranks them
 //                        by (dist, label, element) — hnsw_search's order — and writes labels, distances, element numbers, the count, the
 //                        padded tails and (radius calls) the total; (grouped k-NN, device_grouped_knn.h) the group of every returned row
@@ -56,6 +58,13 @@ __device__ __forceinline__ bool fk_member(uint64_t lab, const uint32_t *bits, ui
 	const uint32_t w = bits[cand ? (size_t) (lab >> 5) : 0];          // (unconditional load, clamped: allow_bits >= 1)
 	return cand && ((w >> (lab & 31u)) & 1u);
 }
+// bitmap b of the call, or NULL: a call without a filter (a.allow == NULL, nfilters == 1: ONE implicit bitmap that every label passes)
+__device__ __forceinline__ const uint32_t *fk_bits(const FkLists &a, uint32_t b) { return a.allow ? a.allow + (size_t) b * a.allow_words : nullptr; }
+// THE membership test of every list and mask kernel: not vacuumed and, with a bitmap, the label passes it (bits: wave-uniform)
+__device__ __forceinline__ bool fk_in(const FkLists &a, uint64_t lab, const uint32_t *bits)
+{
+	return bits ? fk_member(lab, bits, a.allow_bits) : !((lab >> 48) & 1ull);
+}
 
 // grid = nfilters * ceil(nseg / 4) blocks of 256, bitmap-major: wave wib of block (b, x) counts segment x * 4 + wib of bitmap b
 __device__ __forceinline__ bool fk_cell(const FkLists &a, uint32_t &b, uint32_t &seg)
@@ -71,14 +80,14 @@ __global__ __launch_bounds__(256) void fk_count_kernel(const FkLists a, uint32_t
 	const uint32_t lane = threadIdx.x & 63u;
 	uint32_t b, seg;
 	if (!fk_cell(a, b, seg)) return;
-	const uint32_t *bits = a.allow + (size_t) b * a.allow_words;
+	const uint32_t *bits = fk_bits(a, b);
 	const uint32_t r0 = seg * FK_SEG, r1 = min(a.n, r0 + FK_SEG);
 	uint32_t c = 0;
 	for (uint32_t base = r0; base < r1; base += 64)
 	{
 		const uint32_t i = base + lane;
 		const uint64_t lab = a.labels[i < r1 ? i : r1 - 1];
-		c += (uint32_t) __builtin_popcountll(__ballot(i < r1 && fk_member(lab, bits, a.allow_bits)));
+		c += (uint32_t) __builtin_popcountll(__ballot(i < r1 && fk_in(a, lab, bits)));
 	}
 	if (lane == 0) counts[(size_t) b * a.nseg + seg] = c;
 }
@@ -131,7 +140,7 @@ __global__ __launch_bounds__(256) void fk_fill_kernel(const FkLists a, const uin
 	uint32_t b, seg;
 	if (!fk_cell(a, b, seg)) return;
 	const uint64_t below = (1ull << lane) - 1ull;
-	const uint32_t *bits = a.allow + (size_t) b * a.allow_words;
+	const uint32_t *bits = fk_bits(a, b);
 	const uint32_t r0 = seg * FK_SEG, r1 = min(a.n, r0 + FK_SEG);
 	uint32_t *dst = list + off[(size_t) b * a.nseg + seg];
 	uint32_t c = 0;
@@ -139,40 +148,11 @@ __global__ __launch_bounds__(256) void fk_fill_kernel(const FkLists a, const uin
 	{
 		const uint32_t i = base + lane;
 		const uint64_t lab = a.labels[i < r1 ? i : r1 - 1];
-		const bool in = i < r1 && fk_member(lab, bits, a.allow_bits);
+		const bool in = i < r1 && fk_in(a, lab, bits);
 		const uint64_t m = __ballot(in);
 		if (in) dst[c + (uint32_t) __builtin_popcountll(m & below)] = i;
 		c += (uint32_t) __builtin_popcountll(m);
 	}
-}
-
-// ---- the rows that are not vacuumed as ONE list / mask row (a call without a filter) ------------------------------------------------------
-enum { RK_LIVE_COUNT = 0, RK_LIVE_FILL = 1, RK_LIVE_MASK = 2 };
-
-// fk_count_kernel's grid and pass with nfilters = 1.  COUNT: out = counts [nseg];  FILL: out = the list, off = the segments' offsets;
-// MASK: out = the mask row, a ballot per 64 rows
-template <int MODE>
-__global__ __launch_bounds__(256) void rk_live_kernel(const FkLists a, const uint64_t *__restrict__ off, uint32_t *__restrict__ out)
-{
-	const uint32_t lane = threadIdx.x & 63u;
-	uint32_t b, seg;
-	if (!fk_cell(a, b, seg) || b != 0) return;
-	const uint64_t below = (1ull << lane) - 1ull;
-	const uint32_t r0 = seg * FK_SEG, r1 = min(a.n, r0 + FK_SEG);
-	uint32_t *dst = out;
-	if (MODE == RK_LIVE_FILL) dst = out + off[seg];
-	uint32_t c = 0;
-	for (uint32_t base = r0; base < r1; base += 64)
-	{
-		const uint32_t i = base + lane;
-		const uint64_t lab = a.labels[i < r1 ? i : r1 - 1];
-		const bool in = i < r1 && !((lab >> 48) & 1ull);
-		const uint64_t m = __ballot(in);
-		if (MODE == RK_LIVE_FILL && in) dst[c + (uint32_t) __builtin_popcountll(m & below)] = i;
-		if (MODE == RK_LIVE_MASK && lane < 2) dst[(base >> 5) + lane] = (uint32_t) (m >> (32u * lane));
-		c += (uint32_t) __builtin_popcountll(m);
-	}
-	if (MODE == RK_LIVE_COUNT && lane == 0) out[seg] = c;
 }
 
 // The sample of a list of `len` entries (the matrix-core form's bound, device_filtered_knn_mfma.h): its first min(len, max(smin, k len / 2048))
@@ -189,7 +169,9 @@ struct FkScan
 	const float *queries; uint32_t nq, k, splits;
 	const uint32_t *list; const uint64_t *off; uint32_t nseg; const uint32_t *allow_of;
 	uint64_t *part;                  // [nq][splits * 4][k] ascending keys, ~0 = none
-	uint32_t *pcount;                // [nq][splits * 4] qualifying entries of every wave's slice
+	uint32_t *pcount;                // KeyList: [nq][splits * 4] qualifying entries of every wave's slice
+	const uint32_t *glist;           // GroupedList (else NULL): the group words of `list`, entry for entry ...
+	uint32_t *gpart;                 // ... and [nq][splits * 4][k] the groups of part's keys, GK_NONE = none
 	unsigned long long *scored;      // rows scored by the call (one atomic per wave)
 	uint32_t smin;                   // 0: a query's whole list; else the matrix-core form's scan: its sample (fk_sample_len)
 	uint32_t sample_k;               // the k of the sample rule: k (grouped k-NN: k * its sample factor, device_grouped_knn_mfma.h)
@@ -200,34 +182,6 @@ struct FkScan
 
 // a radius that no distance satisfies: NaN, or negative under L2 (a rounded square root: never below +0)
 __device__ __forceinline__ bool rk_selects_nothing(float r, int func) { return r != r || (func == F_L2 && r < 0.f); }
-
-// ---- the wave loop: scan_topk (device_topk_scan.h) with a threshold and a count -------------------------------------------------------------
-// One wave: entries [lo, hi) of `src`; the k smallest keys among those that qualify, ascending, in top[0 .. return value); nqual = how many
-// entries qualified (one ballot + popcount per step, no atomic).  within (wave-uniform): an entry qualifies if d <= radius, else always.
-template <int FUNC, class Source>
-__device__ __forceinline__ uint32_t scan_topk_within(const float *__restrict__ vec, uint32_t stride, const float4 *q4, uint32_t nchunks,
-													 uint32_t kiters, const Source &src, uint32_t lo, uint32_t hi, uint64_t *top, float *sums,
-													 uint32_t k, bool within, float radius, uint32_t &nqual, int lane)
-{
-	float qnorm = 0.f;
-	if (FUNC == F_COSINE) qnorm = query_norm(q4, nchunks, kiters, lane);
-	uint32_t tsize = 0, nin = 0;
-	uint64_t worst = ~0ull;
-	for (uint32_t base = lo; base < hi; base += 64)
-	{
-		const uint32_t cnt = min(64u, hi - base);
-		const uint32_t id = src.id(base, cnt, lane);
-		score_rows<FUNC, 4, 2>(vec, stride, q4, nchunks, kiters, src.rows(base), cnt, sums, lane);
-		wave_sync();
-		const float dl = finish_dist<FUNC>(sums[lane], sums[OUT2 + lane], qnorm);
-		const bool in = (uint32_t) lane < cnt && (!within || dl <= radius);   // (IEEE: false for a NaN on either side)
-		nin += (uint32_t) __builtin_popcountll(__ballot(in));
-		topk_offer(top, tsize, worst, ((uint64_t) ord_f32(dl) << 32) | id, in, k, lane);
-		wave_sync();
-	}
-	nqual = nin;
-	return tsize;
-}
 
 // the waves query qi scans with, out of the launch's splits * 4, from the length of what it scans
 __device__ __forceinline__ uint32_t fk_waves(uint32_t len, uint32_t splits)
@@ -251,8 +205,9 @@ __device__ __forceinline__ void fk_list_of(const FkScan &a, uint32_t qi, const u
 // grid = splits * nq blocks (rounded up to 8), 4 waves each.  Block order: query number fastest within a split, so the blocks resident at
 // one time cover few list slices and many queries.  (With FK_XCD_REMAP each XCD — blocks are dealt to the 8 XCDs round robin — gets a
 // contiguous eighth of that order, so that the blocks of one slice share one L2: measured, not faster, off.)
-// Per wave in LDS behind the query image: k + 1 keys | 2 x 64 sums | 64 element numbers.
-template <int FUNC>
+// In LDS behind the query image: 4 x (k + 1) keys | 4 x 128 sums | 4 x 64 element numbers | 4 x (k + 1) x what a List entry holds beyond
+// its key.  pcount is written only where it is read: by the key lists' merge.
+template <int FUNC, class List>
 __global__ __launch_bounds__(256) void fk_scan_kernel(const FkScan a)
 {
 	extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -275,18 +230,20 @@ __global__ __launch_bounds__(256) void fk_scan_kernel(const FkScan a)
 	const uint32_t wib = threadIdx.x >> 6, w = sp * 4u + wib, k = a.k;
 	if (w >= nw) return;                                              // (wave-uniform; no block barrier below)
 	unsigned char *wbase = smem + (size_t) a.qpad_floats * 4;
-	uint64_t *top = reinterpret_cast<uint64_t *>(wbase) + (size_t) wib * (k + 1);
-	float *sums = reinterpret_cast<float *>(wbase + (size_t) 4 * (k + 1) * 8) + wib * 128;
-	uint32_t *ids = reinterpret_cast<uint32_t *>(wbase + (size_t) 4 * (k + 1) * 8 + 4 * 128 * 4) + wib * 64;
+	const size_t o_sums = (size_t) 4 * (k + 1) * 8, o_ids = o_sums + 4 * 128 * 4, o_more = o_ids + 4 * 64 * 4;
+	float *sums = reinterpret_cast<float *>(wbase + o_sums) + wib * 128;
+	uint32_t *ids = reinterpret_cast<uint32_t *>(wbase + o_ids) + wib * 64;
+	const List top = List::at(reinterpret_cast<uint64_t *>(wbase) + (size_t) wib * (k + 1), wbase + o_more + (size_t) wib * (k + 1) * (List::LDS_ENTRY - 8));
 	const uint32_t lo = (uint32_t) ((uint64_t) len * w / nw), hi = (uint32_t) ((uint64_t) len * (w + 1) / nw);
 	const bool within = a.radius != nullptr;
 	uint32_t nqual = 0;
-	const uint32_t tsize = scan_topk_within<FUNC>(a.vec, a.stride, q4, a.nchunks, a.kiters, StagedRows{list, ids}, lo, hi, top, sums, k, within,
-												  within ? a.radius[qi] : 0.f, nqual, lane);
-	store_partial(a.part + ((size_t) qi * a.splits * 4u + w) * k, top, tsize, k, lane);
+	const uint32_t tsize = scan_list<FUNC>(a.vec, a.stride, q4, a.nchunks, a.kiters, StagedRows{list, ids}, typename List::OfList(a.glist, (size_t) (list - a.list)), top, lo, hi,
+										   sums, k, within, within ? a.radius[qi] : 0.f, nqual, lane);
+	const size_t pw = (size_t) qi * a.splits * 4u + w;
+	top.store(a.part, a.gpart, pw * k, tsize, k, lane);
 	if (lane == 0)
 	{
-		a.pcount[(size_t) qi * a.splits * 4u + w] = nqual;
+		if (List::PART_ENTRY == 8) a.pcount[pw] = nqual;
 		atomicAdd(a.scored, (unsigned long long) (hi - lo));
 	}
 }
@@ -296,15 +253,33 @@ struct FkMerge
 	FkScan s;
 	uint32_t nfilters;
 	uint64_t *keys;                  // [nq][k] the scan's keys, ascending, ~0 = none
-	uint32_t *count;                 // [nq] qualifying rows of the scan where it is the query's answer, else 0 (the re-score's to write)
+	uint32_t *groups;                // GroupedList (else NULL): [nq][k] their groups
+	uint32_t *count;                 // [nq] qualifying rows of the scan where it is the query's answer, else 0 (the re-score's to write);
+	                                 // GroupedList: the groups with a member in R(q), up to k (a query not answered: the sample's)
 	float *tau;                      // NULL (listed form), or [nq] the bound for make_bounds_kernel
 	uint32_t *mask_of;               // [nq] the query's mask row: its bitmap, or nfilters (zeros) when the scan answered it
 };
 
-// One wave per query (block = 64 threads).  LDS: k keys.  The bound (matrix-core form): with k qualifying rows in the sample its k-th
-// distance — the sample is a subset of R, and under a radius its keys are in range, so the k-th is the smaller of the two — else the
-// radius (none: +inf).  A query whose scan is its complete answer — a list no longer than its sample, a radius that selects nothing —
-// needs no candidate: a bound of 0 keeps its pairs out of the block's pass list, the zero mask row out of its candidates.
+// What both merges end in, by one lane: the query's count and (matrix-core form) its bound and mask row.  have = the qualifying rows (the
+// grouped list: the distinct groups) the scan found, *kth = the k-th key of the merged list (read only with have >= k).  The bound: with
+// have >= k the k-th distance — the sample is a subset of R, and under a radius its keys are in range, so the k-th is the smaller of the
+// two; grouped: each of the k groups has a member within it, so the k best representatives over the whole list are — else the radius
+// (none: +inf).  A query whose scan is its complete answer — a list no longer than its sample, a radius that selects nothing — needs no
+// candidate: a bound of 0 keeps its pairs out of the block's pass list, the zero mask row out of its candidates.  unanswered: the count
+// of a query the re-score is to answer (0; the grouped list: what the sample holds — the re-score writes it again).
+__device__ __forceinline__ void fk_merge_tail(const FkMerge &a, uint32_t qi, bool whole, uint32_t b, uint32_t have, const uint64_t *kth, uint32_t unanswered)
+{
+	const float r = a.s.radius ? a.s.radius[qi] : __builtin_inff();
+	const bool answered = whole || rk_selects_nothing(r, a.s.func);
+	a.count[qi] = answered ? have : unanswered;
+	if (a.tau)
+	{
+		a.tau[qi] = answered ? 0.f : have >= a.s.k ? unord_f32((uint32_t) (*kth >> 32)) : r;
+		a.mask_of[qi] = answered ? a.nfilters : b;
+	}
+}
+
+// One wave per query (block = 64 threads).  LDS: k keys.
 __global__ __launch_bounds__(64) void fk_merge_kernel(const FkMerge a)
 {
 	extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -321,17 +296,7 @@ __global__ __launch_bounds__(64) void fk_merge_kernel(const FkMerge a)
 	for (int o = 32; o > 0; o >>= 1) nin += (uint32_t) __shfl_xor((int) nin, o);
 	wave_sync();
 	for (uint32_t i = lane; i < k; i += 64) a.keys[(size_t) qi * k + i] = win[i];
-	if (lane == 0)
-	{
-		const float r = a.s.radius ? a.s.radius[qi] : __builtin_inff();
-		const bool answered = whole || rk_selects_nothing(r, a.s.func);
-		a.count[qi] = answered ? nin : 0u;
-		if (a.tau)
-		{
-			a.tau[qi] = answered ? 0.f : nin >= k ? unord_f32((uint32_t) (win[k - 1] >> 32)) : r;
-			a.mask_of[qi] = answered ? a.nfilters : b;
-		}
-	}
+	if (lane == 0) fk_merge_tail(a, qi, whole, b, nin, win + (k - 1), 0u);
 }
 
 struct FkEmit

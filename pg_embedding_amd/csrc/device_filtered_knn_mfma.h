@@ -5,9 +5,9 @@
 // The listed scan (device_filtered_knn.h) costs |A(b)| canonical rows per query: at a pass rate of 1/10 that is more than scoring EVERY
 // row on the matrix cores (device_bf_mfma.h).  This form keeps the listed form's answer, bit for bit, and moves the bulk of the work:
 //
-//   1. the lists A(b), as the listed form builds them (fk_count / fk_offsets / fk_fill, or rk_live_kernel without a filter)
-//   2. fkm_mask_kernel    one bit per element number and bitmap: bit r of mask row b = (r in A(b)); one more row of zeros
-//      (rk_live_kernel<RK_LIVE_MASK> without a filter: the one row of the rows that are not vacuumed)
+//   1. the lists A(b), as the listed form builds them (fk_count / fk_offsets / fk_fill)
+//   2. fk_mask_kernel     one bit per element number and bitmap: bit r of mask row b = (r in A(b)); one more row of zeros
+//                         (without a filter: the one row of the rows that are not vacuumed)
 //   3. fk_scan_kernel     over the SAMPLE of every query's list, its first S(b) = fk_sample_len(|A(b)|) entries: the query's k best
 //                         qualifying keys and their number.  With totals only the lists no longer than their sample are scanned
 //      fk_merge_kernel    merges them and sets the bound: tau_q = the k-th qualifying distance of the sample, with fewer than k the radius
@@ -17,7 +17,7 @@
 //   4. bf_mfma_filter_kernel<BfAllow<P>, ...>  all Q x N dot products against make_bounds_kernel's margin of tau_q, as the exhaustive
 //                         call runs it; a passing pair is appended to the query's candidate list only if the row's mask bit is set
 //                         (bf_append<true>).  Counters: pairs that passed the comparison | pairs that were appended (bf_count)
-//   5. fkm_rescore_kernel canonical distances of the candidates: the top-k qualifying keys by (dist, element) and their number, over the
+//   5. fk_rescore_kernel  canonical distances of the candidates: the top-k qualifying keys by (dist, element) and their number, over the
 //                         sample's keys and count except where the sample answered
 //      fk_emit_kernel     labels, (dist, label, element) order, counts, tails and totals — from that one key list and count per query
 //
@@ -47,54 +47,59 @@ struct BfAllow : P
 __host__ __device__ inline uint32_t fkm_mask_words(uint32_t n) { return 2u * ((n + 63u) / 64u); }
 
 // fk_count_kernel's grid and pass: wave (b, seg) writes the words of mask row b for its rows, a ballot per 64 rows (every word of the
-// rows [0, nfilters) is written; row nfilters is the host's memset)
-__global__ __launch_bounds__(256) void fkm_mask_kernel(const FkLists a, uint32_t mwords, uint32_t *__restrict__ mask /* [nfilters + 1][mwords] */)
+// rows [0, nfilters) is written; row nfilters is the host's memset).  The bit of element i: it is in A(b) (fk_in: a call without a filter has
+// the one row of the elements that are not vacuumed) and — egroup: NULL, or grouped k-NN's group word of every element
+// (device_grouped_knn_mfma.h) — it takes part: a row that takes no part never becomes a candidate
+__global__ __launch_bounds__(256) void fk_mask_kernel(const FkLists a, const uint32_t *__restrict__ egroup, uint32_t mwords,
+													  uint32_t *__restrict__ mask /* [nfilters + 1][mwords] */)
 {
 	const uint32_t lane = threadIdx.x & 63u;
 	uint32_t b, seg;
 	if (!fk_cell(a, b, seg)) return;
-	const uint32_t *bits = a.allow + (size_t) b * a.allow_words;
+	const uint32_t *bits = fk_bits(a, b);
 	const uint32_t r0 = seg * FK_SEG, r1 = min(a.n, r0 + FK_SEG);
 	uint32_t *dst = mask + (size_t) b * mwords;
 	for (uint32_t base = r0; base < r1; base += 64)
 	{
-		const uint32_t i = base + lane;
-		const uint64_t lab = a.labels[i < r1 ? i : r1 - 1];
-		const uint64_t m = __ballot(i < r1 && fk_member(lab, bits, a.allow_bits));
+		const uint32_t i = base + lane, at = i < r1 ? i : r1 - 1;
+		const uint64_t m = __ballot(i < r1 && fk_in(a, a.labels[at], bits) && (!egroup || egroup[at] != GK_NONE));
 		if (lane < 2) dst[(base >> 5) + lane] = (uint32_t) (m >> (32u * lane));
 	}
 }
 
-// One wave per query, bf_rescore_kernel's shape and LDS (device_topk_scan.h): canonical distances of the filter's candidates; the top-k
-// among those that qualify (d <= r; radius == NULL: all of them) as keys, and their number.  A query the scan answered (mask row nfilters)
-// keeps what fk_merge_kernel wrote.
-template <int FUNC>
-__global__ __launch_bounds__(256) void fkm_rescore_kernel(const float *__restrict__ vec, uint32_t dim, uint32_t stride, uint32_t nchunks,
-														  uint32_t kiters, uint32_t qpad_floats, const float *__restrict__ queries, uint32_t nq,
-														  const float *__restrict__ radius, const uint32_t *__restrict__ mask_of, uint32_t nfilters,
-														  const uint32_t *__restrict__ cand, const uint32_t *__restrict__ cand_cnt, uint32_t cap,
-														  uint32_t k, uint64_t *__restrict__ keys, uint32_t *__restrict__ count,
-														  uint32_t *__restrict__ overflow)
+struct FkRescore
+{
+	const float *vec; uint32_t dim, stride, nchunks, kiters, qpad_floats;
+	const float *queries; uint32_t nq, k;
+	const float *radius;             // NULL: every candidate qualifies; else [nq]
+	const uint32_t *mask_of; uint32_t nfilters;
+	const uint32_t *cand, *cand_cnt; uint32_t cap;
+	const uint32_t *egroup;          // GroupedList (else NULL): the group word of every element
+	uint64_t *keys;                  // [nq][k] <- the answer's keys, ascending, ~0 = none
+	uint32_t *groups;                // GroupedList (else NULL): [nq][k] <- their groups
+	uint32_t *count;                 // [nq] <- KeyList: the candidates that qualified; GroupedList: the groups of the answer
+	uint32_t *overflow;
+};
+
+// One wave per query, bf_rescore_kernel's shape and LDS (rescore_wave, device_topk_scan.h): canonical distances of the filter's candidates;
+// every candidate that takes part and qualifies (d <= r; radius == NULL: all of them) is offered to an EMPTY List — every member of A(b)
+// within the bound is a candidate, the sample's rows included.  A query the scan answered (mask row nfilters) keeps what the merge wrote.
+template <int FUNC, class List>
+__global__ __launch_bounds__(256) void fk_rescore_kernel(const FkRescore a)
 {
 	extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 	const int lane = threadIdx.x & 63;
-	const uint32_t wib = threadIdx.x >> 6;
+	const uint32_t wib = threadIdx.x >> 6, k = a.k;
 	const uint32_t qi = blockIdx.x * 4 + wib;
-	if (qi >= nq || mask_of[qi] == nfilters) return;
-	const size_t wave_bytes = (size_t) qpad_floats * 4 + (size_t) (k + 1) * 8 + 128 * 4;
-	unsigned char *my = smem + wib * ((wave_bytes + 15) & ~(size_t) 15);
-	const float4 *q4 = reinterpret_cast<const float4 *>(my);
-	uint64_t *top = reinterpret_cast<uint64_t *>(my + (size_t) qpad_floats * 4);
-	float *sums = reinterpret_cast<float *>(top + (k + 1));
-	stage_query_wave(reinterpret_cast<float *>(my), queries + (size_t) qi * dim, dim, qpad_floats, lane);
-	uint32_t cnt = cand_cnt[qi];
-	if (cnt > cap) { if (lane == 0) atomicAdd(overflow, 1u); cnt = cap; }
-	const bool within = radius != nullptr;
+	if (qi >= a.nq || a.mask_of[qi] == a.nfilters) return;
+	const RescoreWave w = rescore_wave<List::LDS_ENTRY>(smem, wib, a.qpad_floats, k, a.queries + (size_t) qi * a.dim, a.dim, a.cand_cnt + qi, a.cap, a.overflow, lane);
+	const List top = List::at(w.keys, w.more);
+	const bool within = a.radius != nullptr;
 	uint32_t nqual = 0;
-	const uint32_t tsize = scan_topk_within<FUNC>(vec, stride, q4, nchunks, kiters, CandidateRows{cand + (size_t) qi * cap}, 0u, cnt, top, sums, k,
-												  within, within ? radius[qi] : 0.f, nqual, lane);
-	store_partial(keys + (size_t) qi * k, top, tsize, k, lane);
-	if (lane == 0) count[qi] = nqual;
+	const uint32_t tsize = scan_list<FUNC>(a.vec, a.stride, w.q4, a.nchunks, a.kiters, CandidateRows{a.cand + (size_t) qi * a.cap}, typename List::OfElement(a.egroup), top,
+										   0u, w.cnt, w.sums, k, within, within ? a.radius[qi] : 0.f, nqual, lane);
+	top.store(a.keys, a.groups, (size_t) qi * k, tsize, k, lane);
+	if (lane == 0) a.count[qi] = List::PART_ENTRY == 8 ? nqual : tsize;
 }
 
 // The filter's stand-in: one block per query, its 4 waves stride over all rows 64 at a time with the canonical distance code; a pair passes

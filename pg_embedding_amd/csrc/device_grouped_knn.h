@@ -1,6 +1,6 @@
 // device_grouped_knn.h — exact grouped k-NN: the k nearest DISTINCT GROUPS, each through its nearest member (hnsw_gpu_grouped_knn[_dev],
 // gpu_scan.hip).  The pipeline of device_filtered_knn.h with one new idea: a top-k list that de-duplicates by group while it
-// scans.
+// scans — GroupedList, the second List of the one wave loop (scan_list, device_topk_scan.h).
 //
 // group_of is a table over label VALUES (the allow bitmap's convention): the group of an element with label l is group_of[l]; an element
 // whose label is >= group_entries, or whose group word is GK_NONE, takes no part.  R(q) = hnsw_gpu_range_knn_dev's set — not vacuumed, label
@@ -8,11 +8,12 @@
 // rep(g) = the member of g in R(q) with the smallest (distance, element); the answer is the min(k, groups with a member in R) representatives
 // with the smallest (distance, element), written in hnsw_search's order (distance, label, element).
 //
-//   1. the list build of device_filtered_knn.h, as it stands (fk_count / fk_offsets / fk_fill, or rk_live without a filter)
+//   1. the list build of device_filtered_knn.h, as it stands (fk_count / fk_offsets / fk_fill)
 //   2. gk_groups_kernel  one coalesced pass over the built lists: next to every 4-byte element number its 4-byte group word (GK_NONE where
-//                        the element takes no part), so that the scan loads no label
-//   3. gk_scan_kernel    fk_scan_kernel's launch shape, block order, slicing and scoring; a wave keeps k + 1 keys AND k + 1 group words, the
-//                        keys ascending, the groups PAIRWISE DISTINCT (grouped_offer) -> a partial (key, group) list per wave
+//                        the element takes no part), so that the scan loads no label (the matrix-core form, device_grouped_knn_mfma.h:
+//                        a second pass, over the elements)
+//   3. fk_scan_kernel<FUNC, GroupedList>  a wave keeps k + 1 keys AND k + 1 group words, the keys ascending, the groups PAIRWISE DISTINCT
+//                        (grouped_offer) -> a partial (key, group) list per wave
 //   4. gk_merge_kernel   one wave per query: offers the partial lists' pairs to ONE grouped list with the same grouped_offer
 //   5. fk_emit_kernel    with its optional group output
 //
@@ -34,27 +35,26 @@
 
 namespace pgemb {
 
-constexpr uint32_t GK_NONE = 0xFFFFFFFFu;    // a group word: the element takes no part; an output word: no row
-
 struct GkGroups
 {
-	const uint32_t *list; uint64_t total;            // the built lists, back to back
+	const uint32_t *list; uint64_t total;            // the built lists, back to back (total entries), or NULL: the elements [0, total) themselves
 	const uint64_t *labels;
 	const uint32_t *group_of; uint64_t group_entries;
-	uint32_t *glist;                                 // [total] <- the group word of every entry
+	uint32_t *out;                                   // [total] <- the group word of every entry (of every element)
 };
 
-// grid-stride, one entry per thread: the list is read and the group words are written coalesced; the label and the table word are gathers
-// (the lists are ascending in the element number, so the label loads of a wave fall into few lines)
+// grid-stride, one entry per thread: the group word of element list[e] (listed elements are not vacuumed) or, without a list, of element e
+// (GK_NONE: vacuumed, or takes no part).  The list / the labels are read and the words written coalesced; the table word is a gather, and
+// with a list so is the label (the lists are ascending in the element number, so the label loads of a wave fall into few lines)
 __global__ __launch_bounds__(256) void gk_groups_kernel(const GkGroups a)
 {
 	const uint64_t step = (uint64_t) gridDim.x * 256u;
 	for (uint64_t e = (uint64_t) blockIdx.x * 256u + threadIdx.x; e < a.total; e += step)
 	{
-		const uint64_t lab = a.labels[a.list[e]];                         // (a listed element is not vacuumed: the word is the label)
-		const bool part = lab < a.group_entries;
+		const uint64_t lab = a.labels[a.list ? a.list[e] : e];
+		const bool part = !((lab >> 48) & 1ull) && lab < a.group_entries;
 		const uint32_t g = a.group_of[part ? lab : 0];                    // (unconditional load, clamped: group_entries >= 1)
-		a.glist[e] = part ? g : GK_NONE;
+		a.out[e] = part ? g : GK_NONE;
 	}
 }
 
@@ -127,117 +127,56 @@ __device__ __forceinline__ void grouped_offer(uint64_t *top, uint32_t *grp, uint
 	}
 }
 
-// a partial (or final) list: k keys (~0 = none) and k group words (GK_NONE = none)
-__device__ __forceinline__ void store_grouped(uint64_t *__restrict__ kdst, uint32_t *__restrict__ gdst, const uint64_t *top, const uint32_t *grp,
-											  uint32_t tsize, uint32_t k, int lane)
-{
-	for (uint32_t i = lane; i < k; i += 64)
-	{
-		kdst[i] = i < tsize ? top[i] : ~0ull;
-		gdst[i] = i < tsize ? grp[i] : GK_NONE;
-	}
-}
-
-struct GkScan
-{
-	FkScan s;                        // fk_scan_kernel's arguments (skip_samples = 0; smin = 0: every query's whole list, else the matrix-core form's samples; pcount unused)
-	const uint32_t *glist;           // the group words of s.list, entry for entry
-	uint32_t *gpart;                 // [nq][splits * 4][k] the groups of s.part's keys, GK_NONE = none
-};
-
-// the group of a list entry: the word next to it, loaded coalesced, once per step, like the list itself
+// the group of a list entry: the word next to it (glist: the words of all lists; first: where the query's list starts), loaded coalesced,
+// once per step, like the list itself
 struct ListGroups
 {
 	const uint32_t *glist;
+	__device__ __forceinline__ ListGroups(const uint32_t *all, size_t first) : glist(all + first) {}
 	__device__ __forceinline__ uint32_t operator()(uint32_t base, uint32_t cnt, int lane, uint32_t) const { return glist[base + min((uint32_t) lane, cnt - 1u)]; }
 };
-
-// scan_topk_within with the grouped list: entries [lo, hi) of `src`; an entry is offered if it takes part and (within) d <= radius.
-// group_of(base, cnt, lane, id): the group word of entry base + lane, element id (any word for lane >= cnt: it is not offered)
-template <int FUNC, class Source, class Groups>
-__device__ __forceinline__ uint32_t scan_grouped_within(const float *__restrict__ vec, uint32_t stride, const float4 *q4, uint32_t nchunks,
-														uint32_t kiters, const Source &src, const Groups &group_of, uint32_t lo,
-														uint32_t hi, uint64_t *top, uint32_t *grp, float *sums, uint32_t k, bool within, float radius,
-														int lane)
+// the group of a candidate: its element's word
+struct ElementGroups
 {
-	float qnorm = 0.f;
-	if (FUNC == F_COSINE) qnorm = query_norm(q4, nchunks, kiters, lane);
-	uint32_t tsize = 0;
-	uint64_t worst = ~0ull;
-	for (uint32_t base = lo; base < hi; base += 64)
+	const uint32_t *egroup;
+	__device__ __forceinline__ ElementGroups(const uint32_t *of_element, size_t = 0) : egroup(of_element) {}
+	__device__ __forceinline__ uint32_t operator()(uint32_t, uint32_t, int, uint32_t id) const { return egroup[id]; }
+};
+
+// KeyList's counterpart (device_topk_scan.h): k + 1 keys and, behind the kernel's other per-wave areas, k + 1 group words
+struct GroupedList
+{
+	static constexpr uint32_t LDS_ENTRY = 12, PART_ENTRY = 12;
+	using OfList = ListGroups;
+	using OfElement = ElementGroups;
+	uint64_t *top; uint32_t *grp;
+	__device__ __forceinline__ static GroupedList at(uint64_t *keys, void *more) { return GroupedList{keys, static_cast<uint32_t *>(more)}; }
+	__device__ __forceinline__ void offer(uint32_t &tsize, uint64_t &worst, uint64_t kl, uint32_t gl, bool valid, uint32_t k, int lane) const
 	{
-		const uint32_t cnt = min(64u, hi - base);
-		const uint32_t id = src.id(base, cnt, lane);
-		const uint32_t g = group_of(base, cnt, lane, id);
-		score_rows<FUNC, 4, 2>(vec, stride, q4, nchunks, kiters, src.rows(base), cnt, sums, lane);
-		wave_sync();
-		const float dl = finish_dist<FUNC>(sums[lane], sums[OUT2 + lane], qnorm);
-		const bool in = (uint32_t) lane < cnt && g != GK_NONE && (!within || dl <= radius);   // (IEEE: false for a NaN on either side)
-		grouped_offer(top, grp, tsize, worst, ((uint64_t) ord_f32(dl) << 32) | id, g, in, k, lane);
-		wave_sync();
+		grouped_offer(top, grp, tsize, worst, kl, gl, valid, k, lane);
 	}
-	return tsize;
-}
-
-// fk_scan_kernel's grid, block order and slicing.  Per wave in LDS behind the query image: k + 1 keys | 2 x 64 sums | 64 element numbers
-// (fk_scan_kernel's carve) | k + 1 group words, behind the four waves' other areas.
-template <int FUNC>
-__global__ __launch_bounds__(256) void gk_scan_kernel(const GkScan g)
-{
-	extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-	const FkScan &a = g.s;
-	const uint32_t nblk = a.splits * a.nq;
-	const uint32_t L = blockIdx.x;
-	if (L >= nblk) return;
-	const uint32_t sp = L / a.nq, qi = L - sp * a.nq;
-	const uint32_t *list; uint32_t len, b; bool whole;
-	fk_list_of(a, qi, list, len, whole, b);
-	const uint32_t nw = fk_waves(len, a.splits);
-	if (sp * 4u >= nw) return;                                        // (block-uniform) a short list leaves the later splits idle
-	stage_query_block(reinterpret_cast<float *>(smem), a.queries + (size_t) qi * a.dim, a.dim, a.qpad_floats);
-	const float4 *q4 = reinterpret_cast<const float4 *>(smem);
-	const int lane = threadIdx.x & 63;
-	const uint32_t wib = threadIdx.x >> 6, w = sp * 4u + wib, k = a.k;
-	if (w >= nw) return;                                              // (wave-uniform; no block barrier below)
-	unsigned char *wbase = smem + (size_t) a.qpad_floats * 4;
-	const size_t o_sums = (size_t) 4 * (k + 1) * 8, o_ids = o_sums + 4 * 128 * 4, o_grp = o_ids + 4 * 64 * 4;
-	uint64_t *top = reinterpret_cast<uint64_t *>(wbase) + (size_t) wib * (k + 1);
-	float *sums = reinterpret_cast<float *>(wbase + o_sums) + wib * 128;
-	uint32_t *ids = reinterpret_cast<uint32_t *>(wbase + o_ids) + wib * 64;
-	uint32_t *grp = reinterpret_cast<uint32_t *>(wbase + o_grp) + (size_t) wib * (k + 1);
-	const uint32_t lo = (uint32_t) ((uint64_t) len * w / nw), hi = (uint32_t) ((uint64_t) len * (w + 1) / nw);
-	const bool within = a.radius != nullptr;
-	const uint32_t tsize = scan_grouped_within<FUNC>(a.vec, a.stride, q4, a.nchunks, a.kiters, StagedRows{list, ids}, ListGroups{g.glist + (list - a.list)}, lo, hi,
-													 top, grp, sums, k, within, within ? a.radius[qi] : 0.f, lane);
-	const size_t po = ((size_t) qi * a.splits * 4u + w) * k;
-	store_grouped(a.part + po, g.gpart + po, top, grp, tsize, k, lane);
-	if (lane == 0) atomicAdd(a.scored, (unsigned long long) (hi - lo));
-}
-
-struct GkMerge
-{
-	GkScan g;
-	uint64_t *keys;                  // [nq][k] the answer's keys, ascending, ~0 = none
-	uint32_t *groups;                // [nq][k] their groups
-	uint32_t *count;                 // [nq] the groups with a member in R(q), up to k: the rows of the answer
-	float *tau;                      // NULL (listed form), or [nq] the bound for make_bounds_kernel (device_grouped_knn_mfma.h)
-	uint32_t *mask_of;               // [nq] the query's mask row: its bitmap, or nfilters (zeros) when the scan answered it
-	uint32_t nfilters;
+	// a partial (or final) list, entries [at, at + k) of kdst and gdst: k keys (~0 = none) and k group words (GK_NONE = none)
+	__device__ __forceinline__ void store(uint64_t *__restrict__ kdst, uint32_t *__restrict__ gdst, size_t at, uint32_t tsize, uint32_t k, int lane) const
+	{
+		for (uint32_t i = lane; i < k; i += 64)
+		{
+			kdst[at + i] = i < tsize ? top[i] : ~0ull;
+			gdst[at + i] = i < tsize ? grp[i] : GK_NONE;
+		}
+	}
 };
 
 // One wave per query (block = 64 threads).  LDS: k + 1 keys | k + 1 group words.  The partial lists in wave order, 64 pairs per offer; a
 // partial list is ascending, so it is left at its first step that holds no key or, with a full list, starts at or above the worst key.
-// The bound (matrix-core form), fk_merge_kernel's with groups for rows: with k distinct groups in the sample the key of the k-th — each of
-// them has a member within it, so the k best representatives over the whole list are — else the radius (none: +inf); a query whose scan is
-// its complete answer (a list no longer than its sample, a radius that selects nothing) gets a bound of 0 and the zero mask row.
-__global__ __launch_bounds__(64) void gk_merge_kernel(const GkMerge a)
+// The end is fk_merge_kernel's (fk_merge_tail) with groups for rows: the count is the list's size whether or not the scan answered the query,
+// and the bound takes k distinct groups in the sample.
+__global__ __launch_bounds__(64) void gk_merge_kernel(const FkMerge a)
 {
 	extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-	const FkScan &s = a.g.s;
+	const FkScan &s = a.s;
 	const uint32_t qi = blockIdx.x, k = s.k;
 	const int lane = (int) threadIdx.x;
-	uint64_t *top = reinterpret_cast<uint64_t *>(smem);
-	uint32_t *grp = reinterpret_cast<uint32_t *>(top + (k + 1));
+	const GroupedList top = GroupedList::at(reinterpret_cast<uint64_t *>(smem), reinterpret_cast<uint64_t *>(smem) + (k + 1));
 	const uint32_t *list; uint32_t len, b; bool whole;
 	fk_list_of(s, qi, list, len, whole, b);
 	const uint32_t nw = fk_waves(len, s.splits);
@@ -250,24 +189,14 @@ __global__ __launch_bounds__(64) void gk_merge_kernel(const GkMerge a)
 		{
 			const uint32_t i = base + (uint32_t) lane;
 			const uint64_t key = i < k ? s.part[po + i] : ~0ull;
-			const uint32_t g = i < k ? a.g.gpart[po + i] : GK_NONE;
+			const uint32_t g = i < k ? s.gpart[po + i] : GK_NONE;
 			const uint64_t first = readlane_u64(key, 0);
 			if (first == ~0ull || (tsize == k && first >= worst)) break;
-			grouped_offer(top, grp, tsize, worst, key, g, key != ~0ull, k, lane);
+			top.offer(tsize, worst, key, g, key != ~0ull, k, lane);
 		}
 	}
-	store_grouped(a.keys + (size_t) qi * k, a.groups + (size_t) qi * k, top, grp, tsize, k, lane);
-	if (lane == 0)
-	{
-		a.count[qi] = tsize;                                              // (a query that is not answered here: the re-score's to write again)
-		if (a.tau)
-		{
-			const float r = s.radius ? s.radius[qi] : __builtin_inff();
-			const bool answered = whole || rk_selects_nothing(r, s.func);
-			a.tau[qi] = answered ? 0.f : tsize >= k ? unord_f32((uint32_t) (worst >> 32)) : r;
-			a.mask_of[qi] = answered ? a.nfilters : b;
-		}
-	}
+	top.store(a.keys, a.groups, (size_t) qi * k, tsize, k, lane);
+	if (lane == 0) fk_merge_tail(a, qi, whole, b, tsize, top.top + (k - 1), tsize);
 }
 
 }  // namespace pgemb

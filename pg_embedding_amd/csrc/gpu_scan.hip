@@ -2,7 +2,9 @@
 // the f32 rows or the reduced copy (csrc/device_bf_mfma.h, csrc/device_bf_mfma16.h), and exact filtered k-NN and exact radius search, one
 // pipeline: the canonical scan over lists of allowed rows (csrc/device_filtered_knn.h) or, for loose filters, the MFMA filter with the allow
 // test at its append (csrc/device_filtered_knn_mfma.h), chosen per query in the automatic calls (csrc/device_fk_plan.h); and exact grouped
-// k-NN over the same lists, in the same forms (csrc/device_grouped_knn.h, csrc/device_grouped_knn_mfma.h)
+// k-NN over the same lists, in the same forms (csrc/device_grouped_knn.h, csrc/device_grouped_knn_mfma.h).  Every canonical scorer is ONE
+// wave loop (scan_list, csrc/device_topk_scan.h) and the three families share one kernel per stage — list build, mask, scan, re-score, emit —
+// with the list that takes the offers (KeyList, or grouped k-NN's GroupedList) as a template parameter (with_list); the two merges differ.
 // One translation unit of libhnsw_gpu.so (csrc/gpu_host.h lists them); gfx950 only, plain HIP runtime, no framework types in any signature.
 #include "gpu_host.h"
 #include "device_topk_scan.h"
@@ -36,11 +38,19 @@ struct QueryGeom
 	explicit QueryGeom(size_t stride) : nchunks((uint32_t) (stride / 4)), kiters((nchunks + 15) / 16), qpad((uint32_t) round_up(kiters, 4) * 64) {}
 	size_t lds_dist() const { return (size_t) qpad * 4 + 4 * 128 * 4; }                        // image | 4 x 128 sums: dist_batch_kernel, fkm_standin_kernel
 	size_t lds_scan(size_t k) const { return lds_dist() + 4 * (k + 1) * 8; }                   // image | 4 x (k + 1) keys | 4 x 128 sums: bruteforce_kernel
-	size_t lds_listed(size_t k) const { return lds_scan(k) + 4 * 64 * 4; }                     // ... | 4 x 64 staged element numbers: fk_scan_kernel
-	size_t lds_grouped(size_t k) const { return lds_listed(k) + 4 * (k + 1) * 4; }             // ... | 4 x (k + 1) group words: gk_scan_kernel
-	size_t lds_rescore(size_t k) const { return 4 * round_up((size_t) qpad * 4 + (k + 1) * 8 + 128 * 4, 16); }   // per wave: image | k + 1 keys | 128 sums: bf_rescore_kernel, fkm_rescore_kernel
-	size_t lds_rescore_grouped(size_t k) const { return 4 * round_up((size_t) qpad * 4 + (k + 1) * 8 + 128 * 4 + (k + 1) * 4, 16); }   // ... | k + 1 group words: gkm_rescore_kernel
+	// entry_bytes: a List's LDS_ENTRY (device_topk_scan.h) — a key, and in the grouped list its group word
+	size_t lds_listed(size_t k, size_t entry_bytes) const { return lds_dist() + 4 * 64 * 4 + 4 * (k + 1) * entry_bytes; }   // ... | 4 x 64 staged element numbers | 4 x (k + 1) entries: fk_scan_kernel
+	size_t lds_rescore(size_t k, size_t entry_bytes) const { return 4 * round_up((size_t) qpad * 4 + 128 * 4 + (k + 1) * entry_bytes, 16); }   // per wave: image | 128 sums | k + 1 entries: bf_rescore_kernel, fk_rescore_kernel
 };
+
+// the list of a family as a compile-time type: f(KeyList{}) (filtered k-NN, radius search) or f(GroupedList{}) (grouped k-NN)
+template <class F>
+static void with_list(bool grouped, F &&f)
+{
+	if (grouped) f(GroupedList{});
+	else f(KeyList{});
+}
+static size_t list_entry_bytes(bool grouped) { return grouped ? GroupedList::LDS_ENTRY : KeyList::LDS_ENTRY; }
 
 // ------------------------------------------------------------------------------------
 // batched distances (hnsw_dist_func over many rows)
@@ -369,7 +379,7 @@ static int bruteforce_filter(hnsw_gpu_index *ix, bool reduced, int format, const
 	hipStream_t s = (hipStream_t) stream_;
 	const uint32_t dim = (uint32_t) ix->meta.dim;
 	const QueryGeom g(ix->stride);
-	if (g.lds_rescore(k) > 64 * 1024) return scan();
+	if (g.lds_rescore(k, KeyList::LDS_ENTRY) > 64 * 1024) return scan();
 
 	// the rows' side, current on this stream: the reduced copy and the bound's per-row terms, or the |row|^2 cache
 	int rc = bf_rows_side(ix, reduced, s);
@@ -428,8 +438,8 @@ static int bruteforce_filter(hnsw_gpu_index *ix, bool reduced, int format, const
 	// 3. canonical re-score of the survivors against the fp32 rows
 	with_func(func, [&](auto F) {
 		if constexpr (decltype(F)::value != F_MANHATTAN)           // (answered by the scan above: no re-score kernel is compiled for it)
-			hipLaunchKernelGGL(bf_rescore_kernel<decltype(F)::value>, dim3((uint32_t) ((nq + 3) / 4)), dim3(256), g.lds_rescore(k), s, ix->vec, dim, ix->stride, g.nchunks,
-							   g.kiters, g.qpad, d_queries, (uint32_t) nq, cand, cnt, cap, (uint32_t) k, d_idx, d_dists, overflow);
+			hipLaunchKernelGGL(bf_rescore_kernel<decltype(F)::value>, dim3((uint32_t) ((nq + 3) / 4)), dim3(256), g.lds_rescore(k, KeyList::LDS_ENTRY), s, ix->vec, dim, ix->stride,
+							   g.nchunks, g.kiters, g.qpad, d_queries, (uint32_t) nq, cand, cnt, cap, (uint32_t) k, d_idx, d_dists, overflow);
 	});
 	HIPCHK(hipGetLastError());
 	uint32_t ovf = 0;
@@ -525,7 +535,7 @@ static int fk_check(const FkCall &c, int form, int format)
 	if (filter && (c.allow_bits == 0 || c.nfilters == 0)) return fail(HNSW_GPU_ERR_ARG, "%s: an allow filter of no bits", who);
 	if (filter && ((c.allow_bits + 31) / 32 >= 0xFFFFFFFFull || c.nfilters >= 0xFFFFFFFFull)) return fail(HNSW_GPU_ERR_ARG, "%s: allow filter too large", who);
 	const QueryGeom g(c.ix->stride);
-	if ((grouped ? g.lds_grouped(c.k) : g.lds_listed(c.k)) > 64 * 1024) return fail(HNSW_GPU_ERR_ARG, "k/dim too large for %s", who);
+	if (g.lds_listed(c.k, list_entry_bytes(grouped)) > 64 * 1024) return fail(HNSW_GPU_ERR_ARG, "k/dim too large for %s", who);
 	return form == FK_LISTED ? HNSW_GPU_OK : fk_check_format(who, c.ix, format);
 }
 
@@ -544,8 +554,8 @@ static int fk_begin(FkCall &c)
 	return HNSW_GPU_OK;
 }
 
-// 1. the allowed lists: count per (bitmap, segment), offsets, fill.  c.allow == NULL (radius search without a filter: nfilters == 1): the one
-// list of the rows that are not vacuumed (rk_live_kernel).  hook (the automatic calls; else NULL: not one launch more): the plan's kernel
+// 1. the allowed lists: count per (bitmap, segment), offsets, fill.  c.allow == NULL (a call without a filter: nfilters == 1): the one
+// list of the rows that are not vacuumed (fk_in).  hook (the automatic calls; else NULL: not one launch more): the plan's kernel
 // behind the offsets, before the wait — its words arrive in the same pinned block (fw->host[8 ..])
 struct FkPlanHook { uint64_t thresh; uint8_t *plan; };
 static int fk_lists(FkCall &c, const FkPlanHook *hook = nullptr)
@@ -569,8 +579,7 @@ static int fk_lists(FkCall &c, const FkPlanHook *hook = nullptr)
 	fl.allow = c.allow; fl.allow_bits = c.allow_bits; fl.allow_words = (uint32_t) ((c.allow_bits + 31) / 32); fl.nfilters = (uint32_t) nfilters;
 	fw->host[0] = fw->host[1] = fw->host[2] = 0;
 	HIPCHK(hipEventRecord(fw->ev[0], s));
-	if (c.allow) hipLaunchKernelGGL(fk_count_kernel, dim3((uint32_t) (nsb * nfilters)), dim3(256), 0, s, fl, cells);
-	else hipLaunchKernelGGL(rk_live_kernel<RK_LIVE_COUNT>, dim3((uint32_t) nsb), dim3(256), 0, s, fl, (const uint64_t *) nullptr, cells);
+	hipLaunchKernelGGL(fk_count_kernel, dim3((uint32_t) (nsb * nfilters)), dim3(256), 0, s, fl, cells);
 	hipLaunchKernelGGL(fk_offsets_kernel, dim3(1), dim3(FK_SCAN_THREADS), FK_SCAN_THREADS * 8, s, (const uint32_t *) cells, nseg, (uint32_t) nfilters, off, fw->host);
 	if (hook)
 	{
@@ -582,8 +591,7 @@ static int fk_lists(FkCall &c, const FkPlanHook *hook = nullptr)
 	const size_t total = fw->host[0], longest = fw->host[1];
 	if (longest > n || total > n * nfilters) return fail(HNSW_GPU_ERR_INTERNAL, "%s: %zu listed rows, longest list %zu, of %zu rows", c.fam->who, total, longest, n);
 	if ((rc = buf_reserve(&fw->list, total * 4, c.fam->who, "the lists of allowed rows"))) return rc;
-	if (total && c.allow) hipLaunchKernelGGL(fk_fill_kernel, dim3((uint32_t) (nsb * nfilters)), dim3(256), 0, s, fl, (const uint64_t *) off, (uint32_t *) fw->list.p);
-	else if (total) hipLaunchKernelGGL(rk_live_kernel<RK_LIVE_FILL>, dim3((uint32_t) nsb), dim3(256), 0, s, fl, (const uint64_t *) off, (uint32_t *) fw->list.p);
+	if (total) hipLaunchKernelGGL(fk_fill_kernel, dim3((uint32_t) (nsb * nfilters)), dim3(256), 0, s, fl, (const uint64_t *) off, (uint32_t *) fw->list.p);
 	HIPCHK(hipMemsetAsync(scored, 0, 8, s));
 	HIPCHK(hipEventRecord(fw->ev[1], s));
 	c.off = off; c.scored = scored; c.nsb = nsb; c.total = total; c.longest = longest;
@@ -591,9 +599,9 @@ static int fk_lists(FkCall &c, const FkPlanHook *hook = nullptr)
 }
 
 // Splits as the exhaustive scan chooses them, from the longest run of list entries a query scans (a query with a shorter one uses fewer
-// waves: fk_waves), and room for the partial lists (entry_bytes: a key, and in grouped k-NN its group word).  (FK_XCD_REMAP variant builds:
-// a list long enough for it gets at least one slice per XCD to keep apart.)
-static int fk_splits(const FkCall &c, size_t longest, uint32_t *out, size_t entry_bytes = 8)
+// waves: fk_waves), and room for the partial lists (entry_bytes: the List's PART_ENTRY).  (FK_XCD_REMAP variant builds: a list long enough
+// for it gets at least one slice per XCD to keep apart.)
+static int fk_splits(const FkCall &c, size_t longest, uint32_t *out, size_t entry_bytes)
 {
 	hnsw_gpu_index *ix = c.ix;
 	const size_t nq = c.nq, k = c.k;
@@ -619,8 +627,8 @@ struct FkMfma
 // One pass over the built lists (and masks).  format < 0: the listed form — the scan over every query's whole list, merge, emit.  Else
 // the matrix-core form with the operands of `format`: the scan over the lists no longer than their sample and (without totals) over the
 // samples of the others -> merge + bounds -> filter (or its stand-in) -> re-score -> emit.  *ovf = candidate lists that overflowed (then
-// the outputs are not the answer: the caller hands the call down).  Grouped k-NN: the same pass with its own scan, merge and re-score — a
-// list of (key, group) pairs, one per group, where the others keep keys (device_grouped_knn.h, device_grouped_knn_mfma.h; no totals).
+// the outputs are not the answer: the caller hands the call down).  Grouped k-NN: the same pass and kernels with GroupedList — (key, group)
+// pairs, one per group — where the others keep keys (KeyList; with_list), and a merge of its own (device_grouped_knn.h; no totals).
 static int fk_pass(FkCall &c, int format, const FkMfma &m, uint32_t mwords, uint64_t *ovf)
 {
 	hnsw_gpu_index *ix = c.ix;
@@ -640,7 +648,7 @@ static int fk_pass(FkCall &c, int format, const FkMfma &m, uint32_t mwords, uint
 	// the longest run of list entries a query scans: its whole list, its sample, or (totals) a list no longer than its sample
 	const size_t slongest = listed ? c.longest : skip ? std::min<size_t>(c.longest, smin) : m.sample_len(c.longest);
 	uint32_t splits = 1;
-	if ((rc = fk_splits(c, slongest, &splits, grouped ? 12 : 8))) return rc;
+	if ((rc = fk_splits(c, slongest, &splits, grouped ? GroupedList::PART_ENTRY : KeyList::PART_ENTRY))) return rc;
 	// scratch carve
 	const size_t o_keys = 0;
 	const size_t o_rcnt = o_keys + round_up(nq * k * 8, 256);
@@ -678,32 +686,23 @@ static int fk_pass(FkCall &c, int format, const FkMfma &m, uint32_t mwords, uint
 	fs.part = (uint64_t *) fw->part.p; fs.pcount = pcount; fs.scored = c.scored; fs.smin = listed ? 0u : smin; fs.skip_samples = skip ? 1u : 0u;
 	fs.sample_k = m.sample_k;
 	fs.radius = c.radius; fs.func = func;
-	fm.nfilters = (uint32_t) c.nfilters; fm.keys = keys; fm.count = rcount; fm.tau = listed ? nullptr : tau; fm.mask_of = mask_of;
-	if (sum) HIPCHK(hipMemsetAsync(sum, 0, 8, s));
 	if (grouped)
 	{
-		GkMerge gm;
-		memset(&gm, 0, sizeof(gm));
-		gm.g.s = fs;
-		gm.g.glist = (const uint32_t *) fw->grp.p;
-		gm.g.gpart = (uint32_t *) ((char *) fw->part.p + nq * splits * 4 * k * 8);     // the partial groups behind the partial keys
-		gm.keys = keys; gm.groups = kgroups; gm.count = rcount; gm.tau = fm.tau; gm.mask_of = mask_of; gm.nfilters = fm.nfilters;
+		fs.glist = (const uint32_t *) fw->grp.p;
+		fs.gpart = (uint32_t *) ((char *) fw->part.p + nq * splits * 4 * k * 8);         // the partial groups behind the partial keys
+	}
+	fm.nfilters = (uint32_t) c.nfilters; fm.keys = keys; fm.groups = kgroups; fm.count = rcount; fm.tau = listed ? nullptr : tau; fm.mask_of = mask_of;
+	if (sum) HIPCHK(hipMemsetAsync(sum, 0, 8, s));
+	with_list(grouped, [&](auto l) {
+		using List = decltype(l);
 		if (slongest)
 		{
 			const dim3 grid((uint32_t) round_up((size_t) splits * nq, 8));
-			with_func(func, [&](auto F) { hipLaunchKernelGGL(gk_scan_kernel<decltype(F)::value>, grid, dim3(256), g.lds_grouped(k), s, gm.g); });
+			with_func(func, [&](auto F) { hipLaunchKernelGGL((fk_scan_kernel<decltype(F)::value, List>), grid, dim3(256), g.lds_listed(k, List::LDS_ENTRY), s, fs); });
 		}
-		hipLaunchKernelGGL(gk_merge_kernel, dim3((uint32_t) nq), dim3(64), (k + 1) * 12, s, gm);
-	}
-	else
-	{
-		if (slongest)
-		{
-			const dim3 grid((uint32_t) round_up((size_t) splits * nq, 8));
-			with_func(func, [&](auto F) { hipLaunchKernelGGL(fk_scan_kernel<decltype(F)::value>, grid, dim3(256), g.lds_listed(k), s, fs); });
-		}
-		hipLaunchKernelGGL(fk_merge_kernel, dim3((uint32_t) nq), dim3(64), k * 8, s, fm);
-	}
+		if constexpr (std::is_same<List, GroupedList>::value) hipLaunchKernelGGL(gk_merge_kernel, dim3((uint32_t) nq), dim3(64), (k + 1) * List::LDS_ENTRY, s, fm);
+		else hipLaunchKernelGGL(fk_merge_kernel, dim3((uint32_t) nq), dim3(64), k * 8, s, fm);
+	});
 	if (!listed)
 	{
 		bf_queries_side(reduced, format, c.queries, nq, dim, qchunks, qcopy, qn, qterms, s);
@@ -722,20 +721,15 @@ static int fk_pass(FkCall &c, int format, const FkMfma &m, uint32_t mwords, uint
 		else if ((rc = with_form(format, [&](auto p) { return bf_filter_pick<BfAllow<decltype(p)>>(ix, a, s); })))
 			return rc;
 		HIPCHK(hipEventRecord(fw->ev[4], s));
-		if (grouped)
-			with_func(func, [&](auto F) {
-				if constexpr (decltype(F)::value != F_MANHATTAN)
-					hipLaunchKernelGGL(gkm_rescore_kernel<decltype(F)::value>, dim3((uint32_t) ((nq + 3) / 4)), dim3(256), g.lds_rescore_grouped(k), s, ix->vec, dim,
-									   ix->stride, g.nchunks, g.kiters, g.qpad, c.queries, (uint32_t) nq, c.radius, (const uint32_t *) mask_of, (uint32_t) c.nfilters,
-									   (const uint32_t *) cand, (const uint32_t *) cnt, cap, (const uint32_t *) fw->egrp.p, (uint32_t) k, keys, kgroups, rcount, overflow);
-			});
-		else
+		const FkRescore fr = { ix->vec, dim, ix->stride, g.nchunks, g.kiters, g.qpad, c.queries, (uint32_t) nq, (uint32_t) k, c.radius, mask_of, (uint32_t) c.nfilters,
+							   cand, cnt, cap, grouped ? (const uint32_t *) fw->egrp.p : nullptr, keys, kgroups, rcount, overflow };
+		with_list(grouped, [&](auto l) {
+			using List = decltype(l);
 			with_func(func, [&](auto F) {
 				if constexpr (decltype(F)::value != F_MANHATTAN)           // (answered by the listed form: no re-score kernel is compiled for it)
-					hipLaunchKernelGGL(fkm_rescore_kernel<decltype(F)::value>, dim3((uint32_t) ((nq + 3) / 4)), dim3(256), g.lds_rescore(k), s, ix->vec, dim, ix->stride,
-									   g.nchunks, g.kiters, g.qpad, c.queries, (uint32_t) nq, c.radius, (const uint32_t *) mask_of, (uint32_t) c.nfilters,
-									   (const uint32_t *) cand, (const uint32_t *) cnt, cap, (uint32_t) k, keys, rcount, overflow);
+					hipLaunchKernelGGL((fk_rescore_kernel<decltype(F)::value, List>), dim3((uint32_t) ((nq + 3) / 4)), dim3(256), g.lds_rescore(k, List::LDS_ENTRY), s, fr);
 			});
+		});
 	}
 	// one key list and one count per query -> labels, order, counts, tails, totals
 	const FkEmit fe = { keys, rcount, (uint32_t) k, ix->labels, (uint32_t) ix->n, c.labels, c.dists, c.idx, c.counts, c.totals, sum, kgroups, c.groups };
@@ -775,7 +769,7 @@ static bool fk_have_mfma(hnsw_gpu_index *ix, size_t k, bool grouped, bool *stand
 	const bool have_filter = ix->n >= 4096 && ix->gfx950 && ix->max_lds >= BF_MIN_LDS;
 #endif
 	const QueryGeom g(ix->stride);
-	return (int) ix->meta.dist_func != F_MANHATTAN && (grouped ? g.lds_rescore_grouped(k) : g.lds_rescore(k)) <= 64 * 1024 && (*standin || have_filter);
+	return (int) ix->meta.dist_func != F_MANHATTAN && g.lds_rescore(k, list_entry_bytes(grouped)) <= 64 * 1024 && (*standin || have_filter);
 }
 static uint32_t fk_sample_min() { return (uint32_t) std::min<long long>(0xFFFFFFFFll, std::max<long long>(1, knob(K_FK_SAMPLE_MIN, FKM_SAMPLE_MIN))); }
 static FkMfma fk_mfma_of(hnsw_gpu_index *ix, int format, size_t k, bool grouped)
@@ -788,6 +782,14 @@ static FkMfma fk_mfma_of(hnsw_gpu_index *ix, int format, size_t k, bool grouped)
 	return m;
 }
 
+// the group word of every entry of `list`, or (list == NULL) of every element [0, total)
+static void gk_groups_launch(const FkCall &c, const uint32_t *list, size_t total, uint32_t *out)
+{
+	const GkGroups gg = { list, total, c.ix->labels, c.group_of, c.group_entries, out };
+	const uint32_t blocks = (uint32_t) std::min<size_t>((total + 255) / 256, (size_t) c.ix->num_cu * 8);
+	hipLaunchKernelGGL(gk_groups_kernel, dim3(blocks), dim3(256), 0, c.s, gg);
+}
+
 // 1b. grouped k-NN (device_grouped_knn.h), behind the list build: the group word of every list entry (counted with the
 // build's time, like the masks of the matrix-core form)
 static int gk_groups(FkCall &c)
@@ -796,9 +798,7 @@ static int gk_groups(FkCall &c)
 	if (int rc = buf_reserve(&fw->grp, c.total * 4, c.fam->who, "the group words of the lists")) return rc;
 	if (c.total)
 	{
-		const GkGroups gg = { (const uint32_t *) fw->list.p, c.total, c.ix->labels, c.group_of, c.group_entries, (uint32_t *) fw->grp.p };
-		const uint32_t blocks = (uint32_t) std::min<size_t>((c.total + 255) / 256, (size_t) c.ix->num_cu * 8);
-		hipLaunchKernelGGL(gk_groups_kernel, dim3(blocks), dim3(256), 0, c.s, gg);
+		gk_groups_launch(c, (const uint32_t *) fw->list.p, c.total, (uint32_t *) fw->grp.p);
 		HIPCHK(hipGetLastError());
 	}
 	HIPCHK(hipEventRecord(fw->ev[1], c.s));
@@ -814,16 +814,14 @@ static int fk_masks(FkCall &c, uint32_t *mwords_out)
 	const uint32_t mwords = fkm_mask_words((uint32_t) c.ix->n);
 	int rc = buf_reserve(&fw->mask, (nfilters + 1) * (size_t) mwords * 4, c.fam->who, "the row masks");
 	if (rc) return rc;
+	const uint32_t *egroup = nullptr;
 	if (c.fam->grouped)
 	{
 		if ((rc = buf_reserve(&fw->egrp, c.ix->n * 4, c.fam->who, "the group words of the elements"))) return rc;
-		const GkmGroups gg = { c.ix->labels, (uint32_t) c.ix->n, c.group_of, c.group_entries, (uint32_t *) fw->egrp.p };
-		const uint32_t blocks = (uint32_t) std::min<size_t>((c.ix->n + 255) / 256, (size_t) c.ix->num_cu * 8);
-		hipLaunchKernelGGL(gkm_groups_kernel, dim3(blocks), dim3(256), 0, c.s, gg);
-		hipLaunchKernelGGL(gkm_mask_kernel, dim3((uint32_t) (c.nsb * nfilters)), dim3(256), 0, c.s, c.fl, (const uint32_t *) fw->egrp.p, mwords, (uint32_t *) fw->mask.p);
+		gk_groups_launch(c, nullptr, c.ix->n, (uint32_t *) fw->egrp.p);
+		egroup = (const uint32_t *) fw->egrp.p;
 	}
-	else if (c.allow) hipLaunchKernelGGL(fkm_mask_kernel, dim3((uint32_t) (c.nsb * nfilters)), dim3(256), 0, c.s, c.fl, mwords, (uint32_t *) fw->mask.p);
-	else hipLaunchKernelGGL(rk_live_kernel<RK_LIVE_MASK>, dim3((uint32_t) c.nsb), dim3(256), 0, c.s, c.fl, (const uint64_t *) nullptr, (uint32_t *) fw->mask.p);
+	hipLaunchKernelGGL(fk_mask_kernel, dim3((uint32_t) (c.nsb * nfilters)), dim3(256), 0, c.s, c.fl, egroup, mwords, (uint32_t *) fw->mask.p);
 	HIPCHK(hipMemsetAsync((uint32_t *) fw->mask.p + nfilters * (size_t) mwords, 0, (size_t) mwords * 4, c.s));
 	HIPCHK(hipEventRecord(fw->ev[1], c.s));
 	*mwords_out = mwords;

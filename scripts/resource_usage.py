@@ -37,5 +37,5 @@ for line in r.stderr.splitlines():
 print(f"{'kernel':70s} {'VGPR':>5s} {'AGPR':>5s} {'SGPR':>5s} {'vspill':>6s} {'sspill':>6s} {'scratch':>7s} {'occ':>4s}")
 for c in rows:
     if flt in c["name"]:
-        print(f"{c['name'][:70]:70s} {c.get('VGPRs',0):5d} {c.get('AGPRs',0):5d} {c.get('SGPRs',0):5d} {c.get('VGPRs Spill',0):6d} "
+        print(f"{c['name'][:70]:70s} {c.get('VGPRs',0):5d} {c.get('AGPRs',0):5d} {c.get('TotalSGPRs', c.get('SGPRs', 0)):5d} {c.get('VGPRs Spill',0):6d} "
               f"{c.get('SGPRs Spill',0):6d} {c.get('ScratchSize',0):7d} {c.get('Occupancy',0):4d}")

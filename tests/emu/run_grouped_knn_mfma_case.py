@@ -5,7 +5,7 @@ everything around it — list build, group words of the lists and of the element
 group, the append with its mask test and counters, the grouped re-score, emit, the plan, gather / scatter, the host code — is the product's.
 Run as a subprocess by tests/test_grouped_knn_mfma_emu.py.  Prints one JSON line: a list of case reports.
 
-    python tests/emu/run_grouped_knn_mfma_case.py <group | large_k | fallback | auto | arg_errors> [emulated-library]
+    python tests/emu/run_grouped_knn_mfma_case.py <group | large_k | wide_k | fallback | auto | arg_errors> [emulated-library]
 """
 import json
 import sys
@@ -80,6 +80,26 @@ def group(name, factor=M.FACTOR):
             eq = all(got[n].tobytes() == f[n].tobytes() for n in ("labels", "dists", "idx", "counts"))
             rep["equals_filtered_knn_mfma"] = bool(eq)
             rep["nbad"] += int(not eq)
+        out.append(rep)
+    return out
+
+
+def wide_k():
+    """k = 1024 at the widest row the grouped re-score has LDS for — 768 dimensions: the query image, 1 025 keys, the sums and 1 025 group
+    words per wave — and 4 dimensions beyond it, where the matrix-core form has no pass for the call and the listed form answers.  2 200 rows
+    in 1 100 groups (l % 1100), one query, sample factor 1: the sample of 1 100 rows holds every group, so tau is finite"""
+    out = []
+    for dim, expect in ((768, "f32"), (772, "listed")):
+        X = np.random.default_rng(63).standard_normal((2200, dim)).astype(np.float32)
+        case = G.make(f"k1024_wide_{dim}", X, G.U.COSINE, G.U.queries(X, 1, seed=64), 1024, np.arange(2200, dtype=np.uint32) % 1100)
+        ix = R.mirror(case)
+        knobs(ix.L, True, factor=1)
+        rc, got = call_dev(ix, case["Q"], case["k"], case["group_of"])
+        assert rc == 0, ix.L.hnsw_gpu_last_error()
+        rep = M.check(case, got, ix.last_grouped_knn_form(), ix.last_grouped_knn_mfma(), SAMPLE_MIN, expect, factor=1)
+        rc2, ref = R.call_dev(ix, case["Q"], case["k"], case["group_of"], None, None, None)
+        rep["same_bytes_as_listed"] = bool(rc2 == 0 and same(got, ref))
+        rep["nbad"] += int(not rep["same_bytes_as_listed"])
         out.append(rep)
     return out
 
@@ -193,5 +213,5 @@ def arg_errors():
 
 if __name__ == "__main__":
     g = sys.argv[1]
-    res = {"fallback": fallback, "auto": auto, "arg_errors": arg_errors, "large_k": lambda: group(g, factor=1)}.get(g, lambda: group(g))()
+    res = {"fallback": fallback, "wide_k": wide_k, "auto": auto, "arg_errors": arg_errors, "large_k": lambda: group(g, factor=1)}.get(g, lambda: group(g))()
     print(json.dumps(res))

@@ -12,6 +12,8 @@ bench.py's rows (1M x 768 L2, 1 024 queries, k = 10, groups of 8 labels), `--cal
   filtered_listed_1/100                          filtered_knn_torch
   filtered_mfma_f16_1/10                         filtered_knn_torch(form="mfma", rows="f16")
   range_listed_1/100, range_mfma_f16_1/10        range_knn_torch with a radius that about 1 in 1 000 rows satisfy
+  grouped_mfma_f16_no_filter, grouped_mfma_f16_1/2   grouped_knn_torch(form="mfma", rows="f16"): the grouped scan over the samples, the filter, the grouped re-score
+  grouped_auto_1/10                              grouped_knn_torch(form="auto", rows="f16")
 
 and a checksum of every answer (the builds must return the same bytes).  The record holds min / median / max over all calls of a build and,
 for every figure, whether this build's median lies inside the first build's own min-max band.
@@ -41,7 +43,7 @@ def worker(calls):
     ix.set_reduced_rows("f16")
     Q = gmm_torch(nq, dim, k=1000, sigma=0.3, seed=42, stream=1, device=dev)
     tab = (torch.arange(n, device=dev) // 8).to(torch.int32)
-    w = {e: pg.index._pack_allow_torch(torch.from_numpy(np.random.default_rng(e).random(n) < 1.0 / e).to(dev), dev)[0] for e in (100, 10)}
+    w = {e: pg.index._pack_allow_torch(torch.from_numpy(np.random.default_rng(e).random(n) < 1.0 / e).to(dev), dev)[0] for e in (100, 10, 2)}
     d = torch.cdist(Q[:64], X[:20000])
     radius = float(torch.quantile(d.flatten()[:1_000_000], 0.001))
     fns = {"grouped_listed_1/100": lambda: ix.grouped_knn_torch(Q, k, tab, w[100]),
@@ -49,7 +51,10 @@ def worker(calls):
            "filtered_listed_1/100": lambda: ix.filtered_knn_torch(Q, k, w[100]),
            "filtered_mfma_f16_1/10": lambda: ix.filtered_knn_torch(Q, k, w[10], form="mfma", rows="f16"),
            "range_listed_1/100": lambda: ix.range_knn_torch(Q, radius, k, w[100], totals=True),
-           "range_mfma_f16_1/10": lambda: ix.range_knn_torch(Q, radius, k, w[10], totals=True, form="mfma", rows="f16")}
+           "range_mfma_f16_1/10": lambda: ix.range_knn_torch(Q, radius, k, w[10], totals=True, form="mfma", rows="f16"),
+           "grouped_mfma_f16_no_filter": lambda: ix.grouped_knn_torch(Q, k, tab, form="mfma", rows="f16"),
+           "grouped_mfma_f16_1/2": lambda: ix.grouped_knn_torch(Q, k, tab, w[2], form="mfma", rows="f16"),
+           "grouped_auto_1/10": lambda: ix.grouped_knn_torch(Q, k, tab, w[10], form="auto", rows="f16")}
     out = {"ms": {}, "sha": {}}
     for name, fn in fns.items():
         r = fn()

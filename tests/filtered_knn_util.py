@@ -30,6 +30,19 @@ def flat_image(X, labels, m=4):
     return img.reshape(-1)
 
 
+def meta(dims, func, m=4):
+    """make_meta(dims, m, 16, 8, func) for any row width: make_meta keeps embedding.c's rule that an element fits a Postgres page (about 2 000
+    dimensions); the library has no such rule (hnsw_gpu_index_create_from_flat takes up to 2^20 dimensions and does not read elems_per_page),
+    and the LDS limits of the exact scorers lie at rows wider than a page"""
+    import pg_embedding_amd as pg
+    mt = pg.make_meta(8, m, 16, 8, func)
+    mt.dim, mt.data_size = dims, dims * 4
+    mt.offset_label = mt.offset_data + mt.data_size
+    mt.size_data_per_element = mt.offset_label + 8
+    mt.elems_per_page = max(1, (8192 - 24 - 4) // (mt.size_data_per_element + 4))
+    return mt
+
+
 def members(labels, dead, allow_row):
     """A(b): element numbers, ascending"""
     lab = np.asarray(labels, np.uint64)

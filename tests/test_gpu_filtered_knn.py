@@ -20,7 +20,7 @@ pytestmark = pytest.mark.gpu
 
 def mirror(case):
     X = case["X"]
-    ix = pg.GpuIndex.from_flat(pg.make_meta(X.shape[1], 4, 16, 8, case["func"]), U.flat_image(X, case["labels"]), X.shape[0], device=0)
+    ix = pg.GpuIndex.from_flat(U.meta(X.shape[1], case["func"]), U.flat_image(X, case["labels"]), X.shape[0], device=0)
     if case["dead"].any():
         ix.set_deleted_many(np.nonzero(case["dead"])[0])
     return ix
@@ -168,3 +168,31 @@ def test_an_index_scan_that_runs_to_its_end_passes_the_same_labels():
         mine = got["labels"][i, :int(got["counts"][i])].astype(np.int64).tolist()
         assert len(mine) == int(allow.sum()) and len(set(f)) == len(f)
         assert set(f) == set(mine), i
+
+
+# ---- the LDS carve at its limit ------------------------------------------------------------------------------------------------------
+
+def test_k1024_at_the_widest_row_the_listed_scan_has_lds_for():
+    """k = 1024 at 7 168 dimensions: the query image, 4 x 1 025 keys, the sums and the staged element numbers fill 64 544 of the block's
+    65 536 bytes of LDS.  1 024 rows, a bitmap that passes every label, 2 queries: 4 splits, 16 waves of 64 rows, every row in the answer.
+    4 dimensions more (one more step of the query image) do not fit: HNSW_GPU_ERR_ARG before anything is written"""
+    import torch
+    for dim, fits in ((7168, True), (7172, False)):
+        X = np.random.default_rng(221).standard_normal((1024, dim)).astype(np.float32)
+        case = U.make(f"wide_1024x{dim}_k1024", X, U.L2, U.queries(X, 2, seed=222), 1024, np.ones(1024, bool))
+        ix = mirror(case)
+        if fits:
+            rep, _ = check(case, ix)
+            assert rep["counts"] == [1024, 1024] and rep["rows_scored"] == 2 * 1024
+            continue
+        q = torch.from_numpy(case["Q"]).cuda()
+        words = torch.full((1, 32), -1, dtype=torch.int32).cuda()
+        lab = torch.full((2, 1024), 0x1111111111111111, dtype=torch.int64).cuda()
+        dst = torch.full((2, 1024), -7.0).cuda()
+        idx = torch.full((2, 1024), 0x44444444, dtype=torch.int32).cuda()
+        cnt = torch.full((2,), 0x22222222, dtype=torch.int32).cuda()
+        rc = ix.L.hnsw_gpu_filtered_knn_dev(ix._h, q.data_ptr(), 2, 1024, words.data_ptr(), 1024, 1, None, lab.data_ptr(), dst.data_ptr(), idx.data_ptr(),
+                                            cnt.data_ptr(), None)
+        torch.cuda.synchronize()
+        assert rc == -2                                                               # HNSW_GPU_ERR_ARG
+        assert (lab == 0x1111111111111111).all() and (dst == -7.0).all() and (idx == 0x44444444).all() and (cnt == 0x22222222).all()

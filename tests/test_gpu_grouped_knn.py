@@ -20,7 +20,7 @@ U = G.U
 
 def mirror(case):
     X = case["X"]
-    ix = pg.GpuIndex.from_flat(pg.make_meta(X.shape[1], 4, 16, 8, case["func"]), G.flat_image(X, case["labels"]), X.shape[0], device=0)
+    ix = pg.GpuIndex.from_flat(U.meta(X.shape[1], case["func"]), G.flat_image(X, case["labels"]), X.shape[0], device=0)
     if case["dead"].any():
         ix.set_deleted_many(np.nonzero(case["dead"])[0])
     return ix
@@ -164,3 +164,39 @@ def test_5000x768_four_bitmaps_nq65_groups_of_4():
     allow = np.stack([np.ones(5000, bool), U.exactly(5000, 1237, 34), U.exactly(5000, 311, 35), U.exactly(5000, 77, 36)])
     case = G.make("l2_5000x768_div4", X, U.L2, U.queries(X, 65, seed=37), 10, G.every(5000, 4), allow, (np.arange(65) * 3) % 4)
     check(case)
+
+
+# ---- the LDS carve at its limit ------------------------------------------------------------------------------------------------------
+
+def _wide_call(n, dim, nq, k):
+    """the raw call of n x dim standard-normal rows in groups l % 1500 without a filter, outputs preset to patterns: (rc, outputs untouched)"""
+    import torch
+    X = np.random.default_rng(211).standard_normal((n, dim)).astype(np.float32)
+    case = G.make(f"wide_{n}x{dim}_k{k}", X, U.L2, U.queries(X, nq, seed=212), k, np.arange(n, dtype=np.uint32) % 1500)
+    ix = mirror(case)
+    q = torch.from_numpy(case["Q"]).cuda()
+    tab = torch.from_numpy(case["group_of"].view(np.int32)).cuda()
+    lab = torch.full((nq, k), 0x1111111111111111, dtype=torch.int64).cuda()
+    dst = torch.full((nq, k), -7.0).cuda()
+    idx = torch.full((nq, k), 0x44444444, dtype=torch.int32).cuda()
+    grp = torch.full((nq, k), 0x33333333, dtype=torch.int32).cuda()
+    cnt = torch.full((nq,), 0x22222222, dtype=torch.int32).cuda()
+    rc = ix.L.hnsw_gpu_grouped_knn_dev(ix._h, q.data_ptr(), nq, k, tab.data_ptr(), n, None, None, 0, 0, None, lab.data_ptr(), dst.data_ptr(), idx.data_ptr(),
+                                       grp.data_ptr(), cnt.data_ptr(), None)
+    torch.cuda.synchronize()
+    untouched = bool((lab == 0x1111111111111111).all() and (dst == -7.0).all() and (idx == 0x44444444).all() and (grp == 0x33333333).all() and
+                     (cnt == 0x22222222).all())
+    return case, ix, rc, untouched
+
+
+def test_k1024_at_the_widest_row_the_grouped_scan_has_lds_for():
+    """k = 1024 at 3 072 dimensions: the query image, 4 x 1 025 keys, the sums, the staged element numbers and 4 x 1 025 group words fill 64 560
+    of the block's 65 536 bytes of LDS — a group word or a staged number at a wrong offset lands in another wave's area.  2 048 rows without
+    a filter, 3 queries: 8 splits, every one of the 32 waves scans 64 rows and keeps them all (1 500 groups: 548 of them twice).  4 dimensions
+    more (one more step of the query image) do not fit: HNSW_GPU_ERR_ARG before anything is written"""
+    case, ix, rc, untouched = _wide_call(2048, 3072, 3, 1024)
+    assert rc == 0 and not untouched
+    rep, _ = check(case, ix)
+    assert rep["counts"] == [1024, 1024] and rep["rows_scored"] == 3 * 2048
+    _, _, rc, untouched = _wide_call(2048, 3076, 3, 1024)
+    assert rc == -2 and untouched                                                     # HNSW_GPU_ERR_ARG

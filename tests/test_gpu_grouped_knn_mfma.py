@@ -289,6 +289,30 @@ def test_k_1_64_65_600_1024(k_table, k, spread):
         assert d["appended"] < 3 * 6000, d                       # a finite tau
 
 
+@pytest.mark.parametrize("dim,fits", [(768, True), (772, False)])
+def test_k_1024_at_the_widest_row_the_grouped_rescore_has_lds_for(dim, fits):
+    """the spread case above at k = 1024, rebuilt at 768 dimensions: a wave of the re-score holds the query image, 1 025 keys, the sums and
+    1 025 group words in 15 872 of its 16 384 bytes of LDS — group words at a wrong offset land in the next wave's query image.  4 dimensions
+    more (one more step of the image) do not fit: the matrix-core form has no pass for the call and the listed form answers, the same bytes"""
+    X = np.random.default_rng(63).standard_normal((6000, dim)).astype(np.float32)
+    case = G.make(f"k1024_spread_{dim}", X, U.COSINE, U.queries(X, 3, seed=64), 1024, np.arange(6000, dtype=np.uint32) % 1500)
+    ix = mirror(case)
+    _set(b"HNSW_GPU_GK_SAMPLE_FACTOR", 1)
+    _set(b"HNSW_GPU_BF_BIG_MIN_BLOCKS", 0)
+    got = gk_torch(ix, case)
+    form, d = ix.last_grouped_knn_form(), ix.last_grouped_knn_mfma()
+    listed = gk_torch(ix, case, form=None)
+    assert ix.last_grouped_knn_form() == "listed"
+    print(f"grouped k-NN mfma {case['name']} factor 1: form {form} sample rows {d['rows_scored']} dist_pass {d['dist_pass']} appended {d['appended']}")
+    assert same(got, listed)
+    assert (form != "listed") == fits, form
+    rep = M.check(case, got, form, d, SAMPLE_MIN, "f32" if fits else "listed", factor=1)
+    assert rep["nbad"] == 0, rep["bad"]
+    assert rep["counts"] == [1024, 1024]
+    if fits:
+        assert rep["filtered"] == 3 and 3 * 1024 <= d["appended"] < 3 * 6000, (rep, d)   # a finite tau: the sample of 3 000 rows holds all 1 500 groups
+
+
 def test_k_1024_at_a_factor_where_every_list_is_its_own_sample_is_the_listed_pass(k_table):
     """k F = 4 096 >= 2 048: no list is longer than its sample, so the listed pass answers before any launch of the matrix-core form"""
     base, ix = k_table

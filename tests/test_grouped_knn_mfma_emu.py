@@ -85,6 +85,15 @@ def test_k_600_and_1024_through_the_rescore_at_sample_factor_1(emu_lib):
         assert r["form"] == "f32" and r["counts"] == [k, k] and r["filtered"] == r["nq"] and r["appended"] >= r["nq"] * k, r
 
 
+def test_k_1024_at_the_widest_row_the_grouped_rescore_has_lds_for_and_beyond(emu_lib):
+    """768 dimensions: the per-wave carve of the re-score at its limit; 772: no pass of the matrix-core form, the listed form's bytes"""
+    res = group(emu_lib, "wide_k")
+    assert set(res) == {"k1024_wide_768", "k1024_wide_772"}
+    wide, beyond = res["k1024_wide_768"], res["k1024_wide_772"]
+    assert wide["form"] == "f32" and wide["counts"] == [1024, 1024] and wide["filtered"] == 1 and 1024 <= wide["appended"] < 2200, wide
+    assert beyond["form"] == "listed" and beyond["counts"] == [1024, 1024] and wide["same_bytes_as_listed"] and beyond["same_bytes_as_listed"], beyond
+
+
 def test_equal_distances_inside_and_across_groups_tell_the_rules_apart(emu_lib):
     res = group(emu_lib, "ties")
     assert set(res) == {"grouped_ties_k5", "grouped_ties_k16"}
