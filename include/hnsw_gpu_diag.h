@@ -58,6 +58,18 @@ int hnsw_gpu_replay_roof_dealt(hnsw_gpu_index *ix, const idx_t *d_evals, size_t 
  * HBM and do not care.  *mhz = 0 when the launch recorded nothing (a stream, or a kernel form without the stamps). */
 int hnsw_gpu_last_search_clock_mhz(hnsw_gpu_index *ix, double *mhz);
 
+/* The plan of the most recent search launch of the mirror's default workspace, as HNSW_GPU_SEARCH_PLAN_WORDS 32-bit words (the first
+ * min(cap, that many) are written; all zero before the first launch; a refused request leaves the plan of the launch before it):
+ *   [0] form: 0 beam, 1 generic with its sets in LDS, 2 generic with its sets in HBM, 3 wide   [1] set registers of the beam form (2 / 4 /
+ *   8 / 16, else 0)   [2] the kernel's distance function code   [3] team   [4] narrow-row form   [5] lean   [6] ran in locality order
+ *   [7] waves per block   [8] blocks   [9] workspace slots (= blocks * waves per block)   [10] dynamic LDS bytes per block   [11] team_mains
+ *   the per-wave LDS carve, SearchArgs' words of the same names: [12] qpad_floats [13] off_res [14] off_cand [15] off_newid [16] off_newdist
+ *   [17] wave_bytes [18] off_hash [19] hcap [20] hmagic [21], [22] set_stride (low, high word) [23] wide_p [24] wide_ch [25] wide_nr
+ *   [26] wide_nc [27] off_ctl [28] tm_off_ex [29] tm_off_miss [30] tm_off_lctag [31] tm_off_lcstate [32] tm_off_lclinks [33] tm_lcslots
+ *   [34] tm_off_dc [35] tm_dccap [36] tm_spec   reduced rows: [37] nblk [38] rstride4 */
+#define HNSW_GPU_SEARCH_PLAN_WORDS 39
+int hnsw_gpu_last_search_plan(hnsw_gpu_index *ix, uint32_t *out, size_t cap);
+
 /* Where the mirror and its default search workspace sit in the device's address space: out[2*i] = device address, out[2*i+1] =
  * bytes, for i = 0 arena (one allocation holding rows | links | labels, each on a 2 MiB boundary), 1 rows, 2 links, 3 labels,
  * 4 visited bitmaps, 5 bitmap logs, 6 unused (0, 0: the beam form's prune needs no scratch), 7 ticket words.  `out` holds 16 values. */

@@ -171,6 +171,8 @@ def gpu_lib():
     L.hnsw_gpu_last_search_ms.argtypes = [vp, _f32p]
     L.hnsw_gpu_search_ms.argtypes = [vp, C.c_uint, _f32p]
     L.hnsw_gpu_last_search_slots.argtypes = [vp, _u32p]
+    if hasattr(L, "hnsw_gpu_last_search_plan"):                # (an older build of the library loaded for an A/B: tests/experiments/search_ab.py)
+        L.hnsw_gpu_last_search_plan.argtypes = [vp, _u32p, sz]
     L.hnsw_gpu_last_search_order.argtypes = [vp, vp, vp, sz, C.POINTER(C.c_size_t)]
     L.hnsw_gpu_locality_order_dev.argtypes = [vp, vp, sz, vp, vp]
     L.hnsw_gpu_last_search_chunk.argtypes = [vp, C.POINTER(C.c_uint32)]

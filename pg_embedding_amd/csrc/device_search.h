@@ -8,7 +8,7 @@
 // slots each keeping up to 24 KiB of row reads in flight; a single query is latency-bound by
 // construction (≈ef dependent hops, two memory round trips each).
 //
-// Three forms of the same algorithm (the host picks one per launch, hnsw_gpu.hip launch_search):
+// Three forms of the same algorithm (the host picks one per launch: gpu_search.hip, plan_search):
 //   hnsw_search_kernel_beam (ef <= 256; <= 512 on wide rows; the hot one): ONE unordered set of accepted
 //                           elements in registers, every decision of the reference restated as a count
 //                           over it (banner further down); visited set = exact bucketed tag set in LDS
@@ -591,7 +591,7 @@ constexpr bool TEAM_COUNT = true;
 constexpr bool TEAM_COUNT = false;
 #endif
 // per-section cycle stamps of the walking wave (any beam kernel): compiled in only with -DHNSW_HOP_STAMPS
-// (python pg_embedding_amd/build.py variant <tag> HNSW_HOP_STAMPS); HopDiag below.  A diagnostic build always has team_dbg (launch_search).
+// (python pg_embedding_amd/build.py variant <tag> HNSW_HOP_STAMPS); HopDiag below.  A diagnostic build always has team_dbg (gpu_search.hip, launch_search).
 #ifdef HNSW_HOP_STAMPS
 constexpr bool HOP_STAMPS = true;
 #else

@@ -104,8 +104,8 @@ static int link_range(hnsw_gpu_index *ix, size_t first, size_t count, size_t max
 		else
 		{
 			a.cand_idx = cand_idx; a.cand_dist = cand_dist; a.cand_cnt = cand_cnt;
-			int rc = launch_search(ix, &ix->ws, ix->vec + linked * ix->stride, ix->stride, b, efc, 1, nullptr, cand_idx, cand_dist,
-								   cand_cnt, nullptr, stream);
+			int rc = launch_search(ix, &ix->ws, {.queries = ix->vec + linked * ix->stride, .q_stride = ix->stride, .nq = b, .ef = efc, .mode = 1, .idx = cand_idx,
+												 .dists = cand_dist, .counts = cand_cnt, .stream = stream});
 			if (rc) return rc;
 		}
 		// 2. choose links, emit reverse pairs
@@ -412,8 +412,8 @@ static int insert_impl(hnsw_gpu_index *ix, const coord_t *point, label_t label, 
 		}
 		else                                                 // searchBaseLayer(ef = efConstruction) of the insert itself (hnswalg.cpp:229), the point read as
 		{                                                    // the query straight from pinned memory over the idx elements stored so far; step 1 stores the row
-			rc = launch_search(ix, &ix->ws, (const float *) h, dim, 1, efc_, 1, nullptr, (uint32_t *) ia.b.cand_idx,
-							   (float *) ia.b.cand_dist, (uint32_t *) ia.b.cand_cnt, nullptr, nullptr);
+			rc = launch_search(ix, &ix->ws, {.queries = (const float *) h, .q_stride = dim, .nq = 1, .ef = efc_, .mode = 1, .idx = (uint32_t *) ia.b.cand_idx,
+											 .dists = (float *) ia.b.cand_dist, .counts = (uint32_t *) ia.b.cand_cnt});
 			if (rc) return rc;
 			ia.src_row = (const float *) h; ia.src_label = (const uint64_t *) (h + o_lab);
 			ix->n += 1;

@@ -12,13 +12,9 @@ extern "C" int hnsw_gpu_search_traced_dev(hnsw_gpu_index *ix, const coord_t *d_q
 {
 	if (!ix) return fail(HNSW_GPU_ERR_ARG, "index is NULL");
 	if (!d_evals || evals_cap == 0 || evals_cap > 0xFFFFFFFFull || !d_stats) return fail(HNSW_GPU_ERR_ARG, "trace buffers missing");
-	std::lock_guard<std::recursive_mutex> g(ix->mu);
-	ix->ws.evals_next = d_evals; ix->ws.evals_cap_next = (uint32_t) evals_cap; ix->ws.times_next = d_times;
 	// (in the same order as the untraced launch of the same batch: the replay of this trace re-reads the rows in the order they were walked)
-	const int rc = launch_search(ix, &ix->ws, d_queries, ix->meta.dim, nq, ef, 0, d_labels, nullptr, d_dists, d_counts, d_stats, (hipStream_t) stream,
-								 0, true);
-	ix->ws.evals_next = nullptr; ix->ws.evals_cap_next = 0; ix->ws.times_next = nullptr;
-	return rc;
+	return launch_search(ix, &ix->ws, {.queries = d_queries, .q_stride = ix->meta.dim, .nq = nq, .ef = ef, .labels = d_labels, .dists = d_dists, .counts = d_counts,
+									   .stats = d_stats, .stream = (hipStream_t) stream, .order = true, .evals = d_evals, .evals_cap = (uint32_t) evals_cap, .times = d_times});
 }
 
 extern "C" int hnsw_gpu_team_counters(hnsw_gpu_index *ix, uint32_t *out8)

@@ -3,7 +3,8 @@
 // C ABI (include/hnsw_gpu.h, include/hnsw_gpu_diag.h); everything has hidden visibility.
 //
 //   hnsw_gpu.hip      errors, configuration, workspaces + watchdog, the mirror (create / import / export / append / reserve)
-//   gpu_search.hip    launch planning (launch_search), the search entry points, traces of one walk, search contexts
+//   gpu_search.hip    a search launch (plan_search: the pure plan; launch_search: geometry, workspace, order, launch), the search entry
+//                     points, traces of one walk, search contexts, the batched index scan
 //   gpu_stream.hip    streams: one resident launch fed by the host
 //   gpu_scan.hip      batched distances, exhaustive k-NN (canonical scan, MFMA filter in three operand forms), exact filtered k-NN (listed scan, MFMA filter with an allow test)
 //   gpu_build.hip     insert path: batched link step, single inserts
@@ -71,6 +72,51 @@ static inline long long knob(int k, long long dflt)
 }
 static inline bool knob_is_set(int k) { return g_knob[k].set.load(std::memory_order_acquire); }
 
+// ---- one search launch: the request, and the plan made for it (gpu_search.hip) --------------------
+// Everything ONE launch is asked for.  Call sites name the fields they set; the rest stay at "none".
+struct SearchLaunch
+{
+	const float *queries = nullptr; size_t q_stride = 0, nq = 0, ef = 0;
+	int mode = 0;                                        // 0 = hnsw_search semantics (labels), 1 = searchBaseLayer only (element numbers)
+	uint64_t *labels = nullptr; uint32_t *idx = nullptr; float *dists = nullptr; uint32_t *counts = nullptr, *stats = nullptr;
+	hipStream_t stream = nullptr;
+	int rows = 0;                                        // HNSW_GPU_ROWS_F16 / _BF16 = walk over the reduced copy (mode 1 only; hnsw_gpu_search_batch_reduced_dev)
+	bool order = false;                                  // a batch entry point that runs large batches in locality order (device_order.h)
+	uint32_t *done = nullptr;                            // completion flags, one per query
+	uint32_t *pops = nullptr; uint32_t pops_cap = 0;     // pop-sequence output
+	uint32_t *evals = nullptr; uint32_t evals_cap = 0; uint64_t *times = nullptr;   // evaluation trace
+	// stream mode (hnsw_gpu_stream_open): the host's control words, their device copies, ring size, walking waves per block
+	const uint32_t *stream_host = nullptr; uint32_t *stream_dev = nullptr; uint32_t stream_ring = 0, stream_walkers = 0;
+};
+
+// What the planner knows of the index and its device: plain numbers, so that a plan can be made (and checked) without either.
+struct SearchFacts
+{
+	size_t n = 0, cap = 0, dim = 0;
+	uint32_t stride = 0, lstride = 0;
+	int dist_func = 0, num_cu = 0;
+	size_t max_lds = 0;                                  // dynamic LDS one block may ask for
+	int rows_fmt = 0; uint32_t rows16_bytes = 0;         // the reduced copy: its format (0 = none) and row size
+};
+
+// The plan of one launch.  plan_search fills everything down to `lds` from the facts, the request and the knobs alone (no HIP call, no
+// allocation, nothing written but this value); plan_geometry adds the rest from the one occupancy query.  The workspace keeps the plan
+// of its last launch (hnsw_gpu_last_search_plan, _kernel, _slots).  The carve words carry SearchArgs' names (device_search.h).
+struct SearchPlan
+{
+	SearchForm form = SearchForm::Beam; uint32_t ureg = 0;       // ureg: set registers of the beam form (2 / 4 / 8 / 16), else 0
+	int func_code = 0;                                   // the kernel's distance function (F_*_REF with reference order)
+	int rows = 0; uint32_t kiters = 0; size_t ef = 0;    // the request's reduced format, the row width in 64-float steps, the beam clamped to n
+	bool reforder = false, team_wanted = false, team = false, narrow5 = false, lean = false, stream = false, ordered = false;
+	uint32_t qpad_floats = 0, off_res = 0, off_cand = 0, off_newid = 0, off_newdist = 0, wave_bytes = 0, off_hash = 0, hcap = 0, hmagic = 0;
+	size_t set_stride = 0; uint32_t wide_p = 0, wide_ch = 0, wide_nr = 0, wide_nc = 0;
+	uint32_t off_ctl = 0, tm_off_ex = 0, tm_off_miss = 0, tm_off_lctag = 0, tm_off_lcstate = 0, tm_off_lclinks = 0, tm_lcslots = 0, tm_off_dc = 0, tm_dccap = 0, tm_spec = 0;
+	uint32_t nblk = 0, rstride4 = 0;                     // reduced rows: 256-byte blocks and uint4 units per row
+	uint32_t wpb = 0; size_t lds = 0;                    // waves per block (0: no launch yet), dynamic LDS bytes per block
+	size_t blocks = 0, slots = 0; uint32_t team_mains = 0;
+};
+void search_kernel_name(const SearchPlan &p, char *buf, size_t len);   // as rocprofv3 prints it; "" before the first launch
+
 // ---- the search workspace -------------------------------------------------------------------
 // Per-stream search state: the slots' visited bitmaps + logs, the ticket word and the HIP-event ring.
 // Every mirror owns one (used by the plain entry points); hnsw_gpu_ctx adds more so that batches on
@@ -84,14 +130,8 @@ struct SearchWs
 	uint32_t *ticket = nullptr;
 	hipEvent_t ev0[EV_RING] = {}, ev1[EV_RING] = {};
 	uint64_t launches = 0;
-	uint32_t last_slots = 0;
+	SearchPlan plan;                                     // of the last launch
 	uint32_t walkers_hint = 0;                           // hnsw_gpu_ctx_set_walkers: walking waves per block of a small team launch (0 = by launch size)
-	// stream mode, the next launch only (hnsw_gpu_stream_open): the host's control words, their device copies, ring size, walking waves per block
-	const uint32_t *stream_host_next = nullptr; uint32_t *stream_dev_next = nullptr; uint32_t stream_ring_next = 0, stream_walkers_next = 0;
-	uint32_t *done_next = nullptr;                       // completion flags for the next launch only
-	uint32_t *pops_next = nullptr; uint32_t pops_cap_next = 0;   // pop-sequence output for the next launch only
-	uint32_t *evals_next = nullptr; uint32_t evals_cap_next = 0; uint64_t *times_next = nullptr;   // evaluation trace, next launch only
-	char kname[96] = "";                                 // symbol of the kernel the last launch used (as rocprofv3 prints it)
 	uint32_t *team_dbg = nullptr;                        // 16 launch-wide counters of a diagnostic build (-DHNSW_HOP_STAMPS / -DHNSW_TEAM_COUNTERS), else null
 	// abort word (pinned host memory) + health counters (device memory): device_search.h, banner at abort_requested
 	uint32_t *abort_host = nullptr;
@@ -242,10 +282,8 @@ int import_range(hnsw_gpu_index *ix, const void *elements, size_t first, size_t 
 
 // ---- search (gpu_search.hip) ----------------------------------------------------------------------
 static const size_t LDS_PER_CU = 160 * 1024;
-int launch_search(hnsw_gpu_index *ix, SearchWs *w, const float *d_queries, size_t q_stride, size_t nq, size_t ef, int mode,
-				  uint64_t *d_labels, uint32_t *d_idx, float *d_dists, uint32_t *d_counts, uint32_t *d_stats, hipStream_t stream,
-				  int rows = 0,           // rows: HNSW_GPU_ROWS_F16 / _BF16 = walk over the reduced copy (mode 1 only; hnsw_gpu_search_batch_reduced_dev)
-				  bool order = false);    // order: a batch entry point that runs large batches in locality order (device_order.h)
+int plan_search(const SearchFacts &f, const SearchLaunch &r, SearchPlan *p);
+int launch_search(hnsw_gpu_index *ix, SearchWs *w, const SearchLaunch &r);
 int poll_limit_s();
 int poll_done_flag(const volatile uint32_t *flag, const char *what, SearchWs *w);
 int ws_search_ms(int device, SearchWs *w, unsigned back, float *ms);

@@ -1,4 +1,4 @@
-// gpu_search.hip — launch planning of the search kernels (csrc/device_search.h), the search entry points, one traced walk, search contexts, the batched index scan
+// gpu_search.hip — a launch of the search kernels (csrc/device_search.h): its plan (plan_search) and the launch (launch_search); the search entry points, one traced walk, search contexts, the batched index scan
 // One translation unit of libhnsw_gpu.so (csrc/gpu_host.h lists them); gfx950 only, plain HIP runtime, no framework types in any signature.
 #include "gpu_host.h"
 #include "device_order.h"
@@ -8,28 +8,43 @@
 // search
 // ------------------------------------------------------------------------------------
 // which kernel a launch runs: search_kernels.h (one translation unit per load shape)
-static search_kernel_t pick_search_kernel(int func, uint32_t kiters, int rreg, bool team, bool narrow5, bool lean)
+static search_kernel_t pick_rows16_kernel(int func, uint32_t kiters, uint32_t ureg, int fmt)
 {
 	switch (shape_index(kiters))
 	{
-		case 0:
-			if (narrow5 && !team) return pick_kernel_shape2x2(func, rreg, lean);      // the hot narrow-row form: 8 rows per pass, 96 VGPRs, 5 waves/SIMD
-			return pick_kernel_shape2x4(func, rreg, team);
-		case 1:  return pick_kernel_shape4x2(func, rreg, team);
-		case 2:  return pick_kernel_shape8x2(func, rreg, team);
-		default: return pick_kernel_shape12x2(func, rreg, team);
+		case 0:  return pick_rows16_kernel_shape2x4(func, ureg, fmt);
+		case 1:  return pick_rows16_kernel_shape4x2(func, ureg, fmt);
+		case 2:  return pick_rows16_kernel_shape8x2(func, ureg, fmt);
+		default: return pick_rows16_kernel_shape12x2(func, ureg, fmt);
 	}
 }
 
-static search_kernel_t pick_rows16_kernel(int func, uint32_t kiters, int rreg, int fmt)
+// The kernel of a plan and that kernel's name, from the same fields and side by side: a form added to one is missing from the other in
+// plain sight (tests/test_search_plan_emu.py compares the name with tests/kernel_census.py without a device).
+static search_kernel_t search_kernel_of(const SearchPlan &p)
 {
-	switch (shape_index(kiters))
+	if (p.rows) return pick_rows16_kernel(p.func_code, p.kiters, p.ureg, p.rows);
+	switch (shape_index(p.kiters))
 	{
-		case 0:  return pick_rows16_kernel_shape2x4(func, rreg, fmt);
-		case 1:  return pick_rows16_kernel_shape4x2(func, rreg, fmt);
-		case 2:  return pick_rows16_kernel_shape8x2(func, rreg, fmt);
-		default: return pick_rows16_kernel_shape12x2(func, rreg, fmt);
+		case 0:
+			if (p.narrow5 && !p.team) return pick_kernel_shape2x2(p.func_code, p.ureg, p.lean);      // the hot narrow-row form: 8 rows per pass, 96 VGPRs, 5 waves/SIMD
+			return pick_kernel_shape2x4(p.func_code, p.form, p.ureg, p.team);
+		case 1:  return pick_kernel_shape4x2(p.func_code, p.form, p.ureg, p.team);
+		case 2:  return pick_kernel_shape8x2(p.func_code, p.form, p.ureg, p.team);
+		default: return pick_kernel_shape12x2(p.func_code, p.form, p.ureg, p.team);
 	}
+}
+
+void search_kernel_name(const SearchPlan &p, char *buf, size_t len)
+{
+	static const char *const shapes[4] = { "Shape2x4", "Shape4x2", "Shape8x2", "Shape12x2" };
+	static const char *const rshapes[4] = { "1, 4, 4", "2, 4, 4", "4, 2, 4", "6, 2, 2" };
+	const char *shp = p.narrow5 && !p.team ? "Shape2x2" : shapes[shape_index(p.kiters)];
+	if (!p.wpb) snprintf(buf, len, "%s", "");
+	else if (p.rows) snprintf(buf, len, "pgemb::hnsw_search_kernel_beam<%d, pgemb::ShapeR16<%d, %s>, %u, false, false>", p.func_code, p.rows, rshapes[shape_index(p.kiters)], p.ureg);
+	else if (p.form == SearchForm::Beam) snprintf(buf, len, "pgemb::hnsw_search_kernel_beam<%d, pgemb::%s, %u, %s, %s>", p.func_code, shp, p.ureg, p.team ? "true" : "false", p.lean ? "true" : "false");
+	else if (p.form == SearchForm::Wide) snprintf(buf, len, "pgemb::hnsw_search_kernel_wide<%d, pgemb::%s>", p.func_code, shp);
+	else snprintf(buf, len, "pgemb::hnsw_search_kernel_lds<%d, pgemb::%s, %s>", p.func_code, shp, p.form == SearchForm::GenericHbm ? "true" : "false");
 }
 
 static rerank_kernel_t pick_rerank_kernel(int func, uint32_t kiters)
@@ -115,294 +130,305 @@ static const uint32_t *build_order(hnsw_gpu_index *ix, SearchWs *w, const float 
 	return perm;
 }
 
-int launch_search(hnsw_gpu_index *ix, SearchWs *w, const float *d_queries, size_t q_stride, size_t nq, size_t ef, int mode,
-						 uint64_t *d_labels, uint32_t *d_idx, float *d_dists, uint32_t *d_counts,
-						 uint32_t *d_stats, hipStream_t stream, int rows, bool order)
+// ------------------------------------------------------------------------------------
+// the plan of a launch (SearchPlan, gpu_host.h).  plan_search and everything it calls is pure: the index's facts, the request and the
+// knobs in, one SearchPlan or a refusal out — no HIP call, no allocation, no write to the workspace or the mirror
+// ------------------------------------------------------------------------------------
+static SearchFacts facts_of(const hnsw_gpu_index *ix)
 {
-	std::unique_lock<std::recursive_mutex> lock_;
-	if (ix) lock_ = std::unique_lock<std::recursive_mutex>(ix->mu);
-	if (!ix) return fail(HNSW_GPU_ERR_ARG, "index is NULL");
-	if (nq == 0) return HNSW_GPU_OK;
-	if (!d_queries || !d_counts || (mode == 0 && !d_labels) || (mode == 1 && !d_idx))
-		return fail(HNSW_GPU_ERR_ARG, "NULL buffer");
-	if (ef == 0 || ef >= 0xFFFFFFFFull) return fail(HNSW_GPU_ERR_ARG, "ef %zu out of range", ef);
-	if (nq >= 0xFFFFFFFFull) return fail(HNSW_GPU_ERR_ARG, "too many queries");
-	// A beam wider than the index behaves exactly like a beam of the index size (nothing is ever evicted,
-	// the walk ends when the candidates run out), so the scan's efSearch doubling (embedding.c:334) can go
-	// as far as it likes; the output arrays keep the caller's ef as their row stride.
-	const size_t out_stride = ef;
-	ef = std::min(ef, std::max<size_t>(ix->n, 1));
-	HIPCHK(hipSetDevice(ix->device));
+	SearchFacts f;
+	f.n = ix->n; f.cap = ix->cap; f.dim = ix->meta.dim; f.stride = ix->stride; f.lstride = ix->lstride;
+	f.dist_func = (int) ix->meta.dist_func; f.num_cu = ix->num_cu; f.max_lds = ix->max_lds;
+	f.rows_fmt = ix->rows16 ? ix->rows_fmt : 0; f.rows16_bytes = ix->rows16_bytes;
+	return f;
+}
 
-	SearchArgs a;
-	memset(&a, 0, sizeof(a));
-	a.vec = ix->vec; a.links = ix->links; a.labels = ix->labels;
-	a.n = (uint32_t) ix->n; a.dim = (uint32_t) ix->meta.dim; a.stride = ix->stride;
-	a.nchunks = ix->stride / 4; a.kiters = (a.nchunks + 15) / 16;
-	a.maxM = (uint32_t) ix->meta.maxM; a.lstride = ix->lstride; a.entry = ix->meta.enterpoint_node;
-	a.queries = d_queries; a.q_stride = (uint32_t) q_stride; a.nq = (uint32_t) nq; a.ef = (uint32_t) ef; a.ccap = (uint32_t) (2 * ef);
-	a.out_stride = (uint32_t) out_stride;
-	a.out_labels = d_labels; a.out_idx = d_idx; a.out_dists = d_dists; a.out_counts = d_counts; a.out_stats = d_stats;
-	a.mode = mode;
-	if (a.n > 0 && a.entry >= a.n) return fail(HNSW_GPU_ERR_ARG, "enterpoint_node %u >= count %u", a.entry, a.n);
-
-	// LDS carve per wave
-	a.qpad_floats = (uint32_t) round_up(a.kiters, shape_kb(shape_index(a.kiters))) * 64;
-	// Form of the accepted-set bookkeeping (rreg):
-	//   beam form (one accepted set in registers, acceptance by counting): default up to ef = 256, and up
-	//     to ef = 512 for rows wider than 256 floats — those run at 2 waves/SIMD anyway, so 16 set registers
-	//     beat the LDS form there (+22-28 %, profiles/r1i_beam_form.txt); narrow rows keep the LDS form
-	//     above 256 (it holds 4 waves/SIMD).  Its prune packs the "expanded" bit into bit 31 of the idx.
-	//   LDS (generic) form: everything else — also HNSW_GPU_BEAM=0 and mirrors of >= 2^31 elements (HNSW_GPU_FORCE_LDS_HEAPS=1 forces it).
-	// The beam form uses its LDS "res"/"cand" areas only as scratch of the emit step.
-	knobs_init();
-	const bool use_beam = knob(K_BEAM, 1) != 0 && ix->cap < 0x80000000ull;
-	const bool beam16 = use_beam && ef > 256 && ef <= 512 && (knob_is_set(K_BEAM16) ? knob(K_BEAM16, 0) > 0 : shape_index(a.kiters) >= 2);
+// Form of the accepted-set bookkeeping (SearchForm, search_kernels.h), the arithmetic, and the two wishes team / narrow5:
+//   beam form (one accepted set in registers, acceptance by counting): default up to ef = 256, and up
+//     to ef = 512 for rows wider than 256 floats — those run at 2 waves/SIMD anyway, so 16 set registers
+//     beat the LDS form there (+22-28 %, profiles/r1i_beam_form.txt); narrow rows keep the LDS form
+//     above 256 (it holds 4 waves/SIMD).  Its prune packs the "expanded" bit into bit 31 of the idx.
+//   LDS (generic) form: everything else — also HNSW_GPU_BEAM=0 and mirrors of >= 2^31 elements (HNSW_GPU_FORCE_LDS_HEAPS=1 forces it).
+// The beam form uses its LDS "res"/"cand" areas only as scratch of the emit step.
+static int plan_form(const SearchFacts &f, const SearchLaunch &r, SearchPlan *p)
+{
+	const size_t ef = p->ef;
+	if (r.rows && (r.mode != 1 || f.rows_fmt != r.rows)) return fail(HNSW_GPU_ERR_INTERNAL, "reduced-row walk without its copy");
+	const bool use_beam = knob(K_BEAM, 1) != 0 && f.cap < 0x80000000ull;
+	const bool beam16 = use_beam && ef > 256 && ef <= 512 && (knob_is_set(K_BEAM16) ? knob(K_BEAM16, 0) > 0 : shape_index(p->kiters) >= 2);
 	const size_t wide_min = (size_t) knob(K_WIDE_EF_MIN, (long long) WIDE_EF_MIN);
 	// Reference-order arithmetic (device_dist.h, F_L2_REF / F_MANHATTAN_REF / F_COSINE_REF; opt-in, HNSW_GPU_REF_ORDER=1): the summation order of
 	// oracle/_ref's own build, so that the id lists ARE the compiled reference's, query by query.  One kernel set only: beam form, 4 set
 	// registers, one wave per query; since round 6 with the canonical code's load shape (a timed mode of bench.py).
-	int func_code = (int) ix->meta.dist_func;
-	bool reforder = false;
+	p->func_code = f.dist_func;
 	if (knob(K_REF_ORDER, 0) > 0)
-		{
-			const bool ok = ef <= 128 && ix->cap < 0x80000000ull &&
-							((func_code == F_L2 && ix->meta.dim % 16 == 0) || ((func_code == F_MANHATTAN || func_code == F_COSINE) && ix->meta.dim % 4 == 0));
-			if (!ok)
-				return fail(HNSW_GPU_ERR_ARG, "HNSW_GPU_REF_ORDER: only L2 with dims %% 16 == 0 or cosine / Manhattan with dims %% 4 == 0, ef <= 128");
-			reforder = true;
-			func_code = func_code == F_L2 ? F_L2_REF : (func_code == F_COSINE ? F_COSINE_REF : F_MANHATTAN_REF);
-		}
-	int rreg;
-	if (reforder) rreg = -4;
-	else if (ef > wide_min) rreg = 3;
-	else if (knob(K_FORCE_LDS_HEAPS, 0) > 0) rreg = 0;
-	else if (use_beam && (ef <= 256 || beam16)) rreg = ef <= 64 ? -2 : (ef <= 128 ? -4 : (ef <= 256 ? -8 : -16));
-	else rreg = 0;                                           // HNSW_GPU_BEAM=0, or a mirror of >= 2^31 elements: the generic form
+	{
+		if (r.rows) return fail(HNSW_GPU_ERR_ARG, "reduced rows: HNSW_GPU_REF_ORDER=1 has no reduced-row kernels");
+		const bool ok = ef <= 128 && f.cap < 0x80000000ull &&
+						((f.dist_func == F_L2 && f.dim % 16 == 0) || ((f.dist_func == F_MANHATTAN || f.dist_func == F_COSINE) && f.dim % 4 == 0));
+		if (!ok)
+			return fail(HNSW_GPU_ERR_ARG, "HNSW_GPU_REF_ORDER: only L2 with dims %% 16 == 0 or cosine / Manhattan with dims %% 4 == 0, ef <= 128");
+		p->reforder = true;
+		p->func_code = f.dist_func == F_L2 ? F_L2_REF : (f.dist_func == F_COSINE ? F_COSINE_REF : F_MANHATTAN_REF);
+	}
+	p->form = SearchForm::GenericLds;                        // HNSW_GPU_BEAM=0, or a mirror of >= 2^31 elements: the generic form
+	if (p->reforder) { p->form = SearchForm::Beam; p->ureg = 4; }
+	else if (ef > wide_min) p->form = SearchForm::Wide;
+	else if (knob(K_FORCE_LDS_HEAPS, 0) > 0) p->form = SearchForm::GenericLds;
+	else if (use_beam && (ef <= 256 || beam16)) { p->form = SearchForm::Beam; p->ureg = ef <= 64 ? 2 : (ef <= 128 ? 4 : (ef <= 256 ? 8 : 16)); }
 	// Reduced-row walk (device_rows16.h; hnsw_gpu_search_batch_reduced_dev): the one-wave beam form only — no team, no narrow-row or
-	// LEAN kernels, no wide-beam / generic forms, no reference-order arithmetic, no streams or traces.  Refused here, before anything is
-	// launched or allocated.
-	if (rows)
+	// LEAN kernels, no wide-beam / generic forms, no reference-order arithmetic, no streams or traces.
+	if (r.rows)
 	{
-		if (mode != 1 || !ix->rows16 || ix->rows_fmt != rows) return fail(HNSW_GPU_ERR_INTERNAL, "reduced-row walk without its copy");
-		if (reforder) return fail(HNSW_GPU_ERR_ARG, "reduced rows: HNSW_GPU_REF_ORDER=1 has no reduced-row kernels");
-		if (rreg >= 0)
+		if (p->form != SearchForm::Beam)
 			return fail(HNSW_GPU_ERR_ARG, "reduced rows: ef %zu needs a form the reduced-row walk does not have (the beam form: ef <= 256, "
-						"<= 512 on rows wider than 256 floats; not with HNSW_GPU_BEAM=0 or HNSW_GPU_FORCE_LDS_HEAPS=1)", ef);
-		if (w->stream_host_next || w->pops_next || w->evals_next || w->times_next || w->done_next)
+						"<= 512 on rows wider than 256 floats; not with HNSW_GPU_BEAM=0 or HNSW_GPU_FORCE_LDS_HEAPS=1)", r.ef);
+		if (r.stream_host || r.pops || r.evals || r.times || r.done)
 			return fail(HNSW_GPU_ERR_ARG, "reduced rows: no streams, traces or completion flags");
-		if (!pick_rows16_kernel(func_code, a.kiters, rreg, rows)) return fail(HNSW_GPU_ERR_ARG, "reduced rows: no kernel for %d set registers at this width", -rreg);
+		if (!pick_rows16_kernel(p->func_code, p->kiters, p->ureg, r.rows))
+			return fail(HNSW_GPU_ERR_ARG, "reduced rows: no kernel for %d set registers at this width", (int) p->ureg);
 	}
-	const size_t ucap = rreg < 0 ? (size_t) 64 * (size_t) -rreg : 0;      // beam form: slots of the accepted set
-	// Team form wanted for this launch?  (decided for good further down, once the LDS carve is known)
+	const bool beam = p->form == SearchForm::Beam;
+	// Team form wanted for this launch?  (decided for good in plan_block, once the LDS carve is known)
 	const int treq = (int) knob(K_TEAM, -1);
-	const size_t auto_nq = (size_t) knob(K_TEAM_MAX_NQ, (long long) ix->num_cu);
-	const bool stream_launch = w->stream_host_next != nullptr;
-	const bool team_wanted = rreg < 0 && !reforder && !rows && (stream_launch || (treq != 0 && (treq > 0 || ix->stride > 320 || nq <= auto_nq)));
+	const size_t auto_nq = (size_t) knob(K_TEAM_MAX_NQ, (long long) f.num_cu);
+	p->stream = r.stream_host != nullptr;
+	p->team_wanted = beam && !p->reforder && !r.rows && (p->stream || (treq != 0 && (treq > 0 || f.stride > 320 || r.nq <= auto_nq)));
 	// narrow rows, hot form: beam kernel with <= 4 set registers, one sum per row (L2 / Manhattan), not a team
-	const bool narrow5 = shape_index(a.kiters) == 0 && (rreg == -2 || rreg == -4) && (int) ix->meta.dist_func != F_COSINE &&
-						 !team_wanted && !reforder && !rows && knob(K_NARROW5, 1) != 0;
-	if (rows)
+	p->narrow5 = shape_index(p->kiters) == 0 && beam && (p->ureg == 2 || p->ureg == 4) && f.dist_func != F_COSINE &&
+				 !p->team_wanted && !p->reforder && !r.rows && knob(K_NARROW5, 1) != 0;
+	return HNSW_GPU_OK;
+}
+
+// The per-wave LDS layouts, one function each.  *off comes in as the bytes used so far (the query image and the reference order's stage)
+// and goes out as the offset of the tail that all forms share, [newid | newdist].
+// wide-beam form: both sets in the slot's HBM area [res: P | cand: 2P], P = the power of two >= ef (the output sort is a
+// bitonic network); per-chunk extremes in LDS: chunks of >= 1024 keys, at most 1024 chunks of candidates
+static int carve_wide(SearchPlan *p, size_t *off)
+{
+	const size_t ef = p->ef;
+	size_t P = 2;
+	while (P < ef) P <<= 1;
+	size_t ch = 1024;
+	while ((2 * ef + ch - 1) / ch > 1024) ch <<= 1;
+	p->wide_p = (uint32_t) P; p->wide_ch = (uint32_t) ch;
+	p->wide_nr = (uint32_t) ((ef + ch - 1) / ch); p->wide_nc = (uint32_t) ((2 * ef + ch - 1) / ch);
+	p->set_stride = 3 * P;
+	p->off_res = (uint32_t) *off;  *off += round_up((size_t) p->wide_nr * 8, 16);
+	p->off_cand = (uint32_t) *off; *off += round_up((size_t) p->wide_nc * 8, 16);
+	if (3 * P * 8 > SET_BUDGET_BYTES)
+		return fail(HNSW_GPU_ERR_NOMEM, "ef %zu needs %zu bytes of scratch per query slot (more than the %zu-byte budget)", ef, 3 * P * 8, SET_BUDGET_BYTES);
+	return HNSW_GPU_OK;
+}
+
+// beam form: [query | visited set (overlaid by the emit step's tie scratch) | newid | newdist]
+static void carve_beam(const SearchFacts &f, SearchPlan *p, size_t *off)
+{
+	const size_t ef = p->ef;
+	const size_t fixed = *off + 64 * 4 + 128 * 4 + (p->team_wanted ? sizeof(TeamCtl) : 0);   // (+ the wave's control block behind the regions)
+	// Rows of >= 1.25 KiB make the traversal HBM-bound, and there the LDS set pays (no L2
+	// atomics, ~10 % less HBM traffic; measured 5.4 -> 7.5 TB/s at 768 dims) at 8 waves per CU.
+	// Narrow rows are latency-bound and want 16-20 waves per CU: the beam form gives them a bucketed set of
+	// 3456-4096 16-bit tags (ids whose bucket is full go to the bitmap)
+	// (profiles/r1g_visited_set_by_dim.txt, profiles/r1i_beam_form.md, profiles/r2m_*).
+	// (rows of up to 128 floats in the beam form with ef <= 128, L2 / Manhattan, launches that will not run as
+	// teams: 5 waves/SIMD with the 8-rows-per-pass shape — measured +6-10 % over 4 waves, profiles/r2m_*)
+	const bool wide = f.stride > 320;
+	size_t want_waves = wide ? 8 : (p->narrow5 ? 20 : 16);
+	uint32_t hcap = wide ? 4096 : 2048;
+	if (knob_is_set(K_HASH_ENTRIES)) hcap = (uint32_t) knob(K_HASH_ENTRIES, 0);
+	// emit scratch: [keys | labels]; the beam form sorts up to 64 * ureg survivors, the slots of its accepted set (ties at the bound)
+	const size_t nkeys = (size_t) 64 * p->ureg;
+	const size_t emit = round_up(nkeys * 8, 16) + round_up(ef * 8, 16);
+	// hcap/4 buckets (any count, 128-byte steps of LDS) of eight 16-bit tags (device_search.h, "bucketed");
+	// tag = id / buckets + 1 must fit 16 bits and the 38-bit reciprocal must be exact (ids below 2^28), else the
+	// kernel runs on the HBM bitmap alone
+	hcap = std::min<uint32_t>(hcap, 4096);
+	while (hcap >= 512 && want_waves * (fixed + std::max<size_t>(hcap * 4, emit)) > LDS_PER_CU) hcap -= 128;
+	hcap &= ~31u;
+	if (hcap < 512 || (uint64_t) f.cap > (uint64_t) 65535 * (hcap / 4) || f.cap >= (1u << 28)) hcap = 0;
+	p->hmagic = hcap ? (uint32_t) ((((uint64_t) 1 << 38) + hcap / 4 - 1) / (hcap / 4)) : 0;
+	p->hcap = hcap;
+	p->off_hash = (uint32_t) *off;
+	p->off_res = (uint32_t) *off;
+	p->off_cand = (uint32_t) (*off + round_up(nkeys * 8, 16));
+	*off += round_up(std::max<size_t>((size_t) hcap * 4, emit), 16);
+}
+
+// generic form: [res ef+1 | cand 2ef+1] keys per wave — in LDS while at least HNSW_GPU_LDS_SET_MIN_WAVES
+// (default 4) waves per CU fit, otherwise in a per-slot HBM area (any ef)
+static void carve_generic(SearchPlan *p, size_t *off)
+{
+	const size_t ef = p->ef;
+	const size_t set_bytes = round_up((ef + 1) * 8, 16) + round_up((2 * ef + 1) * 8, 16);
+	const size_t min_waves = knob(K_LDS_SET_MIN_WAVES, 0) > 0 ? (size_t) knob(K_LDS_SET_MIN_WAVES, 0) : 4;
+	if (min_waves * (*off + set_bytes + 64 * 4 + 128 * 4) > LDS_PER_CU)
 	{
-		// the query image covers round_up(blocks, KB) * 2 chunk-steps of the reduced shape (the same as the fp32 shape's for every width)
-		const uint32_t nblk = rows16_blocks(a.kiters), kb = rows16_shape_kb(shape_index(a.kiters));
-		a.qpad_floats = std::max<uint32_t>(a.qpad_floats, (nblk + kb - 1) / kb * kb * 128);
-		a.rows16 = (const uint4 *) ix->rows16; a.nblk = nblk; a.rstride4 = ix->rows16_bytes / 16;
-	}
-	size_t off = (size_t) a.qpad_floats * 4;
-	// reference-order arithmetic: the per-wave stage of its transposed accumulation sits right behind the query image (device_dist.h, score_rows_ref)
-	if (reforder) off += (size_t) 8 * (func_code == F_COSINE_REF ? 2 : 1) * REF_STAGE_ROW * 4;
-	if (rreg == 3)
-	{
-		// wide-beam form: both sets in the slot's HBM area [res: P | cand: 2P], P = the power of two >= ef (the output sort is a
-		// bitonic network); per-chunk extremes in LDS: chunks of >= 1024 keys, at most 1024 chunks of candidates
-		size_t P = 2;
-		while (P < ef) P <<= 1;
-		size_t ch = 1024;
-		while ((2 * ef + ch - 1) / ch > 1024) ch <<= 1;
-		a.wide_p = (uint32_t) P; a.wide_ch = (uint32_t) ch;
-		a.wide_nr = (uint32_t) ((ef + ch - 1) / ch); a.wide_nc = (uint32_t) ((2 * ef + ch - 1) / ch);
-		a.set_stride = 3 * P;
-		a.off_res = (uint32_t) off;  off += round_up((size_t) a.wide_nr * 8, 16);
-		a.off_cand = (uint32_t) off; off += round_up((size_t) a.wide_nc * 8, 16);
-		if (3 * P * 8 > SET_BUDGET_BYTES)
-			return fail(HNSW_GPU_ERR_NOMEM, "ef %zu needs %zu bytes of scratch per query slot (more than the %zu-byte budget)", ef, 3 * P * 8, SET_BUDGET_BYTES);
-	}
-	else if (rreg < 0)
-	{
-		// [query | visited set (overlaid by the emit step's tie scratch) | newid | newdist]
-		const size_t fixed = off + 64 * 4 + 128 * 4 + (team_wanted ? sizeof(TeamCtl) : 0);   // (+ the wave's control block behind the regions)
-		// Rows of >= 1.25 KiB make the traversal HBM-bound, and there the LDS set pays (no L2
-		// atomics, ~10 % less HBM traffic; measured 5.4 -> 7.5 TB/s at 768 dims) at 8 waves per CU.
-		// Narrow rows are latency-bound and want 16-20 waves per CU: the beam form gives them a bucketed set of
-		// 3456-4096 16-bit tags (ids whose bucket is full go to the bitmap)
-		// (profiles/r1g_visited_set_by_dim.txt, profiles/r1i_beam_form.md, profiles/r2m_*).
-		// (rows of up to 128 floats in the beam form with ef <= 128, L2 / Manhattan, launches that will not run as
-		// teams: 5 waves/SIMD with the 8-rows-per-pass shape — measured +6-10 % over 4 waves, profiles/r2m_*)
-		const bool wide = ix->stride > 320;
-		size_t want_waves = wide ? 8 : (narrow5 ? 20 : 16);
-		uint32_t hcap = wide ? 4096 : 2048;
-		if (knob_is_set(K_HASH_ENTRIES)) hcap = (uint32_t) knob(K_HASH_ENTRIES, 0);
-		// emit scratch: [keys | labels]; the beam form sorts up to `ucap` survivors (ties at the bound)
-		const size_t nkeys = ucap;
-		const size_t emit = round_up(nkeys * 8, 16) + round_up(ef * 8, 16);
-		// hcap/4 buckets (any count, 128-byte steps of LDS) of eight 16-bit tags (device_search.h, "bucketed");
-		// tag = id / buckets + 1 must fit 16 bits and the 38-bit reciprocal must be exact (ids below 2^28), else the
-		// kernel runs on the HBM bitmap alone
-		hcap = std::min<uint32_t>(hcap, 4096);
-		while (hcap >= 512 && want_waves * (fixed + std::max<size_t>(hcap * 4, emit)) > LDS_PER_CU) hcap -= 128;
-		hcap &= ~31u;
-		if (hcap < 512 || (uint64_t) ix->cap > (uint64_t) 65535 * (hcap / 4) || ix->cap >= (1u << 28)) hcap = 0;
-		a.hmagic = hcap ? (uint32_t) ((((uint64_t) 1 << 38) + hcap / 4 - 1) / (hcap / 4)) : 0;
-		a.hcap = hcap;
-		a.off_hash = (uint32_t) off;
-		a.off_res = (uint32_t) off;
-		a.off_cand = (uint32_t) (off + round_up(nkeys * 8, 16));
-		off += round_up(std::max<size_t>((size_t) hcap * 4, emit), 16);
+		p->form = SearchForm::GenericHbm;
+		p->off_res = 0;
+		p->off_cand = (uint32_t) (ef + 1);                     // in keys, inside the slot's area
+		p->set_stride = 3 * ef + 2;
 	}
 	else
 	{
-		// generic form: [res ef+1 | cand 2ef+1] keys per wave — in LDS while at least HNSW_GPU_LDS_SET_MIN_WAVES
-		// (default 4) waves per CU fit, otherwise in a per-slot HBM area (any ef)
-		const size_t set_bytes = round_up((ef + 1) * 8, 16) + round_up((2 * ef + 1) * 8, 16);
-		const size_t min_waves = knob(K_LDS_SET_MIN_WAVES, 0) > 0 ? (size_t) knob(K_LDS_SET_MIN_WAVES, 0) : 4;
-		if (min_waves * (off + set_bytes + 64 * 4 + 128 * 4) > LDS_PER_CU)
-		{
-			rreg = 1;
-			a.off_res = 0;
-			a.off_cand = (uint32_t) (ef + 1);                     // in keys, inside the slot's area
-			a.set_stride = 3 * ef + 2;
-		}
-		else
-		{
-			a.off_res = (uint32_t) off;     off += round_up((ef + 1) * 8, 16);
-			a.off_cand = (uint32_t) off;    off += round_up((2 * ef + 1) * 8, 16);
-		}
+		p->off_res = (uint32_t) *off;     *off += round_up((ef + 1) * 8, 16);
+		p->off_cand = (uint32_t) *off;    *off += round_up((2 * ef + 1) * 8, 16);
 	}
-	a.off_newid = (uint32_t) off;   off += 64 * 4;
-	a.off_newdist = (uint32_t) off; off += 128 * 4;      // sums + (cosine) |x|^2
-	a.wave_bytes = (uint32_t) round_up(off, 16);
-	if (a.wave_bytes > LDS_PER_CU)
-		return fail(HNSW_GPU_ERR_ARG, "ef=%zu dim=%zu needs %u bytes of LDS per query (> %zu)", ef, ix->meta.dim,
-					a.wave_bytes, LDS_PER_CU);
-	uint32_t wpb = 4;
-	while (wpb > 1 && (size_t) wpb * a.wave_bytes > 64 * 1024) wpb >>= 1;
-	// Team form of the beam kernel (device_search.h, "Team form"): waves of a block that have no query (left) help a
-	// sibling's walk with packages prepared in their own, otherwise idle LDS regions.  Measured at 1M rows
-	// (profiles/r2_team_form.txt): rows wider than 320 floats gain at every launch size (one query 0.68 -> 0.47 ms,
-	// 256 queries -24 %, 10 000 -3 %, 40 000 -0.7 %: only the tail of a big launch has idle waves); narrow rows gain
-	// up to ~256 queries per launch and lose beyond (the larger kernel costs the 4-waves-per-SIMD steady state 10-16 %).
-	// HNSW_GPU_TEAM=0/1 forces it off/on, HNSW_GPU_TEAM_MAX_NQ moves the narrow-row threshold, HNSW_GPU_TEAM_WPB the
-	// waves per block (default 8 when the LDS of a block allows).
-	bool team = false;
-	if (rreg < 0)
+}
+
+// team form, a donated region: [accepted-set copy | expanded bits | miss ids | package headers | packages | memo], all below
+// off_newid.  As many package slots as leave a useful memo: an element packaged while it was 6th in line may
+// be popped dozens of hops later, and a direct-mapped slot that was reused by then is a lost package.
+// false = not even 4 package slots leave a memo of 128 entries: no team
+static bool carve_team(const SearchFacts &f, SearchPlan *p)
+{
+	const size_t pub = (size_t) 64 * p->ureg * 8;                        // 64*UREG keys
+	uint32_t lcs = 32;
+	size_t o_ex = pub, o_miss = o_ex + 256, o_tag = round_up(o_miss + 256, 8), o_state = 0, o_links = 0, o_dc = 0, dccap = 0;
+	for (; lcs >= 4; lcs >>= 1)
 	{
-		const size_t pub = (size_t) 64 * ucap / 64 * 8;                 // 64*UREG keys
-		// a donated region: [accepted-set copy | expanded bits | miss ids | package headers | packages | memo], all below
-		// off_newid.  As many package slots as leave a useful memo: an element packaged while it was 6th in line may
-		// be popped dozens of hops later, and a direct-mapped slot that was reused by then is a lost package.
-		uint32_t lcs = 32;
-		size_t o_ex = pub, o_miss = o_ex + 256, o_tag = round_up(o_miss + 256, 8), o_state = 0, o_links = 0, o_dc = 0, dccap = 0;
-		for (; lcs >= 4; lcs >>= 1)
+		o_state = o_tag; o_links = o_tag + lcs * 8;                          // headers: lcs x u64; packages: lcs x lstride x u64
+		o_dc = round_up(o_links + (size_t) lcs * f.lstride * 8, 16);
+		const size_t want = lcs >= 16 ? 512 : (lcs == 8 ? 256 : 128);         // memo entries this many slots must leave
+		dccap = 0;
+		if (o_dc + want * 8 <= p->off_newid)
 		{
-			o_state = o_tag; o_links = o_tag + lcs * 8;                          // headers: lcs x u64; packages: lcs x lstride x u64
-			o_dc = round_up(o_links + (size_t) lcs * a.lstride * 8, 16);
-			const size_t want = lcs >= 16 ? 512 : (lcs == 8 ? 256 : 128);         // memo entries this many slots must leave
-			dccap = 0;
-			if (o_dc + want * 8 <= a.off_newid)
-			{
-				dccap = want;
-				while (o_dc + dccap * 2 * 8 <= a.off_newid && dccap < 2048) dccap *= 2;
-				break;
-			}
-		}
-		if (dccap >= 128 && team_wanted)
-		{
-			team = true;
-			a.tm_off_ex = (uint32_t) o_ex; a.tm_off_miss = (uint32_t) o_miss; a.tm_off_lctag = (uint32_t) o_tag;
-			a.tm_off_lcstate = (uint32_t) o_state; a.tm_off_lclinks = (uint32_t) o_links; a.tm_lcslots = lcs;
-			a.tm_off_dc = (uint32_t) o_dc; a.tm_dccap = (uint32_t) dccap;
-			{
-				// helpers of rank < tm_spec prepare packages ahead of the walk; the others score slices of its many-row hops
-				// (device_search.h, banner at TeamCtl).  Measured at 1M rows (profiles/r3a_slice_helpers.txt): 768 dims, 5 of
-				// 7 helpers speculating: one query 0.470 -> 0.438 ms, 16 queries -3.4 %, 256 -4.1 %, 1024 -3.4 %, 10 000 -0.5 %,
-				// 40 000 -0.2 %; 3: 0.452; 0 (nobody speculates): 0.618.  128 dims: a hop rarely has more rows than one pass of 16,
-				// slices lose 1-2 %, so narrow rows let every helper speculate.  HNSW_GPU_TEAM_SPEC overrides (8 = all speculate).
-				a.tm_spec = knob_is_set(K_TEAM_SPEC) ? (uint32_t) std::max<long long>(0, knob(K_TEAM_SPEC, 0)) : (ix->stride > 320 ? 5u : 8u);
-			}
-			int maxlds = 64 * 1024;
-			(void) hipDeviceGetAttribute(&maxlds, hipDeviceAttributeMaxSharedMemoryPerBlock, ix->device);
-			uint32_t want = knob(K_TEAM_WPB, 0) > 0 ? (uint32_t) knob(K_TEAM_WPB, 0) : 8u;
-			want = std::min(want, 8u);
-			wpb = std::max<uint32_t>(1, (uint32_t) std::min<size_t>(want, ((size_t) maxlds - 8 * sizeof(TeamCtl)) / a.wave_bytes));
-			if (wpb < 2) team = false;
+			dccap = want;
+			while (o_dc + dccap * 2 * 8 <= p->off_newid && dccap < 2048) dccap *= 2;
+			break;
 		}
 	}
-	if (!team) { wpb = 4; while (wpb > 1 && (size_t) wpb * a.wave_bytes > 64 * 1024) wpb >>= 1; }
+	if (dccap < 128) return false;
+	p->tm_off_ex = (uint32_t) o_ex; p->tm_off_miss = (uint32_t) o_miss; p->tm_off_lctag = (uint32_t) o_tag;
+	p->tm_off_lcstate = (uint32_t) o_state; p->tm_off_lclinks = (uint32_t) o_links; p->tm_lcslots = lcs;
+	p->tm_off_dc = (uint32_t) o_dc; p->tm_dccap = (uint32_t) dccap;
+	// helpers of rank < tm_spec prepare packages ahead of the walk; the others score slices of its many-row hops
+	// (device_search.h, banner at TeamCtl).  Measured at 1M rows (profiles/r3a_slice_helpers.txt): 768 dims, 5 of
+	// 7 helpers speculating: one query 0.470 -> 0.438 ms, 16 queries -3.4 %, 256 -4.1 %, 1024 -3.4 %, 10 000 -0.5 %,
+	// 40 000 -0.2 %; 3: 0.452; 0 (nobody speculates): 0.618.  128 dims: a hop rarely has more rows than one pass of 16,
+	// slices lose 1-2 %, so narrow rows let every helper speculate.  HNSW_GPU_TEAM_SPEC overrides (8 = all speculate).
+	p->tm_spec = knob_is_set(K_TEAM_SPEC) ? (uint32_t) std::max<long long>(0, knob(K_TEAM_SPEC, 0)) : (f.stride > 320 ? 5u : 8u);
+	return true;
+}
+
+// The block: its waves (computed here, once), whether it is a team for good, where its control blocks sit and its dynamic LDS.
+// Team form of the beam kernel (device_search.h, "Team form"): waves of a block that have no query (left) help a
+// sibling's walk with packages prepared in their own, otherwise idle LDS regions.  Measured at 1M rows
+// (profiles/r2_team_form.txt): rows wider than 320 floats gain at every launch size (one query 0.68 -> 0.47 ms,
+// 256 queries -24 %, 10 000 -3 %, 40 000 -0.7 %: only the tail of a big launch has idle waves); narrow rows gain
+// up to ~256 queries per launch and lose beyond (the larger kernel costs the 4-waves-per-SIMD steady state 10-16 %).
+// HNSW_GPU_TEAM=0/1 forces it off/on, HNSW_GPU_TEAM_MAX_NQ moves the narrow-row threshold, HNSW_GPU_TEAM_WPB the
+// waves per block (default 8 when the LDS of a block allows).
+static void plan_block(const SearchFacts &f, const SearchLaunch &r, SearchPlan *p)
+{
+	uint32_t wpb = 4;
+	while (wpb > 1 && (size_t) wpb * p->wave_bytes > 64 * 1024) wpb >>= 1;
+	if (p->team_wanted && carve_team(f, p))
+	{
+		const uint32_t want = std::min(knob(K_TEAM_WPB, 0) > 0 ? (uint32_t) knob(K_TEAM_WPB, 0) : 8u, 8u);
+		const uint32_t team_wpb = std::max<uint32_t>(1, (uint32_t) std::min<size_t>(want, (f.max_lds - 8 * sizeof(TeamCtl)) / p->wave_bytes));
+		if (team_wpb >= 2) { p->team = true; wpb = team_wpb; }
+	}
 	// (test knob: waves per block of the narrow-row one-wave launches.  A block's LDS and wave slots are released when its LAST wave
 	// ends, so with 4-wave blocks a draining launch holds resources a following launch could use — profiles/r4c_*; 1 = every wave is a
 	// block of its own.  Measured round 6, profiles/r6d_*.)
-	if (!team && narrow5 && knob(K_NARROW_WPB, 0) > 0) wpb = (uint32_t) std::min<long long>(4, knob(K_NARROW_WPB, 0));
-	a.off_ctl = (uint32_t) ((size_t) wpb * a.wave_bytes);
-	const size_t lds = (size_t) wpb * a.wave_bytes + (team ? wpb * sizeof(TeamCtl) : 0);
-	const bool lean = narrow5 && !team && !w->pops_next && !w->evals_next && !w->times_next && knob(K_LEAN, 1) != 0;
-	search_kernel_t kern = rows ? pick_rows16_kernel(func_code, a.kiters, rreg, rows) : pick_search_kernel(func_code, a.kiters, rreg, team, narrow5, lean);
-	if (!kern) return fail(HNSW_GPU_ERR_INTERNAL, "no kernel for this configuration");
+	if (!p->team && p->narrow5 && knob(K_NARROW_WPB, 0) > 0) wpb = (uint32_t) std::min<long long>(4, knob(K_NARROW_WPB, 0));
+	p->wpb = wpb;
+	p->off_ctl = (uint32_t) ((size_t) wpb * p->wave_bytes);
+	p->lds = (size_t) wpb * p->wave_bytes + (p->team ? wpb * sizeof(TeamCtl) : 0);
+	p->lean = p->narrow5 && !p->team && !r.pops && !r.evals && !r.times && knob(K_LEAN, 1) != 0;
+}
+
+int plan_search(const SearchFacts &f, const SearchLaunch &r, SearchPlan *p)
+{
+	*p = SearchPlan();
+	// A beam wider than the index behaves exactly like a beam of the index size (nothing is ever evicted,
+	// the walk ends when the candidates run out), so the scan's efSearch doubling (embedding.c:334) can go
+	// as far as it likes; the output arrays keep the caller's ef as their row stride.
+	p->ef = std::min(r.ef, std::max<size_t>(f.n, 1));
+	p->rows = r.rows;
+	p->kiters = (f.stride / 4 + 15) / 16;
+	if (int rc = plan_form(f, r, p)) return rc;
+	p->qpad_floats = (uint32_t) round_up(p->kiters, shape_kb(shape_index(p->kiters))) * 64;
+	if (r.rows)
 	{
-		static const char *const shapes[4] = { "Shape2x4", "Shape4x2", "Shape8x2", "Shape12x2" };
-		const char *shp = shapes[shape_index(a.kiters)];
-		if (narrow5 && !team) shp = "Shape2x2";
-		static const char *const rshapes[4] = { "1, 4, 4", "2, 4, 4", "4, 2, 4", "6, 2, 2" };
-		if (rows) snprintf(w->kname, sizeof(w->kname), "pgemb::hnsw_search_kernel_beam<%d, pgemb::ShapeR16<%d, %s>, %d, false, false>", func_code, rows, rshapes[shape_index(a.kiters)], -rreg);
-		else if (rreg < 0) snprintf(w->kname, sizeof(w->kname), "pgemb::hnsw_search_kernel_beam<%d, pgemb::%s, %d, %s, %s>", func_code, shp, -rreg, team ? "true" : "false", lean ? "true" : "false");
-		else if (rreg == 3) snprintf(w->kname, sizeof(w->kname), "pgemb::hnsw_search_kernel_wide<%d, pgemb::%s>", (int) ix->meta.dist_func, shp);
-		else snprintf(w->kname, sizeof(w->kname), "pgemb::hnsw_search_kernel_lds<%d, pgemb::%s, %s>", (int) ix->meta.dist_func, shp, rreg == 1 ? "true" : "false");
+		// the query image covers round_up(blocks, KB) * 2 chunk-steps of the reduced shape (the same as the fp32 shape's for every width)
+		const uint32_t nblk = rows16_blocks(p->kiters), kb = rows16_shape_kb(shape_index(p->kiters));
+		p->qpad_floats = std::max<uint32_t>(p->qpad_floats, (nblk + kb - 1) / kb * kb * 128);
+		p->nblk = nblk; p->rstride4 = f.rows16_bytes / 16;
 	}
-	if (lds > 48 * 1024)
-		HIPCHK(hipFuncSetAttribute((const void *) kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
-	int per_cu = 0;
-	HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, (int) (wpb * 64), lds));
+	size_t off = (size_t) p->qpad_floats * 4;
+	// reference-order arithmetic: the per-wave stage of its transposed accumulation sits right behind the query image (device_dist.h, score_rows_ref)
+	if (p->reforder) off += (size_t) 8 * (p->func_code == F_COSINE_REF ? 2 : 1) * REF_STAGE_ROW * 4;
+	if (p->form == SearchForm::Wide) { if (int rc = carve_wide(p, &off)) return rc; }
+	else if (p->form == SearchForm::Beam) carve_beam(f, p, &off);
+	else carve_generic(p, &off);
+	p->off_newid = (uint32_t) off;   off += 64 * 4;
+	p->off_newdist = (uint32_t) off; off += 128 * 4;      // sums + (cosine) |x|^2
+	p->wave_bytes = (uint32_t) round_up(off, 16);
+	if (p->wave_bytes > LDS_PER_CU)
+		return fail(HNSW_GPU_ERR_ARG, "ef=%zu dim=%zu needs %u bytes of LDS per query (> %zu)", p->ef, f.dim, p->wave_bytes, LDS_PER_CU);
+	plan_block(f, r, p);
+	if (p->stream && !p->team) return fail(HNSW_GPU_ERR_ARG, "a stream needs the team form of the beam kernel (ef <= 256, or <= 512 on wide rows)");
+	// locality order: the beam kernel's plain launches of a large batch
+	p->ordered = r.order && p->form == SearchForm::Beam && !p->stream && f.n > 0 && knob(K_LOCALITY, 1) != 0 &&
+				 r.nq >= (size_t) std::max<long long>(1, knob(K_LOCALITY_MIN_NQ, (long long) ORDER_MIN_NQ));
+	return HNSW_GPU_OK;
+}
+
+// ------------------------------------------------------------------------------------
+// the launch: geometry, workspace, arguments, order
+// ------------------------------------------------------------------------------------
+static inline size_t vis_words_of(size_t cap) { return std::max<size_t>(1, (cap + 31) / 32); }   // by capacity: stable while the index grows
+
+// Blocks, walking waves per block and workspace slots: from the plan and the occupancy query's blocks per CU.
+static void plan_geometry(const SearchFacts &f, const SearchLaunch &r, uint32_t walkers_hint, int per_cu, SearchPlan *p)
+{
 	if (per_cu < 1) per_cu = 1;
 	if (knob(K_BLOCKS_PER_CU, 0) > 0) per_cu = std::min(per_cu, (int) knob(K_BLOCKS_PER_CU, 0));
-	size_t blocks = std::min<size_t>((nq + wpb - 1) / wpb, (size_t) per_cu * ix->num_cu);
-	a.team_mains = wpb;
-	if (team && nq < (size_t) per_cu * ix->num_cu * wpb)
+	const size_t resident = (size_t) per_cu * f.num_cu, nq = r.nq;
+	const uint32_t wpb = p->wpb;
+	size_t blocks = std::min<size_t>((nq + wpb - 1) / wpb, resident);
+	p->team_mains = wpb;
+	if (p->team && nq < resident * wpb)
 	{
 		// fewer queries than resident waves: spread them over the blocks, the other waves of a block start as helpers
-		blocks = std::min<size_t>(nq, (size_t) per_cu * ix->num_cu);
-		a.team_mains = (uint32_t) std::min<size_t>(wpb, (nq + blocks - 1) / blocks);
+		blocks = std::min<size_t>(nq, resident);
+		p->team_mains = (uint32_t) std::min<size_t>(wpb, (nq + blocks - 1) / blocks);
 		// ... unless the caller knows better: a host that keeps SEVERAL small launches in flight (the batching server's lanes) says
 		// how many waves of a block should walk — one walk per 8-wave block is the latency shape of a lone launch; six such launches
 		// of 190 queries want 9 000 waves of a device that holds 2 048, i.e. at most 256 walks run at a time however many wait
 		// (profiles/r4d_server_sweep.txt: the server's 0.54 M q/s ceiling is exactly 256 walks of 0.47 ms)
-		if (w->walkers_hint > a.team_mains)
+		if (walkers_hint > p->team_mains)
 		{
-			a.team_mains = std::min<uint32_t>(wpb, w->walkers_hint);
-			blocks = std::min<size_t>((nq + a.team_mains - 1) / a.team_mains, (size_t) per_cu * ix->num_cu);
+			p->team_mains = std::min<uint32_t>(wpb, walkers_hint);
+			blocks = std::min<size_t>((nq + p->team_mains - 1) / p->team_mains, resident);
 		}
 	}
-	if (stream_launch)
+	if (p->stream)
 	{
 		// a resident launch fed by the host (device_search.h, "Stream mode"): exactly the blocks the device holds at once — block 0 is the
 		// doorbell and must be resident for any other block to make progress
-		if (!team) { w->stream_host_next = nullptr; return fail(HNSW_GPU_ERR_ARG, "a stream needs the team form of the beam kernel (ef <= 256, or <= 512 on wide rows)"); }
-		blocks = std::max<size_t>(2, (size_t) per_cu * ix->num_cu);
-		a.team_mains = std::min<uint32_t>(wpb, std::max<uint32_t>(1u, w->stream_walkers_next));
-		a.stream_host = w->stream_host_next; a.stream_dev = w->stream_dev_next; a.stream_ring = w->stream_ring_next;
-		a.stream_light = knob(K_STREAM_LIGHT, 1) != 0 ? 1u : 0u;
-		w->stream_host_next = nullptr; w->stream_dev_next = nullptr;
+		blocks = std::max<size_t>(2, resident);
+		p->team_mains = std::min<uint32_t>(wpb, std::max<uint32_t>(1u, r.stream_walkers));
 	}
 	// (test knob: fewer blocks than the launch would get, so that the waves with queries take SEVERAL each through the
 	// ticket counter while their siblings help — the schedule of a small launch whose other blocks start late,
 	// tests/experiments/team_second_walk_stress.py)
 	if (knob(K_MAX_BLOCKS, 0) > 0) blocks = std::min<size_t>(blocks, (size_t) knob(K_MAX_BLOCKS, 0));
-
-	// workspace: one bitmap + log per resident wave
-	const size_t words = std::max<size_t>(1, (ix->cap + 31) / 32);   // by capacity: stable while the index grows
-	size_t max_slots = std::max<size_t>(wpb, VIS_BUDGET_BYTES / (words * 4));
-	if (rreg == 1 || rreg == 3) max_slots = std::max<size_t>(wpb, std::min(max_slots, SET_BUDGET_BYTES / (a.set_stride * 8)));
+	// one bitmap + log per resident wave, and one set area in the forms that keep their sets in HBM, under the two memory budgets
+	size_t max_slots = std::max<size_t>(wpb, VIS_BUDGET_BYTES / (vis_words_of(f.cap) * 4));
+	if (p->set_stride) max_slots = std::max<size_t>(wpb, std::min(max_slots, SET_BUDGET_BYTES / (p->set_stride * 8)));
 	if (blocks * wpb > max_slots) blocks = std::max<size_t>(1, max_slots / wpb);
-	const size_t slots = blocks * wpb;
+	p->blocks = blocks;
+	p->slots = blocks * wpb;
+}
+
+// The workspace for p.slots resident waves: bitmaps and logs, and the HBM sets of the forms that have them; re-zeroed when the launch
+// before this one was asked to end early.
+static int reserve_workspace(SearchWs *w, const SearchPlan &p, size_t words, hipStream_t stream)
+{
+	const size_t slots = p.slots;
 	const uint32_t logcap = 8192;
 	if (slots > w->vis_slots || words != w->vis_words)
 	{
@@ -417,73 +443,124 @@ int launch_search(hnsw_gpu_index *ix, SearchWs *w, const float *d_queries, size_
 	if (__atomic_load_n(&w->abort_sent, __ATOMIC_SEQ_CST))
 	{
 		// the previous launch of this workspace was asked to end early: its waves left their bitmaps as they were
+		char kname[128];
+		search_kernel_name(w->plan, kname, sizeof(kname));
 		fprintf(stderr, "pg_embedding_amd: the previous search launch of this workspace (%s) was asked to end early (abort word): the queries it did "
-				"not answer have count HNSW_GPU_COUNT_ABORTED; the workspace is re-zeroed\n", w->kname);
+				"not answer have count HNSW_GPU_COUNT_ABORTED; the workspace is re-zeroed\n", kname);
 		HIPCHK(hipStreamSynchronize(stream));
 		if (stream) HIPCHK(hipStreamSynchronize(nullptr));
 		if (w->vis) HIPCHK(hipMemset(w->vis, 0, w->vis_slots * w->vis_words * 4));
 		__atomic_store_n(w->abort_host, 0u, __ATOMIC_SEQ_CST);
 		__atomic_store_n(&w->abort_sent, 0, __ATOMIC_SEQ_CST);
 	}
+	const size_t keys = slots * p.set_stride;
+	if (keys > w->set_keys)
+	{
+		if (w->sets) (void) hipFree(w->sets);
+		w->sets = nullptr; w->set_keys = 0;
+		HIPCHK(hipMalloc(&w->sets, keys * 8));
+		w->set_keys = keys;
+	}
+	return HNSW_GPU_OK;
+}
+
+// the kernel's arguments: from the index, the request, the plan and the reserved workspace
+static SearchArgs search_args(const hnsw_gpu_index *ix, const SearchWs *w, const SearchLaunch &r, const SearchPlan &p)
+{
+	SearchArgs a;
+	memset(&a, 0, sizeof(a));
+	a.vec = ix->vec; a.links = ix->links; a.labels = ix->labels;
+	a.n = (uint32_t) ix->n; a.dim = (uint32_t) ix->meta.dim; a.stride = ix->stride;
+	a.nchunks = ix->stride / 4; a.kiters = p.kiters;
+	a.maxM = (uint32_t) ix->meta.maxM; a.lstride = ix->lstride; a.entry = ix->meta.enterpoint_node;
+	a.queries = r.queries; a.q_stride = (uint32_t) r.q_stride; a.nq = (uint32_t) r.nq; a.ef = (uint32_t) p.ef; a.ccap = (uint32_t) (2 * p.ef);
+	a.out_stride = (uint32_t) r.ef;
+	a.out_labels = r.labels; a.out_idx = r.idx; a.out_dists = r.dists; a.out_counts = r.counts; a.out_stats = r.stats;
+	a.mode = r.mode;
+	a.done = r.done;
+	a.out_pops = r.pops; a.pops_cap = r.pops_cap;
+	a.out_evals = r.evals; a.evals_cap = r.evals_cap; a.out_times = r.times;
+	if (p.rows) { a.rows16 = (const uint4 *) ix->rows16; a.nblk = p.nblk; a.rstride4 = p.rstride4; }
+	a.qpad_floats = p.qpad_floats; a.off_res = p.off_res; a.off_cand = p.off_cand; a.off_newid = p.off_newid; a.off_newdist = p.off_newdist;
+	a.wave_bytes = p.wave_bytes; a.off_hash = p.off_hash; a.hcap = p.hcap; a.hmagic = p.hmagic;
+	a.set_stride = p.set_stride; a.wide_p = p.wide_p; a.wide_ch = p.wide_ch; a.wide_nr = p.wide_nr; a.wide_nc = p.wide_nc;
+	a.team_mains = p.team_mains; a.off_ctl = p.off_ctl;
+	a.tm_off_ex = p.tm_off_ex; a.tm_off_miss = p.tm_off_miss; a.tm_off_lctag = p.tm_off_lctag; a.tm_off_lcstate = p.tm_off_lcstate;
+	a.tm_off_lclinks = p.tm_off_lclinks; a.tm_lcslots = p.tm_lcslots; a.tm_off_dc = p.tm_off_dc; a.tm_dccap = p.tm_dccap; a.tm_spec = p.tm_spec;
+	if (p.stream)
+	{
+		a.stream_host = r.stream_host; a.stream_dev = r.stream_dev; a.stream_ring = r.stream_ring;
+		a.stream_light = knob(K_STREAM_LIGHT, 1) != 0 ? 1u : 0u;
+	}
 	a.health = w->health; a.abort_word = w->abort_host;
 	// a wave reads the abort word (pinned host memory: a read across the host link) at the top of every 2^k-th query, k = 4 (test knob:
 	// 0 = every query, rounds 1-5 — the read rate of a narrow-row launch then depends on where the host serves that page from, banner at
 	// abort_requested in device_search.h)
 	a.abort_mask = (1u << (uint32_t) std::min<long long>(16, std::max<long long>(0, knob(K_ABORT_POLL_LOG2, 4)))) - 1u;
-	a.vis = w->vis; a.vis_words = words; a.vlog = w->vlog; a.logcap = w->logcap;
-	if (rreg == 1 || rreg == 3)
-	{
-		const size_t keys = slots * a.set_stride;
-		if (keys > w->set_keys)
-		{
-			if (w->sets) (void) hipFree(w->sets);
-			w->sets = nullptr; w->set_keys = 0;
-			HIPCHK(hipMalloc(&w->sets, keys * 8));
-			w->set_keys = keys;
-		}
-		a.set_scratch = w->sets;
-	}
+	a.vis = w->vis; a.vis_words = w->vis_words; a.vlog = w->vlog; a.logcap = w->logcap;
+	if (p.set_stride) a.set_scratch = w->sets;
 	a.ticket = w->ticket;
+	return a;
+}
+
+int launch_search(hnsw_gpu_index *ix, SearchWs *w, const SearchLaunch &r)
+{
+	std::unique_lock<std::recursive_mutex> lock_;
+	if (ix) lock_ = std::unique_lock<std::recursive_mutex>(ix->mu);
+	if (!ix) return fail(HNSW_GPU_ERR_ARG, "index is NULL");
+	if (r.nq == 0) return HNSW_GPU_OK;
+	if (!r.queries || !r.counts || (r.mode == 0 && !r.labels) || (r.mode == 1 && !r.idx))
+		return fail(HNSW_GPU_ERR_ARG, "NULL buffer");
+	if (r.ef == 0 || r.ef >= 0xFFFFFFFFull) return fail(HNSW_GPU_ERR_ARG, "ef %zu out of range", r.ef);
+	if (r.nq >= 0xFFFFFFFFull) return fail(HNSW_GPU_ERR_ARG, "too many queries");
+	HIPCHK(hipSetDevice(ix->device));
+	if (ix->n > 0 && ix->meta.enterpoint_node >= (uint32_t) ix->n)
+		return fail(HNSW_GPU_ERR_ARG, "enterpoint_node %u >= count %u", ix->meta.enterpoint_node, (uint32_t) ix->n);
+	knobs_init();
+	const SearchFacts f = facts_of(ix);
+	SearchPlan p;
+	if (int rc = plan_search(f, r, &p)) return rc;            // every refusal of a request: before anything is allocated or launched
+	const search_kernel_t kern = search_kernel_of(p);
+	if (!kern) return fail(HNSW_GPU_ERR_INTERNAL, "no kernel for this configuration");
+	if (p.lds > 48 * 1024)
+		HIPCHK(hipFuncSetAttribute((const void *) kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int) p.lds));
+	int per_cu = 0;
+	HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, (int) (p.wpb * 64), p.lds));
+	plan_geometry(f, r, w->walkers_hint, per_cu, &p);
+	if (int rc = reserve_workspace(w, p, vis_words_of(ix->cap), r.stream)) return rc;
+	SearchArgs a = search_args(ix, w, r, p);
 #if defined(HNSW_HOP_STAMPS) || defined(HNSW_TEAM_COUNTERS)      // diagnostic builds (build.py variant <tag> HNSW_HOP_STAMPS / HNSW_TEAM_COUNTERS): 16 launch-wide counters
 	if (!w->team_dbg) HIPCHK(hipMalloc(&w->team_dbg, 64));
-	HIPCHK(hipMemsetAsync(w->team_dbg, 0, 64, stream));
+	HIPCHK(hipMemsetAsync(w->team_dbg, 0, 64, r.stream));
 	a.team_dbg = w->team_dbg;
 #endif
-	a.done = w->done_next;
-	w->done_next = nullptr;
-	a.out_pops = w->pops_next; a.pops_cap = w->pops_cap_next;
-	w->pops_next = nullptr; w->pops_cap_next = 0;
-	a.out_evals = w->evals_next; a.evals_cap = w->evals_cap_next; a.out_times = w->times_next;
-	w->evals_next = nullptr; w->evals_cap_next = 0; w->times_next = nullptr;
-	// locality order: the beam kernel's plain launches of a large batch (the key and the sort run inside the launch's event pair)
-	const bool want_order = order && rreg < 0 && !stream_launch && a.n > 0 && knob(K_LOCALITY, 1) != 0 &&
-		nq >= (size_t) std::max<long long>(1, knob(K_LOCALITY_MIN_NQ, (long long) ORDER_MIN_NQ));
 	// (the global ticket and the per-XCD counters; an ordered launch's key kernel zeroes them)
-	if (!want_order) HIPCHK(hipMemsetAsync(w->ticket, 0, XCD_TICKET_BYTES, stream));
+	if (!p.ordered) HIPCHK(hipMemsetAsync(w->ticket, 0, XCD_TICKET_BYTES, r.stream));
 
 	const int evi = (int) (w->launches % SearchWs::EV_RING);
-	HIPCHK(hipEventRecord(w->ev0[evi], stream));
+	HIPCHK(hipEventRecord(w->ev0[evi], r.stream));
 	w->ord_nq = 0; w->ord_evals = nullptr; w->ord_log2c = 0;
-	if (want_order)
+	if (p.ordered)
 	{
-		// (the order is only an optimisation: where it cannot be built — no memory for its buffers — the launch runs in the caller's order)
+		// (the key and the sort run inside the launch's event pair.  The order is only an optimisation: where it cannot be built — no
+		// memory for its buffers — the launch runs in the caller's order)
 		bool zeroed = false;
-		a.perm = build_order(ix, w, d_queries, q_stride, nq, stream, w->ticket, &zeroed);
-		if (!zeroed) HIPCHK(hipMemsetAsync(w->ticket, 0, XCD_TICKET_BYTES, stream));
+		a.perm = build_order(ix, w, r.queries, r.q_stride, r.nq, r.stream, w->ticket, &zeroed);
+		if (!zeroed) HIPCHK(hipMemsetAsync(w->ticket, 0, XCD_TICKET_BYTES, r.stream));
 		if (a.perm)
 		{
-			a.xcd_log2c = xcd_chunk_log2(nq);
-			w->ord_nq = (uint32_t) nq; w->ord_evals = a.out_evals; w->ord_log2c = a.xcd_log2c;
+			a.xcd_log2c = xcd_chunk_log2(r.nq);
+			w->ord_nq = (uint32_t) r.nq; w->ord_evals = a.out_evals; w->ord_log2c = a.xcd_log2c;
 		}
-		else (void) hipGetLastError();
+		else { (void) hipGetLastError(); p.ordered = false; }
 	}
 	// (a stream is resident by design: the library's watchdog does not time it — its host stops it, hnsw_gpu_stream_close)
-	__atomic_store_n(&w->busy_since_ms, stream_launch ? (int64_t) 0 : now_ms(), __ATOMIC_SEQ_CST);
-	hipLaunchKernelGGL(kern, dim3((uint32_t) blocks), dim3(wpb * 64), lds, stream, a);
+	__atomic_store_n(&w->busy_since_ms, p.stream ? (int64_t) 0 : now_ms(), __ATOMIC_SEQ_CST);
+	hipLaunchKernelGGL(kern, dim3((uint32_t) p.blocks), dim3(p.wpb * 64), p.lds, r.stream, a);
 	HIPCHK(hipGetLastError());
-	HIPCHK(hipEventRecord(w->ev1[evi], stream));
+	HIPCHK(hipEventRecord(w->ev1[evi], r.stream));
 	__atomic_store_n(&w->launches, w->launches + 1, __ATOMIC_SEQ_CST);
-	w->last_slots = (uint32_t) slots;
+	w->plan = p;
 	return HNSW_GPU_OK;
 }
 
@@ -513,45 +590,40 @@ extern "C" int hnsw_gpu_search_batch_dev(hnsw_gpu_index *ix, const coord_t *d_qu
 										 label_t *d_labels, dist_t *d_dists, uint32_t *d_counts, uint32_t *d_stats,
 										 void *stream)
 {
-	return launch_search(ix, ix ? &ix->ws : nullptr, d_queries, ix ? ix->meta.dim : 0, nq, ef, 0, d_labels, nullptr, d_dists, d_counts, d_stats, (hipStream_t) stream,
-						 0, true);
+	if (!ix) return fail(HNSW_GPU_ERR_ARG, "index is NULL");
+	return launch_search(ix, &ix->ws, {.queries = d_queries, .q_stride = ix->meta.dim, .nq = nq, .ef = ef, .labels = d_labels, .dists = d_dists, .counts = d_counts,
+									   .stats = d_stats, .stream = (hipStream_t) stream, .order = true});
 }
 
 extern "C" int hnsw_gpu_search_batch_caller_order_dev(hnsw_gpu_index *ix, const coord_t *d_queries, size_t nq, size_t ef,
 													  label_t *d_labels, dist_t *d_dists, uint32_t *d_counts, uint32_t *d_stats,
 													  void *stream)
 {
-	return launch_search(ix, ix ? &ix->ws : nullptr, d_queries, ix ? ix->meta.dim : 0, nq, ef, 0, d_labels, nullptr, d_dists, d_counts, d_stats, (hipStream_t) stream);
+	if (!ix) return fail(HNSW_GPU_ERR_ARG, "index is NULL");
+	return launch_search(ix, &ix->ws, {.queries = d_queries, .q_stride = ix->meta.dim, .nq = nq, .ef = ef, .labels = d_labels, .dists = d_dists, .counts = d_counts,
+									   .stats = d_stats, .stream = (hipStream_t) stream});
 }
 
 extern "C" int hnsw_gpu_search_base_dev(hnsw_gpu_index *ix, const coord_t *d_queries, size_t nq, size_t ef,
 										idx_t *d_idx, dist_t *d_dists, uint32_t *d_counts, uint32_t *d_stats,
 										void *stream)
 {
-	return launch_search(ix, ix ? &ix->ws : nullptr, d_queries, ix ? ix->meta.dim : 0, nq, ef, 1, nullptr, d_idx, d_dists, d_counts, d_stats, (hipStream_t) stream);
+	if (!ix) return fail(HNSW_GPU_ERR_ARG, "index is NULL");
+	return launch_search(ix, &ix->ws, {.queries = d_queries, .q_stride = ix->meta.dim, .nq = nq, .ef = ef, .mode = 1, .idx = d_idx, .dists = d_dists, .counts = d_counts,
+									   .stats = d_stats, .stream = (hipStream_t) stream});
 }
 
 // Reduced-row search (device_rows16.h, device_rerank.h): the walk over the 16-bit copy in base mode into the mirror's scratch, then the
 // exact re-rank against the fp32 rows into the caller's buffers.  Every refusal comes before anything is launched (the outputs are
 // untouched).  d_stats: the walk's evaluations and hops (the re-rank's <= ef row evaluations are not counted); the event pair of
 // hnsw_gpu_last_search_ms spans both kernels.
-// the walk form a reduced search of this ef would take, as launch_search decides it (which refuses the same cases again): 0 = the
-// one-wave beam form has it, else the error code with its message
+// whether the walk of a reduced search of this ef exists, asked of the planner itself before the call allocates or copies anything:
+// 0 = the one-wave beam form has it, else the error code with its message
 static int reduced_form_check(hnsw_gpu_index *ix, int format, size_t ef)
 {
 	knobs_init();
-	const size_t efc = std::min(ef, std::max<size_t>(ix->n, 1));
-	const uint32_t kiters = (ix->stride / 4 + 15) / 16;
-	if (knob(K_REF_ORDER, 0) > 0) return fail(HNSW_GPU_ERR_ARG, "reduced rows: HNSW_GPU_REF_ORDER=1 has no reduced-row kernels");
-	const bool use_beam = knob(K_BEAM, 1) != 0 && ix->cap < 0x80000000ull && knob(K_FORCE_LDS_HEAPS, 0) <= 0;
-	const bool beam16 = efc > 256 && efc <= 512 && (knob_is_set(K_BEAM16) ? knob(K_BEAM16, 0) > 0 : shape_index(kiters) >= 2);
-	if (!use_beam || !(efc <= 256 || beam16))
-		return fail(HNSW_GPU_ERR_ARG, "reduced rows: ef %zu needs a form the reduced-row walk does not have (the beam form: ef <= 256, "
-					"<= 512 on rows wider than 256 floats; not with HNSW_GPU_BEAM=0 or HNSW_GPU_FORCE_LDS_HEAPS=1)", ef);
-	const int rreg = efc <= 64 ? -2 : (efc <= 128 ? -4 : (efc <= 256 ? -8 : -16));
-	if (!pick_rows16_kernel((int) ix->meta.dist_func, kiters, rreg, format))
-		return fail(HNSW_GPU_ERR_ARG, "reduced rows: no kernel for %d set registers at this width", -rreg);
-	return HNSW_GPU_OK;
+	SearchPlan p;
+	return plan_search(facts_of(ix), {.nq = 1, .ef = ef, .mode = 1, .rows = format}, &p);
 }
 
 static int search_batch_reduced(hnsw_gpu_index *ix, int format, const coord_t *d_queries, size_t nq, size_t ef,
@@ -594,7 +666,8 @@ static int search_batch_reduced(hnsw_gpu_index *ix, int format, const coord_t *d
 	}
 	int rc = rows16_sync(ix, s);
 	if (rc) return rc;
-	rc = launch_search(ix, &ix->ws, d_queries, ix->meta.dim, nq, ef, 1, nullptr, ix->rr_cand, nullptr, d_counts, d_stats, s, format, order);
+	rc = launch_search(ix, &ix->ws, {.queries = d_queries, .q_stride = ix->meta.dim, .nq = nq, .ef = ef, .mode = 1, .idx = ix->rr_cand, .counts = d_counts,
+									 .stats = d_stats, .stream = s, .rows = format, .order = order});
 	if (rc) return rc;
 	r.vec = ix->vec; r.labels = ix->labels;
 	r.stride = ix->stride; r.nchunks = nchunks; r.kiters = kiters; r.dim = (uint32_t) ix->meta.dim;
@@ -739,9 +812,7 @@ extern "C" int hnsw_gpu_search_batch(hnsw_gpu_index *ix, const coord_t *queries,
 		volatile uint32_t *hf = (volatile uint32_t *) (h + qb + lb + db + cb);
 		memcpy(hq, queries, nq * dim * 4);
 		for (size_t i = 0; i < nq; i++) hf[i] = 0;
-		ix->ws.done_next = (uint32_t *) hf;
-		rc = launch_search(ix, &ix->ws, hq, dim, nq, ef, 0, hl, nullptr, hd, hc, nullptr, nullptr);
-		ix->ws.done_next = nullptr;
+		rc = launch_search(ix, &ix->ws, {.queries = hq, .q_stride = dim, .nq = nq, .ef = ef, .labels = hl, .dists = hd, .counts = hc, .done = (uint32_t *) hf});
 		if (rc) return rc;
 		for (size_t i = 0; i < nq; i++)
 		{
@@ -762,7 +833,7 @@ extern "C" int hnsw_gpu_search_batch(hnsw_gpu_index *ix, const coord_t *queries,
 	ix->hb_valid = false;
 	HIPCHK(hipEventRecord(ix->hb0, nullptr));
 	HIPCHK(hipMemcpy(dq, queries, nq * dim * 4, hipMemcpyHostToDevice));
-	rc = launch_search(ix, &ix->ws, dq, dim, nq, ef, 0, dl, nullptr, dd, dc, nullptr, nullptr);
+	rc = launch_search(ix, &ix->ws, {.queries = dq, .q_stride = dim, .nq = nq, .ef = ef, .labels = dl, .dists = dd, .counts = dc});
 	if (rc) return rc;
 	HIPCHK(hipMemcpy(labels, dl, nq * ef * 8, hipMemcpyDeviceToHost));
 	if (dists) HIPCHK(hipMemcpy(dists, dd, nq * ef * 4, hipMemcpyDeviceToHost));
@@ -821,11 +892,9 @@ extern "C" int hnsw_gpu_search_trace_begin(hnsw_gpu_index *ix, const coord_t *qu
 	memcpy(hq, query, dim * 4);
 	memset(hp, 0xFF, pops_cap * 4);                 // POP_NONE: a slot the walk has not reached yet
 	hf[0] = 0;
-	ix->ws.done_next = (uint32_t *) hf;
-	ix->ws.pops_next = hp; ix->ws.pops_cap_next = (uint32_t) pops_cap;
-	int rc = base ? launch_search(ix, &ix->ws, hq, dim, 1, ef, 1, nullptr, (uint32_t *) hl, hd, hc, hs, nullptr)
-				  : launch_search(ix, &ix->ws, hq, dim, 1, ef, 0, hl, nullptr, hd, hc, hs, nullptr);
-	ix->ws.done_next = nullptr; ix->ws.pops_next = nullptr; ix->ws.pops_cap_next = 0;
+	int rc = launch_search(ix, &ix->ws, {.queries = hq, .q_stride = dim, .nq = 1, .ef = ef, .mode = base ? 1 : 0, .labels = base ? nullptr : hl,
+										 .idx = base ? (uint32_t *) hl : nullptr, .dists = hd, .counts = hc, .stats = hs, .done = (uint32_t *) hf,
+										 .pops = hp, .pops_cap = (uint32_t) pops_cap});
 	if (rc) return rc;
 	ix->trace_active = true; ix->trace_ef = ef; ix->trace_base = base; ix->trace_cap = pops_cap; ix->trace_seen = 0;
 	return HNSW_GPU_OK;
@@ -937,7 +1006,7 @@ extern "C" int hnsw_gpu_last_batch_ms(hnsw_gpu_index *ix, float out[3])
 extern "C" int hnsw_gpu_last_search_kernel(hnsw_gpu_index *ix, char *buf, size_t len)
 {
 	if (!ix || !buf || len == 0) return fail(HNSW_GPU_ERR_ARG, "NULL argument");
-	snprintf(buf, len, "%s", ix->ws.kname);
+	search_kernel_name(ix->ws.plan, buf, len);
 	return HNSW_GPU_OK;
 }
 
@@ -963,7 +1032,23 @@ extern "C" int hnsw_gpu_index_health(hnsw_gpu_index *ix, uint32_t *out8)
 extern "C" int hnsw_gpu_last_search_slots(hnsw_gpu_index *ix, uint32_t *slots)
 {
 	if (!ix || !slots) return fail(HNSW_GPU_ERR_ARG, "NULL argument");
-	*slots = ix->ws.last_slots;
+	*slots = (uint32_t) ix->ws.plan.slots;
+	return HNSW_GPU_OK;
+}
+
+// the stored plan as the words include/hnsw_gpu_diag.h documents, in that order
+extern "C" int hnsw_gpu_last_search_plan(hnsw_gpu_index *ix, uint32_t *out, size_t cap)
+{
+	if (!ix || !out) return fail(HNSW_GPU_ERR_ARG, "NULL argument");
+	const SearchPlan &p = ix->ws.plan;
+	const uint32_t words[HNSW_GPU_SEARCH_PLAN_WORDS] = {
+		(uint32_t) p.form, p.ureg, (uint32_t) p.func_code, p.team, p.narrow5, p.lean, p.ordered,
+		p.wpb, (uint32_t) p.blocks, (uint32_t) p.slots, (uint32_t) p.lds, p.team_mains,
+		p.qpad_floats, p.off_res, p.off_cand, p.off_newid, p.off_newdist, p.wave_bytes, p.off_hash, p.hcap, p.hmagic,
+		(uint32_t) p.set_stride, (uint32_t) ((uint64_t) p.set_stride >> 32), p.wide_p, p.wide_ch, p.wide_nr, p.wide_nc,
+		p.off_ctl, p.tm_off_ex, p.tm_off_miss, p.tm_off_lctag, p.tm_off_lcstate, p.tm_off_lclinks, p.tm_lcslots, p.tm_off_dc, p.tm_dccap, p.tm_spec,
+		p.nblk, p.rstride4 };
+	memcpy(out, words, std::min<size_t>(cap, HNSW_GPU_SEARCH_PLAN_WORDS) * 4);
 	return HNSW_GPU_OK;
 }
 
@@ -999,8 +1084,8 @@ extern "C" int hnsw_gpu_search_batch_ctx(hnsw_gpu_ctx *c, const coord_t *d_queri
 										 void *stream)
 {
 	if (!c) return fail(HNSW_GPU_ERR_ARG, "context is NULL");
-	return launch_search(c->ix, &c->ws, d_queries, c->ix->meta.dim, nq, ef, 0, d_labels, nullptr, d_dists, d_counts, d_stats,
-						 (hipStream_t) stream);
+	return launch_search(c->ix, &c->ws, {.queries = d_queries, .q_stride = c->ix->meta.dim, .nq = nq, .ef = ef, .labels = d_labels, .dists = d_dists,
+										 .counts = d_counts, .stats = d_stats, .stream = (hipStream_t) stream});
 }
 
 // 8-wave team blocks the device holds at once for rows wider than 320 floats (one per CU: 2 waves/SIMD): the figure a host sizes
@@ -1054,7 +1139,7 @@ extern "C" int hnsw_gpu_search_batch_ctx_host(hnsw_gpu_ctx *c, const coord_t *qu
 	float *dq = (float *) p; uint64_t *dl = (uint64_t *) (p + qb); float *dd = (float *) (p + qb + lb);
 	uint32_t *dc = (uint32_t *) (p + qb + lb + db);
 	HIPCHK(hipMemcpyAsync(dq, queries, nq * dim * 4, hipMemcpyHostToDevice, c->stream));
-	int rc = launch_search(ix, &c->ws, dq, dim, nq, ef, 0, dl, nullptr, dd, dc, nullptr, c->stream);
+	int rc = launch_search(ix, &c->ws, {.queries = dq, .q_stride = dim, .nq = nq, .ef = ef, .labels = dl, .dists = dd, .counts = dc, .stream = c->stream});
 	if (rc) return rc;
 	HIPCHK(hipMemcpyAsync(labels, dl, nq * ef * 8, hipMemcpyDeviceToHost, c->stream));
 	if (dists) HIPCHK(hipMemcpyAsync(dists, dd, nq * ef * 4, hipMemcpyDeviceToHost, c->stream));
@@ -1076,12 +1161,8 @@ extern "C" int hnsw_gpu_search_batch_ctx_flags(hnsw_gpu_ctx *c, const coord_t *d
 	if (!d_done) return fail(HNSW_GPU_ERR_ARG, "NULL buffer");
 	HIPCHK(hipSetDevice(c->ix->device));
 	if (!c->stream) HIPCHK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-	std::unique_lock<std::recursive_mutex> lock_(c->ix->mu);      // done_next -> launch is one step
-	c->ws.done_next = d_done;
-	int rc = launch_search(c->ix, &c->ws, d_queries, c->ix->meta.dim, nq, ef, 0, d_labels, nullptr, d_dists, d_counts, d_stats,
-						   c->stream);
-	c->ws.done_next = nullptr;
-	return rc;
+	return launch_search(c->ix, &c->ws, {.queries = d_queries, .q_stride = c->ix->meta.dim, .nq = nq, .ef = ef, .labels = d_labels, .dists = d_dists,
+										 .counts = d_counts, .stats = d_stats, .stream = c->stream, .done = d_done});
 }
 
 
@@ -1169,7 +1250,7 @@ extern "C" int hnsw_gpu_scan_batch_dev(hnsw_gpu_index *ix, const coord_t *d_quer
 			if (!ev[i] && hipEventCreate(&ev[i]) != hipSuccess) { ev[i] = nullptr; rc = fail(HNSW_GPU_ERR_HIP, "index scan: hipEventCreate failed"); break; }
 		if (rc) break;
 		if (hipEventRecord(ev[0], s) != hipSuccess) { rc = fail(HNSW_GPU_ERR_HIP, "index scan: hipEventRecord failed"); break; }
-		if ((rc = launch_search(ix, &ix->ws, qs, dim, nact, ef, 0, rl, nullptr, rd, rcnt, nullptr, s, 0, true))) break;
+		if ((rc = launch_search(ix, &ix->ws, {.queries = qs, .q_stride = dim, .nq = nact, .ef = ef, .labels = rl, .dists = rd, .counts = rcnt, .stream = s, .order = true}))) break;
 		if (hipEventRecord(ev[1], s) != hipSuccess || hipMemsetAsync(tb->p, 0xFF, nact * cap * 8, s) != hipSuccess)
 		{ rc = fail(HNSW_GPU_ERR_HIP, "index scan: enqueue failed"); break; }
 		ScanRound a;

@@ -312,8 +312,8 @@ extern "C" int hnsw_gpu_sharded_search_dev(hnsw_gpu_sharded *s, const coord_t *d
 		}
 		// per-shard searchKnn (hnswalg.cpp:234-252); with peer access the kernel's result stores land in the
 		// home device's memory directly — no copy step, no collective
-		rc = launch_search(ix, s->ws[i], q, dim, nq, ef, 0, (uint64_t *) blk, nullptr, (float *) (blk + o_d), (uint32_t *) (blk + o_c),
-						   nullptr, s->streams[i]);
+		rc = launch_search(ix, s->ws[i], {.queries = q, .q_stride = dim, .nq = nq, .ef = ef, .labels = (uint64_t *) blk, .dists = (float *) (blk + o_d),
+										  .counts = (uint32_t *) (blk + o_c), .stream = s->streams[i]});
 		if (rc) return rc;
 		if (!s->direct[i])
 			HIPCHK(hipMemcpyPeerAsync(s->gather + i * block, s->home, blk, ix->device, block, s->streams[i]));

@@ -46,18 +46,11 @@ extern "C" int hnsw_gpu_stream_open(hnsw_gpu_ctx *c, size_t ef, size_t ring, uns
 	s->Q = (float *) s->pin; s->L = (label_t *) (s->pin + qb); s->D = (dist_t *) (s->pin + qb + lb);
 	s->C = (uint32_t *) (s->pin + qb + lb + db); s->F = (uint32_t *) (s->pin + qb + lb + db + cb);
 	s->host_ctl = (uint32_t *) (s->pin + qb + lb + db + cb + fb);
-	int rc;
-	{
-		std::unique_lock<std::recursive_mutex> lock_(ix->mu);       // the "next launch only" fields and the launch are one step
-		c->ws.done_next = s->F;
-		c->ws.stream_host_next = s->host_ctl; c->ws.stream_dev_next = s->dev_ctl;
-		c->ws.stream_ring_next = (uint32_t) ring; c->ws.stream_walkers_next = s->walkers;
 #ifdef PGEMB_SIMT_EMULATOR
-		simt::next_launch_is_resident();                         // (the CPU tier's emulator runs every other launch at the call)
+	simt::next_launch_is_resident();                             // (the CPU tier's emulator runs every other launch at the call)
 #endif
-		rc = launch_search(ix, &c->ws, s->Q, s->dim, ring, ef, 0, s->L, nullptr, s->D, s->C, nullptr, c->stream);
-		c->ws.done_next = nullptr; c->ws.stream_host_next = nullptr; c->ws.stream_dev_next = nullptr;
-	}
+	const int rc = launch_search(ix, &c->ws, {.queries = s->Q, .q_stride = s->dim, .nq = ring, .ef = ef, .labels = s->L, .dists = s->D, .counts = s->C, .stream = c->stream,
+											  .done = s->F, .stream_host = s->host_ctl, .stream_dev = s->dev_ctl, .stream_ring = (uint32_t) ring, .stream_walkers = s->walkers});
 	if (rc)
 	{
 		(void) hipHostFree(s->pin); (void) hipFree(s->dev_ctl);

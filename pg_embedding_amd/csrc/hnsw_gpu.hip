@@ -167,8 +167,10 @@ static void watchdog_main(int limit_s)
 				(void) __atomic_compare_exchange_n(&w->busy_since_ms, &expect, now, false, __ATOMIC_SEQ_CST, __ATOMIC_SEQ_CST);
 				continue;
 			}
+			char kname[128];
+			search_kernel_name(w->plan, kname, sizeof(kname));
 			fprintf(stderr, "hnsw_gpu watchdog: search kernel %s on device %d has been running for %lld s (limit %d s): aborting it\n",
-					w->kname, w->device, (long long) ((now - since) / 1000), limit_s);
+					kname, w->device, (long long) ((now - since) / 1000), limit_s);
 			(void) abort_ws_locked(w);
 		}
 	}

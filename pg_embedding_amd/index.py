@@ -741,6 +741,20 @@ class GpuIndex:
         check(self.L.hnsw_gpu_last_search_kernel(self._h, buf, 128), "hnsw_gpu_last_search_kernel")
         return buf.value.decode()
 
+    PLAN_WORDS = ("form", "ureg", "func_code", "team", "narrow5", "lean", "ordered", "wpb", "blocks", "slots", "lds", "team_mains",
+                  "qpad_floats", "off_res", "off_cand", "off_newid", "off_newdist", "wave_bytes", "off_hash", "hcap", "hmagic",
+                  "set_stride", "set_stride_hi", "wide_p", "wide_ch", "wide_nr", "wide_nc", "off_ctl", "tm_off_ex", "tm_off_miss",
+                  "tm_off_lctag", "tm_off_lcstate", "tm_off_lclinks", "tm_lcslots", "tm_off_dc", "tm_dccap", "tm_spec", "nblk", "rstride4")
+
+    def last_search_plan(self) -> dict:
+        """The plan of the last search launch (hnsw_gpu_last_search_plan, include/hnsw_gpu_diag.h): form (0 beam, 1 generic in LDS,
+        2 generic in HBM, 3 wide), set registers, flags, launch geometry and the per-wave LDS carve, by SearchArgs' names."""
+        v = (C.c_uint32 * len(self.PLAN_WORDS))()
+        check(self.L.hnsw_gpu_last_search_plan(self._h, v, len(self.PLAN_WORDS)), "hnsw_gpu_last_search_plan")
+        d = dict(zip(self.PLAN_WORDS, (int(x) for x in v)))
+        d["set_stride"] |= d.pop("set_stride_hi") << 32
+        return d
+
     def team_counters(self):
         """Launch-wide counters of the team form (all zero unless the library is a -DHNSW_TEAM_COUNTERS variant build): dict."""
         v = (C.c_uint32 * 16)()

@@ -8,15 +8,19 @@ so this tree's Python drives both).  A child that fails ends the run: nothing el
 headline (1M x 768 L2 m16, 40 000 queries per launch) and its one-query call, C2 (1M x 128 SIFT-like L2 m16, 40 000), C3 (1M x 768 cosine
 m32, 40 000), C5 (1M x 1536 cosine m32, 1 024).  Per child and launch size, scripts/exp_ab.py's loop: one warm-up launch, then 8 timed
 launches (one-query call: 56 launches of different queries, the first 8 dropped); kernel time from the library's own event pair.
+The one-query call also has a wall-clock column: the host's time around search_torch and its synchronise, the same 56 launches with the
+first 8 dropped — what the host side of a launch (arguments, plan, workspace, enqueue) costs shows there, not in the kernel's event time.
 
 The record holds, per shape and build, every timed launch of every round, min / median / max, the CRC, E_q and H_q, and for every shape
-whether the CRCs are equal and whether the last build's median lies inside the first build's own min-max band.
+whether the CRCs are equal and whether the last build's median lies inside the first build's own min-max band (kernel time, and the
+one-query call's wall time against the first build's wall-time band of the same run).
 """
 import argparse
 import json
 import os
 import subprocess
 import sys
+import time
 import zlib
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -44,7 +48,7 @@ def worker(shape):
     Qall = rows(max(max(nqs), 64), 1)
     out = {}
     for nq in nqs:
-        ms, crc = [], 0
+        ms, wall, crc = [], [], 0
 
         def fold(o, crc):                                      # one chained CRC over everything a launch answered, and over every launch
             st = o["stats"].cpu().numpy()
@@ -53,11 +57,15 @@ def worker(shape):
             return st, crc
         if nq == 1:
             for i in range(56):
-                o = ix.search_torch(Qall[i:i + 1].contiguous(), ef, stats=True)
+                q1 = Qall[i:i + 1].contiguous()
                 torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                o = ix.search_torch(q1, ef, stats=True)
+                torch.cuda.synchronize()
+                wall.append((time.perf_counter() - t0) * 1e3)
                 ms.append(ix.last_search_ms())
                 st, crc = fold(o, crc)
-            ms = ms[8:]
+            ms, wall = ms[8:], wall[8:]
         else:
             Q = Qall[:nq].contiguous()
             o = ix.search_torch(Q, ef, stats=True)
@@ -65,7 +73,7 @@ def worker(shape):
                 ix.search_torch(Q, ef, out=o); torch.cuda.synchronize()
                 ms.append(ix.last_search_ms())
             st, crc = fold(o, crc)
-        out[str(nq)] = {"kernel_ms": [round(float(x), 5) for x in ms], "crc": f"{crc:08x}", "E_q": float(st[:, 0].mean()), "H_q": float(st[:, 1].mean()),
+        out[str(nq)] = {"kernel_ms": [round(float(x), 5) for x in ms], "wall_ms": [round(float(x), 5) for x in wall], "crc": f"{crc:08x}", "E_q": float(st[:, 0].mean()), "H_q": float(st[:, 1].mean()),
                         "kernel": ix.last_search_kernel()}
     print("AB_RESULT " + json.dumps(out), flush=True)
 
@@ -92,8 +100,8 @@ def main():
                 if r.returncode != 0 or not line:
                     sys.exit(f"{name} round {rnd} {shape[0]}: exit {r.returncode}\n{r.stdout[-2000:]}\n{r.stderr[-2000:]}")
                 for nq, v in json.loads(line[0][10:]).items():
-                    e = runs.setdefault(f"{shape[0]}/nq{nq}", {}).setdefault(name, {"kernel_ms": [], "crc": [], "E_q": v["E_q"], "H_q": v["H_q"], "kernel": v["kernel"]})
-                    e["kernel_ms"] += v["kernel_ms"]; e["crc"].append(v["crc"])
+                    e = runs.setdefault(f"{shape[0]}/nq{nq}", {}).setdefault(name, {"kernel_ms": [], "wall_ms": [], "crc": [], "E_q": v["E_q"], "H_q": v["H_q"], "kernel": v["kernel"]})
+                    e["kernel_ms"] += v["kernel_ms"]; e["wall_ms"] += v["wall_ms"]; e["crc"].append(v["crc"])
                 print(f"round {rnd} {name:8s} {shape[0]}: done", flush=True)
     base, new = libs[0][0], libs[1][0]
     rec = {"builds": [base, new], "rounds": args.rounds, "shapes": {}}
@@ -101,10 +109,18 @@ def main():
     for key, e in runs.items():
         for v in e.values():
             v["min_median_max"] = [min(v["kernel_ms"]), float(np.median(v["kernel_ms"])), max(v["kernel_ms"])]
+            if v["wall_ms"]:
+                v["wall_min_median_max"] = [min(v["wall_ms"]), float(np.median(v["wall_ms"])), max(v["wall_ms"])]
         same = len(set(e[base]["crc"]) | set(e[new]["crc"])) == 1 and e[base]["E_q"] == e[new]["E_q"] and e[base]["H_q"] == e[new]["H_q"]
         lo, _, hi = e[base]["min_median_max"]
         inside = lo <= e[new]["min_median_max"][1] <= hi
         rec["shapes"][key] = dict(e, same_answers=same, new_median_inside_baseline_band=inside)
+        if e[base]["wall_ms"]:                                 # the one-query call: the host's wall time, held to the same rule
+            wlo, _, whi = e[base]["wall_min_median_max"]
+            winside = wlo <= e[new]["wall_min_median_max"][1] <= whi
+            rec["shapes"][key]["new_wall_median_inside_baseline_wall_band"] = winside
+            inside = inside and winside
+            print(f"{key:40s} wall ms {base} {e[base]['wall_min_median_max']}  {new} {e[new]['wall_min_median_max']}  inside band {winside}", flush=True)
         ok = ok and same and inside
         print(f"{key:40s} {base} {e[base]['min_median_max']}  {new} {e[new]['min_median_max']}  same answers {same}  inside band {inside}", flush=True)
     rec["all_same_and_inside"] = ok

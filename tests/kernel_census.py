@@ -1,7 +1,7 @@
 """The census of the search kernels: one entry per instantiation of hnsw_search_kernel_beam / _wide / _lds and rerank_kernel that
 libhnsw_gpu.so contains (csrc/search_kernels.h + csrc/search_inst.hip spell them out), with the launch that reaches it.
 
-Written from launch_search's rules (csrc/gpu_search.hip), not from a run:
+Written from the rules of plan_search and search_kernel_of (csrc/gpu_search.hip), not from a run:
 
   load shape     shape_index(kiters), kiters = ceil(ceil4(dims) / 64): <= 128 floats Shape2x4 (Shape2x2 for the hot narrow form),
                  <= 256 Shape4x2, <= 512 Shape8x2, wider Shape12x2
@@ -24,7 +24,8 @@ batch and a short one), the second fills its batches.  The reference-order kerne
 Shape12x2 has no such width among 520 / 1000: they run at 128 / 256 / 512 / 768 against the compiled reference.
 
 A new instantiation needs an entry here (tests/test_kernel_census_host.py compares this table with the library's symbols), and
-tests/test_gpu_kernel_census.py launches every entry and compares last_search_kernel() with its name, character for character."""
+tests/test_gpu_kernel_census.py launches every entry and compares last_search_kernel() with its name, character for character;
+tests/test_search_plan_emu.py does the same on the emulated library, with the plan's invariants."""
 from collections import namedtuple
 
 L2, COSINE, MANHATTAN = 0, 1, 2

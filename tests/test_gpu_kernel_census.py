@@ -18,6 +18,7 @@ import pytest
 
 import kernel_census as kc
 import oracle
+import search_plan_util as sp
 import pg_embedding_amd as pg
 from pg_embedding_amd.datasets import gmm
 from util import bits, foreign_toolchain
@@ -182,6 +183,45 @@ def test_sixteen_set_registers_on_a_narrow_reduced_walk_are_refused_before_any_l
                 ix.search_torch(dq, 200, rows=fmt)
                 torch.cuda.synchronize()
         finally:
+            ix.close()
+
+
+def one_entry_per_form():
+    """the first census entry of each form: beam, team, narrow, reference, wide, generic with its sets in LDS / in HBM, reduced"""
+    first = lambda pred: next(e for e in kc.ENTRIES if pred(e))                # noqa: E731
+    return [first(lambda e, f=f: e.form == f) for f in ("beam", "team", "narrow", "reference", "wide")] + \
+           [first(lambda e: e.form == "generic" and e.name.endswith("false>")), first(lambda e: e.form == "generic" and e.name.endswith("true>")),
+            first(lambda e: e.form == "reduced")]
+
+
+def test_the_plan_of_one_launch_per_form_is_sound_on_the_devices_own_numbers(monkeypatch):
+    """tests/search_plan_util.py's conditions on last_search_plan() (the ones tests/test_search_plan_emu.py checks on the emulated library)
+    with the device's occupancy, its per-block LDS limit and its CU count: each entry's first width, 2 000 rows, 64 queries."""
+    import torch
+    n, nq = 2000, 64
+    max_lds = int(getattr(torch.cuda.get_device_properties(0), "shared_memory_per_block", sp.LDS_PER_CU))
+    entries = one_entry_per_form()
+    assert len({e.name for e in entries}) == 8
+    built = {}
+    try:
+        for e in entries:
+            dim = e.dims[0]
+            if (dim, e.func) not in built:
+                X = in_both_formats(gmm(n, dim, k=24, seed=4000 + dim))
+                built[(dim, e.func)] = build(dim, e.func, X)[1], torch.from_numpy(gmm(nq, dim, k=24, seed=4000 + dim, stream=1)).cuda()
+            ix, dq = built[(dim, e.func)]
+            knobs(monkeypatch, {})
+            ix.set_reduced_rows(e.fmt)
+            knobs(monkeypatch, e.env)
+            ix.search_torch(dq, e.ef, rows=e.fmt)
+            torch.cuda.synchronize()
+            p = ix.last_search_plan()
+            print("PLAN", e.name, p)
+            assert ix.last_search_kernel() == e.name, e
+            assert not sp.plan_violations(p, e.ef, max_lds), (e, sp.plan_violations(p, e.ef, max_lds), p)
+            assert bool(p["team"]) == (e.form == "team") and p["slots"] == ix.last_search_slots(), (e, p)
+    finally:
+        for ix, _ in built.values():
             ix.close()
 
 
