@@ -332,6 +332,58 @@ int hnsw_gpu_range_knn_auto(hnsw_gpu_index *ix, int format, const coord_t *queri
 							const uint32_t *allow, size_t allow_bits, size_t nfilters, const uint32_t *allow_of,
 							label_t *labels, dist_t *dists, idx_t *idx, uint32_t *counts, uint32_t *totals, uint8_t *plan);
 
+/* Exact k-NN continuation: the next k after a cursor (csrc/device_filtered_knn.h, csrc/device_filtered_knn_mfma.h) — the exact
+ * plan of  ORDER BY emb <-> q LIMIT n  for any n,  LIMIT k OFFSET m,  and "the next page after the last row shown", with or without
+ * WHERE pred and WHERE emb <-> q <= r.  Every exact call stops at k <= 1024 (the sorted top-k list lives in one wave's LDS); this one is
+ * called again.
+ *   key(q, e) = ord_f32(d(q, e)) << 32 | e, with d the canonical fp32 distance and ord_f32 the order-preserving map of its bits (a float
+ *   with the sign bit set -> all bits flipped, else the sign bit set): the key every exact scan ranks by.  Keys are unique and totally
+ *   ordered, so a position in a result is one 64-bit word.
+ *   d_from   nq uint64, or NULL: the cursor of each query.  0 = from the start; NULL = 0 for every query.
+ *   R(q) is hnsw_gpu_range_knn_dev's set: elements that are vacuumed do not belong; with a filter the label must pass the query's bitmap
+ *   (d_allow == NULL: every label passes; allow_bits, nfilters and d_allow_of are then ignored); with d_radius != NULL the distance must
+ *   satisfy d <= r_q by IEEE <= (a NaN radius, or a negative one under L2, selects nothing); with d_radius == NULL the comparison is
+ *   switched off, as in filtered k-NN: a row with a NaN distance qualifies and sorts wherever its key puts it.
+ *   The set after the cursor: R_from(q) = { e in R(q) : key(q, e) >= from_q }.
+ *   The answer: the min(k, |R_from|) elements of R_from with the smallest keys, written in ascending (distance, label, element) order —
+ *   hnsw_search's order; d_labels, d_dists, d_idx, d_counts and their padded tails exactly as hnsw_gpu_filtered_knn_dev writes them.
+ *   d_totals nq or NULL: |R_from(q)|, the rows in range that have not been paged past, this page included.  On the first page that is
+ *            |R(q)|; totals - counts is what remains.
+ *   d_next   nq uint64 (required): the largest returned key + 1; counts[q] == 0: from_q unchanged.  Feeding it back as d_from returns the
+ *            following rows.  A key is never ~0 (no element has number 0xFFFFFFFF), so the increment cannot wrap.  d_next must not overlap
+ *            d_from (HNSW_GPU_ERR_ARG): a call that hands itself down to another form reads the cursors again.
+ *   from == 0 for every query, or d_from == NULL: labels, dists, idx, counts and totals are byte for byte those of hnsw_gpu_range_knn_dev
+ *   (with a radius) or hnsw_gpu_filtered_knn_dev (without one) in the same form.
+ *   Page walk: starting at 0 and feeding d_next back until counts < k visits every element of R(q) exactly once; the idx lists of the
+ *   pages, concatenated and ordered by key, are the complete key order of R(q); each page is internally in (distance, label, element)
+ *   order.  A run of equal distances that straddles a page boundary is split by element number: selection is by (distance, element), as
+ *   everywhere in this library.
+ * form: HNSW_GPU_RANGE_LISTED, HNSW_GPU_RANGE_MFMA (operands `format`, as in hnsw_gpu_range_knn_dev) or HNSW_GPU_RANGE_AUTO = the form chosen
+ * per query exactly as the automatic calls choose it (d_plan: nq bytes or NULL, 0 = listed, 1 = loose; ignored by the other forms) — the
+ * cursor does not change the plan: the listed form scores every allowed row whatever the cursor is.  The matrix-core form's filter drops
+ * the rows provably before the cursor's distance as well as those beyond its bound, so a deep page does not carry the rows before it
+ * as candidates.  Its cost still grows with depth where more rows lie inside the round-off margin around the cursor (measured on 1M x 768,
+ * k = 100: f32 operands within 2 % of the first page down to depth 100 000, f16 operands + 13 % at depth 10 000 and + 24 % at 100 000),
+ * and a cursor so deep that the sample of the query's list — its first entries in element order — holds fewer than k rows behind it
+ * leaves the bound at the radius (none: +inf): such a call overflows its candidate lists and ends in the listed form.  It
+ * hands the call to the listed form where hnsw_gpu_range_knn_dev does, and always when totals are asked for without a radius (every
+ * remaining row would be a candidate).  hnsw_gpu_last_knn_page_form (hnsw_gpu_diag.h) names the form that answered.
+ * Argument rules are radius search's, without its need for radii: k outside [1, 1024], nq > 65535, a NULL d_queries / d_labels / d_counts /
+ * d_next, a d_next that overlaps d_from, a form that is none of the three, with a filter allow_bits == 0 or nfilters == 0, k and dim too large for one block's LDS:
+ * HNSW_GPU_ERR_ARG before anything is launched (outputs untouched, d_next included); nq == 0: OK, nothing touched.  The call synchronises
+ * `stream`.  Grouped k-NN takes no cursor: a group whose nearest member lies before the cursor still has members after it, so a key alone
+ * does not tell which groups are spent. */
+enum { HNSW_GPU_RANGE_AUTO = 2 };
+int hnsw_gpu_knn_page_dev(hnsw_gpu_index *ix, int form, int format, const coord_t *d_queries, size_t nq, const dist_t *d_radius,
+						  const uint64_t *d_from, size_t k, const uint32_t *d_allow, size_t allow_bits, size_t nfilters,
+						  const uint32_t *d_allow_of, label_t *d_labels, dist_t *d_dists, idx_t *d_idx, uint32_t *d_counts,
+						  uint32_t *d_totals, uint64_t *d_next, uint8_t *d_plan, void *stream);
+/* Host-pointer form: copies in, runs on the default stream, copies out. */
+int hnsw_gpu_knn_page(hnsw_gpu_index *ix, int form, int format, const coord_t *queries, size_t nq, const dist_t *radius,
+					  const uint64_t *from, size_t k, const uint32_t *allow, size_t allow_bits, size_t nfilters,
+					  const uint32_t *allow_of, label_t *labels, dist_t *dists, idx_t *idx, uint32_t *counts,
+					  uint32_t *totals, uint64_t *next, uint8_t *plan);
+
 /* Exact grouped k-NN: the k nearest DISTINCT GROUPS, each shown through its nearest member (csrc/device_grouped_knn.h) — the exact plan of
  *   SELECT DISTINCT ON (doc_id) ... [WHERE pred] [AND emb <-> q <= r] ORDER BY emb <-> q LIMIT k   over a table with several rows per document.
  * d_group_of (required) is a table over label VALUES — the allow bitmap's convention, so one label space serves both: the group of an

@@ -181,6 +181,15 @@ long long hnsw_gpu_last_grouped_knn_overflowed(hnsw_gpu_index *ix);
 int hnsw_gpu_last_filtered_knn_plan(hnsw_gpu_index *ix, uint64_t out[8]);
 int hnsw_gpu_last_range_knn_plan(hnsw_gpu_index *ix, uint64_t out[8]);
 
+/* The mirror's last hnsw_gpu_knn_page[_dev] call (the figures of the other families are not touched): the pass that answered in
+ * hnsw_gpu_last_range_knn's eight figures — out[1], the rows scored canonically, is in the listed form the sum of the queries' own list
+ * lengths whatever the cursors are; out[3], appended, holds in the matrix-core form only pairs that are neither beyond the bound nor
+ * provably before the cursor; out[4] is the sum of |R_from(q)| (listed form, or with totals) — the form that answered (HNSW_GPU_FK_FORM_*,
+ * -1 before the first call), and the plan of the last call with form HNSW_GPU_RANGE_AUTO in hnsw_gpu_last_filtered_knn_plan's eight figures. */
+int hnsw_gpu_last_knn_page(hnsw_gpu_index *ix, uint64_t out[8]);
+int hnsw_gpu_last_knn_page_form(hnsw_gpu_index *ix);
+int hnsw_gpu_last_knn_page_plan(hnsw_gpu_index *ix, uint64_t out[8]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -154,6 +154,12 @@ def gpu_lib():
         L.hnsw_gpu_range_knn_auto.argtypes = [vp, i32, vp, sz, vp, sz, vp, sz, sz, vp, vp, vp, vp, vp, vp, vp]
         L.hnsw_gpu_last_filtered_knn_plan.argtypes = [vp, _u64p]
         L.hnsw_gpu_last_range_knn_plan.argtypes = [vp, _u64p]
+    if hasattr(L, "hnsw_gpu_knn_page_dev"):
+        L.hnsw_gpu_knn_page_dev.argtypes = [vp, i32, i32, vp, sz, vp, vp, sz, vp, sz, sz, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.hnsw_gpu_knn_page.argtypes = [vp, i32, i32, vp, sz, vp, vp, sz, vp, sz, sz, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.hnsw_gpu_last_knn_page.argtypes = [vp, _u64p]
+        L.hnsw_gpu_last_knn_page_form.argtypes = [vp]
+        L.hnsw_gpu_last_knn_page_plan.argtypes = [vp, _u64p]
     if hasattr(L, "hnsw_gpu_grouped_knn_dev"):
         L.hnsw_gpu_grouped_knn_dev.argtypes = [vp, vp, sz, sz, vp, sz, vp, vp, sz, sz, vp, vp, vp, vp, vp, vp, vp]
         L.hnsw_gpu_grouped_knn.argtypes = [vp, vp, sz, sz, vp, sz, vp, vp, sz, sz, vp, vp, vp, vp, vp, vp]

@@ -31,6 +31,22 @@
 //   cosine.  |q.x| errs by <= g |q| |x| (Cauchy-Schwarz), sqrt(|q|^2) sqrt(|x|^2) by <= (g + 2u) |q| |x|, so either side's cosine is within
 //        2 g + O(u) of the exact one, and the comparison dot >= (1 - tau - e) sqrt(|q|^2) sqrt(|x|^2) keeps every row within tau for
 //        e = (5 D + 32) u.
+// The LOWER test (policies with FROM: BfFrom<P>, device_filtered_knn_mfma.h — the page call's cursor).  A page that starts at a cursor
+// whose distance is c wants no row before it, and the same round-off argument read the other way drops them in the filter: for every
+// summation order, no row whose canonical distance d has d >= c (IEEE) is dropped.  Every bound above is two-sided, so
+//   L2.  |q - x|^2 <= |q|^2 + |x|^2 - 2 q.x + eD (|q|^2 + |x|^2) + 2 abs in computed values, and a canonical distance t has
+//        t^2 <= |q - x|^2 (1 + (D + 10) u), i.e. |q - x|^2 >= t^2 (1 - e1).  Hence: drop only if the OVER-estimate
+//            |q|^2 / 2 + (1 + eD) |x|^2 / 2 - q.x  <  (c^2 (1 - e1) - eD |q|^2) / 2 - abs       (make_low_bounds_kernel);
+//        then |q - x|^2 < c^2 (1 - e1) and no canonical order can give d >= c.  (1 + eD) |x|^2 / 2 is a second per-lane value (xh2).
+//   cosine.  Either side's cosine is within 2 g + O(u) of the exact one: drop only if dot > (1 - c + e) sqrt(|q|^2) sqrt(|x|^2) with
+//        the same e — then the canonical 1 - cos is below c.  That argument needs the canonical product |q|^2 |x|^2 to be an ordinary
+//        number (overflowed, it makes the distance 1 whatever the dot is; underflowed, +-inf or NaN): the test is made only for
+//        2^-30 <= |q|, |x| <= 2^31, whose product of squares is normal in any rounding.
+//   16-bit operands take dot16 - E where the upper test takes dot16 + E (dot16 - E <= q.x by the same bound: P::value_low).
+// Whatever is not finite keeps the row here too: a cursor of 0 decodes to a NaN distance, and a NaN, an infinite or (L2) a non-positive c,
+// a c whose square overflows and a non-finite |q|^2 give the query a comparison value nothing is below (L2: -inf, cosine: +inf); a
+// non-finite |x|^2 makes the lane's value NaN; a dot (or dot16 - E) that is not finite is never "before".  Rows AT the cursor's
+// distance, on either side of its element number, survive: the re-score's exact key test decides them.
 // Non-finite values keep rows, never drop them: the comparisons are written so that NaN passes, a non-finite |x|^2 makes the lane's
 // value NaN, and a non-finite |q|^2 or tau (or a cosine tau >= 1: the canonical product |q|^2 |x|^2 may overflow to a distance of 1)
 // keeps every row for that query.  Data for which the margin passes most rows (thousands of ties at tau, a bound that is inf) overflow
@@ -95,6 +111,8 @@ struct BfArgs
 	uint32_t nq, n, qchunks, rchunks, ksteps;
 	int func;
 	float xscale;              // L2: (1 - eD) / 2, the filter's |x|^2 factor (make_bounds_kernel: the margin's |x|^2 share, halved)
+	float xscale_hi;           // policies with FROM, L2: (1 + eD) / 2, the lower test's |x|^2 factor
+	const float *qlow;         // policies with FROM: the lower comparison value of every query (make_low_bounds_kernel, device_filtered_knn_mfma.h)
 	float eabs;                // 16-bit: r16_abs_term(dim)
 	uint32_t *cand;            // [nq][cap]
 	uint32_t *cand_cnt;        // [nq]
@@ -114,11 +132,14 @@ struct BfArgs
 //   Row            its own per-row epilogue operands, one per MFMA column of the lane (row_operands, which returns |x|^2)
 //   step           the MFMAs of one 16-byte LDS operand per tile row
 //   value          what the comparisons use in place of the dot product;  keep: a dot that passes whatever the comparison says
+//   value_low      what the lower test uses in place of the dot product: never above the exact one by more than the margin covers
+//   FROM           whether a passing pair must also not be provably before the query's cursor (BfFrom<P>: one more word per query, the last)
 //   ALLOW          whether a passing pair is tested against the query's row mask before it is appended (BfAllow<P>, device_filtered_knn_mfma.h)
 struct BfF32
 {
 	static constexpr int FMT = ROWS_F32;
 	static constexpr bool ALLOW = false;
+	static constexpr bool FROM = false;
 	static constexpr bool CLAMP = true;
 	static constexpr int EPI_Q = 2;
 	struct Row {};
@@ -138,6 +159,7 @@ struct BfF32
 					acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[i][c], bv[j][c], acc[i][j], 0, 0, 0);
 	}
 	__device__ static __forceinline__ float value(const BfArgs &, float dot, const floatx4 *, int, const Row &) { return dot; }
+	__device__ static __forceinline__ float value_low(const BfArgs &, float dot, const floatx4 *, int, const Row &) { return dot; }
 	__device__ static __forceinline__ bool keep(float) { return false; }
 };
 
@@ -219,12 +241,16 @@ __global__ __launch_bounds__(128 * WM, WM == 2 ? 2 : 1) void bf_mfma_filter_kern
 		for (int w = 2; w < P::EPI_Q; w++) epi[w * TQ + t] = P::query_word(a, qi, w);
 	}
 	float xs2[NJ];
+	[[maybe_unused]] float xh2[P::FROM ? NJ : 1];                    // the lower test's |x| term (header): NaN = never before the cursor
 	typename P::Row xr[NJ];
 #pragma unroll
 	for (int j = 0; j < NJ; j++)
 	{
 		const float xn = P::row_operands(a, min(r0 + wn * (32 * NJ) + j * 32 + col, a.n - 1), xr[j]);
 		xs2[j] = !(xn <= __FLT_MAX__) ? __builtin_nanf("") : (a.func == F_COSINE) ? __builtin_sqrtf(xn) : a.xscale * xn;   // (NaN: always passes)
+		if constexpr (P::FROM)
+			xh2[j] = (a.func == F_COSINE) ? ((xs2[j] >= 0x1p-30f && xs2[j] <= 0x1p31f) ? xs2[j] : __builtin_nanf(""))
+										  : (!(xn <= __FLT_MAX__) ? __builtin_nanf("") : a.xscale_hi * xn);
 	}
 
 	// Tiles go global -> LDS directly (global_load_lds_dwordx4: no staging registers, no ds_write).  The LDS image is what the hardware
@@ -325,6 +351,13 @@ __global__ __launch_bounds__(128 * WM, WM == 2 ? 2 : 1) void bf_mfma_filter_kern
 						pass = pass || !(v < qo[0][e1] * xs2[j]);                 // 1 - dot/sqrt(nq nx) <= tau (+margin)
 					else
 						pass = pass || !(qo[1][e1] + xs2[j] - v > qo[0][e1]);     // |q-x|^2 / 2 <= tau^2 / 2 (+margin)
+					if constexpr (P::FROM)
+					{
+						// provably before the cursor's distance (header): the over-estimate is below the lower comparison value
+						const float vl = P::value_low(a, dot, qo, e1, xr[j]), lw = qo[P::EPI_Q - 1][e1];
+						const bool before = a.func == F_COSINE ? vl > lw * xh2[j] : qo[1][e1] + xh2[j] - vl < lw;
+						pass = pass && !(before && __builtin_fabsf(vl) <= __FLT_MAX__);
+					}
 					if (pass && rok && q < a.nq)
 					{
 						const uint32_t slot = atomicAdd(pass_cnt, 1u);      // (LDS)

@@ -179,6 +179,7 @@ struct Bf16
 {
 	static constexpr int FMT = FMT_;
 	static constexpr bool ALLOW = false;
+	static constexpr bool FROM = false;
 	static constexpr bool CLAMP = false;                      // a reduced row is a whole number of K steps
 	static constexpr int EPI_Q = 4;                           // bound, |q|^2 (halved for L2), rq', |q~|'
 	struct Row { float xl, ex; };                             // |x|', ex'
@@ -207,6 +208,11 @@ struct Bf16
 	__device__ static __forceinline__ float value(const BfArgs &a, float d16, const floatx4 *qo, int e1, const Row &x)
 	{
 		return d16 + __builtin_fmaf(qo[3][e1], x.ex, __builtin_fmaf(qo[2][e1], x.xl, a.eabs));
+	}
+	// the lower test's value (device_bf_mfma.h): dot16 - E <= q.x by the bound of the header, read the other way
+	__device__ static __forceinline__ float value_low(const BfArgs &a, float d16, const floatx4 *qo, int e1, const Row &x)
+	{
+		return d16 - __builtin_fmaf(qo[3][e1], x.ex, __builtin_fmaf(qo[2][e1], x.xl, a.eabs));
 	}
 	__device__ static __forceinline__ bool keep(float d16) { return !(__builtin_fabsf(d16) <= __FLT_MAX__); }
 };

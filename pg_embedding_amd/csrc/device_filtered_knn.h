@@ -30,6 +30,10 @@
 //                        padded tails and (radius calls) the total; (grouped k-NN, device_grouped_knn.h) the group of every returned row
 //
 // Selection by (dist, element), emission by (dist, label): the reference's two steps (topResults, then the sort of searchKnn's output).
+//
+// The page call (hnsw_gpu_knn_page*_dev) is the same pipeline with one more qualifier beside the radius: a cursor per query
+// (FkScan::from), the smallest key that still qualifies — scan_list offers and counts only keys >= it — and one more output: the cursor of
+// the following page (FkEmit::next), the largest returned key + 1.
 #pragma once
 #include "device_topk_scan.h"
 
@@ -178,7 +182,13 @@ struct FkScan
 	uint32_t skip_samples;           // matrix-core form with totals: only the lists that are scanned whole
 	const float *radius;             // NULL: no threshold, every scanned row qualifies; else [nq]
 	int func;
+	const uint64_t *from;            // NULL: no cursor; else [nq] a row qualifies only if its key is not below the query's (hnsw_gpu_knn_page_dev; 0: none)
 };
+
+// the cursor of query qi: the smallest key that still qualifies (0: every key does)
+__device__ __forceinline__ uint64_t fk_from(const uint64_t *from, uint32_t qi) { return from ? from[qi] : 0ull; }
+// the distance of a cursor's key (a cursor of 0 decodes to a NaN: below nothing, above nothing)
+__device__ __forceinline__ float fk_cursor_dist(uint64_t from) { return unord_f32((uint32_t) (from >> 32)); }
 
 // a radius that no distance satisfies: NaN, or negative under L2 (a rounded square root: never below +0)
 __device__ __forceinline__ bool rk_selects_nothing(float r, int func) { return r != r || (func == F_L2 && r < 0.f); }
@@ -207,7 +217,7 @@ __device__ __forceinline__ void fk_list_of(const FkScan &a, uint32_t qi, const u
 // contiguous eighth of that order, so that the blocks of one slice share one L2: measured, not faster, off.)
 // In LDS behind the query image: 4 x (k + 1) keys | 4 x 128 sums | 4 x 64 element numbers | 4 x (k + 1) x what a List entry holds beyond
 // its key.  pcount is written only where it is read: by the key lists' merge.
-template <int FUNC, class List>
+template <int FUNC, class List, bool FROM = false>
 __global__ __launch_bounds__(256) void fk_scan_kernel(const FkScan a)
 {
 	extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -237,8 +247,8 @@ __global__ __launch_bounds__(256) void fk_scan_kernel(const FkScan a)
 	const uint32_t lo = (uint32_t) ((uint64_t) len * w / nw), hi = (uint32_t) ((uint64_t) len * (w + 1) / nw);
 	const bool within = a.radius != nullptr;
 	uint32_t nqual = 0;
-	const uint32_t tsize = scan_list<FUNC>(a.vec, a.stride, q4, a.nchunks, a.kiters, StagedRows{list, ids}, typename List::OfList(a.glist, (size_t) (list - a.list)), top, lo, hi,
-										   sums, k, within, within ? a.radius[qi] : 0.f, nqual, lane);
+	const uint32_t tsize = scan_list<FUNC, FROM>(a.vec, a.stride, q4, a.nchunks, a.kiters, StagedRows{list, ids}, typename List::OfList(a.glist, (size_t) (list - a.list)), top, lo, hi,
+										   sums, k, within, within ? a.radius[qi] : 0.f, FROM ? fk_from(a.from, qi) : 0ull, nqual, lane);
 	const size_t pw = (size_t) qi * a.splits * 4u + w;
 	top.store(a.part, a.gpart, pw * k, tsize, k, lane);
 	if (lane == 0)
@@ -310,9 +320,12 @@ struct FkEmit
 	unsigned long long *sum;         // NULL, or the call's sum of the counts
 	const uint32_t *groups;          // NULL, or [nq][k] the group of every key (grouped k-NN, device_grouped_knn.h) ...
 	uint32_t *out_groups;            // ... and NULL, or [nq][k] <- the group of every returned row, tail 0xFFFFFFFF
+	const uint64_t *from;            // the call's cursors (FkScan::from), read only for ...
+	uint64_t *next;                  // ... fk_emit_kernel<true>: [nq] <- the largest returned key + 1: the cursor of the following page; no row returned: the query's own cursor
 };
 
-// One wave per query (block = 64 threads).  LDS: k winner keys | k labels.
+// One wave per query (block = 64 threads).  LDS: k winner keys | k labels.  NEXT: the page call's instantiation, which writes a.next.
+template <bool NEXT = false>
 __global__ __launch_bounds__(64) void fk_emit_kernel(const FkEmit a)
 {
 	extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -361,6 +374,8 @@ __global__ __launch_bounds__(64) void fk_emit_kernel(const FkEmit a)
 	{
 		a.out_counts[qi] = cnt;
 		if (a.out_totals) a.out_totals[qi] = total;
+		// (win is ascending by key: its last entry is the largest returned; no key is ~0 — no element has number 0xFFFFFFFF — so + 1 cannot wrap)
+		if constexpr (NEXT) a.next[qi] = cnt ? win[cnt - 1] + 1ull : fk_from(a.from, qi);
 		if (a.sum && total) atomicAdd(a.sum, (unsigned long long) total);
 	}
 }

@@ -43,6 +43,50 @@ struct BfAllow : P
 	static constexpr bool ALLOW = true;
 };
 
+// ---- the page call's cursor (hnsw_gpu_knn_page_dev) ---------------------------------------------------------------------------
+// A page wants R_from(q) = the rows of R(q) whose key is not below from_q.  Every canonical step has the test in scan_list, so:
+//   the sample scan keeps the sample's keys of R_from only.  Its k-th is still an upper bound of the k-th distance of R_from: the kept keys
+//     are k members of R_from, so the k smallest keys of R_from are not above the largest of them.  With fewer than k the bound is the
+//     radius (none: +inf), as before; a list no longer than its sample is still answered by its sample (the scan saw the whole list);
+//   the filter drops, besides the pairs above tau_q, the pairs PROVABLY before the cursor's distance c_q = fk_cursor_dist(from_q)
+//     (BfFrom<P>; the derivation is in device_bf_mfma.h) — without that a deep page drags every row before its cursor along as a candidate,
+//     passes the 16 384 a candidate list holds about 16 000 rows in, and pays a re-score that grows with the offset before that;
+//   the re-score applies the exact key test; rows at distance c_q on either side of the cursor's element reach it.
+// With totals the upper bound is the radius and the lower test still applies (totals count R_from).  Totals WITHOUT a radius would make every
+// remaining row a candidate: that call goes to the listed form before any filter launch (fk_run, gpu_scan.hip).  A call without cursors
+// (d_from NULL) launches the BfAllow<P> instantiations as before: no extra word, no extra compare.
+template <class P>
+struct BfFrom : P
+{
+	static constexpr bool FROM = true;
+	static constexpr int EPI_Q = P::EPI_Q + 1;                // the last word: the query's lower comparison value
+	__device__ static __forceinline__ float query_word(const BfArgs &a, uint32_t qi, int w) { return w == P::EPI_Q ? a.qlow[qi] : P::query_word(a, qi, w); }
+};
+
+// from_q -> the filter's lower comparison value (derivation and the keep-all cases: device_bf_mfma.h).  Runs BEFORE make_bounds_kernel, which
+// halves |q|^2 in place.  L2: the over-estimate of |q - x|^2 / 2 is compared with (c^2 (1 - e1) - eD |q|^2) / 2 - abs; cosine: the dot with
+// (1 - c + e) sqrt(|q|^2) sqrt(|x|^2).
+__global__ void make_low_bounds_kernel(const uint64_t *__restrict__ from, const float *__restrict__ qnorm, uint32_t nq, int func, uint32_t dim,
+									   float *__restrict__ qlow)
+{
+	const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
+	if (q >= nq) return;
+	const float c = fk_cursor_dist(from[q]), nqv = qnorm[q];
+	const float d = (float) dim + 32.f, u = 0x1p-24f;
+	if (func == F_COSINE)
+	{
+		const float sq = __builtin_sqrtf(nqv);
+		const bool keep_all = !(__builtin_fabsf(c) <= __FLT_MAX__) || !(sq >= 0x1p-30f && sq <= 0x1p31f);
+		qlow[q] = keep_all ? __builtin_inff() : (1.f - c + (5.f * (float) dim + 32.f) * u) * sq;
+	}
+	else
+	{
+		const float c2 = c * c;
+		const bool keep_all = !(c > 0.f) || !(c2 <= __FLT_MAX__) || !(nqv <= __FLT_MAX__);
+		qlow[q] = keep_all ? -__builtin_inff() : 0.5f * (c2 * (1.f - d * u) - 2.f * d * u * nqv) - d * 0x1p-146f;
+	}
+}
+
 // words of one mask row: whole 64-row ballots
 __host__ __device__ inline uint32_t fkm_mask_words(uint32_t n) { return 2u * ((n + 63u) / 64u); }
 
@@ -79,12 +123,13 @@ struct FkRescore
 	uint32_t *groups;                // GroupedList (else NULL): [nq][k] <- their groups
 	uint32_t *count;                 // [nq] <- KeyList: the candidates that qualified; GroupedList: the groups of the answer
 	uint32_t *overflow;
+	const uint64_t *from;            // NULL, or [nq] the call's cursors (FkScan::from): the exact key >= from test of every candidate
 };
 
 // One wave per query, bf_rescore_kernel's shape and LDS (rescore_wave, device_topk_scan.h): canonical distances of the filter's candidates;
 // every candidate that takes part and qualifies (d <= r; radius == NULL: all of them) is offered to an EMPTY List — every member of A(b)
 // within the bound is a candidate, the sample's rows included.  A query the scan answered (mask row nfilters) keeps what the merge wrote.
-template <int FUNC, class List>
+template <int FUNC, class List, bool FROM = false>
 __global__ __launch_bounds__(256) void fk_rescore_kernel(const FkRescore a)
 {
 	extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -96,17 +141,20 @@ __global__ __launch_bounds__(256) void fk_rescore_kernel(const FkRescore a)
 	const List top = List::at(w.keys, w.more);
 	const bool within = a.radius != nullptr;
 	uint32_t nqual = 0;
-	const uint32_t tsize = scan_list<FUNC>(a.vec, a.stride, w.q4, a.nchunks, a.kiters, CandidateRows{a.cand + (size_t) qi * a.cap}, typename List::OfElement(a.egroup), top,
-										   0u, w.cnt, w.sums, k, within, within ? a.radius[qi] : 0.f, nqual, lane);
+	const uint32_t tsize = scan_list<FUNC, FROM>(a.vec, a.stride, w.q4, a.nchunks, a.kiters, CandidateRows{a.cand + (size_t) qi * a.cap}, typename List::OfElement(a.egroup), top,
+										   0u, w.cnt, w.sums, k, within, within ? a.radius[qi] : 0.f, FROM ? fk_from(a.from, qi) : 0ull, nqual, lane);
 	top.store(a.keys, a.groups, (size_t) qi * k, tsize, k, lane);
 	if (lane == 0) a.count[qi] = List::PART_ENTRY == 8 ? nqual : tsize;
 }
 
 // The filter's stand-in: one block per query, its 4 waves stride over all rows 64 at a time with the canonical distance code; a pair passes
-// if its distance is not above tau_q (a NaN passes, as in the filter).  LDS: the query image | 4 x 128 sums.
+// if its distance is not above tau_q (a NaN passes, as in the filter) and — from: NULL, or the cursors of a page call — not below the
+// cursor's distance c_q (fk_cursor_dist; a NaN on either side passes: the mirror of the filter's lower test, BfFrom).  LDS: the query image |
+// 4 x 128 sums.
 template <int FUNC>
 __global__ __launch_bounds__(256) void fkm_standin_kernel(const BfArgs a, const float *__restrict__ vec, uint32_t dim, uint32_t stride, uint32_t nchunks,
-														  uint32_t kiters, uint32_t qpad_floats, const float *__restrict__ queries, const float *__restrict__ tau)
+														  uint32_t kiters, uint32_t qpad_floats, const float *__restrict__ queries, const float *__restrict__ tau,
+														  const uint64_t *__restrict__ from)
 {
 	extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 	const uint32_t qi = blockIdx.x;
@@ -117,7 +165,7 @@ __global__ __launch_bounds__(256) void fkm_standin_kernel(const BfArgs a, const 
 	float *sums = reinterpret_cast<float *>(smem + (size_t) qpad_floats * 4) + wib * 128;
 	float qnorm = 0.f;
 	if (FUNC == F_COSINE) qnorm = query_norm(q4, nchunks, kiters, lane);
-	const float t = tau[qi];
+	const float t = tau[qi], c = fk_cursor_dist(fk_from(from, qi));
 	uint32_t np = 0, na = 0;
 	for (uint32_t base = wib * 64; base < a.n; base += 256)
 	{
@@ -126,7 +174,7 @@ __global__ __launch_bounds__(256) void fkm_standin_kernel(const BfArgs a, const 
 		score_rows<FUNC, 4, 2>(vec, stride, q4, nchunks, kiters, direct, cnt, sums, lane);
 		wave_sync();
 		const float d = finish_dist<FUNC>(sums[lane], sums[OUT2 + lane], qnorm);
-		if ((uint32_t) lane < cnt && !(d > t))
+		if ((uint32_t) lane < cnt && !(d > t) && !(d < c))
 		{
 			np++;
 			na += bf_append<true>(a, qi, base + (uint32_t) lane) ? 1u : 0u;

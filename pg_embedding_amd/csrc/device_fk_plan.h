@@ -121,6 +121,7 @@ struct FkGather
 	const uint32_t *allow_of; uint32_t *out_allow_of;                // NULL: none
 	const float *radius; float *out_radius;                          // NULL: none
 	uint32_t vec4;                                                   // 1: dim % 4 == 0 and both row arrays start on 16 bytes
+	const uint64_t *from; uint64_t *out_from;                        // the page call's cursors; NULL: none
 };
 
 // grid = ceil(count * (vec4 ? dim / 4 : dim) / 256) blocks of 256: thread t moves chunk t % chunks of position first + t / chunks
@@ -139,6 +140,7 @@ __global__ __launch_bounds__(256) void fkp_gather_kernel(const FkGather a)
 	{
 		if (a.allow_of) a.out_allow_of[pos] = a.allow_of[q];
 		if (a.radius) a.out_radius[pos] = a.radius[q];
+		if (a.from) a.out_from[pos] = a.from[q];
 	}
 }
 
@@ -148,6 +150,7 @@ struct FkScatter
 	const uint64_t *labels; const float *dists; const uint32_t *idx; const uint32_t *counts; const uint32_t *totals;   // [nq][k] / [nq] in perm[] order
 	uint64_t *out_labels; float *out_dists; uint32_t *out_idx; uint32_t *out_counts; uint32_t *out_totals;             // the caller's; dists / idx / totals may be NULL
 	const uint32_t *groups; uint32_t *out_groups;                    // grouped k-NN: [nq][k] in perm[] order, and the caller's; NULL: none
+	const uint64_t *next; uint64_t *out_next;                        // the page call: [nq] in perm[] order, and the caller's; NULL: none
 };
 
 // grid = ceil(count * k / 256) blocks of 256: thread t moves entry t % k of position first + t / k
@@ -166,6 +169,7 @@ __global__ __launch_bounds__(256) void fkp_scatter_kernel(const FkScatter a)
 	{
 		a.out_counts[q] = a.counts[pos];
 		if (a.out_totals) a.out_totals[q] = a.totals[pos];
+		if (a.out_next) a.out_next[q] = a.next[pos];
 	}
 }
 

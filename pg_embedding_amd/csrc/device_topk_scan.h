@@ -118,13 +118,15 @@ struct StagedRows                                            // entry e is list[
 // ---- (c) the wave loop -----------------------------------------------------------------------------------------------------------------------
 // One wave: entries [lo, hi) of `src`, scored against the staged query q4.  An entry is offered to `list` if it takes part — its group word
 // group_of(base, cnt, lane, id) (entry base + lane, element id; any word for lane >= cnt) is not GK_NONE — and qualifies: within
-// (wave-uniform) d <= radius, else always.  The list's entries, ascending, are list's [0 .. return value); nqual = how many entries that take
-// part qualified (one ballot + popcount per step, no atomic; a caller that ignores it pays nothing).  sums: the wave's 128 floats of
-// score_rows output.
-template <int FUNC, class Source, class Groups, class List>
+// (wave-uniform) d <= radius, else always — and, in the instantiations with FROM (the page call, hnsw_gpu_knn_page_dev), its key is not below
+// `from` (wave-uniform; the cursor: keys are unique and totally ordered, so a place in a result is one key, and 0 is below no key).  FROM is
+// a template parameter so that every other call runs the code it ran before there were cursors: without it `from` is not read.  The list's entries,
+// ascending, are list's [0 .. return value); nqual = how many entries that take part qualified (one ballot + popcount per step, no atomic;
+// a caller that ignores it pays nothing).  sums: the wave's 128 floats of score_rows output.
+template <int FUNC, bool FROM = false, class Source, class Groups, class List>
 __device__ __forceinline__ uint32_t scan_list(const float *__restrict__ vec, uint32_t stride, const float4 *q4, uint32_t nchunks, uint32_t kiters,
 											  const Source &src, const Groups &group_of, const List &list, uint32_t lo, uint32_t hi, float *sums,
-											  uint32_t k, bool within, float radius, uint32_t &nqual, int lane)
+											  uint32_t k, bool within, float radius, uint64_t from, uint32_t &nqual, int lane)
 {
 	float qnorm = 0.f;
 	if (FUNC == F_COSINE) qnorm = query_norm(q4, nchunks, kiters, lane);
@@ -138,9 +140,19 @@ __device__ __forceinline__ uint32_t scan_list(const float *__restrict__ vec, uin
 		score_rows<FUNC, 4, 2>(vec, stride, q4, nchunks, kiters, src.rows(base), cnt, sums, lane);
 		wave_sync();
 		const float dl = finish_dist<FUNC>(sums[lane], sums[OUT2 + lane], qnorm);
-		const bool in = (uint32_t) lane < cnt && g != GK_NONE && (!within || dl <= radius);   // (IEEE: false for a NaN on either side)
-		nin += (uint32_t) __builtin_popcountll(__ballot(in));
-		list.offer(tsize, worst, ((uint64_t) ord_f32(dl) << 32) | id, g, in, k, lane);
+		if constexpr (FROM)
+		{
+			const uint64_t kl = ((uint64_t) ord_f32(dl) << 32) | id;
+			const bool in = (uint32_t) lane < cnt && g != GK_NONE && (!within || dl <= radius) && kl >= from;
+			nin += (uint32_t) __builtin_popcountll(__ballot(in));
+			list.offer(tsize, worst, kl, g, in, k, lane);
+		}
+		else
+		{
+			const bool in = (uint32_t) lane < cnt && g != GK_NONE && (!within || dl <= radius);   // (IEEE: false for a NaN on either side)
+			nin += (uint32_t) __builtin_popcountll(__ballot(in));
+			list.offer(tsize, worst, ((uint64_t) ord_f32(dl) << 32) | id, g, in, k, lane);
+		}
 		wave_sync();
 	}
 	nqual = nin;
@@ -215,7 +227,7 @@ __global__ __launch_bounds__(256) void bruteforce_kernel(const float *__restrict
 	const uint32_t lo = (uint32_t) ((uint64_t) n * w / nw), hi = (uint32_t) ((uint64_t) n * (w + 1) / nw);
 	const KeyList list{top};
 	uint32_t nqual;
-	const uint32_t tsize = scan_list<FUNC>(vec, stride, q4, nchunks, kiters, DirectRows{}, NoGroups{}, list, lo, hi, sums, k, false, 0.f, nqual, lane);
+	const uint32_t tsize = scan_list<FUNC>(vec, stride, q4, nchunks, kiters, DirectRows{}, NoGroups{}, list, lo, hi, sums, k, false, 0.f, 0ull, nqual, lane);
 	list.store(part, nullptr, ((size_t) qi * nw + w) * k, tsize, k, lane);
 }
 
@@ -250,7 +262,7 @@ __global__ __launch_bounds__(256) void bf_rescore_kernel(const float *__restrict
 	const uint64_t *top = w.keys;
 	uint32_t nqual;
 	const uint32_t tsize = scan_list<FUNC>(vec, stride, w.q4, nchunks, kiters, CandidateRows{cand + (size_t) qi * cap}, NoGroups{}, KeyList{w.keys}, 0u, w.cnt,
-										   w.sums, k, false, 0.f, nqual, lane);
+										   w.sums, k, false, 0.f, 0ull, nqual, lane);
 	for (uint32_t i = lane; i < k; i += 64)
 	{
 		const bool ok = i < tsize;

@@ -186,10 +186,11 @@ struct FkWs
 	// that answered the last call that ended well (HNSW_GPU_FK_FORM_* = HNSW_GPU_RK_FORM_*); scan_ms: from the end of the list (and mask)
 	// build, or of the pass before, to the end of the emit kernel
 	struct Diag { uint64_t listed = 0, scored = 0, dist_pass = 0, appended = 0, totals = 0, overflowed = 0; float build_ms = 0.f, filter_ms = 0.f, call_ms = 0.f, scan_ms = 0.f; int form = -1; } k, kf, r;
+	Diag p;                                              // the pass that answered the last page call (hnsw_gpu_last_knn_page[_form]: hnsw_gpu_last_range_knn's figures)
 	Diag g, gf;                                          // the last grouped k-NN call: g = the pass that answered (hnsw_gpu_last_grouped_knn[_form]), gf = its last filter launch, as kf (hnsw_gpu_last_grouped_knn_mfma)
 	// the plan of the last automatic call of each kind (hnsw_gpu_last_filtered_knn_plan, hnsw_gpu_last_range_knn_plan, hnsw_gpu_last_grouped_knn_plan): queries and ΣL_q per
 	// class, the threshold in rows, the model's two estimates for the queries above it (µs), the form that answered the loose class
-	struct Plan { uint64_t nq[2] = {0, 0}, rows[2] = {0, 0}, thresh = 0, est_listed_us = 0, est_mfma_us = 0; int loose_form = 0; } plan, rplan, gplan;
+	struct Plan { uint64_t nq[2] = {0, 0}, rows[2] = {0, 0}, thresh = 0, est_listed_us = 0, est_mfma_us = 0; int loose_form = 0; } plan, rplan, gplan, pplan;
 };
 void fk_ws_free(FkWs *s);
 

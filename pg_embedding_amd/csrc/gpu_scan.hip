@@ -349,6 +349,7 @@ static BfArgs bf_args(const hnsw_gpu_index *ix, bool reduced, size_t nq, const u
 	a.nq = (uint32_t) nq; a.n = (uint32_t) ix->n; a.qchunks = bf_qchunks(ix, reduced); a.rchunks = reduced ? ix->rows16_bytes / 16 : ix->stride / 4;
 	a.ksteps = a.qchunks / BF_CH; a.func = (int) ix->meta.dist_func;
 	a.xscale = 0.5f * (1.f - 2.f * ((float) dim + 32.f) * 0x1p-24f);          // (1 - eD) / 2: make_bounds_kernel
+	a.xscale_hi = 0.5f * (1.f + 2.f * ((float) dim + 32.f) * 0x1p-24f);       // (1 + eD) / 2: make_low_bounds_kernel
 	a.eabs = r16_abs_term(dim);
 	a.cand = cand; a.cand_cnt = cnt; a.cap = cap;
 	return a;
@@ -484,7 +485,7 @@ void fk_ws_free(FkWs *s)
 	for (hipEvent_t &e : s->ev) { if (e) (void) hipEventDestroy(e); e = nullptr; }
 }
 
-// what the three families of entry points differ in: their name in a message, what they require, and where their diagnostics go — the
+// what the four families of entry points differ in: their name in a message, what they require, and where their diagnostics go — the
 // figures of one are not touched by a call of the other
 struct FkFamily
 {
@@ -493,10 +494,12 @@ struct FkFamily
 	FkWs::Diag FkWs::*diag;                                       // the pass that answered the last call (both classes of an automatic call)
 	FkWs::Diag FkWs::*filter;                                     // NULL, or: the last filter launch of the last call, whatever form answered in the end
 	FkWs::Plan FkWs::*plan;
+	bool page;                                                    // the page call: radius and filter both optional, the next cursors required
 };
 static const FkFamily FK_KNN = { "filtered k-NN", false, false, &FkWs::k, &FkWs::kf, &FkWs::plan };
 static const FkFamily FK_RANGE = { "radius search", true, false, &FkWs::r, nullptr, &FkWs::rplan };
 static const FkFamily FK_GROUPED = { "grouped k-NN", false, true, &FkWs::g, &FkWs::gf, &FkWs::gplan };
+static const FkFamily FK_PAGE = { "k-NN page", false, false, &FkWs::p, nullptr, &FkWs::pplan, true };
 
 // one call: its arguments (radius, totals: NULL in filtered k-NN), and what its list build found
 struct FkCall
@@ -507,6 +510,7 @@ struct FkCall
 	FkLists fl; uint64_t *off; unsigned long long *scored; size_t nsb, total, longest;
 	bool later;                                                   // a pass that follows another of the call: its scan time counts from ev[5], not from the list build
 	const uint32_t *group_of; size_t group_entries; uint32_t *groups;   // grouped k-NN: the table over label values, and NULL or the output
+	const uint64_t *from; uint64_t *next;                         // the page call: NULL or the cursors, and the cursors of the following page
 };
 struct FkTrim { FkWs *w; ~FkTrim() { buf_trim({&w->cells, &w->list, &w->part, &w->mask, &w->bfs, &w->cand, &w->perm, &w->tmp, &w->grp, &w->egrp}); } };   // on EVERY way out, errors included: no buffer above 64 MiB outlives its call
 
@@ -523,12 +527,15 @@ static int fk_check_format(const char *who, hnsw_gpu_index *ix, int format)
 static int fk_check(const FkCall &c, int form, int format)
 {
 	const char *who = c.fam->who;
-	const bool range = c.fam->range, grouped = c.fam->grouped, filter = c.allow || !(range || grouped);
+	const bool range = c.fam->range, grouped = c.fam->grouped, page = c.fam->page, filter = c.allow || !(range || grouped || page);
 	if (!c.ix) return fail(HNSW_GPU_ERR_ARG, "index is NULL");
-	if (c.nq == 0) return range || form == FK_LISTED ? HNSW_GPU_OK : fk_check_format(who, c.ix, format);
+	if (c.nq == 0) return range || page || form == FK_LISTED ? HNSW_GPU_OK : fk_check_format(who, c.ix, format);
 	if (form != FK_LISTED && form != FK_MFMA) return fail(HNSW_GPU_ERR_ARG, "%s: form %d is neither listed (0) nor matrix cores (1)", who, form);
-	if (!c.queries || (grouped ? !c.group_of : range ? !c.radius : !c.allow) || !c.labels || !c.counts)
-		return fail(HNSW_GPU_ERR_ARG, "%s: NULL buffer%s", who, range || grouped ? "" : " (the filter is required: hnsw_gpu_bruteforce_dev takes none)");
+	if (!c.queries || (grouped ? !c.group_of : range ? !c.radius : page ? !c.next : !c.allow) || !c.labels || !c.counts)
+		return fail(HNSW_GPU_ERR_ARG, "%s: NULL buffer%s", who, range || grouped || page ? "" : " (the filter is required: hnsw_gpu_bruteforce_dev takes none)");
+	// (a call that hands itself down to another form reads the cursors again: the next cursors must not have overwritten them)
+	if (page && c.from && (uintptr_t) c.next < (uintptr_t) c.from + c.nq * 8 && (uintptr_t) c.from < (uintptr_t) c.next + c.nq * 8)
+		return fail(HNSW_GPU_ERR_ARG, "%s: the next cursors overlap the cursors", who);
 	if (grouped && c.group_entries == 0) return fail(HNSW_GPU_ERR_ARG, "%s: a group table of no entries", who);
 	if (c.k == 0 || c.k > 1024) return fail(HNSW_GPU_ERR_ARG, "k %zu out of range [1, 1024]", c.k);
 	if (c.nq > 65535) return fail(HNSW_GPU_ERR_ARG, "at most 65535 queries per call");
@@ -662,16 +669,17 @@ static int fk_pass(FkCall &c, int format, const FkMfma &m, uint32_t mwords, uint
 	const size_t o_mof = o_bound + round_up(nq * 4, 256);
 	const size_t o_cnt = o_mof + round_up(nq * 4, 256);
 	const size_t o_fcnt = o_cnt + round_up(nq * 4 + 64, 256);
-	const size_t o_grp = o_fcnt + 256;                            // (grouped k-NN: the group of every key)
+	const size_t o_low = o_fcnt + 256;                            // (a page call with cursors: the filter's lower comparison values)
+	const size_t o_grp = o_low + round_up(nq * 4, 256);           // (grouped k-NN: the group of every key)
 	const size_t total = o_grp + (grouped ? round_up(nq * k * 4, 256) : 0);
 	if ((rc = buf_reserve(&fw->bfs, total, c.fam->who, "the per-query scratch"))) return rc;
 	if (!listed && (rc = buf_reserve(&fw->cand, nq * (size_t) cap * 4, c.fam->who, "the candidate lists"))) return rc;
 	char *B = (char *) fw->bfs.p;
 	uint64_t *keys = (uint64_t *) (B + o_keys);
 	uint32_t *rcount = (uint32_t *) (B + o_rcnt), *pcount = (uint32_t *) (B + o_pcnt);
-	unsigned long long *sum = c.radius && !grouped ? (unsigned long long *) (B + o_sum) : nullptr, *fcnt = (unsigned long long *) (B + o_fcnt);
+	unsigned long long *sum = (c.radius || c.fam->page) && !grouped ? (unsigned long long *) (B + o_sum) : nullptr, *fcnt = (unsigned long long *) (B + o_fcnt);
 	uint4 *qcopy = (uint4 *) (B + o_q);
-	float *qn = (float *) (B + o_qn), *tau = (float *) (B + o_tau), *bound = (float *) (B + o_bound);
+	float *qn = (float *) (B + o_qn), *tau = (float *) (B + o_tau), *bound = (float *) (B + o_bound), *qlow = (float *) (B + o_low);
 	float2 *qterms = (float2 *) (B + o_qt);
 	uint32_t *mask_of = (uint32_t *) (B + o_mof), *cnt = (uint32_t *) (B + o_cnt), *cand = (uint32_t *) fw->cand.p;
 	uint32_t *overflow = cnt + nq, *kgroups = grouped ? (uint32_t *) (B + o_grp) : nullptr;
@@ -685,7 +693,7 @@ static int fk_pass(FkCall &c, int format, const FkMfma &m, uint32_t mwords, uint
 	fs.list = (const uint32_t *) fw->list.p; fs.off = c.off; fs.nseg = c.fl.nseg; fs.allow_of = c.allow_of;
 	fs.part = (uint64_t *) fw->part.p; fs.pcount = pcount; fs.scored = c.scored; fs.smin = listed ? 0u : smin; fs.skip_samples = skip ? 1u : 0u;
 	fs.sample_k = m.sample_k;
-	fs.radius = c.radius; fs.func = func;
+	fs.radius = c.radius; fs.func = func; fs.from = c.from;
 	if (grouped)
 	{
 		fs.glist = (const uint32_t *) fw->grp.p;
@@ -698,7 +706,12 @@ static int fk_pass(FkCall &c, int format, const FkMfma &m, uint32_t mwords, uint
 		if (slongest)
 		{
 			const dim3 grid((uint32_t) round_up((size_t) splits * nq, 8));
-			with_func(func, [&](auto F) { hipLaunchKernelGGL((fk_scan_kernel<decltype(F)::value, List>), grid, dim3(256), g.lds_listed(k, List::LDS_ENTRY), s, fs); });
+			// (cursors: the instantiation with the key test — key lists only; every other call launches the kernel it launched before)
+			with_func(func, [&](auto F) {
+				if constexpr (std::is_same<List, KeyList>::value)
+					if (c.from) { hipLaunchKernelGGL((fk_scan_kernel<decltype(F)::value, List, true>), grid, dim3(256), g.lds_listed(k, List::LDS_ENTRY), s, fs); return; }
+				hipLaunchKernelGGL((fk_scan_kernel<decltype(F)::value, List>), grid, dim3(256), g.lds_listed(k, List::LDS_ENTRY), s, fs);
+			});
 		}
 		if constexpr (std::is_same<List, GroupedList>::value) hipLaunchKernelGGL(gk_merge_kernel, dim3((uint32_t) nq), dim3(64), (k + 1) * List::LDS_ENTRY, s, fm);
 		else hipLaunchKernelGGL(fk_merge_kernel, dim3((uint32_t) nq), dim3(64), k * 8, s, fm);
@@ -706,34 +719,41 @@ static int fk_pass(FkCall &c, int format, const FkMfma &m, uint32_t mwords, uint
 	if (!listed)
 	{
 		bf_queries_side(reduced, format, c.queries, nq, dim, qchunks, qcopy, qn, qterms, s);
+		// (cursors: the lower comparison values first — make_bounds_kernel halves |q|^2 in place)
+		if (c.from) hipLaunchKernelGGL(make_low_bounds_kernel, dim3((uint32_t) ((nq + 255) / 256)), dim3(256), 0, s, c.from, (const float *) qn, (uint32_t) nq, func, dim, qlow);
 		hipLaunchKernelGGL(make_bounds_kernel, dim3((uint32_t) ((nq + 255) / 256)), dim3(256), 0, s, (const float *) tau, qn, (uint32_t) nq, func, dim, bound);
 		HIPCHK(hipMemsetAsync(cnt, 0, nq * 4 + 64, s));               // (the candidate counts and the overflow word behind them)
 		HIPCHK(hipMemsetAsync(fcnt, 0, 16, s));
 		// the filter over all rows, the allow test (the mask of allowed, or of live, rows) at its append
 		BfArgs a = bf_args(ix, reduced, nq, qcopy, qn, bound, qterms, cand, cnt, cap);
-		a.mask = (const uint32_t *) fw->mask.p; a.mask_of = mask_of; a.mwords = mwords; a.fcnt = fcnt;
+		a.mask = (const uint32_t *) fw->mask.p; a.mask_of = mask_of; a.mwords = mwords; a.fcnt = fcnt; a.qlow = qlow;
 		HIPCHK(hipEventRecord(fw->ev[3], s));
 		if (standin)
 			with_func(func, [&](auto F) {
 				hipLaunchKernelGGL(fkm_standin_kernel<decltype(F)::value>, dim3((uint32_t) nq), dim3(256), g.lds_dist(), s, a, ix->vec, dim, ix->stride, g.nchunks,
-								   g.kiters, g.qpad, c.queries, (const float *) tau);
+								   g.kiters, g.qpad, c.queries, (const float *) tau, c.from);
 			});
-		else if ((rc = with_form(format, [&](auto p) { return bf_filter_pick<BfAllow<decltype(p)>>(ix, a, s); })))
+		else if ((rc = with_form(format, [&](auto p) { return c.from ? bf_filter_pick<BfFrom<BfAllow<decltype(p)>>>(ix, a, s) : bf_filter_pick<BfAllow<decltype(p)>>(ix, a, s); })))
 			return rc;
 		HIPCHK(hipEventRecord(fw->ev[4], s));
 		const FkRescore fr = { ix->vec, dim, ix->stride, g.nchunks, g.kiters, g.qpad, c.queries, (uint32_t) nq, (uint32_t) k, c.radius, mask_of, (uint32_t) c.nfilters,
-							   cand, cnt, cap, grouped ? (const uint32_t *) fw->egrp.p : nullptr, keys, kgroups, rcount, overflow };
+							   cand, cnt, cap, grouped ? (const uint32_t *) fw->egrp.p : nullptr, keys, kgroups, rcount, overflow, c.from };
 		with_list(grouped, [&](auto l) {
 			using List = decltype(l);
 			with_func(func, [&](auto F) {
 				if constexpr (decltype(F)::value != F_MANHATTAN)           // (answered by the listed form: no re-score kernel is compiled for it)
+				{
+					if constexpr (std::is_same<List, KeyList>::value)
+						if (c.from) { hipLaunchKernelGGL((fk_rescore_kernel<decltype(F)::value, List, true>), dim3((uint32_t) ((nq + 3) / 4)), dim3(256), g.lds_rescore(k, List::LDS_ENTRY), s, fr); return; }
 					hipLaunchKernelGGL((fk_rescore_kernel<decltype(F)::value, List>), dim3((uint32_t) ((nq + 3) / 4)), dim3(256), g.lds_rescore(k, List::LDS_ENTRY), s, fr);
+				}
 			});
 		});
 	}
 	// one key list and one count per query -> labels, order, counts, tails, totals
-	const FkEmit fe = { keys, rcount, (uint32_t) k, ix->labels, (uint32_t) ix->n, c.labels, c.dists, c.idx, c.counts, c.totals, sum, kgroups, c.groups };
-	hipLaunchKernelGGL(fk_emit_kernel, dim3((uint32_t) nq), dim3(64), k * 16, s, fe);
+	const FkEmit fe = { keys, rcount, (uint32_t) k, ix->labels, (uint32_t) ix->n, c.labels, c.dists, c.idx, c.counts, c.totals, sum, kgroups, c.groups, c.from, c.next };
+	if (c.next) hipLaunchKernelGGL(fk_emit_kernel<true>, dim3((uint32_t) nq), dim3(64), k * 16, s, fe);
+	else hipLaunchKernelGGL(fk_emit_kernel<false>, dim3((uint32_t) nq), dim3(64), k * 16, s, fe);
 	hipError_t e = hipGetLastError();
 	if (e == hipSuccess) e = hipEventRecord(fw->ev[2], s);
 	fw->host[3] = fw->host[4] = fw->host[5] = fw->host[6] = 0;
@@ -940,21 +960,23 @@ static int fk_auto_settle(FkCall &c, const FkMfma &m, FkAuto *a, uint8_t *d_plan
 
 // The compacted inputs and outputs of a call with two classes, all in perm[] order: position i of each array is query perm[i], so a class is
 // a contiguous run — the listed class positions [0, nq - p), the loose class the rest
-struct FkTmp { float *q; uint32_t *aof; float *radius; uint64_t *labels; float *dists; uint32_t *idx, *counts, *totals, *groups; };
+struct FkTmp { float *q; uint32_t *aof; float *radius; uint64_t *labels; float *dists; uint32_t *idx, *counts, *totals, *groups; uint64_t *from, *next; };
 static int fk_auto_gather(FkCall &c, FkTmp *t)
 {
 	FkWs *fw = &c.ix->fk;
 	const size_t nq = c.nq, k = c.k, dim = c.ix->meta.dim;
 	const size_t o_aof = round_up(nq * dim * 4, 256), o_rad = o_aof + round_up(nq * 4, 256), o_lab = o_rad + round_up(nq * 4, 256),
 				 o_dst = o_lab + round_up(nq * k * 8, 256), o_idx = o_dst + round_up(nq * k * 4, 256), o_cnt = o_idx + round_up(nq * k * 4, 256),
-				 o_tot = o_cnt + round_up(nq * 4, 256), o_grp = o_tot + round_up(nq * 4, 256), bytes = o_grp + round_up(c.groups ? nq * k * 4 : 0, 256);
+				 o_tot = o_cnt + round_up(nq * 4, 256), o_grp = o_tot + round_up(nq * 4, 256), o_from = o_grp + round_up(c.groups ? nq * k * 4 : 0, 256), o_next = o_from + round_up(c.from ? nq * 8 : 0, 256),
+				 bytes = o_next + round_up(c.next ? nq * 8 : 0, 256);
 	if (int rc = buf_reserve(&fw->tmp, bytes, c.fam->who, "the classes' compacted queries and results")) return rc;
 	char *B = (char *) fw->tmp.p;
 	t->q = (float *) B; t->aof = c.allow_of ? (uint32_t *) (B + o_aof) : nullptr; t->radius = c.radius ? (float *) (B + o_rad) : nullptr;
 	t->labels = (uint64_t *) (B + o_lab); t->dists = c.dists ? (float *) (B + o_dst) : nullptr; t->idx = c.idx ? (uint32_t *) (B + o_idx) : nullptr;
 	t->counts = (uint32_t *) (B + o_cnt); t->totals = c.totals ? (uint32_t *) (B + o_tot) : nullptr; t->groups = c.groups ? (uint32_t *) (B + o_grp) : nullptr;
+	t->from = c.from ? (uint64_t *) (B + o_from) : nullptr; t->next = c.next ? (uint64_t *) (B + o_next) : nullptr;
 	FkGather g = { (const uint32_t *) fw->perm.p, 0u, (uint32_t) nq, c.queries, (uint32_t) dim, t->q, c.allow_of, t->aof, c.radius, t->radius,
-				   (dim % 4 == 0 && (uintptr_t) c.queries % 16 == 0) ? 1u : 0u };
+				   (dim % 4 == 0 && (uintptr_t) c.queries % 16 == 0) ? 1u : 0u, c.from, t->from };
 	const size_t chunks = nq * (g.vec4 ? dim / 4 : dim);            // (both classes in one launch: each is a run of positions)
 	hipLaunchKernelGGL(fkp_gather_kernel, dim3((uint32_t) ((chunks + 255) / 256)), dim3(256), 0, c.s, g);
 	HIPCHK(hipGetLastError());
@@ -968,12 +990,13 @@ static FkCall fk_auto_class(const FkCall &c, const FkTmp &t, size_t first, size_
 	s.queries = t.q + first * dim; s.nq = count; s.allow_of = t.aof ? t.aof + first : nullptr; s.radius = t.radius ? t.radius + first : nullptr;
 	s.labels = t.labels + first * c.k; s.dists = t.dists ? t.dists + first * c.k : nullptr; s.idx = t.idx ? t.idx + first * c.k : nullptr;
 	s.counts = t.counts + first; s.totals = t.totals ? t.totals + first : nullptr; s.groups = t.groups ? t.groups + first * c.k : nullptr; s.longest = longest;
+	s.from = t.from ? t.from + first : nullptr; s.next = t.next ? t.next + first : nullptr;
 	return s;
 }
 static int fk_auto_scatter(const FkCall &c, const FkTmp &t, size_t first, size_t count)
 {
 	FkScatter sc = { (const uint32_t *) c.ix->fk.perm.p, (uint32_t) first, (uint32_t) count, (uint32_t) c.k, t.labels, t.dists, t.idx, t.counts, t.totals,
-					 c.labels, c.dists, c.idx, c.counts, c.totals, t.groups, c.groups };
+					 c.labels, c.dists, c.idx, c.counts, c.totals, t.groups, c.groups, t.next, c.next };
 	hipLaunchKernelGGL(fkp_scatter_kernel, dim3((uint32_t) ((count * c.k + 255) / 256)), dim3(256), 0, c.s, sc);
 	HIPCHK(hipGetLastError());
 	return HNSW_GPU_OK;
@@ -997,7 +1020,9 @@ static int fk_run(FkCall c, int form, int format, bool aut, uint8_t *d_plan)
 	FkWs::Diag &d = fw->*c.fam->diag;
 	FkWs::Plan &pl = fw->*c.fam->plan;
 	const size_t nq = c.nq;
-	const FkMfma m = fk_mfma_of(ix, format, c.k, c.fam->grouped);
+	FkMfma m = fk_mfma_of(ix, format, c.k, c.fam->grouped);
+	// a page with totals and no radius: every remaining row would be a candidate — the listed form, before any filter launch
+	if (c.fam->page && c.totals && !c.radius) m.avail = false;
 	FkAuto a = {};
 	if (aut) fk_auto_begin(ix, m, &a);
 	int rc = fk_begin(c);
@@ -1055,7 +1080,8 @@ static int fk_host(const FkCall &h, int form, int format, bool aut, uint8_t *pla
 	const size_t qb = round_up(nq * dim * 4, 256), rb = round_up(h.radius ? nq * 4 : 0, 256), fb = round_up(h.allow ? h.nfilters * words * 4 : 0, 256),
 				 ob = round_up(of ? nq * 4 : 0, 256), lb = round_up(nq * k * 8, 256), db = round_up(nq * k * 4, 256), cb = round_up(nq * 4, 256);
 	const size_t tb = round_up(h.group_of ? h.group_entries * 4 : 0, 256), o_tab = qb + rb + fb + ob + lb + 2 * db + 2 * cb + round_up(plan ? nq : 0, 256);
-	int rc = ensure_scratch(ix, o_tab + tb + (h.groups ? db : 0));   // (grouped k-NN: the group table and the groups behind everything else)
+	const size_t o_cur = o_tab + tb + (h.groups ? db : 0), ub = round_up(nq * 8, 256);   // (the page call: the cursors and the next cursors behind that)
+	int rc = ensure_scratch(ix, o_cur + (h.from ? ub : 0) + (h.next ? ub : 0));   // (grouped k-NN: the group table and the groups behind everything else)
 	if (rc) return rc;
 	char *p = (char *) ix->scratch, *o = p + qb + rb + fb + ob;
 	FkCall d = h;
@@ -1065,6 +1091,8 @@ static int fk_host(const FkCall &h, int form, int format, bool aut, uint8_t *pla
 	d.totals = h.totals ? (uint32_t *) (o + lb + 2 * db + cb) : nullptr; d.s = nullptr;
 	uint8_t *dp = plan ? (uint8_t *) (o + lb + 2 * db + 2 * cb) : nullptr;
 	d.group_of = h.group_of ? (uint32_t *) (p + o_tab) : nullptr; d.groups = h.groups ? (uint32_t *) (p + o_tab + tb) : nullptr;
+	d.from = h.from ? (uint64_t *) (p + o_cur) : nullptr; d.next = h.next ? (uint64_t *) (p + o_cur + (h.from ? ub : 0)) : nullptr;
+	if (h.from) HIPCHK(hipMemcpy((void *) d.from, h.from, nq * 8, hipMemcpyHostToDevice));
 	if (h.group_of) HIPCHK(hipMemcpy((void *) d.group_of, h.group_of, h.group_entries * 4, hipMemcpyHostToDevice));
 	HIPCHK(hipMemcpy((void *) d.queries, h.queries, nq * dim * 4, hipMemcpyHostToDevice));
 	if (h.radius) HIPCHK(hipMemcpy((void *) d.radius, h.radius, nq * 4, hipMemcpyHostToDevice));
@@ -1077,6 +1105,7 @@ static int fk_host(const FkCall &h, int form, int format, bool aut, uint8_t *pla
 	HIPCHK(hipMemcpy(h.counts, d.counts, nq * 4, hipMemcpyDeviceToHost));
 	if (h.totals) HIPCHK(hipMemcpy(h.totals, d.totals, nq * 4, hipMemcpyDeviceToHost));
 	if (h.groups) HIPCHK(hipMemcpy(h.groups, d.groups, nq * k * 4, hipMemcpyDeviceToHost));
+	if (h.next) HIPCHK(hipMemcpy(h.next, d.next, nq * 8, hipMemcpyDeviceToHost));
 	if (plan) HIPCHK(hipMemcpy(plan, dp, nq, hipMemcpyDeviceToHost));
 	return HNSW_GPU_OK;
 }
@@ -1168,6 +1197,37 @@ extern "C" int hnsw_gpu_range_knn_auto(hnsw_gpu_index *ix, int format, const coo
 	return fk_host(fk_range_call(ix, queries, nq, radius, k, allow, allow_bits, nfilters, allow_of, labels, dists, idx, counts, totals, nullptr), FK_MFMA, format, true, plan);
 }
 
+// The page call (include/hnsw_gpu.h): radius search's pipeline with a cursor per query as one more qualifier and the
+// cursors of the following page as one more output.  form: listed, matrix cores, or HNSW_GPU_RANGE_AUTO = per query, as the automatic calls
+// plan — the cursor does not change the plan: the listed form scores every allowed row whatever the cursor is
+static FkCall fk_page_call(hnsw_gpu_index *ix, const coord_t *queries, size_t nq, const dist_t *radius, const uint64_t *from, size_t k, const uint32_t *allow,
+						   size_t allow_bits, size_t nfilters, const uint32_t *allow_of, label_t *labels, dist_t *dists, idx_t *idx, uint32_t *counts,
+						   uint32_t *totals, uint64_t *next, void *stream)
+{
+	FkCall c = { &FK_PAGE, ix, queries, nq, radius, k, allow, allow_bits, nfilters, allow_of, labels, dists, idx, counts, totals, (hipStream_t) stream };
+	c.from = from; c.next = next;
+	return c;
+}
+
+extern "C" int hnsw_gpu_knn_page_dev(hnsw_gpu_index *ix, int form, int format, const coord_t *d_queries, size_t nq, const dist_t *d_radius,
+									 const uint64_t *d_from, size_t k, const uint32_t *d_allow, size_t allow_bits, size_t nfilters,
+									 const uint32_t *d_allow_of, label_t *d_labels, dist_t *d_dists, idx_t *d_idx, uint32_t *d_counts,
+									 uint32_t *d_totals, uint64_t *d_next, uint8_t *d_plan, void *stream)
+{
+	const bool aut = form == HNSW_GPU_RANGE_AUTO;
+	return fk_run(fk_page_call(ix, d_queries, nq, d_radius, d_from, k, d_allow, allow_bits, nfilters, d_allow_of, d_labels, d_dists, d_idx, d_counts, d_totals, d_next, stream),
+				  aut ? FK_MFMA : form, format, aut, aut ? d_plan : nullptr);
+}
+
+extern "C" int hnsw_gpu_knn_page(hnsw_gpu_index *ix, int form, int format, const coord_t *queries, size_t nq, const dist_t *radius, const uint64_t *from,
+								 size_t k, const uint32_t *allow, size_t allow_bits, size_t nfilters, const uint32_t *allow_of, label_t *labels,
+								 dist_t *dists, idx_t *idx, uint32_t *counts, uint32_t *totals, uint64_t *next, uint8_t *plan)
+{
+	const bool aut = form == HNSW_GPU_RANGE_AUTO;
+	return fk_host(fk_page_call(ix, queries, nq, radius, from, k, allow, allow_bits, nfilters, allow_of, labels, dists, idx, counts, totals, next, nullptr),
+				   aut ? FK_MFMA : form, format, aut, aut ? plan : nullptr);
+}
+
 static FkCall gk_call(hnsw_gpu_index *ix, const coord_t *queries, size_t nq, size_t k, const uint32_t *group_of, size_t group_entries, const dist_t *radius,
 					  const uint32_t *allow, size_t allow_bits, size_t nfilters, const uint32_t *allow_of, label_t *labels, dist_t *dists, idx_t *idx,
 					  uint32_t *groups, uint32_t *counts, void *stream)
@@ -1216,6 +1276,7 @@ static int fk_plan_out(hnsw_gpu_index *ix, FkWs::Plan FkWs::*which, uint64_t out
 extern "C" int hnsw_gpu_last_filtered_knn_plan(hnsw_gpu_index *ix, uint64_t out[8]) { return fk_plan_out(ix, &FkWs::plan, out); }
 extern "C" int hnsw_gpu_last_range_knn_plan(hnsw_gpu_index *ix, uint64_t out[8]) { return fk_plan_out(ix, &FkWs::rplan, out); }
 extern "C" int hnsw_gpu_last_grouped_knn_plan(hnsw_gpu_index *ix, uint64_t out[8]) { return fk_plan_out(ix, &FkWs::gplan, out); }
+extern "C" int hnsw_gpu_last_knn_page_plan(hnsw_gpu_index *ix, uint64_t out[8]) { return fk_plan_out(ix, &FkWs::pplan, out); }
 
 static uint64_t fk_us(float ms) { return (uint64_t) std::llround((double) ms * 1000.0); }
 
@@ -1250,11 +1311,11 @@ extern "C" int hnsw_gpu_last_filtered_knn_mfma(hnsw_gpu_index *ix, uint64_t out[
 extern "C" int hnsw_gpu_last_grouped_knn_mfma(hnsw_gpu_index *ix, uint64_t out[7]) { return fk_filter_out(ix, &FkWs::gf, out); }
 extern "C" long long hnsw_gpu_last_grouped_knn_overflowed(hnsw_gpu_index *ix) { return ix ? (long long) ix->fk.gf.overflowed : -1; }
 
-extern "C" int hnsw_gpu_last_range_knn(hnsw_gpu_index *ix, uint64_t out[8])
+static int fk_range_out(hnsw_gpu_index *ix, FkWs::Diag FkWs::*which, uint64_t out[8])
 {
 	if (!ix || !out) return fail(HNSW_GPU_ERR_ARG, "NULL argument");
 	std::lock_guard<std::recursive_mutex> lock_(ix->mu);
-	const FkWs::Diag &m = ix->fk.r;
+	const FkWs::Diag &m = ix->fk.*which;
 	out[0] = m.listed; out[1] = m.scored; out[2] = m.dist_pass; out[3] = m.appended; out[4] = m.totals;
 	out[5] = fk_us(m.build_ms); out[6] = fk_us(m.filter_ms); out[7] = fk_us(m.call_ms);
 	return HNSW_GPU_OK;
@@ -1266,6 +1327,9 @@ static int fk_form_out(hnsw_gpu_index *ix, FkWs::Diag FkWs::*which)
 	std::lock_guard<std::recursive_mutex> lock_(ix->mu);
 	return (ix->fk.*which).form;
 }
+extern "C" int hnsw_gpu_last_range_knn(hnsw_gpu_index *ix, uint64_t out[8]) { return fk_range_out(ix, &FkWs::r, out); }
+extern "C" int hnsw_gpu_last_knn_page(hnsw_gpu_index *ix, uint64_t out[8]) { return fk_range_out(ix, &FkWs::p, out); }
+extern "C" int hnsw_gpu_last_knn_page_form(hnsw_gpu_index *ix) { return fk_form_out(ix, &FkWs::p); }
 extern "C" int hnsw_gpu_last_filtered_knn_form(hnsw_gpu_index *ix) { return fk_form_out(ix, &FkWs::k); }
 extern "C" int hnsw_gpu_last_range_knn_form(hnsw_gpu_index *ix) { return fk_form_out(ix, &FkWs::r); }
 extern "C" int hnsw_gpu_last_grouped_knn_form(hnsw_gpu_index *ix) { return fk_form_out(ix, &FkWs::g); }

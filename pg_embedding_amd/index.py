@@ -608,6 +608,185 @@ class GpuIndex:
         return {"listed": int(v[0]), "rows_scored": int(v[1]), "dist_pass": int(v[2]), "appended": int(v[3]), "totals": int(v[4]),
                 "build_ms": v[5] / 1000.0, "filter_ms": v[6] / 1000.0, "call_ms": v[7] / 1000.0}
 
+    # ---------------------------------------------------------------- exact k-NN continuation
+    @staticmethod
+    def _page_form(form, rows):
+        """(form, format) of hnsw_gpu_knn_page: listed (0), matrix cores (1), automatic (2)"""
+        code = GpuIndex._fk_form(form, rows)
+        return (0 if code is None else 2 if form == "auto" else 1), code or 0
+
+    def knn_page(self, queries: np.ndarray, k: int, start=None, radius=None, allow=None, allow_of=None, return_idx: bool = False,
+                 totals: bool = False, form=None, rows=None):
+        """The next k exact nearest elements after a cursor per query, host buffers (hnsw_gpu_knn_page): ORDER BY distance LIMIT k OFFSET
+        anything, page by page.  start: None (from the start) or a uint64 array [nq] of cursors — 0, or the `next` of an earlier page of
+        the same query, filter and radius; radius: None (no radius), a scalar or one value per query, as in range_knn(); allow / allow_of
+        as in range_knn() (allow=None: every label passes).  Returns filtered_knn()'s dict — labels [nq, k] u64 in ascending (distance,
+        label, element) order (tail ~0), dists [nq, k] f32 (tail +inf), counts [nq] u32, idx with return_idx=True — plus next [nq] u64 =
+        the cursor of the following page (the largest returned key ord(distance) << 32 | element, plus 1; the query's own cursor where
+        nothing was returned) and with totals=True totals [nq] u32 = the rows in range not yet paged past, this page included.  A page
+        shorter than k is the last.  form / rows as in range_knn(); form="auto" adds plan [nq] u8 (last_knn_page_plan())."""
+        fm, code = self._page_form(form, rows)
+        queries = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, self.meta.dim)
+        nq, k = queries.shape[0], int(k)
+        rad = None if radius is None else np.ascontiguousarray(np.broadcast_to(np.asarray(radius, dtype=np.float32).reshape(-1), (nq,)))
+        cur = None if start is None else np.ascontiguousarray(start, dtype=np.uint64).reshape(nq)
+        words, bits, nf = _pack_allow_numpy(allow)
+        of = None if allow_of is None or words is None else np.ascontiguousarray(allow_of, dtype=np.uint32).reshape(nq)
+        out = {"labels": np.empty((nq, k), np.uint64), "dists": np.empty((nq, k), np.float32), "counts": np.empty(nq, np.uint32),
+               "next": np.empty(nq, np.uint64)}
+        if return_idx:
+            out["idx"] = np.empty((nq, k), np.uint32)
+        if totals:
+            out["totals"] = np.empty(nq, np.uint32)
+        if form == "auto":
+            out["plan"] = np.empty(nq, np.uint8)
+        ptr = lambda a: None if a is None else a.ctypes.data
+        check(self.L.hnsw_gpu_knn_page(self._h, fm, code, queries.ctypes.data, nq, ptr(rad), ptr(cur), k, ptr(words), bits, nf, ptr(of),
+                                       out["labels"].ctypes.data, out["dists"].ctypes.data, ptr(out.get("idx")), out["counts"].ctypes.data,
+                                       ptr(out.get("totals")), out["next"].ctypes.data, ptr(out.get("plan"))), "hnsw_gpu_knn_page")
+        return out
+
+    def knn_page_torch(self, queries, k: int, start=None, radius=None, allow=None, allow_of=None, return_idx: bool = False, totals: bool = False,
+                       form=None, rows=None):
+        """knn_page() with everything resident in HBM (hnsw_gpu_knn_page_dev on torch's current stream, which the call synchronises).
+        start: None or an int64 tensor [nq] (the bits of a uint64); radius: None, a number or a float tensor [nq]; allow / allow_of as in
+        range_knn_torch().  Returns range_knn_torch()'s dict plus next [nq] int64 (the bits of a uint64); plan [nq] uint8 with form="auto"."""
+        fm, code = self._page_form(form, rows)
+        torch = _torch()
+        assert queries.is_cuda and queries.dtype == torch.float32 and queries.is_contiguous()
+        nq, k, dev = queries.shape[0], int(k), queries.device
+        if radius is None:
+            rad = None
+        elif torch.is_tensor(radius):
+            rad = radius.to(device=dev, dtype=torch.float32).reshape(-1).expand(nq).contiguous()
+        else:
+            rad = torch.full((nq,), float(radius), dtype=torch.float32, device=dev)
+        cur = None
+        if start is not None:
+            if start.dtype != torch.int64 or start.numel() != nq:
+                raise ValueError("start is an int64 tensor with one cursor per query")
+            cur = start.to(device=dev).contiguous()
+        words, bits, nf = _pack_allow_torch(allow, dev)
+        of = None if allow_of is None or words is None else allow_of.to(device=dev, dtype=torch.int32).contiguous()
+        if of is not None and of.numel() != nq:
+            raise ValueError("allow_of names one filter per query")
+        out = {"labels": torch.empty((nq, k), dtype=torch.int64, device=dev),
+               "dists": torch.empty((nq, k), dtype=torch.float32, device=dev),
+               "counts": torch.empty(nq, dtype=torch.int32, device=dev),
+               "next": torch.empty(nq, dtype=torch.int64, device=dev)}
+        if return_idx:
+            out["idx"] = torch.empty((nq, k), dtype=torch.int32, device=dev)
+        if totals:
+            out["totals"] = torch.empty(nq, dtype=torch.int32, device=dev)
+        if form == "auto":
+            out["plan"] = torch.empty(nq, dtype=torch.uint8, device=dev)
+        s = torch.cuda.current_stream(dev).cuda_stream
+        check(self.L.hnsw_gpu_knn_page_dev(self._h, fm, code, queries.data_ptr(), nq, _dptr(rad), _dptr(cur), k, _dptr(words), bits, nf, _dptr(of),
+                                           out["labels"].data_ptr(), out["dists"].data_ptr(), _dptr(out.get("idx")), out["counts"].data_ptr(),
+                                           _dptr(out.get("totals")), out["next"].data_ptr(), _dptr(out.get("plan")), s), "hnsw_gpu_knn_page_dev")
+        return out
+
+    def last_knn_page(self) -> dict:
+        """The pass that answered the last knn_page call on this mirror, in last_range_knn()'s figures (hnsw_gpu_last_knn_page)."""
+        v = (C.c_uint64 * 8)()
+        check(self.L.hnsw_gpu_last_knn_page(self._h, v), "hnsw_gpu_last_knn_page")
+        return {"listed": int(v[0]), "rows_scored": int(v[1]), "dist_pass": int(v[2]), "appended": int(v[3]), "totals": int(v[4]),
+                "build_ms": v[5] / 1000.0, "filter_ms": v[6] / 1000.0, "call_ms": v[7] / 1000.0}
+
+    def last_knn_page_form(self) -> Optional[str]:
+        """The form that answered the last knn_page call on this mirror: "listed", "f32", "f16" or "bf16", or None before the first one
+        (hnsw_gpu_last_knn_page_form)."""
+        return {0: "listed", 1: "f32", 2: "f16", 3: "bf16"}.get(int(self.L.hnsw_gpu_last_knn_page_form(self._h)))
+
+    def last_knn_page_plan(self) -> dict:
+        """last_filtered_knn_plan() for the last form="auto" knn_page call (hnsw_gpu_last_knn_page_plan)."""
+        v = (C.c_uint64 * 8)()
+        check(self.L.hnsw_gpu_last_knn_page_plan(self._h, v), "hnsw_gpu_last_knn_page_plan")
+        return self._plan_dict(v)
+
+    def knn_limit_torch(self, queries, limit: int, page: int = 1024, radius=None, allow=None, allow_of=None, return_idx: bool = False, form=None,
+                        rows=None):
+        """The exact LIMIT n for any n: what one call with k = limit would return if the exact calls took a k above 1 024.  Walks
+        knn_page_torch() in pages of at most min(page, 1 024) rows — after each page only the queries whose page was full go on, scan_torch's
+        rule — concatenates the pages, and puts each query's rows into (distance, label, element) order: stable sorts by element, label and
+        the order-preserving image of the distance bits.  Returns labels [nq, limit] int64 (tail -1), dists [nq, limit] (tail +inf), counts
+        [nq] int32 = min(limit, rows in range), idx [nq, limit] int32 (tail -1) with return_idx=True.  radius / allow / allow_of / form /
+        rows as in knn_page_torch()."""
+        torch = _torch()
+        nq, limit, dev = queries.shape[0], int(limit), queries.device
+        if limit < 1:
+            raise ValueError("limit is at least 1")
+        step = max(1, min(int(page), 1024, limit))
+        if radius is not None and torch.is_tensor(radius):
+            radius = radius.to(device=dev, dtype=torch.float32).reshape(-1).expand(nq)
+        labels = torch.full((nq, limit), -1, dtype=torch.int64, device=dev)
+        dists = torch.full((nq, limit), float("inf"), dtype=torch.float32, device=dev)
+        idx = torch.full((nq, limit), -1, dtype=torch.int32, device=dev)
+        counts = torch.zeros(nq, dtype=torch.int32, device=dev)
+        active = torch.arange(nq, device=dev)
+        cur, done = None, 0
+        while active.numel() and done < limit:
+            kk = min(step, limit - done)
+            everyone = active.numel() == nq
+            got = self.knn_page_torch(queries if everyone else queries[active].contiguous(), kk, start=cur,
+                                      radius=radius[active] if torch.is_tensor(radius) else radius, allow=allow,
+                                      allow_of=None if allow_of is None else allow_of.to(dev)[active], return_idx=True, form=form, rows=rows)
+            labels[active, done:done + kk] = got["labels"]
+            dists[active, done:done + kk] = got["dists"]
+            idx[active, done:done + kk] = got["idx"]
+            counts[active] += got["counts"]
+            more = got["counts"] == kk
+            active, cur, done = active[more], got["next"][more].contiguous(), done + kk
+        # (distance, label, element) order over the whole answer; the unused tail stays behind every row, whatever its distance is
+        u = dists.view(torch.int32).to(torch.int64) & 0xFFFFFFFF
+        od = torch.where((u & 0x80000000) != 0, ~u & 0xFFFFFFFF, u | 0x80000000)
+        unused = (torch.arange(limit, device=dev)[None, :] >= counts[:, None]).to(torch.int8)
+        order = torch.argsort(idx.to(torch.int64) & 0xFFFFFFFF, dim=1, stable=True)
+        for key in (labels ^ (-1 << 63), od, unused):                 # (labels compare as unsigned)
+            order = order.gather(1, torch.argsort(key.gather(1, order), dim=1, stable=True))
+        out = {"labels": labels.gather(1, order), "dists": dists.gather(1, order), "counts": counts}
+        if return_idx:
+            out["idx"] = idx.gather(1, order)
+        return out
+
+    def knn_limit(self, queries: np.ndarray, limit: int, page: int = 1024, radius=None, allow=None, allow_of=None, return_idx: bool = False,
+                  form=None, rows=None):
+        """knn_limit_torch() over host buffers (knn_page()): labels [nq, limit] u64 (tail ~0), dists [nq, limit] f32 (tail +inf), counts [nq]
+        u32, idx [nq, limit] u32 (tail 0xFFFFFFFF) with return_idx=True."""
+        queries = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, self.meta.dim)
+        nq, limit = queries.shape[0], int(limit)
+        if limit < 1:
+            raise ValueError("limit is at least 1")
+        step = max(1, min(int(page), 1024, limit))
+        rad = None if radius is None else np.broadcast_to(np.asarray(radius, dtype=np.float32).reshape(-1), (nq,))
+        of = None if allow_of is None else np.asarray(allow_of).reshape(nq)
+        labels = np.full((nq, limit), 0xFFFFFFFFFFFFFFFF, np.uint64)
+        dists = np.full((nq, limit), np.inf, np.float32)
+        idx = np.full((nq, limit), 0xFFFFFFFF, np.uint32)
+        counts = np.zeros(nq, np.uint32)
+        active = np.arange(nq)
+        cur, done = None, 0
+        while active.size and done < limit:
+            kk = min(step, limit - done)
+            got = self.knn_page(queries[active], kk, start=cur, radius=None if rad is None else rad[active], allow=allow,
+                                allow_of=None if of is None else of[active], return_idx=True, form=form, rows=rows)
+            labels[active, done:done + kk] = got["labels"]
+            dists[active, done:done + kk] = got["dists"]
+            idx[active, done:done + kk] = got["idx"]
+            counts[active] += got["counts"]
+            more = got["counts"] == kk
+            active, cur, done = active[more], got["next"][more], done + kk
+        u = dists.view(np.uint32)
+        od = np.where(u & np.uint32(0x80000000), ~u, u | np.uint32(0x80000000))
+        unused = np.arange(limit)[None, :] >= counts[:, None]
+        for i in range(nq):
+            o = np.lexsort((idx[i], labels[i], od[i], unused[i]))
+            labels[i], dists[i], idx[i] = labels[i][o], dists[i][o], idx[i][o]
+        out = {"labels": labels, "dists": dists, "counts": counts}
+        if return_idx:
+            out["idx"] = idx
+        return out
+
     # ---------------------------------------------------------------- exact grouped k-NN
     def grouped_knn(self, queries: np.ndarray, k: int, group_of, allow=None, allow_of=None, radius=None, return_idx: bool = False, form=None,
                     rows=None):
