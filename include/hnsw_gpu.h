@@ -371,8 +371,8 @@ int hnsw_gpu_range_knn_auto(hnsw_gpu_index *ix, int format, const coord_t *queri
  * Argument rules are radius search's, without its need for radii: k outside [1, 1024], nq > 65535, a NULL d_queries / d_labels / d_counts /
  * d_next, a d_next that overlaps d_from, a form that is none of the three, with a filter allow_bits == 0 or nfilters == 0, k and dim too large for one block's LDS:
  * HNSW_GPU_ERR_ARG before anything is launched (outputs untouched, d_next included); nq == 0: OK, nothing touched.  The call synchronises
- * `stream`.  Grouped k-NN takes no cursor: a group whose nearest member lies before the cursor still has members after it, so a key alone
- * does not tell which groups are spent. */
+ * `stream`.  This call takes no groups: a group whose nearest member lies before the cursor still has members after it, so the key test
+ * alone does not tell which groups are spent.  Paging through distinct groups is hnsw_gpu_grouped_knn_page_dev, which marks them first. */
 enum { HNSW_GPU_RANGE_AUTO = 2 };
 int hnsw_gpu_knn_page_dev(hnsw_gpu_index *ix, int form, int format, const coord_t *d_queries, size_t nq, const dist_t *d_radius,
 						  const uint64_t *d_from, size_t k, const uint32_t *d_allow, size_t allow_bits, size_t nfilters,
@@ -444,6 +444,45 @@ int hnsw_gpu_grouped_knn_auto(hnsw_gpu_index *ix, int format, const coord_t *que
 							  const uint32_t *group_of, size_t group_entries, const dist_t *radius,
 							  const uint32_t *allow, size_t allow_bits, size_t nfilters, const uint32_t *allow_of,
 							  label_t *labels, dist_t *dists, idx_t *idx, uint32_t *groups, uint32_t *counts, uint8_t *plan);
+
+/* Exact grouped k-NN continuation: the next k distinct GROUPS after a cursor (csrc/device_grouped_page.h) — the exact plan of
+ *   SELECT DISTINCT ON (doc_id) ... ORDER BY emb <-> q LIMIT k OFFSET anything, page by page, with filter and radius both optional.
+ * Notation of hnsw_gpu_grouped_knn_dev and hnsw_gpu_knn_page_dev: R(q) restricted to the elements that take part; key(q, e) = ord_f32(d(q, e))
+ * << 32 | e; rep(g) = the member of g in R(q) with the smallest key; G(q) = the groups with a member in R(q).
+ *   d_from    nq uint64, or NULL: the cursor of each query.  0 = from the start; NULL = 0 for every query.  ANY value has a meaning:
+ *   G_from(q) = { g in G(q) : key(q, rep(g)) >= from_q } — equivalently: no member of g in R(q) has a key below from_q.
+ *   The answer: the min(k, |G_from|) representatives with the smallest keys, written in ascending (distance, label, element) order; d_labels,
+ *             d_dists, d_idx, d_groups, d_counts and their padded tails exactly as hnsw_gpu_grouped_knn_dev writes them.
+ *   d_next    nq uint64 (required; must not overlap d_from): the largest returned key + 1, or from_q where nothing was returned.
+ *   d_totals  nq or NULL: |G_from(q)|, the distinct groups in range not yet paged past, this page included.  On a first page that is
+ *             COUNT(DISTINCT group) in range.
+ *   With every cursor 0 (or d_from NULL) and no totals the five outputs are byte for byte hnsw_gpu_grouped_knn_dev's, from that call's
+ *   kernels: no mark pass, no extra buffer (with d_from given, one small kernel and one wait find out that no cursor is set).
+ *   Page walk: feeding d_next back until counts < k visits every group of G(q) exactly once, in ascending representative key — as long as
+ *   rows, vacuum bits, filter, radius and group table do not change between the pages.
+ *   A cursor above the radius selects nothing: counts 0, totals 0, next == from.  NaN distances stay outside the grouped contract.
+ * How: pages come out in the order of the representatives' keys, so the groups already shown are those with a member in R(q) whose key
+ * lies below the cursor.  A first pass over the query's list marks them in a bit row over the group words [0, W), W = 1 + the largest
+ * word of the table that is not 0xFFFFFFFF; the second pass is grouped k-NN's scan, to which a marked group takes no part.  So a page
+ * behind the first scores the query's list twice.  The marks — W / 8 bytes per query, twice that with totals, zeroed per call — obey the
+ * 64 MiB keep-between-calls rule and a budget of 1 GiB per call: a call whose marks exceed it gets HNSW_GPU_ERR_ARG, with the largest nq
+ * that fits in the message, before any list is built (one query always fits).  Group words far apart cost memory, not time.
+ * This is the LISTED form only (no form, no format): the matrix-core and automatic forms take no cursor.
+ * Argument rules are hnsw_gpu_grouped_knn_dev's and the page call's: k outside [1, 1024], nq > 65535, a NULL d_queries / d_group_of /
+ * d_labels / d_counts / d_next, a d_next that overlaps d_from, group_entries == 0, with a filter allow_bits == 0 or nfilters == 0, k and dim
+ * too large for one block's LDS: HNSW_GPU_ERR_ARG before anything is launched (outputs untouched, d_next included); nq == 0: OK, nothing
+ * touched.  The call synchronises `stream`.  hnsw_gpu_last_grouped_knn_page (hnsw_gpu_diag.h) reports its counters. */
+int hnsw_gpu_grouped_knn_page_dev(hnsw_gpu_index *ix, const coord_t *d_queries, size_t nq, size_t k,
+								  const uint32_t *d_group_of, size_t group_entries, const dist_t *d_radius, const uint64_t *d_from,
+								  const uint32_t *d_allow, size_t allow_bits, size_t nfilters, const uint32_t *d_allow_of,
+								  label_t *d_labels, dist_t *d_dists, idx_t *d_idx, uint32_t *d_groups, uint32_t *d_counts,
+								  uint32_t *d_totals, uint64_t *d_next, void *stream);
+/* Host-pointer form: copies in, runs on the default stream, copies out. */
+int hnsw_gpu_grouped_knn_page(hnsw_gpu_index *ix, const coord_t *queries, size_t nq, size_t k,
+							  const uint32_t *group_of, size_t group_entries, const dist_t *radius, const uint64_t *from,
+							  const uint32_t *allow, size_t allow_bits, size_t nfilters, const uint32_t *allow_of,
+							  label_t *labels, dist_t *dists, idx_t *idx, uint32_t *groups, uint32_t *counts,
+							  uint32_t *totals, uint64_t *next);
 
 /* Milliseconds the most recent search kernel of this index spent on the device,
  * from HIP events recorded on its stream around the launch (waits for it). */

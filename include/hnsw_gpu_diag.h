@@ -190,6 +190,13 @@ int hnsw_gpu_last_knn_page(hnsw_gpu_index *ix, uint64_t out[8]);
 int hnsw_gpu_last_knn_page_form(hnsw_gpu_index *ix);
 int hnsw_gpu_last_knn_page_plan(hnsw_gpu_index *ix, uint64_t out[8]);
 
+/* The mirror's last hnsw_gpu_grouped_knn_page[_dev] call (the figures of the other families are not touched): out[0] = entries of all
+ * lists, out[1] = rows scored canonically, BOTH passes counted (a query that ran the mark pass scores its list twice), out[2] = queries
+ * that ran the mark pass (a cursor that is not 0, or totals; none whose radius selects nothing or whose list is empty), out[3] = the mark
+ * width W (0: the call did not need it), out[4] = bytes of the marks (0: none were made), and in MICROSECONDS from HIP events on the
+ * call's stream out[5] = the list build with the lists' group words, out[6] = the mark pass, out[7] = both passes + merge + emit. */
+int hnsw_gpu_last_grouped_knn_page(hnsw_gpu_index *ix, uint64_t out[8]);
+
 #ifdef __cplusplus
 }
 #endif

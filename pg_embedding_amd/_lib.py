@@ -164,6 +164,10 @@ def gpu_lib():
         L.hnsw_gpu_grouped_knn_dev.argtypes = [vp, vp, sz, sz, vp, sz, vp, vp, sz, sz, vp, vp, vp, vp, vp, vp, vp]
         L.hnsw_gpu_grouped_knn.argtypes = [vp, vp, sz, sz, vp, sz, vp, vp, sz, sz, vp, vp, vp, vp, vp, vp]
         L.hnsw_gpu_last_grouped_knn.argtypes = [vp, _u64p]
+    if hasattr(L, "hnsw_gpu_grouped_knn_page_dev"):
+        L.hnsw_gpu_grouped_knn_page_dev.argtypes = [vp, vp, sz, sz, vp, sz, vp, vp, vp, sz, sz, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.hnsw_gpu_grouped_knn_page.argtypes = [vp, vp, sz, sz, vp, sz, vp, vp, vp, sz, sz, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.hnsw_gpu_last_grouped_knn_page.argtypes = [vp, _u64p]
     if hasattr(L, "hnsw_gpu_grouped_knn_mfma_dev"):
         L.hnsw_gpu_grouped_knn_mfma_dev.argtypes = [vp, i32, vp, sz, sz, vp, sz, vp, vp, sz, sz, vp, vp, vp, vp, vp, vp, vp]
         L.hnsw_gpu_grouped_knn_mfma.argtypes = [vp, i32, vp, sz, sz, vp, sz, vp, vp, sz, sz, vp, vp, vp, vp, vp, vp]

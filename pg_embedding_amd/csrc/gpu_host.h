@@ -177,8 +177,9 @@ struct FkWs
 	ScanBuf mask, bfs, cand;                             // row masks (matrix-core form, device_filtered_knn_mfma.h); per-query scratch (both forms); candidate lists
 	ScanBuf perm, tmp;                                   // the automatic calls (device_fk_plan.h): the partition of the query numbers; a class's compacted inputs and outputs
 	ScanBuf grp, egrp;                                   // grouped k-NN (device_grouped_knn.h): the group word of every list entry; (matrix-core form, device_grouped_knn_mfma.h) of every element
-	uint64_t *host = nullptr;                            // pinned, 16 words: [0] entries of all lists, [1] the longest list, [2] rows scored, [3] pairs that passed the filter's comparison, [4] pairs appended, [5] candidate lists that overflowed; [8 .. 12] the plan's words (FkPlan::host)
-	hipEvent_t ev[6] = {};                               // before the list build | after it | after the emit kernel | before the filter | after it | before a listed scan that follows a filter
+	ScanBuf marks;                                       // the grouped page call (device_grouped_page.h): per query a bit row `spent` over the group words and (totals) a row `seen`
+	uint64_t *host = nullptr;                            // pinned, 16 words: [0] entries of all lists, [1] the longest list, [2] rows scored, [3] pairs that passed the filter's comparison, [4] pairs appended, [5] candidate lists that overflowed; [8 .. 12] the plan's words (FkPlan::host); [13] the grouped page call's mark width and whether a cursor is not 0 (GpWidth::out), [14] its queries that ran the mark pass
+	hipEvent_t ev[8] = {};                               // before the list build | after it | after the emit kernel | before the filter | after it | before a listed scan that follows a filter | before the grouped page call's mark pass | after it
 	// What the last call of each family left (include/hnsw_gpu_diag.h), one record type: k = the pass that answered the last filtered k-NN
 	// call (hnsw_gpu_last_filtered_knn[_form]: listed, scored, build_ms, scan_ms, form), kf = the last filter launch of that call, whatever form
 	// answered in the end, zeros when it ran none (hnsw_gpu_last_filtered_knn_mfma), r = the pass that answered the last radius search
@@ -187,6 +188,8 @@ struct FkWs
 	// build, or of the pass before, to the end of the emit kernel
 	struct Diag { uint64_t listed = 0, scored = 0, dist_pass = 0, appended = 0, totals = 0, overflowed = 0; float build_ms = 0.f, filter_ms = 0.f, call_ms = 0.f, scan_ms = 0.f; int form = -1; } k, kf, r;
 	Diag p;                                              // the pass that answered the last page call (hnsw_gpu_last_knn_page[_form]: hnsw_gpu_last_range_knn's figures)
+	Diag gp;                                             // the last grouped page call (hnsw_gpu_last_grouped_knn_page), and what only it has: the queries that ran the mark pass, W, the bytes of the marks, the mark pass's ms
+	struct GpDiag { uint64_t marked = 0, width = 0, mark_bytes = 0; float mark_ms = 0.f; } gpx;
 	Diag g, gf;                                          // the last grouped k-NN call: g = the pass that answered (hnsw_gpu_last_grouped_knn[_form]), gf = its last filter launch, as kf (hnsw_gpu_last_grouped_knn_mfma)
 	// the plan of the last automatic call of each kind (hnsw_gpu_last_filtered_knn_plan, hnsw_gpu_last_range_knn_plan, hnsw_gpu_last_grouped_knn_plan): queries and ΣL_q per
 	// class, the threshold in rows, the model's two estimates for the queries above it (µs), the form that answered the loose class

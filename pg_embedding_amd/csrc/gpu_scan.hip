@@ -2,7 +2,8 @@
 // the f32 rows or the reduced copy (csrc/device_bf_mfma.h, csrc/device_bf_mfma16.h), and exact filtered k-NN and exact radius search, one
 // pipeline: the canonical scan over lists of allowed rows (csrc/device_filtered_knn.h) or, for loose filters, the MFMA filter with the allow
 // test at its append (csrc/device_filtered_knn_mfma.h), chosen per query in the automatic calls (csrc/device_fk_plan.h); and exact grouped
-// k-NN over the same lists, in the same forms (csrc/device_grouped_knn.h, csrc/device_grouped_knn_mfma.h).  Every canonical scorer is ONE
+// k-NN over the same lists, in the same forms (csrc/device_grouped_knn.h, csrc/device_grouped_knn_mfma.h) and, in the listed form, page by page
+// (csrc/device_grouped_page.h).  Every canonical scorer is ONE
 // wave loop (scan_list, csrc/device_topk_scan.h) and the three families share one kernel per stage — list build, mask, scan, re-score, emit —
 // with the list that takes the offers (KeyList, or grouped k-NN's GroupedList) as a template parameter (with_list); the two merges differ.
 // One translation unit of libhnsw_gpu.so (csrc/gpu_host.h lists them); gfx950 only, plain HIP runtime, no framework types in any signature.
@@ -15,6 +16,7 @@
 #include "device_fk_plan.h"
 #include "device_grouped_knn.h"
 #include "device_grouped_knn_mfma.h"
+#include "device_grouped_page.h"
 
 #include <type_traits>
 
@@ -473,19 +475,20 @@ extern "C" int hnsw_gpu_bruteforce_reduced_dev(hnsw_gpu_index *ix, int format, c
 // suits its own list in the automatic calls (device_fk_plan.h; §4.11c).  Filtered k-NN is the radius call with no radius and no totals.
 // ------------------------------------------------------------------------------------
 static const size_t FK_PART_BYTES = (size_t) 1 << 30;         // the partial lists of a call: more splits are not worth more memory than this
+static const size_t GK_MARK_BYTES = (size_t) 1 << 30;         // the marks of a grouped page call (device_grouped_page.h): one query always fits (2 rows of 2^32 bits = 2 x 512 MiB)
 enum { FK_LISTED = HNSW_GPU_RANGE_LISTED, FK_MFMA = HNSW_GPU_RANGE_MFMA };   // the form a caller asks for (the automatic calls: per query)
 static_assert(HNSW_GPU_RK_FORM_LISTED == HNSW_GPU_FK_FORM_LISTED && HNSW_GPU_RK_FORM_F32 == HNSW_GPU_FK_FORM_F32 && HNSW_GPU_RK_FORM_F16 == HNSW_GPU_FK_FORM_F16 &&
 			  HNSW_GPU_RK_FORM_BF16 == HNSW_GPU_FK_FORM_BF16, "one set of names for the form that answered");
 
 void fk_ws_free(FkWs *s)
 {
-	buf_trim({&s->cells, &s->list, &s->part, &s->mask, &s->bfs, &s->cand, &s->perm, &s->tmp, &s->grp, &s->egrp}, 0);
+	buf_trim({&s->cells, &s->list, &s->part, &s->mask, &s->bfs, &s->cand, &s->perm, &s->tmp, &s->grp, &s->egrp, &s->marks}, 0);
 	if (s->host) (void) hipHostFree(s->host);
 	s->host = nullptr;
 	for (hipEvent_t &e : s->ev) { if (e) (void) hipEventDestroy(e); e = nullptr; }
 }
 
-// what the four families of entry points differ in: their name in a message, what they require, and where their diagnostics go — the
+// what the five families of entry points differ in: their name in a message, what they require, and where their diagnostics go — the
 // figures of one are not touched by a call of the other
 struct FkFamily
 {
@@ -500,6 +503,7 @@ static const FkFamily FK_KNN = { "filtered k-NN", false, false, &FkWs::k, &FkWs:
 static const FkFamily FK_RANGE = { "radius search", true, false, &FkWs::r, nullptr, &FkWs::rplan };
 static const FkFamily FK_GROUPED = { "grouped k-NN", false, true, &FkWs::g, &FkWs::gf, &FkWs::gplan };
 static const FkFamily FK_PAGE = { "k-NN page", false, false, &FkWs::p, nullptr, &FkWs::pplan, true };
+static const FkFamily FK_GROUPED_PAGE = { "grouped k-NN page", false, true, &FkWs::gp, nullptr, &FkWs::gplan, true };   // (the listed form only: no plan is ever written)
 
 // one call: its arguments (radius, totals: NULL in filtered k-NN), and what its list build found
 struct FkCall
@@ -511,8 +515,9 @@ struct FkCall
 	bool later;                                                   // a pass that follows another of the call: its scan time counts from ev[5], not from the list build
 	const uint32_t *group_of; size_t group_entries; uint32_t *groups;   // grouped k-NN: the table over label values, and NULL or the output
 	const uint64_t *from; uint64_t *next;                         // the page call: NULL or the cursors, and the cursors of the following page
+	GpMarks marks;                                                // the grouped page call: spent == NULL (a call no cursor of which is set, without totals: grouped k-NN's launches) or the marks
 };
-struct FkTrim { FkWs *w; ~FkTrim() { buf_trim({&w->cells, &w->list, &w->part, &w->mask, &w->bfs, &w->cand, &w->perm, &w->tmp, &w->grp, &w->egrp}); } };   // on EVERY way out, errors included: no buffer above 64 MiB outlives its call
+struct FkTrim { FkWs *w; ~FkTrim() { buf_trim({&w->cells, &w->list, &w->part, &w->mask, &w->bfs, &w->cand, &w->perm, &w->tmp, &w->grp, &w->egrp, &w->marks}); } };   // on EVERY way out, errors included: no buffer above 64 MiB outlives its call
 
 // the matrix-core form's operands: the f32 rows, or the reduced copy the index holds (hnsw_gpu_bruteforce_reduced_dev's rule)
 static int fk_check_format(const char *who, hnsw_gpu_index *ix, int format)
@@ -531,7 +536,7 @@ static int fk_check(const FkCall &c, int form, int format)
 	if (!c.ix) return fail(HNSW_GPU_ERR_ARG, "index is NULL");
 	if (c.nq == 0) return range || page || form == FK_LISTED ? HNSW_GPU_OK : fk_check_format(who, c.ix, format);
 	if (form != FK_LISTED && form != FK_MFMA) return fail(HNSW_GPU_ERR_ARG, "%s: form %d is neither listed (0) nor matrix cores (1)", who, form);
-	if (!c.queries || (grouped ? !c.group_of : range ? !c.radius : page ? !c.next : !c.allow) || !c.labels || !c.counts)
+	if (!c.queries || (grouped ? !c.group_of : range ? !c.radius : page ? !c.next : !c.allow) || (page && !c.next) || !c.labels || !c.counts)
 		return fail(HNSW_GPU_ERR_ARG, "%s: NULL buffer%s", who, range || grouped || page ? "" : " (the filter is required: hnsw_gpu_bruteforce_dev takes none)");
 	// (a call that hands itself down to another form reads the cursors again: the next cursors must not have overwritten them)
 	if (page && c.from && (uintptr_t) c.next < (uintptr_t) c.from + c.nq * 8 && (uintptr_t) c.from < (uintptr_t) c.next + c.nq * 8)
@@ -631,6 +636,55 @@ struct FkMfma
 	bool samples(size_t len) const { return sample_len(len) < len; }   // a list of len rows is longer than its sample: the filter has work
 };
 
+// ---- the grouped page call's own steps (device_grouped_page.h) ------------------------------------------------------------------
+// Before the list build: the mark width W from the group table and whether any cursor is set (one small kernel, one wait), then the marks —
+// sized, refused above GK_MARK_BYTES, zeroed.  A call without totals whose cursors are all 0 (or NULL) gets none: from there on it is
+// grouped k-NN's call, launch for launch, with the emit kernel that writes the next cursors.
+static int gp_prepare(FkCall &c)
+{
+	FkWs *fw = &c.ix->fk;
+	fw->gpx = FkWs::GpDiag();
+	if (!c.from && !c.totals) return HNSW_GPU_OK;
+	if (int rc = buf_reserve(&fw->cells, 256, c.fam->who, "the mark width")) return rc;
+	uint32_t *out = (uint32_t *) fw->cells.p;
+	HIPCHK(hipMemsetAsync(out, 0, 8, c.s));
+	const GpWidth gw = { c.group_of, c.group_entries, c.from, (uint32_t) c.nq, out };
+	const uint32_t blocks = (uint32_t) std::min<size_t>((c.group_entries + 255) / 256, (size_t) c.ix->num_cu * 8);
+	hipLaunchKernelGGL(gp_width_kernel, dim3(blocks), dim3(256), 0, c.s, gw);
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipMemcpyAsync(&fw->host[13], out, 8, hipMemcpyDeviceToHost, c.s));
+	HIPCHK(hipStreamSynchronize(c.s));
+	const uint32_t width = (uint32_t) fw->host[13];
+	const bool any = (fw->host[13] >> 32) != 0;
+	fw->gpx.width = width;
+	if (!any && !c.totals) return HNSW_GPU_OK;
+	const size_t words = std::max<size_t>(1, ((size_t) width + 31) / 32), per_query = (c.totals ? 2 : 1) * words * 4;
+	if (c.nq * per_query > GK_MARK_BYTES)
+		return fail(HNSW_GPU_ERR_ARG, "%s: the marks of %zu queries over group words below %u take %zu bytes, a call has %zu: at most %zu queries fit", c.fam->who, c.nq,
+					width, c.nq * per_query, GK_MARK_BYTES, GK_MARK_BYTES / per_query);
+	if (int rc = buf_reserve(&fw->marks, c.nq * per_query, c.fam->who, "the marks")) return rc;
+	HIPCHK(hipMemsetAsync(fw->marks.p, 0, c.nq * per_query, c.s));
+	c.marks.spent = (uint32_t *) fw->marks.p;
+	c.marks.seen = c.totals ? c.marks.spent + c.nq * words : nullptr;
+	c.marks.width = width; c.marks.words = (uint32_t) words;
+	fw->gpx.mark_bytes = c.nq * per_query;
+	return HNSW_GPU_OK;
+}
+
+// in place of grouped k-NN's scan launch: the mark pass, then the page scan that reads the marks — same grid, same LDS, one stream
+template <int FUNC>
+static void gp_scans(const FkCall &c, const FkScan &fs, dim3 grid, size_t lds)
+{
+	FkWs *fw = &c.ix->fk;
+	GpScan gs = { fs, c.marks };
+	gs.m.marked = c.scored + 1;                                   // (the word behind the rows-scored word, which counts both passes)
+	(void) hipMemsetAsync(gs.m.marked, 0, 8, c.s);
+	(void) hipEventRecord(fw->ev[6], c.s);
+	hipLaunchKernelGGL((gp_scan_kernel<FUNC, true>), grid, dim3(256), lds, c.s, gs);
+	(void) hipEventRecord(fw->ev[7], c.s);
+	hipLaunchKernelGGL((gp_scan_kernel<FUNC, false>), grid, dim3(256), lds, c.s, gs);
+}
+
 // One pass over the built lists (and masks).  format < 0: the listed form — the scan over every query's whole list, merge, emit.  Else
 // the matrix-core form with the operands of `format`: the scan over the lists no longer than their sample and (without totals) over the
 // samples of the others -> merge + bounds -> filter (or its stand-in) -> re-score -> emit.  *ovf = candidate lists that overflowed (then
@@ -710,6 +764,9 @@ static int fk_pass(FkCall &c, int format, const FkMfma &m, uint32_t mwords, uint
 			with_func(func, [&](auto F) {
 				if constexpr (std::is_same<List, KeyList>::value)
 					if (c.from) { hipLaunchKernelGGL((fk_scan_kernel<decltype(F)::value, List, true>), grid, dim3(256), g.lds_listed(k, List::LDS_ENTRY), s, fs); return; }
+				// (a grouped page with marks: the mark pass, then the scan that reads them — device_grouped_page.h)
+				if constexpr (std::is_same<List, GroupedList>::value)
+					if (c.marks.spent) { gp_scans<decltype(F)::value>(c, fs, grid, g.lds_listed(k, List::LDS_ENTRY)); return; }
 				hipLaunchKernelGGL((fk_scan_kernel<decltype(F)::value, List>), grid, dim3(256), g.lds_listed(k, List::LDS_ENTRY), s, fs);
 			});
 		}
@@ -750,8 +807,9 @@ static int fk_pass(FkCall &c, int format, const FkMfma &m, uint32_t mwords, uint
 			});
 		});
 	}
-	// one key list and one count per query -> labels, order, counts, tails, totals
-	const FkEmit fe = { keys, rcount, (uint32_t) k, ix->labels, (uint32_t) ix->n, c.labels, c.dists, c.idx, c.counts, c.totals, sum, kgroups, c.groups, c.from, c.next };
+	// one key list and one count per query -> labels, order, counts, tails, totals (a grouped page: its totals are groups, counted from the marks)
+	if (c.marks.seen) hipLaunchKernelGGL(gp_totals_kernel, dim3((uint32_t) nq), dim3(64), 0, s, c.marks, c.totals);
+	const FkEmit fe = { keys, rcount, (uint32_t) k, ix->labels, (uint32_t) ix->n, c.labels, c.dists, c.idx, c.counts, c.marks.seen ? nullptr : c.totals, sum, kgroups, c.groups, c.from, c.next };
 	if (c.next) hipLaunchKernelGGL(fk_emit_kernel<true>, dim3((uint32_t) nq), dim3(64), k * 16, s, fe);
 	else hipLaunchKernelGGL(fk_emit_kernel<false>, dim3((uint32_t) nq), dim3(64), k * 16, s, fe);
 	hipError_t e = hipGetLastError();
@@ -761,6 +819,8 @@ static int fk_pass(FkCall &c, int format, const FkMfma &m, uint32_t mwords, uint
 	if (e == hipSuccess && sum) e = hipMemcpyAsync(&fw->host[6], sum, 8, hipMemcpyDeviceToHost, s);
 	if (e == hipSuccess && !listed) e = hipMemcpyAsync(&fw->host[3], fcnt, 16, hipMemcpyDeviceToHost, s);
 	if (e == hipSuccess && !listed) e = hipMemcpyAsync(&fw->host[5], overflow, 4, hipMemcpyDeviceToHost, s);
+	const bool marked = c.marks.spent && slongest;                // (the mark pass ran: its word behind the rows-scored word, its events)
+	if (e == hipSuccess && marked) e = hipMemcpyAsync(&fw->host[14], c.scored + 1, 8, hipMemcpyDeviceToHost, s);
 	const hipError_t e2 = hipStreamSynchronize(s);
 	if (e == hipSuccess) e = e2;
 	if (e != hipSuccess) return fail(HNSW_GPU_ERR_HIP, "%s: %s", c.fam->who, hipGetErrorString(e));
@@ -773,6 +833,11 @@ static int fk_pass(FkCall &c, int format, const FkMfma &m, uint32_t mwords, uint
 	(void) hipEventElapsedTime(&d.call_ms, fw->ev[0], fw->ev[2]);
 	(void) hipEventElapsedTime(&d.scan_ms, fw->ev[c.later ? 5 : 1], fw->ev[2]);
 	if (!listed && c.fam->filter) fw->*c.fam->filter = d;
+	if (marked)
+	{
+		fw->gpx.marked = fw->host[14];
+		(void) hipEventElapsedTime(&fw->gpx.mark_ms, fw->ev[6], fw->ev[7]);
+	}
 	return HNSW_GPU_OK;
 }
 
@@ -1026,6 +1091,7 @@ static int fk_run(FkCall c, int form, int format, bool aut, uint8_t *d_plan)
 	FkAuto a = {};
 	if (aut) fk_auto_begin(ix, m, &a);
 	int rc = fk_begin(c);
+	if (!rc && c.fam->grouped && c.fam->page) rc = gp_prepare(c);     // (refuses marks above their budget before a list is built or an output written)
 	if (!rc && aut) rc = buf_reserve(&fw->perm, nq * 4, c.fam->who, "the plan's order of the queries");
 	const FkPlanHook hook = { a.thresh, d_plan };
 	if (!rc) rc = fk_lists(c, aut ? &hook : nullptr);
@@ -1263,6 +1329,36 @@ extern "C" int hnsw_gpu_grouped_knn_auto(hnsw_gpu_index *ix, int format, GK_ARGS
 	return fk_host(GK_CALL_HOST, FK_MFMA, format, true, plan);
 }
 
+// The grouped page call (include/hnsw_gpu.h): grouped k-NN's listed call with a cursor per query, the cursors of the following
+// page and, if asked for, the groups not yet paged past.  The listed form only: no `form`, no `format`
+static FkCall gp_call(hnsw_gpu_index *ix, const coord_t *queries, size_t nq, size_t k, const uint32_t *group_of, size_t group_entries, const dist_t *radius,
+					  const uint64_t *from, const uint32_t *allow, size_t allow_bits, size_t nfilters, const uint32_t *allow_of, label_t *labels, dist_t *dists,
+					  idx_t *idx, uint32_t *groups, uint32_t *counts, uint32_t *totals, uint64_t *next, void *stream)
+{
+	FkCall c = { &FK_GROUPED_PAGE, ix, queries, nq, radius, k, allow, allow_bits, nfilters, allow_of, labels, dists, idx, counts, totals, (hipStream_t) stream };
+	c.group_of = group_of; c.group_entries = group_entries; c.groups = groups;
+	c.from = from; c.next = next;
+	return c;
+}
+
+extern "C" int hnsw_gpu_grouped_knn_page_dev(hnsw_gpu_index *ix, const coord_t *d_queries, size_t nq, size_t k, const uint32_t *d_group_of, size_t group_entries,
+											 const dist_t *d_radius, const uint64_t *d_from, const uint32_t *d_allow, size_t allow_bits, size_t nfilters,
+											 const uint32_t *d_allow_of, label_t *d_labels, dist_t *d_dists, idx_t *d_idx, uint32_t *d_groups, uint32_t *d_counts,
+											 uint32_t *d_totals, uint64_t *d_next, void *stream)
+{
+	return fk_run(gp_call(ix, d_queries, nq, k, d_group_of, group_entries, d_radius, d_from, d_allow, allow_bits, nfilters, d_allow_of, d_labels, d_dists, d_idx, d_groups,
+						  d_counts, d_totals, d_next, stream), FK_LISTED, ROWS_F32, false, nullptr);
+}
+
+extern "C" int hnsw_gpu_grouped_knn_page(hnsw_gpu_index *ix, const coord_t *queries, size_t nq, size_t k, const uint32_t *group_of, size_t group_entries,
+										 const dist_t *radius, const uint64_t *from, const uint32_t *allow, size_t allow_bits, size_t nfilters,
+										 const uint32_t *allow_of, label_t *labels, dist_t *dists, idx_t *idx, uint32_t *groups, uint32_t *counts, uint32_t *totals,
+										 uint64_t *next)
+{
+	return fk_host(gp_call(ix, queries, nq, k, group_of, group_entries, radius, from, allow, allow_bits, nfilters, allow_of, labels, dists, idx, groups, counts, totals, next,
+						   nullptr), FK_LISTED, ROWS_F32, false, nullptr);
+}
+
 // ---- what the last call of either family left (include/hnsw_gpu_diag.h) -------------------------------------------------------------------
 static int fk_plan_out(hnsw_gpu_index *ix, FkWs::Plan FkWs::*which, uint64_t out[8])
 {
@@ -1295,6 +1391,17 @@ extern "C" int hnsw_gpu_last_grouped_knn(hnsw_gpu_index *ix, uint64_t out[4])
 	std::lock_guard<std::recursive_mutex> lock_(ix->mu);
 	const FkWs::Diag &m = ix->fk.g;
 	out[0] = m.listed; out[1] = m.scored; out[2] = fk_us(m.build_ms); out[3] = fk_us(m.scan_ms);
+	return HNSW_GPU_OK;
+}
+
+extern "C" int hnsw_gpu_last_grouped_knn_page(hnsw_gpu_index *ix, uint64_t out[8])
+{
+	if (!ix || !out) return fail(HNSW_GPU_ERR_ARG, "NULL argument");
+	std::lock_guard<std::recursive_mutex> lock_(ix->mu);
+	const FkWs::Diag &m = ix->fk.gp;
+	const FkWs::GpDiag &x = ix->fk.gpx;
+	out[0] = m.listed; out[1] = m.scored; out[2] = x.marked; out[3] = x.width; out[4] = x.mark_bytes;
+	out[5] = fk_us(m.build_ms); out[6] = fk_us(x.mark_ms); out[7] = fk_us(m.scan_ms);
 	return HNSW_GPU_OK;
 }
 

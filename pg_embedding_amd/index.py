@@ -895,6 +895,196 @@ class GpuIndex:
         check(self.L.hnsw_gpu_last_grouped_knn_plan(self._h, v), "hnsw_gpu_last_grouped_knn_plan")
         return self._plan_dict(v)
 
+    # ---------------------------------------------------------------- exact grouped k-NN continuation
+    GK_MARK_BYTES = 1 << 30                                   # the marks of one hnsw_gpu_grouped_knn_page call (csrc/gpu_scan.hip)
+
+    @staticmethod
+    def _gp_queries_per_call(width: int, totals: bool) -> int:
+        """how many queries' marks fit one call: a bit row over the group words [0, width) per query, two with totals"""
+        words = max(1, (int(width) + 31) // 32)
+        return max(1, GpuIndex.GK_MARK_BYTES // ((2 if totals else 1) * words * 4))
+
+    def grouped_knn_page(self, queries: np.ndarray, k: int, group_of, start=None, radius=None, allow=None, allow_of=None,
+                         return_idx: bool = False, totals: bool = False):
+        """The next k exact nearest distinct GROUPS after a cursor per query, host buffers (hnsw_gpu_grouped_knn_page): SELECT DISTINCT ON
+        (doc_id) ... ORDER BY distance LIMIT k OFFSET anything, page by page.  group_of / allow / allow_of / radius as in grouped_knn();
+        start: None (from the start) or a uint64 array [nq] of cursors — 0, or the `next` of an earlier page of the same query, filter,
+        radius and table.  Returns grouped_knn()'s dict plus next [nq] u64 = the cursor of the following page and with totals=True totals
+        [nq] u32 = the distinct groups in range not yet paged past, this page included.  A page shorter than k is the last.  The listed
+        form only.  A batch whose marks (a bit per group word and query) would exceed one call's budget runs in parts."""
+        queries = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, self.meta.dim)
+        nq, k = queries.shape[0], int(k)
+        tab = np.asarray(group_of)
+        if tab.dtype not in (np.uint32, np.int32) or tab.ndim != 1:
+            raise ValueError("group_of is a uint32 or int32 array over label values")
+        tab = np.ascontiguousarray(tab).view(np.uint32)
+        rad = None if radius is None else np.ascontiguousarray(np.broadcast_to(np.asarray(radius, dtype=np.float32).reshape(-1), (nq,)))
+        cur = None if start is None else np.ascontiguousarray(start, dtype=np.uint64).reshape(nq)
+        words, bits, nf = _pack_allow_numpy(allow)
+        of = None if allow_of is None or words is None else np.ascontiguousarray(allow_of, dtype=np.uint32).reshape(nq)
+        out = {"labels": np.empty((nq, k), np.uint64), "dists": np.empty((nq, k), np.float32), "groups": np.empty((nq, k), np.uint32),
+               "counts": np.empty(nq, np.uint32), "next": np.empty(nq, np.uint64)}
+        if return_idx:
+            out["idx"] = np.empty((nq, k), np.uint32)
+        if totals:
+            out["totals"] = np.empty(nq, np.uint32)
+        step = max(nq, 1)
+        if (cur is not None or totals) and tab.size:
+            used = tab[tab != NO_GROUP]
+            step = self._gp_queries_per_call(int(used.max()) + 1 if used.size else 0, totals)
+        ptr = lambda a, lo: None if a is None else a[lo:].ctypes.data
+        for lo in range(0, max(nq, 1), step):
+            n = min(step, nq - lo)
+            check(self.L.hnsw_gpu_grouped_knn_page(self._h, queries[lo:].ctypes.data, n, k, tab.ctypes.data, tab.shape[0], ptr(rad, lo), ptr(cur, lo),
+                                                   None if words is None else words.ctypes.data, bits, nf, ptr(of, lo), out["labels"][lo:].ctypes.data,
+                                                   out["dists"][lo:].ctypes.data, ptr(out.get("idx"), lo), out["groups"][lo:].ctypes.data,
+                                                   out["counts"][lo:].ctypes.data, ptr(out.get("totals"), lo), out["next"][lo:].ctypes.data),
+                  "hnsw_gpu_grouped_knn_page")
+        return out
+
+    def grouped_knn_page_torch(self, queries, k: int, group_of, start=None, radius=None, allow=None, allow_of=None, return_idx: bool = False,
+                               totals: bool = False):
+        """grouped_knn_page() with everything resident in HBM (hnsw_gpu_grouped_knn_page_dev on torch's current stream, which the call
+        synchronises).  start: None or an int64 tensor [nq] (the bits of a uint64); the rest as in grouped_knn_torch().  Returns
+        grouped_knn_torch()'s dict plus next [nq] int64 (the bits of a uint64) and with totals=True totals [nq] int32."""
+        torch = _torch()
+        assert queries.is_cuda and queries.dtype == torch.float32 and queries.is_contiguous()
+        nq, k, dev = queries.shape[0], int(k), queries.device
+        if group_of.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) or group_of.dim() != 1:
+            raise ValueError("group_of is an int32 or uint32 tensor over label values")
+        tab = group_of.to(dev).contiguous()
+        if radius is None:
+            rad = None
+        elif torch.is_tensor(radius):
+            rad = radius.to(device=dev, dtype=torch.float32).reshape(-1).expand(nq).contiguous()
+        else:
+            rad = torch.full((nq,), float(radius), dtype=torch.float32, device=dev)
+        cur = None
+        if start is not None:
+            if start.dtype != torch.int64 or start.numel() != nq:
+                raise ValueError("start is an int64 tensor with one cursor per query")
+            cur = start.to(device=dev).contiguous()
+        words, bits, nf = _pack_allow_torch(allow, dev)
+        of = None if allow_of is None or words is None else allow_of.to(device=dev, dtype=torch.int32).contiguous()
+        if of is not None and of.numel() != nq:
+            raise ValueError("allow_of names one filter per query")
+        out = {"labels": torch.empty((nq, k), dtype=torch.int64, device=dev),
+               "dists": torch.empty((nq, k), dtype=torch.float32, device=dev),
+               "groups": torch.empty((nq, k), dtype=torch.int32, device=dev),
+               "counts": torch.empty(nq, dtype=torch.int32, device=dev),
+               "next": torch.empty(nq, dtype=torch.int64, device=dev)}
+        if return_idx:
+            out["idx"] = torch.empty((nq, k), dtype=torch.int32, device=dev)
+        if totals:
+            out["totals"] = torch.empty(nq, dtype=torch.int32, device=dev)
+        step = max(nq, 1)
+        if (cur is not None or totals) and tab.numel():
+            w = tab.view(torch.int32).to(torch.int64) & 0xFFFFFFFF
+            step = self._gp_queries_per_call(int(torch.where(w == NO_GROUP, torch.full_like(w, -1), w).max()) + 1, totals)
+        s = torch.cuda.current_stream(dev).cuda_stream
+        at = lambda t, lo: None if t is None else t[lo:].data_ptr()
+        for lo in range(0, max(nq, 1), step):
+            n = min(step, nq - lo)
+            check(self.L.hnsw_gpu_grouped_knn_page_dev(self._h, queries[lo:].data_ptr(), n, k, tab.data_ptr(), tab.numel(), at(rad, lo), at(cur, lo),
+                                                       _dptr(words), bits, nf, at(of, lo), out["labels"][lo:].data_ptr(), out["dists"][lo:].data_ptr(),
+                                                       at(out.get("idx"), lo), out["groups"][lo:].data_ptr(), out["counts"][lo:].data_ptr(),
+                                                       at(out.get("totals"), lo), out["next"][lo:].data_ptr(), s), "hnsw_gpu_grouped_knn_page_dev")
+        return out
+
+    def last_grouped_knn_page(self) -> dict:
+        """The last grouped_knn_page call on this mirror (hnsw_gpu_last_grouped_knn_page; of a batch run in parts: the last part): entries
+        of all lists, rows scored (both passes), queries that ran the mark pass, the mark width W, bytes of the marks; list-build,
+        mark-pass and scan (both passes + merge + emit) ms."""
+        v = (C.c_uint64 * 8)()
+        check(self.L.hnsw_gpu_last_grouped_knn_page(self._h, v), "hnsw_gpu_last_grouped_knn_page")
+        return {"listed": int(v[0]), "rows_scored": int(v[1]), "marked": int(v[2]), "width": int(v[3]), "mark_bytes": int(v[4]),
+                "build_ms": v[5] / 1000.0, "mark_ms": v[6] / 1000.0, "scan_ms": v[7] / 1000.0}
+
+    def grouped_knn_limit_torch(self, queries, limit: int, group_of, page: int = 1024, radius=None, allow=None, allow_of=None,
+                                return_idx: bool = False):
+        """The exact SELECT DISTINCT ON (group) ... LIMIT n for any n: knn_limit_torch()'s walk over grouped_knn_page_torch() — pages of at
+        most min(page, 1 024) groups, only the queries whose page was full go on, then one ordering by (distance, label, element).  Returns
+        labels [nq, limit] int64 (tail -1), dists [nq, limit] (tail +inf), groups [nq, limit] int32 (tail -1), counts [nq] int32 =
+        min(limit, groups in range), idx [nq, limit] int32 (tail -1) with return_idx=True."""
+        torch = _torch()
+        nq, limit, dev = queries.shape[0], int(limit), queries.device
+        if limit < 1:
+            raise ValueError("limit is at least 1")
+        step = max(1, min(int(page), 1024, limit))
+        if radius is not None and torch.is_tensor(radius):
+            radius = radius.to(device=dev, dtype=torch.float32).reshape(-1).expand(nq)
+        labels = torch.full((nq, limit), -1, dtype=torch.int64, device=dev)
+        dists = torch.full((nq, limit), float("inf"), dtype=torch.float32, device=dev)
+        idx = torch.full((nq, limit), -1, dtype=torch.int32, device=dev)
+        groups = torch.full((nq, limit), -1, dtype=torch.int32, device=dev)
+        counts = torch.zeros(nq, dtype=torch.int32, device=dev)
+        active = torch.arange(nq, device=dev)
+        cur, done = None, 0
+        while active.numel() and done < limit:
+            kk = min(step, limit - done)
+            everyone = active.numel() == nq
+            got = self.grouped_knn_page_torch(queries if everyone else queries[active].contiguous(), kk, group_of, start=cur,
+                                              radius=radius[active] if torch.is_tensor(radius) else radius, allow=allow,
+                                              allow_of=None if allow_of is None else allow_of.to(dev)[active], return_idx=True)
+            labels[active, done:done + kk] = got["labels"]
+            dists[active, done:done + kk] = got["dists"]
+            idx[active, done:done + kk] = got["idx"]
+            groups[active, done:done + kk] = got["groups"]
+            counts[active] += got["counts"]
+            more = got["counts"] == kk
+            active, cur, done = active[more], got["next"][more].contiguous(), done + kk
+        # (distance, label, element) order over the whole answer, as knn_limit_torch() puts it
+        u = dists.view(torch.int32).to(torch.int64) & 0xFFFFFFFF
+        od = torch.where((u & 0x80000000) != 0, ~u & 0xFFFFFFFF, u | 0x80000000)
+        unused = (torch.arange(limit, device=dev)[None, :] >= counts[:, None]).to(torch.int8)
+        order = torch.argsort(idx.to(torch.int64) & 0xFFFFFFFF, dim=1, stable=True)
+        for key in (labels ^ (-1 << 63), od, unused):                 # (labels compare as unsigned)
+            order = order.gather(1, torch.argsort(key.gather(1, order), dim=1, stable=True))
+        out = {"labels": labels.gather(1, order), "dists": dists.gather(1, order), "groups": groups.gather(1, order), "counts": counts}
+        if return_idx:
+            out["idx"] = idx.gather(1, order)
+        return out
+
+    def grouped_knn_limit(self, queries: np.ndarray, limit: int, group_of, page: int = 1024, radius=None, allow=None, allow_of=None,
+                          return_idx: bool = False):
+        """grouped_knn_limit_torch() over host buffers (grouped_knn_page()): labels [nq, limit] u64 (tail ~0), dists [nq, limit] f32 (tail
+        +inf), groups [nq, limit] u32 (tail 0xFFFFFFFF), counts [nq] u32, idx [nq, limit] u32 (tail 0xFFFFFFFF) with return_idx=True."""
+        queries = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, self.meta.dim)
+        nq, limit = queries.shape[0], int(limit)
+        if limit < 1:
+            raise ValueError("limit is at least 1")
+        step = max(1, min(int(page), 1024, limit))
+        rad = None if radius is None else np.broadcast_to(np.asarray(radius, dtype=np.float32).reshape(-1), (nq,))
+        of = None if allow_of is None else np.asarray(allow_of).reshape(nq)
+        labels = np.full((nq, limit), 0xFFFFFFFFFFFFFFFF, np.uint64)
+        dists = np.full((nq, limit), np.inf, np.float32)
+        idx = np.full((nq, limit), 0xFFFFFFFF, np.uint32)
+        groups = np.full((nq, limit), NO_GROUP, np.uint32)
+        counts = np.zeros(nq, np.uint32)
+        active = np.arange(nq)
+        cur, done = None, 0
+        while active.size and done < limit:
+            kk = min(step, limit - done)
+            got = self.grouped_knn_page(queries[active], kk, group_of, start=cur, radius=None if rad is None else rad[active], allow=allow,
+                                        allow_of=None if of is None else of[active], return_idx=True)
+            labels[active, done:done + kk] = got["labels"]
+            dists[active, done:done + kk] = got["dists"]
+            idx[active, done:done + kk] = got["idx"]
+            groups[active, done:done + kk] = got["groups"]
+            counts[active] += got["counts"]
+            more = got["counts"] == kk
+            active, cur, done = active[more], got["next"][more], done + kk
+        u = dists.view(np.uint32)
+        od = np.where(u & np.uint32(0x80000000), ~u, u | np.uint32(0x80000000))
+        unused = np.arange(limit)[None, :] >= counts[:, None]
+        for i in range(nq):
+            o = np.lexsort((idx[i], labels[i], od[i], unused[i]))
+            labels[i], dists[i], idx[i], groups[i] = labels[i][o], dists[i][o], idx[i][o], groups[i][o]
+        out = {"labels": labels, "dists": dists, "groups": groups, "counts": counts}
+        if return_idx:
+            out["idx"] = idx
+        return out
+
     def last_search_ms(self, back: int = 0) -> float:
         """Device time of the search kernel launched `back` launches ago (HIP events recorded on
         the launch stream around the kernel; the last 64 launches are kept)."""
